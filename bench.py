@@ -19,6 +19,8 @@ all-gather of the per-shard top-k (behind the C ABI: ss_topk_allgather_merge), i
 `value` = merged answers per second over the N-times larger corpus.
 
   python bench.py --gpus N --steps K --warmup W      (N > 1 without a launcher: re-executes itself under torchrun)
+  --dump-outputs DIR: the answers the primary leg's last timed step returned, as DIR/doc.npy, score.npy, count.npy, total.npy (one row
+  per query; seeded inputs, so two builds run with the same arguments can be compared answer for answer)
 """
 import argparse
 import ctypes as C
@@ -241,6 +243,26 @@ def emit(line, world):
     print_line(json.dumps(compact_line(line)))
 
 
+DUMP_LIMIT = 64 << 20  # --dump-outputs: bytes written at most
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: what the timed path returned in its last step -> DIR/<name>.npy.  `arrays`: name -> array whose rows are the
+    step's answers, one per query in call order.  Scores stay float32; ids, counts and totals become float64 (exact below 2^53).
+    Past DUMP_LIMIT bytes a fixed seeded sample of the rows is written, their indices as row_index.npy."""
+    arrays = {n: np.asarray(a) for n, a in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    as_float = lambda a: a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    per_row = sum(as_float(a[:1]).nbytes for a in arrays.values()) + 8
+    if rows * per_row > DUMP_LIMIT:
+        idx = np.sort(np.random.default_rng(0).choice(rows, DUMP_LIMIT // per_row, replace=False))
+        arrays = {n: a[idx] for n, a in arrays.items()}
+        arrays["row_index"] = idx
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, n + ".npy"), as_float(a))
+
+
 def one_process_main(args):
     """bench.py --one-process S: C2 through the C++ mirror's Index::search_lexical_batch over S shards of ONE process (VERDICT r5 "next" 9).
     Shard i = the docs g % S == i of one generator stream of S x --docs docs on GPU i; a call = 1000 queries resolved per shard (shard-local
@@ -277,12 +299,15 @@ def one_process_main(args):
     offs = [np.concatenate([[0], np.cumsum([len(q) for q in tl_])]).astype(np.uint32) for tl_ in rot]
     doc = np.empty((nq, k), np.uint64); score = np.empty((nq, k), np.float32); cnt = np.empty(nq, np.uint32); tot = np.empty(nq, np.uint64)
     it = [0]
+    # --dump-outputs: the calls of the last timed step answer into these (call j into block j; touched here, not in the timed region)
+    cap = [np.full((args.calls_per_step,) + a.shape, 0, a.dtype) for a in (doc, score, cnt, tot)] if args.dump_outputs else None
 
-    def call():
+    def call(j=None):
         b = it[0] % NB
         it[0] += 1
+        out = (doc, score, cnt, tot) if j is None else [a[j] for a in cap]
         N.check(HL.ssh_index_search_lexical_batch(ix, nq, flats[b].ctypes.data, offs[b].ctypes.data, int(S.QueryType.Union), k, N.RT_TOPK, 1,
-                                                  doc.ctypes.data, score.ctypes.data, cnt.ctypes.data, tot.ctypes.data), "ssh_index_search_lexical_batch")
+                                                  *(a.ctypes.data for a in out)), "ssh_index_search_lexical_batch")
 
     call()
     # self-check: every query of batch 0 has k results, scores descending, global ids spread over all shards (id % S = its shard)
@@ -292,11 +317,14 @@ def one_process_main(args):
     checksum = float(score.astype(np.float64).sum())
     for _ in range(args.warmup * args.calls_per_step):
         call()
-    t0 = time.perf_counter()
-    for _ in range(args.steps * args.calls_per_step):
-        call()
-    dt = time.perf_counter() - t0
     calls = args.steps * args.calls_per_step
+    last = calls - args.calls_per_step if cap is not None else calls
+    t0 = time.perf_counter()
+    for i in range(calls):
+        call(i - last if i >= last else None)
+    dt = time.perf_counter() - t0
+    if cap is not None:
+        dump_outputs(args.dump_outputs, {"doc": cap[0].reshape(-1, k), "score": cap[1].reshape(-1, k), "count": cap[2].ravel(), "total": cap[3].ravel()})
     line = {"metric": "queries/sec (BM25 3-term OR top-10)", "value": nq * calls / dt, "unit": "queries/s", "n_gpus": n_sh, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32 sums of 16-bit posting weight codes (BM25)", "data": "synthetic",
@@ -345,6 +373,8 @@ def main():
     ap.add_argument("--one-process", type=int, default=0, metavar="S",
                     help="the reference's OWN shape instead of one rank per GPU: ONE process, S shards on GPUs 0 .. S-1, one host thread per shard and call "
                          "(search.rs:1637-1650), the lists exchanged over RCCL communicators made by ss_comm_create_all; prints one line of the same form")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps: the answers of the primary leg's last timed step as "
+                                                           "DIR/<name>.npy (float32 / float64, <= 64 MB; the same arguments give the same inputs)")
     args = ap.parse_args()
     claim_stdout()
     if args.one_process:
@@ -486,19 +516,31 @@ def main():
             bm_call(qd=rot_dev[rot_i[0] % NB])
             rot_i[0] += 1
 
-        def bm_host_rot_call():
+        # --dump-outputs: the calls of the last timed step answer into these (N = 1: call j into block j, touched here and not in the
+        # timed region; N > 1: the merged answers each call returns)
+        cap = None
+        if args.dump_outputs:
+            cap = [np.full((args.calls_per_step,) + a.shape, 0, a.dtype) for a in (hp_doc, hp_score, hp_cnt, hp_tot)] if world == 1 else []
+        steps_run = [0]
+
+        def bm_host_rot_call(j=None):
             """THE primary call: host pointers in, answers on the host (N > 1: + one all-gather and the merge, on every rank's host)"""
             qn_ = rot_np[rot_i[0] % NB]
             rot_i[0] += 1
             if world > 1:
                 merged["bm25_host"] = comm.search_lexical_sharded(sh, qn_, k, N.RT_TOPK)
+                if j is not None:
+                    cap.append(merged["bm25_host"])
             else:
-                N.check(L.ss_bm25_search(sh._h, nq, qn_.ctypes.data_as(C.c_void_p), k, N.RT_TOPK, N.ptr(hp_doc, N.u32p), N.ptr(hp_score, N.f32p),
-                                         N.ptr(hp_cnt, N.u32p), N.ptr(hp_tot, N.u64p)), "ss_bm25_search")
+                out = (hp_doc, hp_score, hp_cnt, hp_tot) if j is None else [a[j] for a in cap]
+                N.check(L.ss_bm25_search(sh._h, nq, qn_.ctypes.data_as(C.c_void_p), k, N.RT_TOPK, N.ptr(out[0], N.u32p), N.ptr(out[1], N.f32p),
+                                         N.ptr(out[2], N.u32p), N.ptr(out[3], N.u64p)), "ss_bm25_search")
 
         def bm_step():
-            for _ in range(args.calls_per_step):
-                bm_host_rot_call()
+            last = cap is not None and steps_run[0] == args.warmup + args.steps - 1  # (--warmup steps, then the --steps timed ones)
+            steps_run[0] += 1
+            for j in range(args.calls_per_step):
+                bm_host_rot_call(j if last else None)
 
         # exact union sizes for the roofline's "1 B per scored candidate" term: one untimed TopkCount pass (exhaustive scan)
         sh.set_strategy(N.BM25_EXHAUSTIVE)
@@ -550,6 +592,11 @@ def main():
         sh.profile_read(0, reset=True)  # the accumulators count the timed launches only
         dt = timed(bm_step, args.steps, 0)
         launches, kms = sh.profile_read(0, reset=True)
+        if cap is not None and rank == 0:
+            if world > 1:
+                cap = [np.stack(a) for a in zip(*cap)]
+            dump_outputs(args.dump_outputs, {"doc": cap[0].reshape(-1, k), "score": cap[1].reshape(-1, k), "count": cap[2].ravel(),
+                                             "total": cap[3].ravel()})
         calls = args.steps * args.calls_per_step
         assert launches == calls, (launches, calls)
         avg_ms = kms / max(launches, 1)
@@ -1244,7 +1291,13 @@ def main():
         torch.cuda.synchronize()
         sh.profile(True)
         sh.profile_read(1, reset=True)
-        vn, dtv = timed_for(vec_call)
+        if bm is None:  # the primary leg (--workload vec): --warmup calls, then exactly --steps timed ones
+            vn, dtv = args.steps, timed(vec_call, args.steps, args.warmup)
+            if args.dump_outputs and rank == 0:
+                m_ = merged["vec"] if world > 1 else (v_doc, v_score, v_cnt, v_tot)
+                dump_outputs(args.dump_outputs, dict(zip(("doc", "score", "count", "total"), (a.cpu().numpy() for a in m_))))
+        else:
+            vn, dtv = timed_for(vec_call)
         launches, kms = sh.profile_read(1, reset=True)
         sh.profile(False)
         cnt = v_cnt.cpu().numpy()

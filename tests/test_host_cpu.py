@@ -439,3 +439,31 @@ def test_bench_stdout_carries_one_line():
     assert out.returncode == 0, out.stderr
     assert out.stdout == '{"x": 1}\n', repr(out.stdout)
     assert "banner through C stdio" in out.stderr and "raw write to fd 1" in out.stderr and "python print" in out.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_bound(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: one DIR/<name>.npy per answer array, scores float32 and ids / counts / totals float64 with their
+    values intact; past the byte bound a seeded sample of the rows, the same from run to run, with the rows it kept"""
+    import bench
+    rng = np.random.default_rng(7)
+    doc = rng.integers(0, 10_000_000, (600, 10), dtype=np.uint64).astype(np.uint32)
+    score = rng.random((600, 10), dtype=np.float32)
+    cnt = np.full(600, 10, np.uint32)
+    tot = rng.integers(0, 2 ** 40, 600, dtype=np.uint64)
+    arrays = {"doc": doc, "score": score, "count": cnt, "total": tot}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("doc", "score", "count", "total")}
+    assert sorted(os.listdir(tmp_path / "all")) == ["count.npy", "doc.npy", "score.npy", "total.npy"]
+    assert got["score"].dtype == np.float32 and np.array_equal(got["score"], score)
+    for n in ("doc", "count", "total"):
+        assert got[n].dtype == np.float64 and np.array_equal(got[n].astype(np.uint64), arrays[n].astype(np.uint64)), n
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 100 * (10 * 8 + 10 * 4 + 8 + 8 + 8))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_LIMIT + 5 * 128  # (+ .npy headers)
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    idx = np.load(tmp_path / "a" / "row_index.npy").astype(np.int64)
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "score.npy"), score[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "doc.npy"), doc[idx].astype(np.float64))
