@@ -123,7 +123,12 @@ int ss_shard_sync(ss_shard* s);
 /* ------------------------------------------------------------------ BM25 image
  * Host passes DECODED postings (CSR by term, shard-local doc ids ascending per term, tf = positions_count
  * of the single indexed field) and the per-doc SmallFloat length bytes (index.rs:5397); the library builds
- * the HBM image (sub-block CSR of packed postings, bm25_component_cache per commit.rs:318-325). */
+ * the HBM image (sub-block CSR of packed postings, bm25_component_cache per commit.rs:318-325).
+ * WEIGHT RANGE (every upload, append and commit entry below): a posting carries its weight tf (K+1) / (tf + comp[len]) as a code
+ * that holds [2^-14, 4) within 2^-16 relative.  A weight below 2^-14 -- a doc some 4 10^4 times longer than avgdl, e.g. one long
+ * text among many empty ones -- has no code: such a posting is never clamped and scored, the call answers SS_ENOTSUP and the
+ * shard stays with the crate's own path.  An upload leaves no image; a refused commit (ss_bm25_append_level*, _fields,
+ * ss_bm25_append_sparse_level) keeps the previous image and levels, with the sparse tier's postings checked under the new avgdl. */
 int ss_bm25_upload(ss_shard* s, uint64_t n_docs, const uint8_t* doclen_bytes, uint32_t n_terms,
                    const uint64_t* term_offsets, const uint32_t* doc_ids, const uint16_t* tfs);
 /* Several indexed fields (BM25F, get_bm25f_multiterm_multifield, add_result.rs:1171-1426): a posting is (term, doc, field, tf)
@@ -346,7 +351,9 @@ int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, ui
  * the image; a shard whose image came from another builder answers SS_ESTATE.  One indexed field; positions and a sparse tier: below.
  * Cost: the level's bytes over PCIe + a device-side rebuild of the image from the levels' postings kept in HBM (6 bytes per posting):
  * BM25 weights depend on avgdl, which every commit moves (commit.rs:318-325), so the reference too refreshes every block's scores.
- * Searches keep running on the previous image until the new one is swapped in (the call then waits for the searches in flight). */
+ * Searches keep running on the previous image until the new one is swapped in (the call then waits for the searches in flight).
+ * SS_ENOTSUP when a posting of the new image -- any level's, the sparse tier's included -- has a weight the code cannot hold (the
+ * WEIGHT RANGE above): the previous image and levels stay. */
 int ss_bm25_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms,
                          const uint64_t* term_offsets /*[n_terms+1]*/, const uint32_t* doc_ids, const uint16_t* tfs);
 /* ... of an image with SEVERAL indexed fields (ABI v7; commit.rs:142-148): the level's entries (term, doc, field, tf) sorted by (doc, field)

@@ -86,3 +86,35 @@ def rrf(lex_ids, vec_ids, length):  # search.rs:1962-2035 (k = 0.6, 0-based rank
         sc[int(d)] = np.float32(sc[int(d)] + r) if int(d) in sc else r
     items = sorted(sc.items(), key=lambda kv: (-float(kv[1]), kv[0]))[:length]
     return [d for d, _ in items], [s for _, s in items]
+
+
+def bm25_exact(n_docs, doclen_bytes, postings, op_and, not_docs=(), deleted=(), n_idf=None):
+    """Every match of a lexical query, scored as the crate rounds each term's factors -- f32 idf (search.rs:3225-3230), f32
+    component cache (commit.rs:318-325), f32 tf (K + 1) / (tf + comp) (add_result.rs:1445-1447) -- and summed over the doc's
+    terms in float64: the yardstick for kernels whose own rounding of the sum (or of the weight) differs from the crate's.
+    postings: (docs, tfs) per query term; not_docs: doc arrays of the NOT terms (add_result.rs:3440-3497); deleted: tombstones;
+    n_idf: the doc count of idf (default n_docs).  -> (doc ids ascending, float64 scores); len(ids) = result_count_total."""
+    comp = component_cache(avgdl(doclen_bytes))
+    N = n_docs if n_idf is None else n_idf
+    sc = np.zeros(n_docs, np.float64)
+    cnt = np.zeros(n_docs, np.int32)
+    for docs, tfs in postings:
+        docs = np.asarray(docs, np.int64)
+        w_idf = np.float64(idf(N, len(docs)))
+        tf = np.asarray(tfs).astype(np.float32)
+        w = ((tf * (K + np.float32(1.0))) / (tf + comp[doclen_bytes[docs]])).astype(np.float32)
+        sc[docs] += w_idf * w.astype(np.float64)
+        cnt[docs] += 1
+    m = (cnt == len(postings)) if op_and else (cnt > 0)
+    for d in not_docs:
+        m[np.asarray(d, np.int64)] = False
+    if len(deleted):
+        m[np.asarray(deleted, np.int64)] = False
+    ids = np.nonzero(m)[0].astype(np.uint32)
+    return ids, sc[ids]
+
+
+def topk_exact(ids, scores, k):
+    """top-k of bm25_exact's answer by (score desc, doc asc)"""
+    order = np.lexsort((ids, -np.asarray(scores, np.float64)))[:k]
+    return ids[order], np.asarray(scores, np.float64)[order]

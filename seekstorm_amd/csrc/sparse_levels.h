@@ -8,7 +8,11 @@
 bool ssi_bm25_sparse_levels_has(const ss_shard* s);
 void ssi_bm25_sparse_levels_drop(const ss_shard* s);
 // every sparse posting's code again from its tf, the image's d_doclen and d_comp (after a commit moved the average length)
+// (SS_ENOTSUP: a weight the code cannot hold, bm_w_codable)
 int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st);
+// the same weights under the component cache and length bytes of `img` (a commit's new dense image), counted and not written: SS_ENOTSUP
+// when one has no code -- the commit is refused before the image is swapped in
+int ssi_bm25_sparse_levels_check(ss_shard* s, const ss_shard* img, hipStream_t st);
 // the postings of the rare terms in `level` (the level the dense image committed last): list i continues sparse list i (ascending
 // docs, all behind the list's last), lists past the tier's current count are new terms; a level the tier has seen already is
 // replaced.  Caller holds s->mu, the device is idle.

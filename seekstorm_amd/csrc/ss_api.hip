@@ -517,6 +517,11 @@ int ssi_bm25_upload_fields(ss_shard* s, uint64_t n_docs, uint32_t n_fields, cons
     });
     if (bad.load()) return SS_EINVAL;
   }
+  {  // a (term, field) weight the code cannot hold: refused before the present image is released (a re-upload of ss_bm25_append_level_fields
+     // keeps the image and levels it had)
+    const int rc_codable = ssi_bm25_fields_codable(n_docs, n_fields, doclen, n_terms, offs, fields, tfs, docs, positions_sum);
+    if (rc_codable) return rc_codable;
+  }
   ShardLock g(s);
   SS_HIP(hipSetDevice(s->device));
   SS_HIP(hipStreamSynchronize(s->stream));
@@ -758,6 +763,10 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
     if (level > s->raw.size() || level + 1 < s->raw.size()) return fail(SS_ESTATE);  // another commit got in between (the caller's write lock forbids it)
     (void)hipStreamSynchronize(s->stream);
     for (auto& kv : s->bm_ws) (void)hipStreamSynchronize(kv.first);
+    if (s->sp_n) {  // the sparse postings under the new average length: a weight the code cannot hold refuses the commit before anything changes
+      const int rc_check = ssi_bm25_sparse_levels_check(s, img.get(), bst);
+      if (rc_check) return fail(rc_check);
+    }
     ss_raw_level replaced;
     const bool replace = level < s->raw.size();
     if (replace) replaced = s->raw[level];
@@ -1927,6 +1936,10 @@ static int bm25_shape_of(const ss_shard* s, const ss_bm25_query& Q, uint32_t kk,
     if (Q.phrase_len < 2 || Q.phrase_len > SS_MAX_PHRASE || Q.phrase_seq[0] >= np) return SS_EINVAL;
     for (uint32_t j = 1; j < Q.phrase_len; j++)
       if (Q.phrase_seq[j] >= np && Q.phrase_seq[j] != SS_PHRASE_SKIP) return SS_EINVAL;
+    // the phrase kernels keep positions for the unique terms 0 .. SS_MAX_PHRASE - 1 only (bm25_gallop.hip GP_NT; the staged kernel: 6): a
+    // word naming a later one (an n-gram key's components before it) is the crate's to answer
+    for (uint32_t j = 0; j < Q.phrase_len; j++)
+      if (Q.phrase_seq[j] >= SS_MAX_PHRASE && Q.phrase_seq[j] != SS_PHRASE_SKIP) return SS_ENOTSUP;
     if (L > 1 && !s->bm_merged) return SS_ENOTSUP;  // phrases of several indexed fields run over the merged lists' field-tagged positions
     if (np > 6 || kk > 128) *shape = SH_GALLOP_PHRASE;
     // a rationed vocabulary: the phrase kernel of the probe index needs a row for EVERY list it reads and has no scan to fall back on -- a

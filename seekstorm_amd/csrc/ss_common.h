@@ -69,7 +69,9 @@ constexpr uint32_t BM_NO_PROBE_ROW = 0xFFFFFFFFu;
 //   bits 13..31  W19 = the posting's weight  tf (K + 1) / (tf + bm25_component_cache[len])  (add_result.rs:1445-1447 without
 //                idf), computed in f32 exactly as the reference computes it and then rounded to 15 mantissa bits:
 //                weight = as_float((W19 << 8) + BM_W_BASE), binades 2^-14 .. 2^2, relative rounding error <= 2^-16 = 1.5e-5
-//                (north_star's tolerance is 1e-4).  Any tf fits: there is no tf field, no table and no exception list.
+//                (north_star's tolerance is 1e-4).  There is no tf field, no table and no exception list, but not every weight
+//                fits: one below 2^-14 (a doc some 4 10^4 times longer than avgdl) has no code.  Every producer counts such
+//                postings (bm_w_codable) and refuses the image with SS_ENOTSUP rather than clamp them (include/seekstorm_hip.h).
 //                Lists that can take part in the all_terms_frequent shortcut (df >= N / 2, intersection.rs:198-209) give
 //                up the last mantissa bit for the one thing that rule asks of a posting: W19 bit 0 = (tf < 10).
 // The all-zero dword is the NULL posting (segment padding, and what an out-of-range buffer load returns): its doc field
@@ -83,6 +85,8 @@ __host__ __device__ inline uint32_t bm_wcode(float w) {  // round to nearest; we
   const uint32_t c = (b - BM_W_BASE + 128u) >> 8;
   return c > 0x7FFFFu ? 0x7FFFFu : c;
 }
+// the weights bm_wcode represents within its rounding (2^-16 relative): [2^-14, 4); a producer refuses an image holding any other
+__host__ __device__ inline bool bm_w_codable(float w) { return w >= 6.103515625e-05f && w < 4.0f; }
 __host__ __device__ inline float bm_wdecode(uint32_t c) { return bm_u2f((c << 8) + BM_W_BASE); }
 __host__ __device__ inline float bm_weight(uint32_t p) { return bm_u2f(((p >> 13) << 8) + BM_W_BASE); }  // weight of a posting
 __host__ __device__ inline uint32_t bm_pack(uint32_t doc_in_sub, uint32_t wcode) { return (wcode << 13) | ((doc_in_sub + 1u) & 0x1FFFu); }

@@ -104,10 +104,13 @@ static inline bool bm_list_flagged(const ss_shard* s, uint64_t df) {
 static inline bool bm_merged_list_flagged(const ss_shard* s, uint64_t df) {
   return s->bm_merged && (float)df / (float)s->bm_n_docs >= 0.5f;
 }
-static inline uint32_t bm_code_of(uint32_t tf, float comp_len, bool flagged) {
-  uint32_t c = bm_wcode(bm_weight_exact(tf, comp_len));
+// false: the weight lies outside what the code holds (bm_w_codable) -- the caller refuses the image (SS_ENOTSUP) instead of clamping
+static inline bool bm_code_of(uint32_t tf, float comp_len, bool flagged, uint32_t* code) {
+  const float w = bm_weight_exact(tf, comp_len);
+  uint32_t c = bm_wcode(w);
   if (flagged) c = (c & ~1u) | (tf < 10u ? 1u : 0u);
-  return c;
+  *code = c;
+  return bm_w_codable(w);
 }
 
 // an image array: from the owner's block pool when the image is an incremental one (ss_block_pool), else a plain allocation
@@ -178,6 +181,25 @@ int ssi_bm25_build_from_host(ss_shard* s, const uint8_t* doclen, const uint64_t*
   (void)merged_scale;
   if (merged_boost || s->bm_merged) return SS_EINVAL;  // images with merged lists: ssi_bm25_build_from_host_merged
   return ssi_bm25_build_from_host_merged(s, doclen, offs, docs, tfs, positions_sum, nullptr, nullptr);
+}
+
+int ssi_bm25_fields_codable(uint64_t n_docs, uint32_t n_fields, const uint8_t* doclen, uint32_t n_terms, const uint64_t* offs,
+                            const uint8_t* fields, const uint16_t* tfs, const uint32_t* docs, uint64_t positions_sum) {
+  u64 psum = positions_sum;
+  if (!psum)
+    for (u64 d = 0; d < n_docs * n_fields; d++) psum += ss_byte4_to_int(doclen[d]);  // (ssi_bm25_build_from_host_merged's average)
+  float comp[SS_COMP_N];
+  fill_comp((float)psum / (float)n_docs, comp);
+  std::atomic<int> fail{SS_OK};
+  ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
+    for (size_t t = ta; t < tb; t++)
+      for (u64 j = offs[t]; j < offs[t + 1]; j++) {
+        if (docs[j] >= n_docs || fields[j] >= n_fields || tfs[j] == 0) continue;  // (the builder refuses these: SS_EINVAL)
+        uint32_t code;
+        if (!bm_code_of(tfs[j], comp[doclen[(size_t)fields[j] * n_docs + docs[j]]], false, &code)) { fail.store(SS_ENOTSUP); return; }
+      }
+  });
+  return fail.load();
 }
 
 int ssi_bm25_build_from_host_merged(ss_shard* s, const uint8_t* doclen, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
@@ -311,7 +333,7 @@ int ssi_bm25_build_from_host_merged(ss_shard* s, const uint8_t* doclen, const ui
           code = bm_wcode(mw[mw_base[t / L] + (j - offs[t])] / mscale);
           if (bm_merged_list_flagged(s, s->h_df[t])) code = (code & ~1u) | mw_lt10[mw_base[t / L] + (j - offs[t])];
         } else {
-          code = bm_code_of(tfs[j], comp[dl[docs[j]]], flagged);
+          if (!bm_code_of(tfs[j], comp[dl[docs[j]]], flagged, &code)) { fail.store(SS_ENOTSUP); return; }
         }
         post[w] = bm_pack(docs[j] & (BM_SUB - 1), code);
         umax[t] = std::max(umax[t], bm_wdecode(code));  // the bound of the pruned kernel: over the weights as the kernels see them
@@ -449,7 +471,7 @@ __global__ void raw_fill_kernel(const RawLevelDev* __restrict__ levels, uint32_t
                                 const float* __restrict__ comp, float k1, const uint32_t* __restrict__ sub, const u64* __restrict__ term_base,
                                 uint32_t* __restrict__ post, uint2* __restrict__ probe, uint32_t* __restrict__ probe_z,
                                 const uint32_t* __restrict__ probe_row, uint32_t* __restrict__ umax_bits, float* __restrict__ submax,
-                                const uint8_t* __restrict__ flagged) {
+                                const uint8_t* __restrict__ flagged, uint32_t* __restrict__ n_uncodable) {
   __shared__ unsigned long long masks[4][BM_SUB / 64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const u64 gw = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -465,10 +487,12 @@ __global__ void raw_fill_kernel(const RawLevelDev* __restrict__ levels, uint32_t
   masks[w][lane] = 0ull;
   __builtin_amdgcn_wave_barrier();
   float wmax = 0.f;
+  uint32_t n_bad = 0;  // postings whose weight the code cannot hold (bm_w_codable): the image is refused
   for (u64 i = lo + (u64)lane; i < hi; i += 64u) {
     const uint32_t d = dp[i], tf = tp[i];
     const float tt = (float)tf;
     const float wgt = __fdiv_rn(ss_fmul(tt, k1), ss_fadd(tt, comp[doclen[d]]));  // bm_weight_exact
+    n_bad += bm_w_codable(wgt) ? 0u : 1u;
     uint32_t code = bm_wcode(wgt);
     if (flg) code = (code & ~1u) | (tf < 10u ? 1u : 0u);
     const uint32_t din = d & (uint32_t)(BM_SUB - 1);
@@ -479,6 +503,10 @@ __global__ void raw_fill_kernel(const RawLevelDev* __restrict__ levels, uint32_t
   const uint32_t n = (uint32_t)(hi - lo);
   if ((uint32_t)lane < ((4u - (n & 3u)) & 3u)) post[base + n + lane] = 0u;  // NULL padding
   for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o));
+  if (__any(n_bad != 0u)) {  // (one atomic per wave that met one)
+    for (int o = 32; o > 0; o >>= 1) n_bad += __shfl_xor(n_bad, o);
+    if (lane == 0) atomicAdd(n_uncodable, n_bad);
+  }
   if (lane == 0) {
     submax[(size_t)t * n_sub + sb] = wmax;
     if (wmax > 0.f) atomicMax(&umax_bits[t], __float_as_uint(wmax));
@@ -590,7 +618,8 @@ int ssi_bm25_rebuild_from_raw(const ss_shard* s, const std::vector<ss_raw_level>
   RawLevelDev* d_lv = nullptr;
   u64 *d_tot = nullptr, *d_df = nullptr;
   uint8_t* d_flg = nullptr;
-  auto cleanup = [&]() { for (void* p : {(void*)d_lv, (void*)d_tot, (void*)d_df, (void*)d_flg}) if (p) (void)hipFree(p); };
+  uint32_t* d_bad = nullptr;
+  auto cleanup = [&]() { for (void* p : {(void*)d_lv, (void*)d_tot, (void*)d_df, (void*)d_flg, (void*)d_bad}) if (p) (void)hipFree(p); };
 #define SS_HIP_C(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return e_ == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE; } } while (0)
   SS_HIP_C(hipMalloc(&d_lv, lv.size() * sizeof(RawLevelDev)));
   SS_HIP_C(hipMemcpyAsync(d_lv, lv.data(), lv.size() * sizeof(RawLevelDev), hipMemcpyHostToDevice, st));
@@ -632,10 +661,12 @@ int ssi_bm25_rebuild_from_raw(const ss_shard* s, const std::vector<ss_raw_level>
   for (uint32_t t = 0; t < nt; t++) flg[t] = bm_list_flagged(img, img->h_df[t]) ? 1 : 0;
   SS_HIP_C(hipMalloc(&d_flg, nt));
   SS_HIP_C(hipMemcpyAsync(d_flg, flg.data(), nt, hipMemcpyHostToDevice, st));
+  SS_HIP_C(hipMalloc(&d_bad, sizeof(uint32_t)));
+  SS_HIP_C(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), st));
   const volatile float k1 = 1.2f + 1.0f;  // (K + 1) as bm_weight_exact forms it
   raw_fill_kernel<<<(uint32_t)((pairs + 3) / 4), 256, 0, st>>>(d_lv, level_shift, nt, ns, img->d_doclen, img->d_comp, k1, img->d_sub_off,
                                                               (const u64*)img->d_term_base, img->d_post, img->d_probe, img->d_probe_z,
-                                                              img->d_probe_row, (uint32_t*)img->d_umax, img->d_submax, d_flg);
+                                                              img->d_probe_row, (uint32_t*)img->d_umax, img->d_submax, d_flg, d_bad);
   SS_HIP_C(hipGetLastError());
   if (with_pos) {  // the position arrays, from the levels' pools
     u64 *d_ptot = nullptr, *d_lstart = nullptr;
@@ -658,6 +689,9 @@ int ssi_bm25_rebuild_from_raw(const ss_shard* s, const std::vector<ss_raw_level>
     if (e != hipSuccess) { cleanup(); return SS_EDEVICE; }
   }
   SS_HIP_C(hipStreamSynchronize(st));
+  uint32_t n_bad = 0;
+  SS_HIP_C(hipMemcpy(&n_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (n_bad) { cleanup(); return SS_ENOTSUP; }  // weights the code cannot hold: not an image the kernels may score
   const auto t4 = now();
   // block maxima worth a pass per search?  (the host builder's rule, on the 64 longest lists)
   {
@@ -698,7 +732,9 @@ int ssi_bm25_append_sparse(ss_shard* s, uint32_t n_lists, const uint64_t* offs, 
     for (size_t i = a; i < b; i++)
       for (u64 j = offs[i]; j < offs[i + 1]; j++) {
         if (docs[j] >= s->bm_n_docs || tfs[j] == 0 || (j > offs[i] && docs[j] <= docs[j - 1])) { fail.store(SS_EINVAL); return; }
-        packed[j - offs[0]] = ((u64)bm_code_of(tfs[j], comp[dl[docs[j]]], false) << 32) | docs[j];
+        uint32_t code;
+        if (!bm_code_of(tfs[j], comp[dl[docs[j]]], false, &code)) { fail.store(SS_ENOTSUP); return; }  // a weight the code cannot hold
+        packed[j - offs[0]] = ((u64)code << 32) | docs[j];
       }
   });
   if (fail.load()) return fail.load();
@@ -929,14 +965,23 @@ __global__ void __launch_bounds__(256) sp_extend_kernel(SpExtend A) {
   }
 }
 // a sparse posting's code from its tf and its doc's length byte -- the operations of bm_weight_exact / raw_fill_kernel
+// n_uncodable: counts the postings whose weight the code cannot hold (bm_w_codable), one atomic per wave that met one; write = false
+// only counts (the check of a commit, before the dense image is swapped)
 __global__ void __launch_bounds__(256) sp_recode_kernel(uint64_t* __restrict__ post, const uint16_t* __restrict__ tf, uint64_t n,
-                                                        const uint8_t* __restrict__ doclen, uint32_t n_docs, const float* __restrict__ comp, float k1) {
+                                                        const uint8_t* __restrict__ doclen, uint32_t n_docs, const float* __restrict__ comp, float k1,
+                                                        uint32_t* __restrict__ n_uncodable, int write) {
+  uint32_t n_bad = 0;
   for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256u) {
     const uint32_t d = (uint32_t)post[p];
     if (d >= n_docs) continue;  // (a re-committed level that shrank: its sparse postings go with the sparse re-commit)
     const float tt = (float)tf[p];
     const float wgt = __fdiv_rn(ss_fmul(tt, k1), ss_fadd(tt, comp[doclen[d]]));
-    post[p] = ((uint64_t)bm_wcode(wgt) << 32) | d;
+    n_bad += bm_w_codable(wgt) ? 0u : 1u;
+    if (write) post[p] = ((uint64_t)bm_wcode(wgt) << 32) | d;
+  }
+  if (__any(n_bad != 0u)) {
+    for (int o = 32; o > 0; o >>= 1) n_bad += __shfl_xor(n_bad, o);
+    if ((threadIdx.x & 63u) == 0u) atomicAdd(n_uncodable, n_bad);
   }
 }
 
@@ -951,7 +996,8 @@ void ssi_bm25_sparse_levels_drop(const ss_shard* s) {
   if (it->second.d_tf) (void)hipFree(it->second.d_tf);
   g_spl.erase(it);
 }
-int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st) {
+// write = false: counts only, against the given length bytes and component cache (a commit's new image, before it is swapped in)
+static int sparse_levels_recode(ss_shard* s, hipStream_t st, const uint8_t* doclen, uint64_t n_docs, const float* comp, bool write) {
   uint16_t* d_tf = nullptr;
   {
     std::lock_guard<std::mutex> g(g_spl_mu);
@@ -961,11 +1007,28 @@ int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st) {
   }
   const uint64_t n = s->h_sp_base.empty() ? 0 : s->h_sp_base.back();
   if (!n) return SS_OK;
-  if (!s->d_sp_post || !d_tf || !s->d_doclen || !s->d_comp) return SS_ESTATE;
+  if (!s->d_sp_post || !d_tf || !doclen || !comp) return SS_ESTATE;
+  uint32_t* d_bad = nullptr;
+  SS_HIP(hipMalloc(&d_bad, sizeof(uint32_t)));
+  uint32_t n_bad = 0;
+  hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(uint32_t), st);
   const volatile float k1 = 1.2f + 1.0f;  // (K + 1) as bm_weight_exact forms it
-  sp_recode_kernel<<<(uint32_t)std::min<uint64_t>((n + 255) / 256, 65536), 256, 0, st>>>(s->d_sp_post, d_tf, n, s->d_doclen, s->bm_n_docs, s->d_comp, k1);
-  SS_HIP(hipGetLastError());
-  return SS_OK;
+  if (e == hipSuccess) {
+    sp_recode_kernel<<<(uint32_t)std::min<uint64_t>((n + 255) / 256, 65536), 256, 0, st>>>(s->d_sp_post, d_tf, n, doclen, (uint32_t)n_docs, comp, k1,
+                                                                                           d_bad, write ? 1 : 0);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&n_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_bad);
+  if (e != hipSuccess) return SS_EDEVICE;
+  return n_bad ? SS_ENOTSUP : SS_OK;
+}
+int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st) {
+  return sparse_levels_recode(s, st, s->d_doclen, s->bm_n_docs, s->d_comp, true);
+}
+int ssi_bm25_sparse_levels_check(ss_shard* s, const ss_shard* img, hipStream_t st) {
+  return sparse_levels_recode(s, st, img->d_doclen, img->bm_n_docs, img->d_comp, false);
 }
 
 int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
@@ -1001,11 +1064,17 @@ int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, 
   const bool replace = !drop_n.empty();
   if (replace && (drop_n.size() != n_old || (with_pos && drop_p.size() != n_old))) return SS_ESTATE;
   const uint64_t d_lo = (uint64_t)level << 16;
+  if (s->h_doclen.size() != s->bm_n_docs) return SS_ESTATE;
+  float comp[SS_COMP_N];  // (the image's, d_comp: the level's weights are checked here, before the tier changes; the older postings
+  fill_comp(s->bm_avgdl, comp);  // were checked against this average length by the dense commit, ssi_bm25_sparse_levels_check)
   std::atomic<int> fail{SS_OK};
   ss_parallel_for(n_lists, 4096, [&](size_t a, size_t b, unsigned) {
     for (size_t i = a; i < b; i++)
-      for (uint64_t j = offs[i]; j < offs[i + 1]; j++)
+      for (uint64_t j = offs[i]; j < offs[i + 1]; j++) {
         if (docs[j] < d_lo || docs[j] >= s->bm_n_docs || tfs[j] == 0 || (j > offs[i] && docs[j] <= docs[j - 1])) { fail.store(SS_EINVAL); return; }
+        uint32_t code;
+        if (!bm_code_of(tfs[j], comp[s->h_doclen[docs[j]]], false, &code)) { fail.store(SS_ENOTSUP); return; }  // a weight the code cannot hold
+      }
   });
   if (fail.load()) return fail.load();
   // the new starts of the lists (postings; positions), the level's own offsets
@@ -1449,9 +1518,15 @@ int ssi_bm25_synth(ss_shard* s, uint64_t seed, const uint32_t* d_thresh, const u
   rc = alloc_probe(s, st);
   if (rc) return rc;
   // weight codes of every (tf, len) the generator can produce, computed on the host like every other image's
+  // (the length bytes the generator can draw -- those of the length table -- must have a code for every tf; the others are never read)
+  std::vector<uint8_t> lentab(1024);
+  SS_HIP(hipMemcpy(lentab.data(), d_lentab, lentab.size(), hipMemcpyDeviceToHost));
+  std::vector<uint8_t> drawn(256, 0);
+  for (uint8_t b : lentab) drawn[b] = 1;
   std::vector<uint32_t> wtab((size_t)(SS_SYNTH_TF_MAX + 1) * 256, 0u);
   for (uint32_t tf = 1; tf <= (uint32_t)SS_SYNTH_TF_MAX; tf++)
-    for (uint32_t l = 0; l < 256; l++) wtab[(tf << 8) + l] = bm_code_of(tf, comp[l], false);
+    for (uint32_t l = 0; l < 256; l++)
+      if (!bm_code_of(tf, comp[l], false, &wtab[(tf << 8) + l]) && drawn[l]) return SS_ENOTSUP;
   std::vector<uint8_t> flg(nt);
   for (uint32_t t = 0; t < nt; t++) flg[t] = bm_list_flagged(s, s->h_df[t]) ? 1 : 0;
   uint32_t* d_wtab = nullptr;

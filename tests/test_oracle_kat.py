@@ -605,3 +605,60 @@ def test_geo_morton_and_distances():
     m0, m1 = O.geo_morton_range(base, 100.0, "km")
     lat_d, lon_d = 100.0 / (d2r * r_km), 100.0 / (d2r * r_km * np.cos(d2r * base[0]))
     assert m0 == int(O.morton_encode([base[0] - lat_d], [base[1] - lon_d])[0]) and m1 == int(O.morton_encode([base[0] + lat_d], [base[1] + lon_d])[0])
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_naive_exact_scorer_agrees_with_the_oracle(seed):
+    """naive.bm25_exact (f32 factors, float64 sum) against the oracle's exhaustive search (f32 sum): scores within 2e-6
+    relative, identical doc sets outside the tie band, exact counts -- unions and intersections, NOT terms, tombstones"""
+    rng = np.random.default_rng(seed)
+    n_docs = 20_000
+    lens = np.clip(np.round(np.exp(np.log(120) + 0.6 * rng.standard_normal(n_docs))), 8, 2000).astype(np.int64)
+    doclen = np.array([naive.int_to_byte4(int(x)) for x in lens], np.uint8)
+    offs, docs, tfs = [0], [], []
+    for df in (0.0005, 0.004, 0.03, 0.2, 0.55, 0.9):
+        n = int(df * n_docs)
+        d = np.sort(rng.choice(n_docs, n, replace=False)).astype(np.uint32)
+        t = rng.geometric(0.5, n).clip(1, 300).astype(np.uint16)
+        docs.append(d); tfs.append(t); offs.append(offs[-1] + n)
+    offs = np.asarray(offs, np.uint64)
+    docs, tfs = np.concatenate(docs), np.concatenate(tfs)
+    sh = O.Shard(n_docs, doclen, offs, docs, tfs)
+    lists = [(docs[offs[t]:offs[t + 1]], tfs[offs[t]:offs[t + 1]]) for t in range(len(offs) - 1)]
+    deleted = np.sort(rng.choice(n_docs, 300, replace=False))
+    for dele in (np.zeros(0, np.int64), deleted):
+        sh.set_deleted(dele)
+        for terms, nots in (([0], []), ([3], [5]), ([0, 1, 2], []), ([2, 3, 4], [1]), ([4, 5], []), ([1, 3, 4, 5], [0]), ([5], [])):
+            for op in (O.OP_OR, O.OP_AND):
+                ids, sc = naive.bm25_exact(n_docs, doclen, [lists[t] for t in terms], op == O.OP_AND,
+                                           not_docs=[lists[t][0] for t in nots], deleted=dele)
+                for k in (1, 10, 1000):
+                    od, os_, otot = sh.search_exhaustive(terms, op, k, not_terms=nots)
+                    assert otot == len(ids)
+                    rd, rs = naive.topk_exact(ids, sc, k)
+                    assert len(rd) == len(od)
+                    if not len(od):
+                        continue
+                    # the oracle's docs carry the exact scores of the same docs, within the f32 sum's rounding
+                    exact = dict(zip(ids.tolist(), sc.tolist()))
+                    got = np.array([exact[int(d)] for d in od])
+                    assert np.allclose(os_.astype(np.float64), got, rtol=2e-6, atol=0)
+                    assert np.allclose(os_.astype(np.float64), rs, rtol=2e-6, atol=0)
+                    band = abs(rs[-1]) * 2e-6
+                    assert {int(d) for d, s in zip(od, os_) if s > rs[-1] + band} == {int(d) for d, s in zip(rd, rs) if s > rs[-1] + band}
+
+
+def test_weight_code_range_in_the_naive_model():
+    """the figures of the weight code's range the kernels' range check (ss_common.h bm_w_codable) rests on: a doc some 2 10^4
+    times avgdl lands in the code's lowest binade, one some 4 10^4 times below it"""
+    lens = np.zeros(1_000_001, np.uint8)
+    lens[:1_000_000] = naive.int_to_byte4(20)
+    lens[-1] = naive.int_to_byte4(1_000_000)
+    comp = naive.component_cache(naive.avgdl(lens))
+    w = np.float32(2.2) / (np.float32(1) + comp[lens[-1]])
+    assert 5.0e-5 < w < 2.0 ** -14  # the giant doc's tf = 1 weight has no code
+    mostly_empty = np.zeros(300_000, np.uint8)
+    mostly_empty[::10_000] = naive.int_to_byte4(2000)  # 30 texts: a ratio of 10^4 -- inside the code
+    comp = naive.component_cache(naive.avgdl(mostly_empty))
+    w = np.float32(2.2) / (np.float32(1) + comp[mostly_empty[0]])
+    assert w >= 2.0 ** -14
