@@ -530,6 +530,9 @@ typedef struct ss_facet_filter {
   uint32_t values[8];
   uint32_t reserved;    /* numeric types: SS_FACET_LO_EXCLUSIVE | SS_FACET_HI_INCLUSIVE turn the ends around (0 = [lo, hi)) */
 } ss_facet_filter;
+/* Floats: -0.0 and +0.0 compare equal everywhere (filters, counts, pivots, sorts).  NaN -- a value or an end -- never passes a filter,
+ * and ss_bm25_facet_count counts a NaN value as "other": the reference panics there (partial_cmp(..).unwrap() in its F32 / F64 range
+ * buckets), so this is the library's own choice. */
 #define SS_FACET_IDS_EXTERN 0xFFFFFFFFu
 #define SS_FACET_HI_INCLUSIVE 1u
 #define SS_FACET_LO_EXCLUSIVE 2u
@@ -576,7 +579,9 @@ int ss_facet_values(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t f
  * bitmaps turn into scored lists and a compose kernel orders by (field 1, ..., field n, score desc, doc asc).  The host only
  * launches: one synchronisation per call.  n_sorts <= SS_MAX_SORT_FIELDS numeric or Point fields (n_sorts = 0: by score alone);
  * every list of every query needs a probe row (SS_ENOTSUP otherwise, as for ss_bm25_facet_kth); no phrase queries.
- * out_doc / out_score [n_queries][k], out_count [n_queries], out_total [n_queries] = all matches of the query. */
+ * out_doc / out_score [n_queries][k], out_count [n_queries], out_total [n_queries] = all matches of the query.
+ * -0.0 and +0.0 tie in a sort field (partial_cmp, min_heap.rs:807-830); a pivot at zero comes back as +0.0.  NaN in a sort field has
+ * no reference order and is out of scope. */
 #define SS_MAX_SORT_FIELDS 4
 typedef struct ss_result_sort {   /* search.rs ResultSort */
   uint32_t facet_offset;

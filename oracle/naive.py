@@ -118,3 +118,103 @@ def topk_exact(ids, scores, k):
     """top-k of bm25_exact's answer by (score desc, doc asc)"""
     order = np.lexsort((ids, -np.asarray(scores, np.float64)))[:k]
     return ids[order], np.asarray(scores, np.float64)[order]
+
+
+# ---- facets: filter (add_result.rs:341-482), counts (add_result.rs:484-640) and result sort (min_heap.rs:574-1050), read as
+# plain values -- Python ints for the integer types, Python floats for F32 / F64 -- with no key transform of any kind
+FACET_HI_INCLUSIVE, FACET_LO_EXCLUSIVE = 1, 2  # ss_facet_filter.reserved (seekstorm_hip.h)
+FACET_NP = {"u8": "<u1", "u16": "<u2", "u32": "<u4", "u64": "<u8", "i8": "<i1", "i16": "<i2", "i32": "<i4", "i64": "<i8",
+            "f32": "<f4", "f64": "<f8"}
+
+
+def facet_value(bits, ty):
+    """stored bits (zero-extended) -> the value they hold"""
+    dt = np.dtype(FACET_NP[ty])
+    x = np.array([int(bits) & ((1 << (8 * dt.itemsize)) - 1)], "<u%d" % dt.itemsize).view(dt)[0]
+    return float(x) if ty[0] == "f" else int(x)
+
+
+def facet_bits(value, ty):
+    """a value of the type -> its stored bits (zero-extended)"""
+    dt = np.dtype(FACET_NP[ty])
+    return int(np.array([value], dt).view("<u%d" % dt.itemsize)[0])
+
+
+def facet_pass(value, ty, lo, hi, flags=0):
+    """Rust's Range::contains, lo <= value < hi; FACET_LO_EXCLUSIVE / FACET_HI_INCLUSIVE turn the ends around.  NaN (a value or
+    an end) passes nothing; -0.0 == +0.0."""
+    if ty[0] == "f" and (np.isnan(value) or np.isnan(lo) or np.isnan(hi)):
+        return False
+    above = value > lo if flags & FACET_LO_EXCLUSIVE else value >= lo
+    below = value <= hi if flags & FACET_HI_INCLUSIVE else value < hi
+    return bool(above and below)
+
+
+def facet_bucket(value, bounds):
+    """the range a numeric facet value is counted in: index of the last lower bound <= value (binary_search_by_key, add_result.rs:484-640);
+    None ("other") below the first bound and for NaN.  bounds strictly ascending."""
+    assert all(a < b for a, b in zip(bounds, bounds[1:])), "bounds must be strictly ascending"
+    if isinstance(value, float) and np.isnan(value):
+        return None
+    b = None
+    for i, x in enumerate(bounds):
+        if x <= value:
+            b = i
+    return b
+
+
+def _sort_key(value, descending):
+    assert not (isinstance(value, float) and np.isnan(value)), "NaN has no order under a result sort"
+    if isinstance(value, float) and value == 0.0:
+        value = 0.0  # partial_cmp: -0.0 == +0.0
+    return -value if descending else value
+
+
+def sorted_order(docs, scores, columns, directions):
+    """indices of docs in result-sort order: the fields (columns[f][i] the value of doc i, directions[f] True = descending), then
+    score descending, then doc ascending -- the total order the header promises for deep pages"""
+    return sorted(range(len(docs)), key=lambda i: tuple(_sort_key(c[i], d) for c, d in zip(columns, directions))
+                  + (-float(scores[i]), int(docs[i])))
+
+
+def kth(values, k, descending):
+    """the pivot of a result sort: (k-th best value, number strictly better, number equal to it); k beyond the values: the worst.
+    Equality as the reference's partial_cmp (-0.0 == +0.0).  No values: (None, 0, 0)."""
+    if not values:
+        return None, 0, 0
+    keys = sorted(_sort_key(x, descending) for x in values)
+    p = keys[min(k, len(keys)) - 1]
+    v = next(x for x in values if _sort_key(x, descending) == p)
+    return v, sum(1 for x in keys if x < p), sum(1 for x in keys if x == p)
+
+
+def facet_palette(ty):
+    """every type's edge values: min / max and their neighbours, -1 / 0 / 1, the middle of an unsigned type, pairs that differ only
+    in the lowest or only in the top byte (each radix pass of the pivot select decides something); for floats +-inf, +-max, +-1,
+    the smallest normals and subnormals and both zeros.  NaN is left to facet_nan_palette."""
+    if ty[0] == "f":
+        fi = np.finfo(np.float32 if ty == "f32" else np.float64)
+        dt = fi.dtype.type
+        sub = float(np.nextafter(dt(0), dt(1)))
+        one_ulp = float(np.nextafter(dt(1), dt(2)))
+        return [-np.inf, -float(fi.max), -1.0, -float(fi.tiny), -sub, -0.0, 0.0, sub, float(fi.tiny), 1.0, one_ulp, float(fi.max), np.inf]
+    nb = 8 * np.dtype(FACET_NP[ty]).itemsize
+    if ty[0] == "u":
+        lo, hi = 0, (1 << nb) - 1
+        vals = [lo, lo + 1, hi - 1, hi, (1 << (nb - 1)) - 1, 1 << (nb - 1), (1 << (nb - 1)) + 1]
+    else:
+        lo, hi = -(1 << (nb - 1)), (1 << (nb - 1)) - 1
+        vals = [lo, lo + 1, -1, 0, 1, hi - 1, hi]
+    if nb > 8:
+        base = int.from_bytes(bytes([0x35]) + bytes([0xA5] * (nb // 8 - 1)), "big")  # positive in every width
+        vals += [base, base + 1, base + (1 << (nb - 8))]  # lowest byte; top byte
+        if ty[0] == "i":
+            vals += [-base, -base - 1, -base - (1 << (nb - 8))]
+        else:
+            vals += [base | (1 << (nb - 1)), (base | (1 << (nb - 1))) + 1]  # above 2^(b-1)
+    return sorted(set(vals))
+
+
+def facet_nan_palette(ty):
+    """NaN bit patterns of a float type: quiet, negative with a payload, signalling"""
+    return [0x7FC00000, 0xFFC00001, 0x7F800001] if ty == "f32" else [0x7FF8000000000000, 0xFFF8000000000001, 0x7FF0000000000001]

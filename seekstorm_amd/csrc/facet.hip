@@ -294,14 +294,19 @@ int ssi_facet_count(ss_shard* s, const unsigned long long* d_bits, uint64_t n_do
 // set: one histogram pass per byte of the field), after which "strictly better than the pivot" and "equal to the pivot" are
 // ordinary facet filters on ordinary searches (the hosts compose them: seekstorm_amd/search.py search_lexical_sorted).
 // key: the stored value mapped to an unsigned integer that orders like the value (sign bit flipped for integers, the usual
-// transform for floats), complemented for an ascending sort, so that a larger key is always the better one.
+// transform for floats), complemented for an ascending sort, so that a larger key is always the better one.  -0.0 is read as
+// +0.0 first: the reference compares floats with partial_cmp (min_heap.rs:807-830), which ties them, so they share one key.
 __host__ __device__ inline unsigned long long facet_order_key(unsigned long long v, uint32_t type, uint32_t bits, bool descending) {
   const unsigned long long mask = bits == 64 ? ~0ull : ((1ull << bits) - 1ull), top = 1ull << (bits - 1);
   unsigned long long k = v & mask;
   if (type >= SS_FACET_I8 && type <= SS_FACET_I64) k ^= top;
-  else if (type == SS_FACET_F32 || type == SS_FACET_F64) k = (k & top) ? (~k & mask) : (k | top);
+  else if (type == SS_FACET_F32 || type == SS_FACET_F64) {
+    if (k == top) k = 0;  // -0.0 -> +0.0
+    k = (k & top) ? (~k & mask) : (k | top);
+  }
   return descending ? k : (~k & mask);
 }
+// the inverse of facet_order_key: the key the two zeros share comes back as +0.0
 __host__ inline unsigned long long facet_order_value(unsigned long long k, uint32_t type, uint32_t bits, bool descending) {
   const unsigned long long mask = bits == 64 ? ~0ull : ((1ull << bits) - 1ull), top = 1ull << (bits - 1);
   if (!descending) k = ~k & mask;

@@ -527,13 +527,16 @@ int Shard::facet_count(const ss_bm25_query& query, uint32_t facet_offset, uint32
 // field among the matches (ss_bm25_facet_kth[_point]): "strictly better" holds fewer than k docs, which are fetched by a
 // search filtered to that range and ordered here by their values; the "equal" ones recurse on the remaining fields.
 namespace {
-uint64_t order_key(uint64_t bits, uint32_t type, bool descending) {  // larger = better under the sort
+uint64_t order_key(uint64_t bits, uint32_t type, bool descending) {  // larger = better under the sort; -0.0 and +0.0 share a key
   static const uint32_t width[] = {8, 16, 32, 64, 8, 16, 32, 64, 32, 64};
   const uint32_t nb = width[type];
   const uint64_t mask = nb == 64 ? ~0ull : ((1ull << nb) - 1ull), top = 1ull << (nb - 1);
   uint64_t k = bits & mask;
   if (type >= SS_FACET_I8 && type <= SS_FACET_I64) k ^= top;
-  else if (type == SS_FACET_F32 || type == SS_FACET_F64) k = (k & top) ? (~k & mask) : (k | top);
+  else if (type == SS_FACET_F32 || type == SS_FACET_F64) {
+    if (k == top) k = 0;  // -0.0 -> +0.0 (partial_cmp ties them, min_heap.rs:807-830)
+    k = (k & top) ? (~k & mask) : (k | top);
+  }
   return descending ? k : (~k & mask);
 }
 uint64_t filter_bits(uint64_t v, uint32_t type) {  // stored bits -> ss_facet_filter's form (signed integers sign-extended)

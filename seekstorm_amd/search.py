@@ -755,13 +755,16 @@ class Shard:
 
     @staticmethod
     def _facet_order_key(bits, ty, descending):
-        """stored bits -> an integer that orders like the value (larger = better under the sort)"""
+        """stored bits -> an integer that orders like the value (larger = better under the sort); -0.0 and +0.0 share a key
+        (partial_cmp ties them, min_heap.rs:807-830)"""
         nb = Shard._FACET_BITS[ty]
         mask, top = (1 << nb) - 1, 1 << (nb - 1)
         k = int(bits) & mask
         if ty[0] == "i":
             k ^= top
         elif ty[0] == "f":
+            if k == top:
+                k = 0  # -0.0 -> +0.0
             k = (~k & mask) if (k & top) else (k | top)
         return k if descending else (~k & mask)
 

@@ -572,6 +572,37 @@ def test_cpp_shard_result_sort_point_facets_and_counts(H):
 
 
 @pytest.mark.gpu
+def test_cpp_shard_result_sort_at_the_type_edges(H):
+    """The C++ mirror's result sort (order_key: the batched call up to four fields, its own composition beyond) on the world of
+    tests/test_gpu_facet_edges.py -- i8 / i64 / u32 / u64 above 2^63 / f32 / f64 with +-0, +-inf and subnormals, large tie groups --
+    against oracle/naive.py's sort order of the oracle's match set"""
+    from oracle import oracle as O
+    import seekstorm_amd as S
+    import test_gpu_facet_edges as E
+    W = E.facet_world(S, O)
+    W.sh.close()
+    ix = H.ssh_index_create(1, None)
+    try:
+        assert H.ssh_upload_lexical(ix, 0, E.N_DOCS, P(W.dl, u8p), len(W.offs) - 1, P(W.offs, u64p), P(W.docs, u32p), P(W.tfs, u16p)) == 0
+        assert H.ssh_upload_facets(ix, 0, E.N_DOCS + E.N_EXTRA, E.REC.itemsize, W.rec.ctypes.data) == 0
+        gone = np.asarray(W.gone, np.uint64)
+        assert H.ssh_set_deleted(ix, 0, P(gone, u64p), len(gone)) == 0
+        nonneg = E._filter(S, W, "f32", -0.0, np.inf, E.HI)
+        for qi in (0, 1, 2, 5):
+            terms, qt, _, neg = W.queries[qi]
+            md, ms = W.matches[qi]
+            for srt in (E.SORTS[0], E.SORTS[1], E.SORTS[3], E.SORTS[7], E.SORTS[8], E.SORTS[10], E.SORT5):
+                for f in (None, nonneg):
+                    ref = E._reference_order(W, md, ms, srt, None if f is None else f[1])
+                    for k in E._tie_ks(W, ref, srt):
+                        cd, cs, ctot = _cpp_lexical_ex(H, ix, terms, int(qt), 0, k, 2, facet_filter=None if f is None else [f[0]],
+                                                       not_terms=neg, sorts=E._spec(W, srt))
+                        E.check_sorted(W, cd.astype(np.int64), cs, ctot, ref, srt, k, ("cpp", terms, srt, k, f is not None))
+    finally:
+        H.ssh_index_destroy(ix)
+
+
+@pytest.mark.gpu
 def test_cpp_shard_union_under_a_field_filter(H):
     """The C++ mirror's search_lexical_shard for a union of several terms under a field filter (the reference's sub-query
     decomposition, union.rs:1168-1479) against the Python mirror, which

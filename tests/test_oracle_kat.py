@@ -662,3 +662,99 @@ def test_weight_code_range_in_the_naive_model():
     comp = naive.component_cache(naive.avgdl(mostly_empty))
     w = np.float32(2.2) / (np.float32(1) + comp[mostly_empty[0]])
     assert w >= 2.0 ** -14
+
+
+def test_facet_reference_kats():
+    """oracle/naive.py's facet reference (filter, bucket, sort order, pivot) on hand-written cases at the types' edges"""
+    HI, LO = naive.FACET_HI_INCLUSIVE, naive.FACET_LO_EXCLUSIVE
+    i64_min, i64_max = -(1 << 63), (1 << 63) - 1
+    # i64 min / max: the full range [min, max) excludes max; HI_INCLUSIVE takes it in
+    assert naive.facet_pass(i64_min, "i64", i64_min, i64_max)
+    assert not naive.facet_pass(i64_max, "i64", i64_min, i64_max)
+    assert naive.facet_pass(i64_max, "i64", i64_min, i64_max, HI)
+    assert not naive.facet_pass(i64_min, "i64", i64_min, i64_max, LO)
+    # a u64 above 2^63 compares as unsigned
+    big = (1 << 63) + 5
+    assert naive.facet_pass(big, "u64", 1 << 63, (1 << 64) - 1) and not naive.facet_pass(big, "u64", 0, 1 << 63)
+    assert naive.facet_value(naive.facet_bits(big, "u64"), "u64") == big
+    assert naive.facet_value(0xFF, "i8") == -1 and naive.facet_bits(-128, "i8") == 0x80
+    # a value on either end under all four flag combinations
+    for flags, at_lo, at_hi in ((0, True, False), (HI, True, True), (LO, False, False), (LO | HI, False, True)):
+        assert naive.facet_pass(-3, "i16", -3, 7, flags) == at_lo
+        assert naive.facet_pass(7, "i16", -3, 7, flags) == at_hi
+        assert naive.facet_pass(5, "i16", -3, 7, flags)
+        assert naive.facet_pass(4, "u8", 4, 4, flags) == (flags == HI)  # lo == hi: only [lo, hi] holds the value
+        assert not naive.facet_pass(4, "u8", 5, 3, flags)  # lo > hi: empty
+    # +-0 in a range: -0.0 == +0.0 at either end
+    assert naive.facet_pass(-0.0, "f32", 0.0, 1.0) and naive.facet_pass(0.0, "f64", -0.0, 1.0)
+    assert not naive.facet_pass(-0.0, "f64", -1.0, 0.0) and naive.facet_pass(-0.0, "f64", -1.0, 0.0, HI)
+    assert not naive.facet_pass(0.0, "f32", -0.0, 1.0, LO)
+    # NaN passes nothing, and a NaN end passes nothing
+    nan = float("nan")
+    for flags in (0, HI, LO, LO | HI):
+        assert not naive.facet_pass(nan, "f32", -np.inf, np.inf, flags)
+        assert not naive.facet_pass(1.0, "f64", nan, 2.0, flags) and not naive.facet_pass(1.0, "f64", 0.0, nan, flags)
+    assert naive.facet_pass(np.inf, "f64", 0.0, np.inf, HI) and not naive.facet_pass(np.inf, "f64", 0.0, np.inf)
+    # buckets: the last bound <= value; below the first one (and NaN) is "other"
+    assert naive.facet_bucket(i64_min, [i64_min, 0]) == 0 and naive.facet_bucket(-1, [i64_min, 0]) == 0
+    assert naive.facet_bucket(0, [i64_min, 0]) == 1 and naive.facet_bucket(i64_max, [i64_min, 0, i64_max]) == 2
+    assert naive.facet_bucket(4, [5, 9]) is None and naive.facet_bucket(5, [5, 9]) == 0
+    assert naive.facet_bucket(-0.0, [-1.0, 0.0, 1.0]) == 1 and naive.facet_bucket(0.0, [-0.0, 1.0]) == 0
+    assert naive.facet_bucket(nan, [-np.inf, 0.0]) is None
+    with pytest.raises(AssertionError):
+        naive.facet_bucket(1, [2, 2])
+    # sort order: fields (+-0 tie), score descending, doc ascending
+    docs, scores = [7, 3, 9, 4, 5], [1.0, 2.0, 2.0, 3.0, 2.0]
+    col = [-0.0, 0.0, -0.0, 1.0, 0.0]
+    assert naive.sorted_order(docs, scores, [col], [True]) == [3, 1, 4, 2, 0]
+    assert naive.sorted_order(docs, scores, [col], [False]) == [1, 4, 2, 0, 3]
+    assert naive.sorted_order(docs, scores, [[i64_max, i64_min, i64_max, 0, 0]], [False]) == [1, 3, 4, 2, 0]
+    assert naive.sorted_order(docs, scores, [[1, 1, 0, 0, 1], col], [True, False]) == [1, 4, 0, 2, 3]
+    # pivot: (k-th best, strictly better, equal) with +-0 one value
+    vals = [-0.0, 0.0, 1.0, -1.0, 0.0, -np.inf]
+    assert naive.kth(vals, 1, True) == (1.0, 0, 1)
+    v, nb, ne = naive.kth(vals, 2, True)
+    assert v == 0.0 and (nb, ne) == (1, 3)
+    v, nb, ne = naive.kth(vals, 4, True)
+    assert v == 0.0 and (nb, ne) == (1, 3)
+    assert naive.kth(vals, 5, True) == (-1.0, 4, 1) and naive.kth(vals, 99, True) == (-np.inf, 5, 1)
+    v, nb, ne = naive.kth(vals, 3, False)
+    assert v == 0.0 and (nb, ne) == (2, 3)
+    assert naive.kth([big, 1, big], 2, True) == (big, 0, 2) and naive.kth([], 1, True) == (None, 0, 0)
+
+
+FACET_TYPES_NUMERIC = ["u8", "u16", "u32", "u64", "i8", "i16", "i32", "i64", "f32", "f64"]
+
+
+def test_facet_order_key_filter_bits_and_type_range_at_the_edges():
+    """Shard._facet_order_key (the composed route's and Index.search's sort key) orders every pair of a type's edge values like the
+    values themselves, in both directions, with -0.0 and +0.0 one key; _facet_filter_bits / _facet_type_range give the filter's
+    form of every edge value, so that facet_pass in that form equals the reference."""
+    from seekstorm_amd.search import Shard
+    for ty in FACET_TYPES_NUMERIC:
+        pal = naive.facet_palette(ty)
+        bits = [naive.facet_bits(x, ty) for x in pal]
+        for desc in (True, False):
+            keys = [Shard._facet_order_key(b, ty, desc) for b in bits]
+            nb = 8 * np.dtype(naive.FACET_NP[ty]).itemsize
+            assert all(0 <= k < (1 << nb) for k in keys)
+            for a, ka in zip(pal, keys):
+                for b, kb in zip(pal, keys):
+                    want = (a > b) - (a < b)
+                    assert ((ka > kb) - (ka < kb)) == (want if desc else -want), (ty, desc, a, b)
+            if ty[0] == "f":
+                assert Shard._facet_order_key(naive.facet_bits(-0.0, ty), ty, desc) == Shard._facet_order_key(0, ty, desc)
+        lo, hi = Shard._facet_type_range(ty)
+        assert naive.facet_value(lo, ty) == pal[0] and naive.facet_value(hi, ty) == pal[-1]
+        for x, b in zip(pal, bits):
+            fb = Shard._facet_filter_bits(b, ty)
+            assert 0 <= fb < (1 << 64)
+            if ty[0] == "i":  # sign-extended to 64 bits: the i64 reading of the filter's form is the value
+                assert naive.facet_value(fb, "i64") == x
+            else:
+                assert fb == b
+            # the composed route's "better" and "equal" filters around a pivot at x, in the filter's form
+            for y in pal:
+                assert naive.facet_pass(y, ty, x, x, naive.FACET_HI_INCLUSIVE) == (y == x)
+                assert naive.facet_pass(y, ty, x, pal[-1], naive.FACET_LO_EXCLUSIVE | naive.FACET_HI_INCLUSIVE) == (y > x)
+                assert naive.facet_pass(y, ty, pal[0], x) == (y < x)
