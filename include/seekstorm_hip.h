@@ -616,7 +616,14 @@ int ss_vec_upload(ss_shard* s, uint64_t n_rows, uint32_t dim, const float* rows,
  * search is then -similarity_threshold (vector.rs:398), scores come back as -distance^2 (vector_score = -score, vector.rs:
  * 1495).  Returned f32 scores are recomputed in the reference's own summation order (euclidean_f32_avx2 when dim % 8 == 0).
  * Must be set BEFORE the image is uploaded / generated (the f32 image is laid out with two extra columns); SS_ESTATE
- * otherwise.  Applies to AnnMode::All and the ANN modes (medoids are scored with the same similarity). */
+ * otherwise.  Applies to AnnMode::All and the ANN modes (medoids are scored with the same similarity).
+ * Exactness of the f32 answers (u = 2^-24, gamma(n) = n u / (1 - n u)):
+ *   - Euclidean: the returned SET is the exact top k up to the reference's own rounding (gamma(dim + 2) d^2 per record), for data
+ *     anywhere, far from the origin included: the scan keeps every candidate within its error bound of the k-th, all of them are
+ *     rescored in the reference's order and the k best kept; a batch whose margin overflows the candidate slots is answered by an
+ *     exact pass in the reference's order.
+ *   - Dot / cosine: scores come from the matrix cores' f32 order, not dot_f32_avx2's: each within gamma(dim + 1) sum |x_i q_i| of
+ *     the exact dot product, and so of the reference's. */
 enum { SS_SIM_DOT = 0, SS_SIM_EUCLIDEAN = 1 };
 int ss_vec_set_similarity(ss_shard* s, int similarity);
 /* i8 records under Euclidean + ScalarQuantizationI8: VectorHeader.norm of every record (vector.bin uploads with

@@ -218,3 +218,106 @@ def facet_palette(ty):
 def facet_nan_palette(ty):
     """NaN bit patterns of a float type: quiet, negative with a payload, signalling"""
     return [0x7FC00000, 0xFFC00001, 0x7F800001] if ty == "f32" else [0x7FF8000000000000, 0xFFF8000000000001, 0x7FF0000000000001]
+
+
+# ---- dense vectors: exact values (float64 from the f32 inputs) and the rounding band of any f32 summation order
+U_F32 = 2.0 ** -24  # unit roundoff of f32
+
+
+def gamma(n):
+    """gamma(n) = n u / (1 - n u), u = 2^-24: the relative error bound of n rounded f32 operations in a row (Higham, Accuracy and
+    Stability of Numerical Algorithms, 3.1) -- any summation order, fma included"""
+    return n * U_F32 / (1.0 - n * U_F32)
+
+
+def vec_exact_dot(rows, q):
+    """x . q of every row in float64: the products of two f32 values are exact, the f64 sum is ~2^-29 of the f32 band below"""
+    r = np.asarray(rows, np.float32).astype(np.float64).reshape(-1, np.asarray(q).size)
+    return r @ np.asarray(q, np.float32).astype(np.float64).ravel()
+
+
+def vec_exact_l2(rows, q):
+    """|q - x|^2 of every row in float64 (the difference of two f32 values of like magnitude is exact in f64)"""
+    r = np.asarray(rows, np.float32).astype(np.float64).reshape(-1, np.asarray(q).size)
+    d = np.asarray(q, np.float32).astype(np.float64).ravel()[None, :] - r
+    return np.einsum("ij,ij->i", d, d)
+
+
+def bound_dot(rows, q):
+    """how far an f32 dot product of any order may fall from vec_exact_dot: gamma(dim + 1) sum |x_i q_i|"""
+    r = np.abs(np.asarray(rows, np.float32).astype(np.float64).reshape(-1, np.asarray(q).size))
+    return gamma(r.shape[1] + 1) * (r @ np.abs(np.asarray(q, np.float32).astype(np.float64).ravel()))
+
+
+def bound_l2(rows, q, d2=None):
+    """how far the reference's squared distance (sub, mul, add each rounded: euclidean_f32[_avx2]) may fall from vec_exact_l2:
+    gamma(dim + 2) d^2 -- relative to the distance itself, since every term is >= 0"""
+    dim = np.asarray(q).size
+    return gamma(dim + 2) * (vec_exact_l2(rows, q) if d2 is None else np.asarray(d2, np.float64))
+
+
+def check_vector_topk(doc, score, cnt, exact, bound, k, row_doc=None, tie_order=True):
+    """A vector top-k (doc ids, f32 scores, count) against the exact similarity of every row (-inf: the row may not be returned --
+    tombstoned, filtered, below the threshold, in a cluster the mode skips) and each row's rounding band `bound`.  With row_doc
+    (several records per doc) a doc's exact value is the best of its rows', its band the widest.  Asserts:
+      1. every returned score is within its doc's band of the exact value;
+      2. the scores are non-increasing;
+      3. every doc whose exact value beats the exact k-th by more than band(doc) + band(k-th) is returned;
+      4. no returned doc falls below the exact k-th by more than that band;
+      5. among equal scores the docs come in ascending order (tie_order; the reference's own lists keep its TopK slots' order,
+         vector.rs:1472);
+      6. the count is min(k, live docs), every doc at most once."""
+    exact = np.asarray(exact, np.float64).ravel()
+    bound = np.broadcast_to(np.asarray(bound, np.float64), exact.shape)
+    if row_doc is not None:
+        ids, inv = np.unique(np.asarray(row_doc, np.int64), return_inverse=True)
+        ex = np.full(len(ids), -np.inf)
+        np.maximum.at(ex, inv, exact)
+        bd = np.zeros(len(ids))
+        np.maximum.at(bd, inv, np.where(np.isfinite(exact), bound, 0.0))
+    else:
+        ids, ex, bd = np.arange(len(exact), dtype=np.int64), exact, np.asarray(bound)
+    live = np.isfinite(ex)
+    n = int(cnt)
+    want = min(int(k), int(live.sum()))
+    assert n == want, "count %d, want min(k=%d, live=%d) = %d" % (n, k, int(live.sum()), want)
+    if n == 0:
+        return
+    d = np.asarray(doc[:n], np.int64)
+    s = np.asarray(score[:n], np.float32).astype(np.float64)
+    assert len(np.unique(d)) == n, "a doc returned twice"
+    pos = np.searchsorted(ids, d)
+    assert np.all(pos < len(ids)) and np.all(ids[np.minimum(pos, len(ids) - 1)] == d), "unknown doc returned"
+    for j in np.nonzero(~live[pos])[0]:
+        raise AssertionError("position %d: doc %d may not be returned" % (j, d[j]))
+    tiny = 1e-300  # (bands are 0 for exact scores)
+    err = np.abs(s - ex[pos])
+    for j in np.nonzero(err > bd[pos] + tiny)[0][:3]:
+        raise AssertionError("position %d: doc %d scored %.9g, exact %.17g, off by %.3g > band %.3g" % (j, d[j], s[j], ex[pos[j]], err[j], bd[pos[j]]))
+    for j in np.nonzero(np.diff(s) > 0)[0][:3]:
+        raise AssertionError("scores rise at position %d: %.9g -> %.9g" % (j, s[j], s[j + 1]))
+    for j in np.nonzero((np.diff(s) == 0) & (np.diff(d) < 0) & tie_order)[0][:3]:
+        raise AssertionError("equal scores %.9g at positions %d, %d: docs %d before %d" % (s[j], j, j + 1, d[j], d[j + 1]))
+    li = np.nonzero(live)[0]
+    o = li[np.lexsort((ids[li], -ex[li]))]
+    kth, kb = ex[o[want - 1]], bd[o[want - 1]]
+    got = set(d.tolist())
+    must = np.nonzero(live & (ex > kth + bd + kb))[0]
+    miss = [int(i) for i in must if int(ids[i]) not in got]
+    if miss:
+        i = miss[0]
+        worst = int(np.argmin(ex[pos]))
+        raise AssertionError("%d docs missing: doc %d with exact %.17g (k-th %.17g, band %.3g) not returned; worst returned doc %d at %.17g"
+                             % (len(miss), ids[i], ex[i], kth, bd[i] + kb, d[worst], ex[pos[worst]]))
+    low = np.nonzero(ex[pos] < kth - bd[pos] - kb)[0]
+    for j in low[:1]:
+        raise AssertionError("%d returned docs beyond the band: doc %d at exact %.17g, k-th %.17g" % (len(low), d[j], ex[pos[j]], kth))
+
+
+def vec_offcentre(seed, n, dim, c, sigma):
+    """f32 rows c * u + sigma * N(0, 1) around one centre of norm c (u: a unit vector of positive components, the same for every
+    seed of a dim): all-positive embeddings, a shared mean component -- the data on which 2 q.x - |x|^2 - |q|^2 cancels"""
+    u = np.random.default_rng(dim).random(dim) + 0.5
+    u /= np.linalg.norm(u)
+    rng = np.random.default_rng(seed)
+    return (c * u[None, :] + sigma * rng.standard_normal((n, dim))).astype(np.float32)

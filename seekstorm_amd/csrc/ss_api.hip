@@ -185,10 +185,10 @@ static void free_vec(ss_shard* s) {
     for (void* p : wp) if (p) (void)hipFree(p);
   }
   s->vec_ws.clear();
-  void* ptrs[] = {s->d_X, s->d_X8, s->d_row_scale, s->d_row_doc, s->d_Qf, s->d_vstate, s->d_cand, s->d_row_field, s->d_row_norm, s->d_row_sq, s->d_qaux};
+  void* ptrs[] = {s->d_X, s->d_X8, s->d_row_scale, s->d_row_doc, s->d_Qf, s->d_vstate, s->d_cand, s->d_row_field, s->d_row_norm, s->d_row_sq, s->d_qaux, s->d_vec_r2};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   s->d_X = nullptr; s->d_X8 = nullptr; s->d_row_scale = nullptr; s->d_row_doc = nullptr; s->d_Qf = nullptr;
-  s->d_row_norm = nullptr; s->d_row_sq = nullptr; s->d_qaux = nullptr;
+  s->d_row_norm = nullptr; s->d_row_sq = nullptr; s->d_qaux = nullptr; s->d_vec_r2 = nullptr;
   s->d_vstate = nullptr; s->d_cand = nullptr; s->d_row_field = nullptr;
   s->n_rows = s->n_rows_pad = 0; s->dim = s->dim_pad = s->dim_pad8 = 0; s->vec_multi_record = false; s->vec_rows_cap = 0;
   ssi_vec_free_clusters(s);
@@ -3038,8 +3038,9 @@ static int vec_search_deep_locked(ss_shard* s, uint32_t nq, const void* queries,
     for (uint32_t i = 0; i < nb; i++) {
       for (uint32_t r = got[i]; r < k; r++) { out_doc[(size_t)(g0 + i) * k + r] = SS_NO_DOC; out_score[(size_t)(g0 + i) * k + r] = 0.f; }
       out_count[g0 + i] = got[i];
-      // f32 Euclidean: a pass is CUT by the scan's MFMA form of the distance and ordered by the rescored values (the reference's summation
-      // order) -- across a seam the last of one pass and the first of the next may stand the other way round by a rounding: one stable sort
+      // f32 Euclidean: a pass is the exact top SS_MAX_K of what is left up to the reference's own rounding (the cut keeps a margin, see
+      // vec_euclid_margin_kernel), ordered by the rescored values: the seams stand in order but for records tied within that rounding,
+      // which one stable sort of the assembled page puts right
       if (s->vec_similarity == SS_SIM_EUCLIDEAN && elem == sizeof(float) && got[i] > SS_MAX_K) {
         uint32_t* dd = out_doc + (size_t)(g0 + i) * k;
         float* ss = out_score + (size_t)(g0 + i) * k;

@@ -254,6 +254,7 @@ struct ss_shard {
   float* d_row_scale = nullptr;  // i8 image: per-record scale (VectorHeader.scale) for dot_i8_quantized, null = raw integer dot
   float* d_row_norm = nullptr;   // i8 image, Euclidean + ScalarQuantizationI8: per-record norm (VectorHeader.norm), euclidean_i8_quantized
   int32_t* d_row_sq = nullptr;   // i8 image, Euclidean without scales: sum of squares of every record (euclidean_i8 as dot products)
+  float* d_vec_r2 = nullptr;     // f32 Euclidean image: the largest |x|^2 of its rows (ssi_vec_augment), which bounds the scan's error
   float* d_qaux = nullptr;       // [2][64] per-query side values of the batch in flight (i8 Euclidean: norm | sum of squares)
   int vec_similarity = SS_SIM_DOT;  // ss_vec_set_similarity: Dot / Cosine (dot product) or Euclidean (minus the squared distance)
   uint32_t dim_pad8 = 0;         // row stride of the i8 image in bytes (multiple of 128)

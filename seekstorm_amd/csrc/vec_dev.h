@@ -14,6 +14,7 @@ struct VState {
   uint32_t ovf;
   uint32_t pad[63];
   unsigned long long total[64];
+  float margin[64];  // f32 Euclidean: the width of the cut below the k-th scan value (vec_euclid_margin_kernel)
 };
 
 __device__ __forceinline__ uint32_t f2ord(float f) {

@@ -51,60 +51,139 @@ __global__ void vec_qprep_kernel(const float* __restrict__ Q, uint32_t nq, uint3
   }
 }
 
-// f32 Euclidean image: column dim = |x|^2, column dim + 1 = 1 (one thread per row)
-__global__ void vec_augment_kernel(float* __restrict__ X, unsigned long long r0, unsigned long long n_rows, uint32_t dim, uint32_t dim_pad) {
+// f32 Euclidean image: column dim = |x|^2, column dim + 1 = 1 (one thread per row); r2 = the largest |x|^2 so far (a
+// non-negative float orders like its bits: one atomicMax per wave)
+__global__ void vec_augment_kernel(float* __restrict__ X, unsigned long long r0, unsigned long long n_rows, uint32_t dim, uint32_t dim_pad,
+                                   float* __restrict__ r2) {
   const unsigned long long r = r0 + (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_rows) return;
-  float* row = X + r * dim_pad;
   float ss = 0.0f;
-  for (uint32_t i = 0; i < dim; i++) ss = fmaf(row[i], row[i], ss);
-  row[dim] = ss;
-  row[dim + 1] = 1.0f;
+  if (r < n_rows) {
+    float* row = X + r * dim_pad;
+    for (uint32_t i = 0; i < dim; i++) ss = fmaf(row[i], row[i], ss);
+    row[dim] = ss;
+    row[dim + 1] = 1.0f;
+  }
+  float m = ss;
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63u) == 0 && m > 0.0f) atomicMax((unsigned int*)r2, __float_as_uint(m));
 }
 int ssi_vec_augment(ss_shard* s, hipStream_t st, uint64_t r0) {
   if (!s->d_X || s->dim_pad < s->dim + 2) return SS_ESTATE;
+  if (!s->d_vec_r2) {
+    SS_HIP(hipMalloc(&s->d_vec_r2, sizeof(float)));
+    r0 = 0;  // (the rows already there count too)
+  }
+  if (r0 == 0) SS_HIP(hipMemsetAsync(s->d_vec_r2, 0, sizeof(float), st));
   if (r0 >= s->n_rows) return SS_OK;
-  vec_augment_kernel<<<(unsigned)((s->n_rows - r0 + 255) / 256), 256, 0, st>>>(s->d_X, (unsigned long long)r0, (unsigned long long)s->n_rows, s->dim, s->dim_pad);
+  vec_augment_kernel<<<(unsigned)((s->n_rows - r0 + 255) / 256), 256, 0, st>>>(s->d_X, (unsigned long long)r0, (unsigned long long)s->n_rows, s->dim, s->dim_pad,
+                                                                             s->d_vec_r2);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }
 
-// The kept candidates of a Euclidean f32 search get the score the reference computes: -euclidean_f32_avx2 (eight lanes of
-// sub / mul / add over dim / 8 steps, lanes summed 0..7, vector_similarity.rs:938-966) when dim % 8 == 0, else
-// -euclidean_f32 (sequential, 912-918) -- every operation rounded on its own, no fma.  One thread per candidate.
+// The squared distance as the reference computes it: euclidean_f32_avx2 (eight lanes of sub / mul / add over dim / 8 steps,
+// lanes summed 0..7, vector_similarity.rs:938-966) when dim % 8 == 0, else euclidean_f32 (sequential, 912-918) -- every
+// operation rounded on its own, no fma.
+__device__ __forceinline__ float vs_euclid_ref(const float* __restrict__ qv, const float* __restrict__ x, uint32_t dim) {
+  float d2;
+  if ((dim & 7u) == 0) {
+    float l[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (uint32_t c = 0; c < dim; c += 8)
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const float d = ss_fsub(qv[c + j], x[c + j]);
+        l[j] = ss_fadd(l[j], ss_fmul(d, d));
+      }
+    d2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; j++) d2 = ss_fadd(d2, l[j]);
+  } else {
+    d2 = 0.f;
+    for (uint32_t c = 0; c < dim; c++) {
+      const float d = ss_fsub(qv[c], x[c]);
+      d2 = ss_fadd(d2, ss_fmul(d, d));
+    }
+  }
+  return d2;
+}
+
+// The f32 Euclidean CUT.  The scan's value 2 q.x - |x|^2 - |q|^2 is off from -|q - x|^2 by up to
+//   E(q) = gamma(2 dim + 4) (|q| + R)^2,   gamma(n) = n u / (1 - n u), u = 2^-24, R = the image's largest row norm
+// (the f32 dot of dim + 2 terms: gamma(dim + 2) (2 |q| |x| + |x|^2 + |q|^2); the two f32 sums of squares: gamma(dim) each) --
+// an error that grows with the distance from the ORIGIN, not between the neighbours: far larger than their gaps when the data
+// sits off the origin.  So the refine keeps every candidate within 2 E(q) of the k-th scan value (a row of the exact top k can
+// trail the k-th scan value by at most 2 E: some row ahead of it by scan value is not in the exact top k, so its exact value is
+// no better), the rescoring below gives all of them the reference's value, and a last select keeps the k best of those.
+__global__ void vec_euclid_margin_kernel(const float* __restrict__ Q, uint32_t nq, uint32_t dim, const float* __restrict__ r2, VState* __restrict__ st) {
+  const uint32_t q = threadIdx.x;
+  if (q >= 64) return;
+  float m = 0.f;
+  if (q < nq) {
+    double qq = 0.0;
+    for (uint32_t i = 0; i < dim; i++) qq += (double)Q[(size_t)q * dim + i] * (double)Q[(size_t)q * dim + i];
+    const double n = 2.0 * dim + 4.0, u = 5.9604644775390625e-8, g = n * u / (1.0 - n * u);
+    const double r = sqrt(qq) + sqrt((double)*r2);
+    m = (float)(2.0 * g * r * r * (1.0 + 1e-6));  // (rounded up: the margin is 2 E)
+  }
+  st->margin[q] = m;
+}
+
+// The kept candidates of a Euclidean f32 search -- all of them: see the cut above -- get the score the reference computes,
+// -vs_euclid_ref.  One thread per candidate.  Afterwards kept = 0: vec_refine_kernel<VR_EXACT> selects the k best again.
 // thr: the search's raw threshold is applied HERE, on the exact score (`score < threshold -> reject`, vector.rs:423): the scan
-// runs without it, because its expanded form 2 q.x - |x|^2 - |q|^2 may land on the other side of a threshold the exact
-// distance meets.  A rejected candidate's key becomes 0 (vec_final_kernel drops it).
-__global__ void vec_rescore_euclid_kernel(const VState* __restrict__ st, unsigned long long* __restrict__ cand, const float* __restrict__ X,
-                                          uint32_t dim, uint32_t dim_pad, const float* __restrict__ Q, uint32_t nq, uint32_t k, float thr) {
+// runs without it, because its expanded form may land on the other side of a threshold the exact distance meets.  A rejected
+// candidate's key becomes 0 (the refine and vec_final_kernel drop it).
+__global__ void vec_rescore_euclid_kernel(VState* __restrict__ st, unsigned long long* __restrict__ cand, const float* __restrict__ X,
+                                          uint32_t dim, uint32_t dim_pad, const float* __restrict__ Q, uint32_t nq, float thr) {
   const uint32_t q = blockIdx.x;
   if (q >= nq) return;
-  const uint32_t n = st->cnt[q * VS_CNT_STRIDE] < k ? st->cnt[q * VS_CNT_STRIDE] : k;
+  const uint32_t n = st->cnt[q * VS_CNT_STRIDE] < VS_CAP ? st->cnt[q * VS_CNT_STRIDE] : VS_CAP;
   const float* qv = Q + (size_t)q * dim;
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     const unsigned long long key = cand[(size_t)q * VS_CAP + i];
+    if (!key) continue;
     const uint32_t row = 0xFFFFFFFFu - (uint32_t)key;
-    const float* x = X + (size_t)row * dim_pad;
-    float d2;
-    if ((dim & 7u) == 0) {
-      float l[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (uint32_t c = 0; c < dim; c += 8)
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-          const float d = ss_fsub(qv[c + j], x[c + j]);
-          l[j] = ss_fadd(l[j], ss_fmul(d, d));
-        }
-      d2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; j++) d2 = ss_fadd(d2, l[j]);
-    } else {
-      d2 = 0.f;
-      for (uint32_t c = 0; c < dim; c++) {
-        const float d = ss_fsub(qv[c], x[c]);
-        d2 = ss_fadd(d2, ss_fmul(d, d));
+    const float d2 = vs_euclid_ref(qv, X + (size_t)row * dim_pad, dim);
+    cand[(size_t)q * VS_CAP + i] = (-d2 < thr) ? 0ull : mk_key(-d2, row);
+  }
+  if (threadIdx.x == 0) st->kept[q] = 0;
+}
+
+// The exact pass of an f32 Euclidean batch (safe mode: the batch overflowed its candidate slots -- an adversarial row order, or
+// more rows inside the cut's margin than the slots hold): every (row, query) pair scored on the VALU in the reference's own
+// order, appended when it beats tau, the refine between chunks as for the scan.  Workgroup = a tile x two queries (blockIdx.y):
+// thread = one row, the two halves of the workgroup take one query each (a wave's query is uniform).
+static_assert(256 % VS_TR == 0, "vec_exact_euclid_kernel: whole tiles per workgroup");
+template <bool ANN>
+__global__ void __launch_bounds__(256) vec_exact_euclid_kernel(const float* __restrict__ X, uint32_t dim, uint32_t dim_pad, unsigned long long n_rows,
+                                                                const float* __restrict__ Q, uint32_t nq, uint32_t tile0, uint32_t ntiles,
+                                                                VState* __restrict__ st, unsigned long long* __restrict__ cand, VAnn ann) {
+  if (st->ovf) return;
+  if (ANN && ann.tiles) {
+    const uint32_t na = *ann.n_tiles;
+    ntiles = na > tile0 ? min(ntiles, na - tile0) : 0u;
+  }
+  for (uint32_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const unsigned long long tix = (ANN && ann.tiles) ? (unsigned long long)ann.tiles[tile0 + t] : (unsigned long long)(tile0 + t);
+    const unsigned long long row = tix * VS_TR + (threadIdx.x & (VS_TR - 1));
+    if (row >= n_rows) continue;
+    const uint32_t q = blockIdx.y * (256 / VS_TR) + threadIdx.x / VS_TR;
+    if (q >= nq) continue;
+    if (ANN) {
+      if (ann.sel) {
+        const uint32_t c = ann.row_cluster[row];
+        if (!((ann.sel[(size_t)q * ann.sel_words + (c >> 5)] >> (c & 31u)) & 1u)) continue;
+      }
+      if (ann.row_field) {
+        const uint32_t fld = ann.row_field[row];
+        if (fld >= 64u || !((ann.field_mask >> fld) & 1ull)) continue;
       }
     }
-    cand[(size_t)q * VS_CAP + i] = (-d2 < thr) ? 0ull : mk_key(-d2, row);
+    const float sc = -vs_euclid_ref(Q + (size_t)q * dim, X + row * dim_pad, dim);
+    if (sc > st->tau[q]) {
+      const uint32_t at = atomicAdd(&st->cnt[q * VS_CNT_STRIDE], 1u);
+      if (at < VS_CAP) cand[(size_t)q * VS_CAP + at] = mk_key(sc, (uint32_t)row);
+    }
   }
 }
 
@@ -420,6 +499,10 @@ __device__ __forceinline__ void vr_bitonic(unsigned long long* keys, uint32_t* d
 }
 
 constexpr int VR_THREADS = 1024;  // (256 threads measured twice as slow on the ~1700 candidates a growth-16 chunk leaves)
+// MODE: VR_PLAIN the k best; VR_MARGIN (f32 Euclidean scan values) every candidate within st->margin of the k-th, and tau that much
+// lower; VR_EXACT (after vec_rescore_euclid_kernel) the k best of the exact values, leaving the counts and tau alone
+constexpr int VR_PLAIN = 0, VR_MARGIN = 1, VR_EXACT = 2;
+template <int MODE>
 __global__ void __launch_bounds__(VR_THREADS) vec_refine_kernel(VState* __restrict__ st, unsigned long long* __restrict__ cand,
                                                          uint32_t k, const uint32_t* __restrict__ row_doc /* non-null: dedup */,
                                                          const uint32_t* __restrict__ doc_map /* row -> doc, null = identity */,
@@ -453,6 +536,7 @@ __global__ void __launch_bounds__(VR_THREADS) vec_refine_kernel(VState* __restri
       if ((doc >> 5) < del_words && ((del[doc >> 5] >> (doc & 31u)) & 1u)) {
         key = 0ull;
         atomicAdd(&dropped, 1u);
+        if (MODE == VR_MARGIN && row_doc) base[i] = 0ull;  // (the margin pass below re-reads the records from base)
       }
     }
     keys[i] = key;
@@ -523,11 +607,38 @@ __global__ void __launch_bounds__(VR_THREADS) vec_refine_kernel(VState* __restri
       __syncthreads();
       kth = s_kth;
     }
+    float lo = 0.f;  // VR_MARGIN: keep the keys of scan value >= lo
+    if (MODE == VR_MARGIN && nl >= k) {
+      unsigned long long m = kth;
+      if (nl == k) {  // exactly k candidates: the smallest of them
+        __shared__ unsigned int s_min_hi;
+        if (threadIdx.x == 0) s_min_hi = 0xFFFFFFFFu;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) if (keys[i]) atomicMin(&s_min_hi, (unsigned int)(keys[i] >> 32));
+        __syncthreads();
+        m = (unsigned long long)s_min_hi << 32;
+      }
+      lo = nextafterf(ord2f((uint32_t)(m >> 32)) - st->margin[q], -INFINITY);
+      kth = (unsigned long long)f2ord(lo) << 32;
+    }
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
       const unsigned long long key = keys[i];
       if (key && key >= kth) base[atomicAdd(&s_slot, 1u)] = key;
     }
     __syncthreads();
+    if (MODE == VR_EXACT) {
+      if (threadIdx.x == 0) st->cnt[q * VS_CNT_STRIDE] = s_slot;
+      return;
+    }
+    if (MODE == VR_MARGIN) {
+      if (threadIdx.x == 0) {
+        st->total[q] += (unsigned long long)(n - kept - dropped);
+        st->cnt[q * VS_CNT_STRIDE] = s_slot;  // >= min(nl, k)
+        st->kept[q] = s_slot;
+        if (nl >= k) st->tau[q] = lo;
+      }
+      return;
+    }
     if (threadIdx.x == 0) {
       const uint32_t keep = s_slot;  // = min(nl, k)
       st->total[q] += (unsigned long long)(n - kept - dropped);
@@ -561,7 +672,30 @@ __global__ void __launch_bounds__(VR_THREADS) vec_refine_kernel(VState* __restri
   __syncthreads();
   const uint32_t nl = live;
   const uint32_t keep = nl < k ? nl : k;
+  if (MODE == VR_MARGIN) {
+    // every RECORD (not only each doc's best by scan value: its exact best may be another) within the margin of the k-th doc
+    const unsigned long long lo_key = nl >= k ? (unsigned long long)f2ord(nextafterf(ord2f((uint32_t)(keys[k - 1] >> 32)) - st->margin[q], -INFINITY)) << 32 : 1ull;
+    unsigned long long mine[VS_CAP / VR_THREADS];
+    for (uint32_t j = 0, i = threadIdx.x; i < n; i += blockDim.x, j++) mine[j] = base[i];
+    __shared__ uint32_t s_slot2;
+    if (threadIdx.x == 0) s_slot2 = 0;
+    __syncthreads();
+    for (uint32_t j = 0, i = threadIdx.x; i < n; i += blockDim.x, j++)
+      if (mine[j] && mine[j] >= lo_key) base[atomicAdd(&s_slot2, 1u)] = mine[j];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      st->total[q] += (unsigned long long)(n - kept - dropped);
+      st->cnt[q * VS_CNT_STRIDE] = s_slot2;
+      st->kept[q] = s_slot2;
+      if (nl >= k) st->tau[q] = ord2f((uint32_t)(lo_key >> 32));
+    }
+    return;
+  }
   for (uint32_t i = threadIdx.x; i < keep; i += blockDim.x) base[i] = keys[i];
+  if (MODE == VR_EXACT) {
+    if (threadIdx.x == 0) st->cnt[q * VS_CNT_STRIDE] = keep;
+    return;
+  }
   if (threadIdx.x == 0) {
     st->total[q] += (unsigned long long)(n - kept - dropped);
     st->cnt[q * VS_CNT_STRIDE] = keep;
@@ -634,7 +768,9 @@ int ssi_vec_alloc_ws(ss_shard* s) {
   SS_SET_MAX_LDS((vec_scan_kernel<false, false>), VS_LDS);
   SS_SET_MAX_LDS((vec_scan_kernel<true, true>), VS_LDS);
   SS_SET_MAX_LDS((vec_scan_kernel<false, true>), VS_LDS);
-  SS_SET_MAX_LDS(vec_refine_kernel, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)));
+  SS_SET_MAX_LDS(vec_refine_kernel<VR_PLAIN>, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)));
+  SS_SET_MAX_LDS(vec_refine_kernel<VR_MARGIN>, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)));
+  SS_SET_MAX_LDS(vec_refine_kernel<VR_EXACT>, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)));
   return SS_OK;
 }
 
@@ -657,6 +793,11 @@ int ssi_vec_search(ss_shard* s, uint32_t nq, const void* d_queries, const float*
   if (observed) { rc = ssi_vec_observed_prepare(s, ann_mode->field_mask, st); if (rc) return rc; }
   // a mode that only asks for the report scans like AnnMode::All
   if (ann_mode && !ann_clusters && !ann_mode->field_mask) ann_mode = nullptr;
+  // f32 Euclidean: the scan's cut keeps a margin, every kept candidate is rescored in the reference's order and the k best
+  // selected again (vec_euclid_margin_kernel); in safe mode -- the batch overflowed its slots -- the exact pass replaces the scan
+  const bool ex_cut = euclid && !i8;
+  const bool ex_pass = ex_cut && safe_mode;
+  if (ex_cut && !s->d_vec_r2) return SS_ESTATE;
   const uint32_t nch = s->dim_pad / VS_KC;
   const uint32_t T = (uint32_t)(s->n_rows_pad / VS_TR);
   VState* vst = (VState*)s->d_vstate;
@@ -693,6 +834,7 @@ int ssi_vec_search(ss_shard* s, uint32_t nq, const void* d_queries, const float*
       if (euclid) { rc = ssi_vec8_qaux(s, (const int8_t*)d_queries + (size_t)g0 * s->dim, nb, d_qnorm ? d_qnorm + g0 : nullptr, st); if (rc) return rc; }
     } else vec_qprep_kernel<<<nch, 512, 0, st>>>((const float*)d_queries + (size_t)g0 * s->dim, nb, s->dim, s->d_Qf, euclid ? 1 : 0);
     vec_init_kernel<<<1, 64, 0, st>>>(vst, tau_init);
+    if (ex_cut && !ex_pass) vec_euclid_margin_kernel<<<1, 64, 0, st>>>((const float*)d_queries + (size_t)g0 * s->dim, nb, s->dim, s->d_vec_r2, vst);
     VAnn ann{};
     if (ann_clusters) {  // medoid scores -> per-query cluster selection -> the batch's tile list
       rc = ssi_vec_ann_prepare(s, nb, d_qscale ? d_qscale + g0 : nullptr, ann_mode, &ann,
@@ -725,7 +867,16 @@ int ssi_vec_search(ss_shard* s, uint32_t nq, const void* d_queries, const float*
       // the tiles: a workgroup retires every few hundred microseconds and the dispatcher hands its CU to the higher-priority queue first.
       uint32_t grid = std::min<uint32_t>(c, 512u * VS_GRID_MULT);
       if (i8) ssi_vec8_launch_scan(s, tile0, c, d_qscale ? d_qscale + g0 : nullptr, ann_mode ? &ann : nullptr, st);
-      else if (ann_mode && sparse_nv) {
+      else if (ex_pass) {
+        const float* qraw = (const float*)d_queries + (size_t)g0 * s->dim;
+        const dim3 eg(std::min<uint32_t>(c, 2048u), (nb + 1) / 2);
+        if (ann_mode)
+          vec_exact_euclid_kernel<true><<<eg, 256, 0, st>>>(s->d_X, s->dim, s->dim_pad, (unsigned long long)s->n_rows, qraw, nb,
+                                                                                      tile0, c, vst, cand, ann);
+        else
+          vec_exact_euclid_kernel<false><<<eg, 256, 0, st>>>(s->d_X, s->dim, s->dim_pad, (unsigned long long)s->n_rows, qraw, nb,
+                                                                                       tile0, c, vst, cand, ann);
+      } else if (ann_mode && sparse_nv) {
         const uint32_t sg = std::min<uint32_t>(c, 1024);
         const float* qraw = (const float*)d_queries + (size_t)g0 * s->dim;
 #define SS_SPARSE(NV_) vec_ann_sparse_kernel<NV_><<<sg, 256, 0, st>>>(s->d_X, s->dim_pad, (unsigned long long)s->n_rows, qraw, nb, tile0, c, vst, cand, ann)
@@ -744,14 +895,22 @@ int ssi_vec_search(ss_shard* s, uint32_t nq, const void* d_queries, const float*
       else
         vec_scan_kernel<false, false><<<grid, VS_WAVES * 64, VS_LDS, st>>>(s->d_X, s->dim_pad, (unsigned long long)s->n_rows,
                                                                            s->d_Qf, nch, tile0, c, vst, cand, ann);
-      vec_refine_kernel<<<SS_VEC_BATCH, VR_THREADS, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)), st>>>(
-          vst, cand, k, s->vec_multi_record ? s->d_row_doc : nullptr, s->d_row_doc, s->n_deleted ? s->d_deleted : nullptr,
-          (uint32_t)s->deleted_words, s->n_deleted ? s->vec_del_stride : 0u, nb);
+      if (ex_cut && !ex_pass)
+        vec_refine_kernel<VR_MARGIN><<<SS_VEC_BATCH, VR_THREADS, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)), st>>>(
+            vst, cand, k, s->vec_multi_record ? s->d_row_doc : nullptr, s->d_row_doc, s->n_deleted ? s->d_deleted : nullptr,
+            (uint32_t)s->deleted_words, s->n_deleted ? s->vec_del_stride : 0u, nb);
+      else
+        vec_refine_kernel<VR_PLAIN><<<SS_VEC_BATCH, VR_THREADS, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)), st>>>(
+            vst, cand, k, s->vec_multi_record ? s->d_row_doc : nullptr, s->d_row_doc, s->n_deleted ? s->d_deleted : nullptr,
+            (uint32_t)s->deleted_words, s->n_deleted ? s->vec_del_stride : 0u, nb);
       tile0 += c;
     }
     ssi_prof_end(s, 1, st, e0, e1);
-    if (euclid && !i8)
-      vec_rescore_euclid_kernel<<<nb, 256, 0, st>>>(vst, cand, s->d_X, s->dim, s->dim_pad, (const float*)d_queries + (size_t)g0 * s->dim, nb, k, thr);
+    if (ex_cut) {
+      vec_rescore_euclid_kernel<<<nb, 256, 0, st>>>(vst, cand, s->d_X, s->dim, s->dim_pad, (const float*)d_queries + (size_t)g0 * s->dim, nb, thr);
+      vec_refine_kernel<VR_EXACT><<<nb, VR_THREADS, VS_CAP * (sizeof(unsigned long long) + sizeof(uint32_t)), st>>>(
+          vst, cand, k, s->vec_multi_record ? s->d_row_doc : nullptr, s->d_row_doc, nullptr, 0u, 0u, nb);
+    }
     vec_final_kernel<<<nb, 256, 0, st>>>(vst, cand, s->d_row_doc, nb, k, d_out_doc + (size_t)g0 * k,
                                          d_out_score + (size_t)g0 * k, d_out_count + g0,
                                          (unsigned long long*)d_out_total + g0);

@@ -758,3 +758,94 @@ def test_facet_order_key_filter_bits_and_type_range_at_the_edges():
                 assert naive.facet_pass(y, ty, x, x, naive.FACET_HI_INCLUSIVE) == (y == x)
                 assert naive.facet_pass(y, ty, x, pal[-1], naive.FACET_LO_EXCLUSIVE | naive.FACET_HI_INCLUSIVE) == (y > x)
                 assert naive.facet_pass(y, ty, pal[0], x) == (y < x)
+
+
+# ---- exact vector reference (naive.vec_exact_*, check_vector_topk)
+def _expanded_f32(rows, q):
+    """2 q.x - |x|^2 - |q|^2 accumulated term by term in f32: the expanded form an MFMA Euclidean scan computes"""
+    r = rows.astype(np.float32)
+    q2 = (np.float32(2) * q).astype(np.float32)
+    acc = np.zeros(len(r), np.float32)
+    xx = np.zeros(len(r), np.float32)
+    qq = np.float32(0)
+    for i in range(r.shape[1]):
+        acc = (acc + r[:, i] * q2[i]).astype(np.float32)
+        xx = (xx + r[:, i] * r[:, i]).astype(np.float32)
+        qq = np.float32(qq + q[i] * q[i])
+    return ((acc - xx) - qq).astype(np.float32)
+
+
+def test_exact_vector_reference_kats():
+    assert naive.gamma(1) == pytest.approx(2.0 ** -24, rel=1e-6) and naive.gamma(100) > 100 * 2.0 ** -24
+    x = np.array([[1, 2, 3], [0.5, -0.25, 8]], np.float32)
+    q = np.array([3, -1, 0.125], np.float32)
+    assert list(naive.vec_exact_dot(x, q)) == [1.375, 2.75]
+    assert list(naive.vec_exact_l2(x, q)) == [4 + 9 + 2.875 ** 2, 2.5 ** 2 + 0.75 ** 2 + 7.875 ** 2]
+    # products of f32 values are exact in f64: a dot that cancels to 2^-20 is seen as such, where an f32 sum sees 0
+    x = np.array([[2.0 ** 20, 1.0, -(2.0 ** 20)]], np.float32)
+    q = np.array([1.0, 2.0 ** -20, 1.0], np.float32)
+    assert naive.vec_exact_dot(x, q)[0] == 2.0 ** -20 and (x[0, 0] * q[0] + x[0, 1] * q[1]) + x[0, 2] * q[2] == np.float32(0)
+    assert naive.bound_dot(x, q)[0] == pytest.approx(naive.gamma(4) * 2.0 ** 21)
+    assert naive.bound_l2(x, q)[0] == pytest.approx(naive.gamma(5) * naive.vec_exact_l2(x, q)[0])
+    # the f32 results of both reference orders lie inside the bands
+    rng = np.random.default_rng(5)
+    rows = (rng.standard_normal((300, 40)) * 10.0 ** rng.integers(-3, 4, (300, 1))).astype(np.float32)
+    q = rng.standard_normal(40).astype(np.float32)
+    ex, bd = naive.vec_exact_dot(rows, q), naive.bound_dot(rows, q)
+    assert np.all(np.abs((rows @ q).astype(np.float64) - ex) <= bd)
+    for simd in (True, False):
+        d2 = np.array([O.euclidean_f32(q, r, simd_order=simd) for r in rows[:, :40]], np.float64)
+        assert np.all(np.abs(d2 - naive.vec_exact_l2(rows, q)) <= naive.bound_l2(rows, q))
+
+
+def test_check_vector_topk_rules():
+    ex = np.array([5.0, 4.0, 4.0, 3.0, -np.inf, 1.0])
+    bd = np.zeros(6)
+    f = np.float32
+    naive.check_vector_topk(np.array([0, 1, 2]), f([5, 4, 4]), 3, ex, bd, 3)
+    naive.check_vector_topk(np.array([0, 1, 2, 3, 5]), f([5, 4, 4, 3, 1]), 5, ex, bd, 10)  # k past the live rows
+    bad = [((np.array([0, 2, 1]), f([5, 4, 4]), 3), "equal scores"),  # tie order
+           ((np.array([1, 2, 3]), f([4, 4, 3]), 3), "missing"),  # a better row dropped
+           ((np.array([0, 1, 3]), f([5, 4, 3]), 3), "beyond the band"),  # a worse row in its place
+           ((np.array([0, 1]), f([5, 4]), 2), "count"),
+           ((np.array([0, 1, 4]), f([5, 4, 0]), 3), "may not"),  # a dead row
+           ((np.array([0, 1, 1]), f([5, 4, 4]), 3), "twice"),
+           ((np.array([0, 1, 2]), f([5, 4, 4.5]), 3), "off by")]
+    for args, msg in bad:
+        with pytest.raises(AssertionError, match=msg):
+            naive.check_vector_topk(*args, ex, bd, 3)
+    with pytest.raises(AssertionError, match="rise"):
+        naive.check_vector_topk(np.array([1, 0]), f([4, 5]), 2, ex, np.full(6, 2.0), 2)
+    # inside the band either of two near-equal rows may stand at the seam
+    naive.check_vector_topk(np.array([0, 2]), f([5, 4]), 2, ex, np.full(6, 1e-3), 2)
+    # several records per doc: the doc's best record counts, each doc once
+    rd = np.array([7, 7, 8, 8, 9, 9])
+    naive.check_vector_topk(np.array([7, 8]), f([5, 4]), 2, ex, bd, 2, row_doc=rd)
+    with pytest.raises(AssertionError, match="beyond the band"):
+        naive.check_vector_topk(np.array([7, 9]), f([5, 1]), 2, ex, bd, 2, row_doc=rd)
+    with pytest.raises(AssertionError, match="missing"):
+        naive.check_vector_topk(np.array([8, 9]), f([4, 1]), 2, ex, bd, 2, row_doc=rd)
+
+
+@pytest.mark.parametrize("c,sigma", [(0.0, 1.0), (10.0, 0.1), (100.0, 0.1), (30.0, 0.01), (1000.0, 1.0), (1000.0, 0.1)])
+def test_reference_vector_searches_meet_the_exact_cut(c, sigma):
+    """the C oracle's dot and Euclidean searches return the exact top-k up to their own rounding band, off-centre data
+    included -- the reference sums (q_i - x_i)^2 directly; while the expanded form 2 q.x - |x|^2 - |q|^2 in f32 misses
+    most of the exact neighbours off the origin"""
+    dim, n, k = 128, 4000, 10
+    rows = naive.vec_offcentre(1, n, dim, c, sigma)
+    qs = naive.vec_offcentre(2, 4, dim, c, sigma)
+    missed = 0
+    for q in qs:
+        d2 = naive.vec_exact_l2(rows, q)
+        for simd in (True, False):
+            od, os_, *_ = O.vec_search_euclid(rows, q, k, simd_order=simd)
+            naive.check_vector_topk(od, os_, len(od), -d2, naive.bound_l2(rows, q, d2), k, tie_order=False)
+        od, os_, *_ = O.vec_search(rows, q, k)
+        naive.check_vector_topk(od, os_, len(od), naive.vec_exact_dot(rows, q), naive.bound_dot(rows, q), k, tie_order=False)
+        top = set(np.lexsort((np.arange(n), d2))[:k].tolist())
+        missed += len(top - set(np.argsort(-_expanded_f32(rows, q), kind="stable")[:k].tolist()))
+    if c / sigma >= 3000.0:  # (the data the f32 Euclidean scan must not select by its expanded form)
+        assert missed >= (4 * k // 2 if c / sigma >= 10000.0 else 1), missed
+    if c == 0.0:
+        assert missed == 0
