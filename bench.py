@@ -5,20 +5,23 @@ Primary workload (BASELINE.json configs[1], "C2"): 10 M synthetic docs, 3-term O
 One C-ABI call = one batch of 1000 resolved queries through ss_bm25_search -- HOST pointers in, answers on the HOST when the call
 returns (SURVEY 8d's timing protocol: submit -> results on host; round 6, VERDICT r5 "next" 6; N > 1: ss_bm25_search_sharded, which ends
 in the all-gather and the merged answers on every rank's host); one "step" = --calls-per-step (default 200) such calls, so that the timed
-region (exactly --steps steps) covers >= 200 batches and >= 2 s.  The device-resident rate (ss_bm25_search_dev: queries and answers in
-HBM, what rounds 1-5 headlined) is the secondary key `device_resident`.  Secondary legs in the same JSON line: the exhaustive strategy (the kernel that
-streams SURVEY 8d's algorithmic bytes), TopkCount, C3 (10 M x 768 f32 cosine top-100, batch 64) + i8, C4 hybrid, ANN,
-host-pointer end-to-end rates, latencies (>= 1000 samples), concurrent single-query callers through the C++ mirror (T = 64 / 256
-threads), the multi-shard entry points (one all-gather per call, allgather_us), full-size parity against the oracle on ALL queries
-of the batches, and the CPU baseline
-(the oracle's reference-structured dispatch, union_docid_3, timed on the host cores).
+region (exactly --steps steps) covers >= 200 batches and >= 2 s.
+
+A plain run does only what the headline needs: it builds the shard, warms up, times the --steps steps, writes --dump-outputs and
+prints the line.  --full adds the secondary legs to the same JSON line (and their details to bench_details.json): the device-resident
+rate (ss_bm25_search_dev: queries and answers in HBM, what rounds 1-5 headlined) as the key `device_resident`, the exhaustive strategy
+(the kernel that streams SURVEY 8d's algorithmic bytes) and the rooflines, TopkCount, C3 (10 M x 768 f32 cosine top-100, batch 64) +
+i8, C4 hybrid, ANN, host-pointer end-to-end rates, latencies (>= 1000 samples), concurrent single-query callers through the C++ mirror
+(T = 64 / 256 threads), the multi-shard entry points (one all-gather per call, allgather_us), full-size parity against the oracle on
+ALL queries of the batches, and the CPU baseline (the oracle's reference-structured dispatch, union_docid_3, timed on the host cores).
+The --no-* switches and --scale-check select among these legs.
 
 Multi-GPU (SURVEY 8e, weak scaling): one process per GPU; rank r holds shard r of ONE generator stream of
 docs_per_shard x N docs (doc g -> shard g % N, index.rs:5284); every rank answers the same batch on its shard, one RCCL
 all-gather of the per-shard top-k (behind the C ABI: ss_topk_allgather_merge), identical merge on every rank.
 `value` = merged answers per second over the N-times larger corpus.
 
-  python bench.py --gpus N --steps K --warmup W      (N > 1 without a launcher: re-executes itself under torchrun)
+  python bench.py --gpus N --steps K --warmup W [--full]      (N > 1 without a launcher: re-executes itself under torchrun)
   --dump-outputs DIR: the answers the primary leg's last timed step returned, as DIR/doc.npy, score.npy, count.npy, total.npy (one row
   per query; seeded inputs, so two builds run with the same arguments can be compared answer for answer)
 """
@@ -117,8 +120,9 @@ def _r(x, nd=4):
     return x
 
 
-def compact_line(line):
-    """The ONE stdout line the driver parses (<= 4 KB).  Everything else goes to bench_details.json.
+def compact_line(line, details=True):
+    """The ONE stdout line a caller parses (<= 4 KB).  Everything else goes to bench_details.json (`details`: the
+    file was written; a plain run writes none and its line carries only the headline and the config).
 
     roofline = SURVEY 8(d)'s own fraction -- algorithmic bytes / live launch time -- of the kernel that STREAMS those bytes
     (bm25_scan16_kernel, the exhaustive strategy on the same batches); the pruned kernel the headline `value` is timed on answers
@@ -149,7 +153,8 @@ def compact_line(line):
     else:
         roof = _pick(rf, ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "mfma_util_pmc", "algorithmic_flops_per_launch",
                           "algorithmic_bytes_per_launch", "avg_launch_ms", "launches"))
-    out["roofline"] = roof
+    if roof:
+        out["roofline"] = roof
     if is_bm:
         # the shapes off the uniform corpus, as a caller gets them (AUTO) beside the forced exhaustive scan, queries/s
         ou = {}
@@ -169,7 +174,8 @@ def compact_line(line):
         out["cpu_baseline"] = _pick(cb, ("value", "unit", "cores", "threads", "kind", "algorithm", "shards"))
         out["cpu_baseline"]["sample"] = str(cb.get("sample", ""))[:160]
     lat = line.get("latency_ms") or {}
-    out["latency_ms"] = _pick(lat, ("batch_p50", "batch_p99", "single_query_p50", "single_query_p99", "batch64_p50", "batch64_p99"))
+    if lat:
+        out["latency_ms"] = _pick(lat, ("batch_p50", "batch_p99", "single_query_p50", "single_query_p99", "batch64_p50", "batch64_p99"))
     e2e = line.get("end_to_end") or {}
     if e2e:
         out["end_to_end"] = _pick(e2e, ("batch_ms_p50", "batch_ms_p99", "single_query_ms_p50", "single_query_ms_p99", "batch64_ms_p50"))
@@ -193,7 +199,8 @@ def compact_line(line):
         out["scale_check"] = {"agree": sc.get("agree"), "ranks": [_pick(e, ("rank", "ranks_seen", "allgather_us", "merged_checksum_dev")) for e in sc.get("ranks", [])]}
     if line.get("parity_full_size"):
         out["parity_full_size"] = {n_: (p_.get("queries") if isinstance(p_, dict) else p_) for n_, p_ in line["parity_full_size"].items()}
-    out["details"] = "bench_details.json (every secondary leg; also on stderr)"
+    if details:
+        out["details"] = "bench_details.json (every secondary leg; also on stderr)"
     out = _r(out)
     # hard bound: the driver keeps a bounded tail of stdout and must find ONE parseable line in it
     for drop in ("off_uniform", "parity_full_size", "concurrent_callers", "hybrid", "end_to_end", "latency_ms", "device_resident"):
@@ -345,6 +352,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls-per-step", type=int, default=200, help="C-ABI calls (1000-query batches) per step of the primary leg")
     ap.add_argument("--workload", default="all", choices=["all", "bm25", "vec"])
+    ap.add_argument("--full", action="store_true", help="run the secondary legs as well (the --no-* switches and --scale-check pick among "
+                    "them): rooflines, other strategies, result types, corpora and precisions, the vector legs beside BM25, latencies, "
+                    "callers, full-size parity, CPU baselines.  Without it a run times the primary leg and prints its line")
     ap.add_argument("--docs", type=int, default=10_000_000, help="docs per shard (= per GPU)")
     ap.add_argument("--rows", type=int, default=10_000_000, help="vector rows per shard")
     ap.add_argument("--dim", type=int, default=768)
@@ -357,7 +367,7 @@ def main():
     ap.add_argument("--no-fields", action="store_true", help="skip the multi-field (BM25F) leg")
     ap.add_argument("--no-vocab", action="store_true", help="skip the realistic-vocabulary leg (1 M rare terms in the sparse tier)")
     ap.add_argument("--vocab-terms", type=int, default=1_000_000)
-    ap.add_argument("--scale-check", action="store_true", help="self-verification of a multi-rank run (always on when N > 1): every rank reports the ranks its "
+    ap.add_argument("--scale-check", action="store_true", help="self-verification of a multi-rank run (with --full always on when N > 1): every rank reports the ranks its "
                     "communicator spans, the microseconds of the all-gather and a checksum of the merged answers; rank 0 asserts they agree")
     ap.add_argument("--no-clustered", action="store_true", help="skip the clustered-corpus leg (10 M docs whose term densities vary with the doc's cluster)")
     ap.add_argument("--no-real-format", action="store_true", help="skip the drop-in rehearsal on a million-doc index.bin / vector.bin / delete.bin")
@@ -422,7 +432,7 @@ def main():
     sh = S.Shard(local_rank, shard_id=rank)
     sh.synth_partition(rank, world)
     # RCCL communicator behind the C ABI (ss_comm_create); at N = 1 only for the sharded legs (one rank: the exchange is the identity)
-    comm = D.ShardComm(rank, world, local_rank) if (world > 1 or not args.no_sharded) else None
+    comm = D.ShardComm(rank, world, local_rank) if (world > 1 or (args.full and not args.no_sharded)) else None
     merged = {}
 
     def timed(step_fn, steps, warmup):
@@ -480,7 +490,9 @@ def main():
     # ------------------------------------------------------------------ BM25 (primary)
     bm = None
     parity = {}
-    if args.workload in ("all", "bm25"):
+    run_bm = args.workload in ("all", "bm25")
+    # the section runs as four blocks: set-up, (--full) the legs before the timed region, the timed region, (--full) the legs after it
+    if run_bm:
         k = 10
         term_lists, th = make_c2_queries(O, args.queries)
         tab = O.len_table()
@@ -542,6 +554,7 @@ def main():
             for j in range(args.calls_per_step):
                 bm_host_rot_call(j if last else None)
 
+    if run_bm and args.full:
         # exact union sizes for the roofline's "1 B per scored candidate" term: one untimed TopkCount pass (exhaustive scan)
         sh.set_strategy(N.BM25_EXHAUSTIVE)
         N.check(L.ss_bm25_search_dev(sh._h, nq, q_dev.data_ptr(), k, N.RT_TOPKCOUNT, OPS, o_doc.data_ptr(),
@@ -583,10 +596,16 @@ def main():
         ex_qps, ex_ms = nq * ex_n / ex_dt, ex_dt / ex_n * 1e3
         # (2) the default strategy (AUTO): top-k unions take the pruned path (MaxScore over the probe index)
         check_strategy(N.BM25_AUTO)
+
+    if run_bm:
+        sh.set_strategy(N.BM25_AUTO)
+        sh.profile(True)  # (--full: on since the exhaustive leg) the timed region's launches are counted below
         rot_i[0] = 0
         bm_host_rot_call()  # batch 0 through the host-pointer call: the answers every check refers to
         if world == 1:
-            assert np.array_equal(hp_score, ref_scores), "host-pointer entry point differs from the device-pointer one"
+            assert int(hp_cnt.min()) == k and np.all(np.diff(hp_score, axis=1) <= 0), "host-pointer answers are not top-k lists"
+            if args.full:
+                assert np.array_equal(hp_score, ref_scores), "host-pointer entry point differs from the device-pointer one"
         for _ in range(args.warmup):
             bm_step()
         sh.profile_read(0, reset=True)  # the accumulators count the timed launches only
@@ -601,6 +620,9 @@ def main():
         assert launches == calls, (launches, calls)
         avg_ms = kms / max(launches, 1)
         qps, ms_step = nq * calls / dt, dt / args.steps * 1e3
+        bm = dict(qps=qps, ms_per_step=ms_step, build_s=build_s, info=info)
+
+    if run_bm and args.full:
         # the device-resident form of the same call (ss_bm25_search_dev: queries and answers stay in HBM, asynchronous on the caller's
         # stream; N > 1: + the all-gather of the per-shard lists): what a host that keeps its batches on the device gets
         dev_n, dev_dt = timed_for(bm_rot_call)
@@ -1269,7 +1291,7 @@ def main():
 
     # ------------------------------------------------------------------ vector (secondary)
     vec = None
-    if args.workload in ("all", "vec"):
+    if args.workload == "vec" or (args.workload == "all" and args.full):
         kv, B = 100, 64
         t0 = time.perf_counter()
         sh.synth_vectors(O.VEC_SEED, args.rows, args.dim)
@@ -1302,6 +1324,9 @@ def main():
         sh.profile(False)
         cnt = v_cnt.cpu().numpy()
         assert np.all(cnt.astype(np.int64) == min(kv, args.rows)), "vector candidate overflow or short result in bench"
+        vec = dict(qps=B * vn / dtv, ms_per_step=dtv / vn * 1e3, calls=vn, build_s=vbuild)
+
+    if vec is not None and args.full:
         flops = 2.0 * args.dim * args.rows * B  # per pass (2*dim*N per query)
         avg_ms = kms / max(launches, 1)
         ach = flops / (avg_ms * 1e-3) / 1e12 if avg_ms > 0 else 0.0
@@ -1627,16 +1652,16 @@ def main():
             "global_qps": prim["qps"],
             "shard_queries_per_s": prim["qps"] * world,
             "docs_scanned_per_s": prim["qps"] * world * (args.docs if is_bm else args.rows),
-            "roofline": prim["roofline"],
+            "roofline": prim.get("roofline"),
             "cpu_baseline": prim.get("cpu_baseline"),
-            "latency_ms": prim["latency_ms"],
+            "latency_ms": prim.get("latency_ms"),
             "end_to_end": prim.get("end_to_end"),
             "value_protocol": ("ss_bm25_search: host pointers in, answers on the host (SURVEY 8d: submit -> results on host)" if is_bm else
                                "ss_vec_search_dev (device resident)"),
             "device_resident": prim.get("device_resident"),
             "parity_full_size": parity or None,
         }
-        if is_bm:
+        if is_bm and args.full:
             line["exhaustive"] = bm["exhaustive"]
             line["topk_count"] = bm["topk_count"]
             if bm.get("intersection"):
@@ -1673,7 +1698,7 @@ def main():
                 line["sharded"] = vec["sharded"]
             if vec.get("concurrent_callers"):
                 line["concurrent_callers"] = vec["concurrent_callers"]
-        elif vec is not None:
+        elif vec is not None and args.full:
             line["i8"] = vec.get("i8")
         final_line = line
     else:
@@ -1684,7 +1709,10 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     if final_line is not None:  # LAST: whatever the libraries print while they shut down stands before the line the driver parses
-        emit(final_line, world)
+        if args.full:
+            emit(final_line, world)
+        else:  # a plain run: the line alone, no details file
+            print_line(json.dumps(compact_line(final_line, details=False)))
 
 
 if __name__ == "__main__":

@@ -404,6 +404,23 @@ def test_bench_compact_line_keeps_the_contract_and_its_bound():
         assert back["cpu_baseline"]["kind"] in ("port", "reference")
 
 
+def test_bench_compact_line_of_a_plain_run_is_the_headline_alone():
+    """bench.py without --full times the primary leg only: its line keeps the headline keys as a full run's line has them, and carries no
+    empty secondary section and no pointer to a details file it did not write"""
+    import json
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r5_bench_details.json")))
+    head = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
+    plain = {k: full[k] for k in head + ("global_qps", "shard_queries_per_s", "docs_scanned_per_s")}
+    plain.update(roofline=None, cpu_baseline=None, latency_ms=None, end_to_end=None, device_resident=None, parity_full_size=None)
+    out = json.loads(json.dumps(bench.compact_line(plain, details=False)))
+    assert sorted(out) == sorted(head)
+    want = bench.compact_line(full)
+    for k in head:
+        assert out[k] == want[k], k
+    assert "details" in want
+
+
 def test_committed_bench_line_and_counter_file_belong_together():
     """the line of the round's final run (profiles/<pmc_traffic.json's collected_as>_bench_line.json); its `traffic` figures come from
     profiles/pmc_traffic.json, which bench.py only uses while it was collected on the kernel sources of the tree (kernel_source_hash)."""

@@ -1,9 +1,10 @@
 #!/bin/bash
-# rocprofv3 --kernel-trace --stats of the default bench command minus its host-only legs (run on the GPU box):
+# rocprofv3 --kernel-trace --stats of bench.py --full minus its host-only legs (run on the GPU box):
 #   bash tools/collect_stats.sh <tag> ["extra bench flags"]
 # -> gpurun_out/<tag>_kernel_stats.md (per-kernel table) + gpurun_out/<tag>_bench.json (bench line of the same run)
 set -u
 TAG=${1:-x}
+set -- "$TAG" "--full ${2:-}"  # the legs the table covers run under --full
 cd "${GRAFT_REPO_ROOT:-.}"
 export TMPDIR=/tmp
 R=$PWD

@@ -50,7 +50,7 @@ def main():
     d, tag = sys.argv[1], sys.argv[2]
     db = lambda g: os.path.join(d, f"pmc_{tag}_{g}", "x_results.db")
     out, lines = {}, [f"# PMC summary ({tag})", "",
-                      "`rocprofv3 --pmc <group> --kernel-trace -- python bench.py --workload all --quick --no-topk-count --steps 4 --warmup 1`, "
+                      "`rocprofv3 --pmc <group> --kernel-trace -- python bench.py --full --workload all --quick --no-topk-count --steps 4 --warmup 1`, "
                       "one run per counter group (tools/collect_pmc.sh).  SQ_* wave counters are in quad-cycles "
                       "(MI355X_MICROARCH.md); GRBM_GUI_ACTIVE is summed over the 8 XCDs.", ""]
     LAUNCHES_PER_PASS = 4  # chunk schedule of the vector scans: 16 tiles, then 16 x the prefix (10 M rows)

@@ -3,7 +3,7 @@
 # integer-exact one the parity tests can regenerate (uniform(-1, 1), then normalize_f32): same scan, same work.
 cd "${GRAFT_REPO_ROOT:-.}"
 for g in 0 1; do
-  SS_VEC_SYNTH_BOXMULLER=$g python bench.py --workload vec --no-cpu --no-parity --no-concurrent --no-sharded --min-seconds 1.0 2>/dev/null | grep '^{' | python -c "
+  SS_VEC_SYNTH_BOXMULLER=$g python bench.py --full --workload vec --no-cpu --no-parity --no-concurrent --no-sharded --min-seconds 1.0 2>/dev/null | grep '^{' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 v=d.get('vector', d)

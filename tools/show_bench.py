@@ -9,13 +9,14 @@ def g(o, *ks):
     return o
 f = lambda x: "None" if x is None else ("%.4g" % x if isinstance(x, float) else str(x))
 print("value", f(d["value"]), "q/s  ms/step", f(d["ms_per_step"]), " end_to_end", f(d.get("value_end_to_end")))
-r = d["roofline"]; print("  roofline: achieved", f(r["achieved"]), r["unit"], "frac", f(r["frac"]), "avg_launch_ms", f(r["avg_launch_ms"]), "alg GB/s", f(r.get("effective_GBs_on_algorithmic_bytes")))
+r = d.get("roofline")  # (a plain run reports the headline alone: the rest comes with --full)
+if r: print("  roofline: achieved", f(r["achieved"]), r["unit"], "frac", f(r["frac"]), "avg_launch_ms", f(r["avg_launch_ms"]), "alg GB/s", f(r.get("effective_GBs_on_algorithmic_bytes")))
 e = d.get("exhaustive"); 
 if e: print("exhaustive", f(e["value"]), "q/s  roofline", f(e["roofline"]["achieved"]), "GB/s frac", f(e["roofline"]["frac"]), "kernel ms", f(e["roofline"]["avg_launch_ms"]))
 tc = d.get("topk_count") or {}
 print("topk_count", {k: f(v["value"]) for k, v in tc.items() if isinstance(v, dict)})
 print("intersection", f(g(d, "intersection", "value")))
-print("latency", {k: f(v) for k, v in d["latency_ms"].items() if k != "clock"})
+print("latency", {k: f(v) for k, v in (d.get("latency_ms") or {}).items() if k != "clock"})
 print("e2e", {k: f(v) for k, v in (d.get("end_to_end") or {}).items() if k not in ("entry_point", "unit")})
 print("rationed", f(g(d, "rationed_vocabulary", "value")), "churn", f(g(d, "rationed_vocabulary", "churn_value")), " multi_field", {k: f(v["value"]) for k, v in (d.get("multi_field") or {}).items() if isinstance(v, dict)})
 rv = d.get("realistic_vocabulary")

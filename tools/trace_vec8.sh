@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 R=$PWD
 d=$R/gpurun_out/trace_$TAG
 rm -rf $d
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace -d $d -o x -- python $R/bench.py --workload vec --no-cpu --steps 4 --warmup 1 > $R/gpurun_out/${TAG}_trace_bench.json 2> $R/gpurun_out/${TAG}_trace_bench.err )
+( cd "$TMPDIR" && timeout 600 rocprofv3 --kernel-trace -d $d -o x -- python $R/bench.py --full --workload vec --no-cpu --steps 4 --warmup 1 > $d.bench.json 2> $d.bench.err )
 db=$(find $d -name "*results.db" | head -1)
 python - "$db" > gpurun_out/${TAG}_trace.txt <<'PY'
 import sqlite3, sys
