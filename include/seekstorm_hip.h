@@ -764,10 +764,12 @@ int ss_merge_results(int mode, const uint64_t* lex_doc, const float* lex_score, 
 
 /* Device-side variant for the multi-GPU path: per-shard top-k lists of a whole query batch, laid out
  * [n_shards][n_queries][k] exactly as an RCCL all-gather of the ss_*_search_dev outputs leaves them, are merged
- * per query into global ids (local*S + shard), sorted by score desc (ties: shard order, as the reference's stable
- * sort of the concatenation).  Unused slots: doc = UINT64_MAX.  Any n_shards * k: up to 8192 keys per query are sorted in LDS; beyond
- * that (more than 8 shards at k = 1024, a deep page) every entry finds its slot by binary searches in the other shards' lists -- the
- * lists must then arrive sorted by score descending, as the searches leave them. */
+ * per query into global ids (local*S + shard), sorted by score desc (ties: shard order, then the shard's own order, as the
+ * reference's stable sort of the concatenation; -0.0 and +0.0 tie, as partial_cmp has them, and come back with their own bits).
+ * Unused slots: doc = UINT64_MAX, score 0.  A count above k is read as k, UINT32_MAX as 0.  Any n_shards * k: up to 8192 keys per
+ * query are sorted in LDS; beyond that (more than 8 shards at k = 1024, a deep page) every entry finds its slot by binary searches
+ * in the other shards' lists -- the lists must then arrive sorted by score descending (either zero may come first), as the
+ * searches leave them. */
 int ss_topk_merge_dev(int device, uint32_t n_queries, uint32_t n_shards, uint32_t k, const uint32_t* d_doc,
                       const float* d_score, const uint32_t* d_count, uint64_t* d_out_doc, float* d_out_score,
                       uint32_t* d_out_count, void* stream);

@@ -88,6 +88,62 @@ def rrf(lex_ids, vec_ids, length):  # search.rs:1962-2035 (k = 0.6, 0-based rank
     return [d for d, _ in items], [s for _, s in items]
 
 
+# ---- the cross-shard merge (search.rs:1875-2119), restated over the lists each shard returned
+MODE_LEXICAL, MODE_VECTOR, MODE_HYBRID = 0, 1, 2  # SearchMode
+SRC_LEXICAL, SRC_VECTOR, SRC_HYBRID = 0, 1, 2  # ResultSource
+# scores at a merge's edges: -inf, negatives, the smallest normal and subnormal of either sign, both zeros (f32)
+MERGE_PALETTE = np.array([-np.inf, -3.5, -1.0, -2.0 ** -126, -2.0 ** -149, -0.0, 0.0, 2.0 ** -149, 2.0 ** -126, 0.5, 1.0, 2.0],
+                         np.float32)
+
+
+def reference_sorted(scores):
+    """f32 scores in the order the reference's stable sort leaves them: descending, -0.0 and +0.0 tied (either may come first)"""
+    return np.array(sorted(np.asarray(scores, np.float32).tolist(), key=lambda x: -x), np.float32)
+
+
+def merge_exact(mode, shard_lists, S, offset, length):
+    """The last stage of every multi-shard and every hybrid search.  shard_lists[s] = (lex, vec) of shard s, each None or
+    (local ids, f32 scores) or (local ids, f32 scores, result_count_total), a list as the shard returned it.
+      global id = local * S + s (search.rs:1671); the lists of a mode are concatenated in shard order and stable-sorted by score
+      descending (sorted() on Python floats: -0.0 and +0.0 tie, as partial_cmp has them; equal scores keep concatenation order);
+      Lexical / Vector: that order is the answer.  Hybrid: RRF over the two sorted concatenations -- rank i (0-based, over the
+      whole concatenation) weighs f32 1 / (0.6 + i); a lexical entry inserts (or overwrites) its doc, a vector entry adds to a
+      doc already there (f32 lex + vec, source Hybrid) or inserts it (search.rs:1962-2035); then score descending, equal fused
+      scores by doc ascending (the project's choice: the reference leaves them in hash order).
+    Then offset and length (2098-2119).  -> (doc uint64, score float32, source uint8, total): total = the sum over the shards of
+    the mode's totals, max(lexical, vector) per shard for Hybrid (1884-1921); None when a needed total was not given."""
+    def concat(which):
+        out = []
+        for s, lists in enumerate(shard_lists):
+            lst = lists[which]
+            if lst is not None:
+                out += [(int(d) * S + s, np.float32(x)) for d, x in zip(lst[0], lst[1])]
+        return sorted(out, key=lambda e: -float(e[1]))
+
+    def total(lst):
+        return 0 if lst is None else (lst[2] if len(lst) > 2 else None)
+
+    if mode == MODE_HYBRID:
+        fused = {}
+        for i, (d, _) in enumerate(concat(0)):
+            fused[d] = (np.float32(1) / (np.float32(0.6) + np.float32(i)), SRC_LEXICAL)
+        for i, (d, _) in enumerate(concat(1)):
+            r = np.float32(1) / (np.float32(0.6) + np.float32(i))
+            fused[d] = (np.float32(fused[d][0] + r), SRC_HYBRID) if d in fused else (r, SRC_VECTOR)
+        res = sorted(((d, x, so) for d, (x, so) in fused.items()), key=lambda e: (-float(e[1]), e[0]))
+        tots = [(total(lex), total(vec)) for lex, vec in shard_lists]
+        tot = None if any(None in t for t in tots) else sum(max(t) for t in tots)
+    else:
+        which = 0 if mode == MODE_LEXICAL else 1
+        src = SRC_LEXICAL if mode == MODE_LEXICAL else SRC_VECTOR
+        res = [(d, x, src) for d, x in concat(which)]
+        tots = [total(lists[which]) for lists in shard_lists]
+        tot = None if None in tots else sum(tots)
+    page = res[offset:offset + length]
+    return (np.array([e[0] for e in page], np.uint64), np.array([e[1] for e in page], np.float32),
+            np.array([e[2] for e in page], np.uint8), tot)
+
+
 def bm25_exact(n_docs, doclen_bytes, postings, op_and, not_docs=(), deleted=(), n_idf=None):
     """Every match of a lexical query, scored as the crate rounds each term's factors -- f32 idf (search.rs:3225-3230), f32
     component cache (commit.rs:318-325), f32 tf (K + 1) / (tf + comp) (add_result.rs:1445-1447) -- and summed over the doc's

@@ -6,8 +6,11 @@
 
 typedef unsigned long long u64;
 
+// a score as an unsigned integer that orders like the score.  -0.0 is read as +0.0 first: the reference's stable sort compares
+// with partial_cmp, which ties them (a list may hold -0.0 before +0.0), so they share one key and keep concatenation order.
 __device__ __forceinline__ uint32_t mg_f2ord(float f) {
   uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;  // -0.0 -> +0.0
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 

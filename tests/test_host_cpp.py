@@ -816,3 +816,48 @@ def test_cpp_string_facet_rank_column_equals_the_python_mirror(H):
         out = np.zeros((len(v), rec.itemsize + 4), np.uint8)
         got_off = H.ssh_string_rank_column(raw.ctypes.data, len(v), rec.itemsize, off, N.FACET_TYPES[ty], blob, len(blob), len(words), out.ctypes.data)
         assert got_off == woff == rec.itemsize and np.array_equal(out, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S_n", [2, 3])
+def test_cpp_index_hybrid_determined_world_equals_the_exact_merge(H, S_n):
+    """Index::search(Hybrid) over shards that hold the same lexical data (few (tf, length byte) pairs) and the same i8 rows (integer
+    dots): every leg is fixed by the tie rules and every entry ties its twins in the other shards, so the fused page -- ids, f32
+    scores, sources -- and the total are naive.merge_exact's over the exact legs, bit for bit"""
+    from oracle import naive
+    from test_gpu_merge_edges import DIM, N_DOCS, N_ROWS, QUERIES, _int_rows, _lex_exact, _lex_world, _vec_exact_int
+    rng = np.random.default_rng(900 + S_n)
+    doclen, lists = _lex_world(rng, N_DOCS, True)
+    rows = _int_rows(rng, N_ROWS, DIM)
+    q8 = rng.integers(-1, 2, DIM).astype(np.int8)
+    qv = q8.astype(np.float32) / np.float32(127.0)
+    offs = np.zeros(len(lists) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(d) for d, _ in lists])
+    docs = np.concatenate([d for d, _ in lists]).astype(np.uint32)
+    tfs = np.concatenate([t for _, t in lists]).astype(np.uint16)
+    dots = _vec_exact_int(rows, q8)
+    vo = np.lexsort((np.arange(N_ROWS), -dots))
+    dev = (C.c_int * S_n)(*([0] * S_n))
+    ix = H.ssh_index_create(S_n, dev)
+    try:
+        for sid in range(S_n):
+            assert H.ssh_shard_ok(ix, sid) == 1
+            assert H.ssh_upload_lexical(ix, sid, N_DOCS, P(doclen, u8p), len(lists), P(offs, u64p), P(docs, u32p), P(tfs, u16p)) == 0
+            assert H.ssh_upload_vectors_i8(ix, sid, N_ROWS, DIM, rows.ctypes.data, None) == 0
+        for terms in QUERIES:
+            ids, sc = _lex_exact(N_DOCS, doclen, lists, terms)
+            for offset, length in ((0, 10), (3, 50), (650, 100), (1000, 1200)):
+                k = offset + length
+                lex = (ids[:k], sc[:k].astype(np.float32), len(ids))
+                vec = (vo[:k], dots[vo[:k]].astype(np.float32), N_ROWS)
+                want = naive.merge_exact(naive.MODE_HYBRID, [(lex, vec)] * S_n, S_n, offset, length)
+                d, s, src, _, _, meta = _search(H, ix, terms, qv, 1, 2, offset, length, normalize=False)
+                where = f"S={S_n} terms {terms} offset {offset} length {length}"
+                assert np.int64(meta[3]) == 0 and len(d) == meta[0] == len(want[0]), where
+                assert np.array_equal(d, want[0]), f"{where}: docs {d[:8].tolist()} ..., want {want[0][:8].tolist()} ..."
+                assert np.array_equal(s.view(np.uint32), want[1].view(np.uint32)), f"{where}: fused scores"
+                assert np.array_equal(src, want[2]), f"{where}: sources"
+                if N_ROWS <= k:  # (the vector leg's total is the row count only when it returns every row)
+                    assert meta[1] == want[3], f"{where}: total {int(meta[1])}, want {want[3]}"
+    finally:
+        H.ssh_index_destroy(ix)

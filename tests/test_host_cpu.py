@@ -188,6 +188,34 @@ def test_merge_results_matches_oracle(mode):
         assert np.array_equal(d, od) and np.allclose(s, os_, rtol=1e-6) and np.array_equal(src, osrc)
 
 
+@pytest.mark.parametrize("seed", range(3))
+def test_host_merge_equals_the_exact_merge_at_the_edges(seed):
+    """ss_merge_results (the host merge of Index.search and of the host-fused sharded hybrid) == naive.merge_exact bit for bit:
+    cross-shard lists from the edge palette (exact ties, both zeros in reference order, -inf, subnormals), every mode"""
+    import seekstorm_amd as S
+    from oracle import naive
+    rng = np.random.default_rng(40 + seed)
+    for trial in range(40):
+        Sn = int(rng.integers(1, 6))
+        lists, cat = [], [[], [], [], []]
+        for s in range(Sn):
+            pair = []
+            for w in range(2):
+                n = int(rng.integers(0, 15))
+                ids, sc = rng.choice(40, n, replace=False), naive.reference_sorted(rng.choice(naive.MERGE_PALETTE, n))
+                pair.append((ids, sc))
+                cat[2 * w] += [int(x) * Sn + s for x in ids]
+                cat[2 * w + 1] += sc.tolist()
+            lists.append(tuple(pair))
+        n_all = len(cat[0]) + len(cat[2])
+        offset, length = int(rng.integers(0, n_all + 2)), int(rng.integers(1, n_all + 2))
+        for mode in (0, 1, 2):
+            wd, ws, wsrc, _ = naive.merge_exact(mode, lists, Sn, offset, length)
+            d, s_, src = S.merge_results(mode, (cat[0], cat[1]), (cat[2], cat[3]), offset, length)
+            assert d.tolist() == wd.tolist() and np.array_equal(s_.view(np.uint32), ws.view(np.uint32)), (trial, mode)
+            assert src.tolist() == wsrc.tolist()
+
+
 def test_rrf_semantics():
     import seekstorm_amd as S
     # search.rs:1962-2035: k = 0.6, ranks from 0; doc in both lists sums and becomes Hybrid

@@ -849,3 +849,73 @@ def test_reference_vector_searches_meet_the_exact_cut(c, sigma):
         assert missed >= (4 * k // 2 if c / sigma >= 10000.0 else 1), missed
     if c == 0.0:
         assert missed == 0
+
+
+def _bits(x):
+    return np.asarray(x, np.float32).view(np.uint32).tolist()
+
+
+def test_merge_exact_hand_worked():
+    """naive.merge_exact on cases worked by hand: the stable sort of the cross-shard concatenation, RRF ranks over it, the final
+    order of equal fused scores (doc ascending), offset / length, totals"""
+    f = np.float32
+    # cross-shard exact ties keep concatenation order (shard order), not doc order: globals 10, 2 | 1, 7
+    lists = [(([5, 1], f([2.0, 1.0]), 4), None), (([0, 3], f([2.0, 1.0]), 6), None)]
+    d, s, src, tot = naive.merge_exact(naive.MODE_LEXICAL, lists, 2, 0, 10)
+    assert d.tolist() == [10, 1, 2, 7] and s.tolist() == [2.0, 2.0, 1.0, 1.0] and src.tolist() == [0] * 4 and tot == 10
+    # -0.0 ties +0.0 in either order and keeps its bits; -inf sorts last, ties too
+    lists = [(None, ([0, 1, 2], f([3.0, -0.0, -np.inf]), 3)), (None, ([0, 1, 2], f([0.0, -0.0, -np.inf]), 3)),
+             (None, ([0], f([-0.0]), 1))]
+    d, s, src, tot = naive.merge_exact(naive.MODE_VECTOR, lists, 3, 0, 10)
+    assert d.tolist() == [0, 3, 1, 4, 2, 6, 7]
+    assert _bits(s) == _bits([3.0, -0.0, 0.0, -0.0, -0.0, -np.inf, -np.inf]) and src.tolist() == [1] * 7 and tot == 7
+    # an offset past the end: an empty page, the total still counted
+    d, s, src, tot = naive.merge_exact(naive.MODE_VECTOR, lists, 3, 7, 5)
+    assert len(d) == len(s) == len(src) == 0 and tot == 7
+    assert len(naive.merge_exact(naive.MODE_VECTOR, lists, 3, 6, 5)[0]) == 1
+    r = [f(1) / (f(0.6) + f(i)) for i in range(4)]
+    # Hybrid: a lexical-only and a vector-only doc at the same rank tie -> doc ascending; (a, b) against (b, a) ties too
+    lists = [(([9, 7, 3], f([5.0, 4.0, 3.0]), 30), ([2, 3, 7], f([0.9, 0.8, 0.7]), 40))]
+    d, s, src, tot = naive.merge_exact(naive.MODE_HYBRID, lists, 1, 0, 10)
+    assert d.tolist() == [2, 9, 3, 7] and src.tolist() == [1, 0, 2, 2] and tot == 40
+    assert _bits(s) == _bits([r[0], r[0], r[2] + r[1], r[1] + r[2]])
+    # the ranks run over the whole cross-shard concatenation; totals: max(lexical, vector) per shard, summed
+    lists = [(([0, 1], f([4.0, 1.0]), 7), ([1], f([0.5]), 2)), (([0], f([2.0]), 1), ([0], f([0.75]), 5))]
+    d, s, src, tot = naive.merge_exact(naive.MODE_HYBRID, lists, 2, 1, 2)  # lex 0, 1, 2 (ranks 0-2); vec 1, 2 (ranks 0, 1): 1, 0, 2
+    assert d.tolist() == [0, 2] and src.tolist() == [0, 2] and _bits(s) == _bits([r[0], r[2] + r[1]]) and tot == 7 + 5
+    # a doc twice in the lexical concatenation: the later rank overwrites (AHashMap::insert)
+    d, s, src, _ = naive.merge_exact(naive.MODE_HYBRID, [(([5, 5, 6], f([2.0, 1.0, 0.5])), None)], 1, 0, 5)
+    assert d.tolist() == [5, 6] and _bits(s) == _bits([r[1], r[2]])
+    # a total left out is not invented
+    assert naive.merge_exact(naive.MODE_LEXICAL, [(([1], f([1.0])), None)], 1, 0, 5)[3] is None
+    assert naive.reference_sorted([0.0, -1.0, -0.0, 2.0]).tolist() == [2.0, 0.0, -0.0, -1.0]
+    assert _bits(naive.reference_sorted([-0.0, 0.0]))[0] == 0x80000000
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_merge_exact_agrees_with_the_oracle_merge(seed):
+    """naive.merge_exact == ss_oracle.c so_merge (two restatements of search.rs:1875-2119) bit for bit, on lists drawn from the
+    edge palette (exact ties across shards, both zeros, -inf, subnormals) and many equal fused scores"""
+    rng = np.random.default_rng(seed)
+    for trial in range(40):
+        S = int(rng.integers(1, 6))
+        lists, cat = [], [[], [], [], []]
+        for s in range(S):
+            pair = []
+            for w in range(2):
+                n = int(rng.integers(0, 12))
+                ids = rng.choice(30, n, replace=False)
+                sc = naive.reference_sorted(rng.choice(naive.MERGE_PALETTE, n))
+                pair.append((ids, sc, n + int(rng.integers(0, 3))) if n or rng.random() < 0.5 else None)
+                if pair[-1] is not None:
+                    cat[2 * w] += [int(x) * S + s for x in ids]
+                    cat[2 * w + 1] += sc.tolist()
+            lists.append(tuple(pair))
+        n_all = len(cat[0]) + len(cat[2])
+        offset, length = int(rng.integers(0, n_all + 3)), int(rng.integers(1, n_all + 3))
+        for mode in (naive.MODE_LEXICAL, naive.MODE_VECTOR, naive.MODE_HYBRID):
+            d, s_, src, tot = naive.merge_exact(mode, lists, S, offset, length)
+            od, os_, osrc = O.merge(mode, (cat[0], cat[1]), (cat[2], cat[3]), offset, length)
+            assert d.tolist() == od.tolist() and _bits(s_) == _bits(os_) and src.tolist() == osrc.tolist(), (seed, trial, mode)
+            t = [(0 if lx is None else lx[2], 0 if vx is None else vx[2]) for lx, vx in lists]
+            assert tot == sum(max(a, b) if mode == 2 else (a if mode == 0 else b) for a, b in t)
