@@ -551,7 +551,11 @@ int ss_bm25_search_filtered_dev(ss_shard* s, uint32_t n_queries, const ss_bm25_q
  * the last one <= the value (range_lower_bounds[n_buckets], ascending, the value's bits as in ss_facet_filter).
  * out_counts [n_buckets + 1]: the last slot = docs outside the buckets (an id >= n_buckets, a value below the first
  * bound).  *out_total (may be NULL) = the match count.  The match set is read from the probe index's bit records:
- * SS_ENOTSUP if a list of the query has no probe row (ss_bm25_term_probed). */
+ * SS_ENOTSUP if a dense list of the query has no probe row (ss_bm25_term_probed).  Terms of the SPARSE tier
+ * (ss_bm25_append_sparse[_fields]), scored or NOT, are answered too: their lists are merged into the bit records' match set on
+ * the device.  Left to the caller's own path (SS_ENOTSUP) when the query names a sparse term: phrases, SS_OP_ALL_TERMS_FREQUENT,
+ * unions of several terms under a field filter.  The same holds for ss_bm25_facet_kth, ss_bm25_search_sorted and the *_point
+ * entries below. */
 int ss_bm25_facet_count(ss_shard* s, const ss_bm25_query* query, uint32_t n_filters, const ss_facet_filter* filters,
                         uint32_t facet_offset, uint32_t facet_type, uint32_t n_buckets, const uint64_t* range_lower_bounds,
                         uint64_t* out_counts, uint64_t* out_total);

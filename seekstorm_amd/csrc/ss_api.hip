@@ -21,6 +21,7 @@
 #include "ss_threads.h"
 #include "facet_point.h"
 #include "bm25_build.h"
+#include "bm25_match.h"
 
 #define SS_TRY(x)          \
   do {                     \
@@ -3191,6 +3192,30 @@ int ss_hybrid_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const ss_bm25
                               out_count, out_total, s->stream, host_fuse);
 }
 
+// A batch for the entries that walk MATCH SETS (facet counts, the sort pivot, result sorts) on an image with a sparse tier: validated
+// with tier awareness and planned (bm25_match.h).  plan->any_tiered false: nothing names a sparse term, the caller's own path applies
+// untouched.  Else the dense lists of the whole batch have their probe rows and the dense parts have passed check_queries;
+// SS_ENOTSUP for what the tiered match set leaves to the caller's own path.
+static int tier_prepare(ss_shard* s, uint32_t nq, const ss_bm25_query* q, BmTierPlan* plan, hipStream_t st) {
+  plan->any_tiered = false;
+  if (!s->sp_n || nq > 64) return SS_OK;
+  SS_TRY(ssi_bm25_tier_plan(s, nq, q, plan));
+  if (!plan->any_tiered) return SS_OK;
+  SS_TRY(ssi_bm25_ensure_probe_rows(s, nq, q, st));  // (terms of the sparse tier are passed over)
+  std::vector<ss_bm25_query> dense;
+  for (uint32_t i = 0; i < nq; i++)
+    if (plan->has_sub[i]) dense.push_back(plan->sub[i]);
+  if (!dense.empty()) {
+    bool has_and, has_or, all_probed, any_frequent, phrase = false, any_filter = false, uniform = false, gated = false;
+    uint32_t nt_max, np_max;
+    SS_TRY(check_queries(s, (uint32_t)dense.size(), dense.data(), &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter,
+                         &uniform, &gated));
+    if (!all_probed || phrase) return SS_ENOTSUP;
+  }
+  if (!s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
+  return SS_OK;
+}
+
 // Facet counts of ONE query (query_facets / facet_count, add_result.rs:484-640): histogram of a facet over the query's match
 // set (after NOT terms, tombstones and the facet filter).  out_counts [n_buckets + 1]: a string facet's ids 0 .. n_buckets-1,
 // or the numeric ranges given by their ascending lower bounds; the last slot collects what falls outside.
@@ -3205,14 +3230,18 @@ static int facet_count_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_
   bool has_and, has_or, all_probed, any_frequent;
   uint32_t nt_max, np_max;
   ShardLock g(s);
-  SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, query, s->stream));
-  SS_TRY(check_queries(s, 1, query, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
-  if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
+  BmTierPlan plan;  // (a query naming a sparse-tier term: bm25_match.h)
+  SS_TRY(tier_prepare(s, 1, query, &plan, s->stream));
+  if (!plan.any_tiered) {
+    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, query, s->stream));
+    SS_TRY(check_queries(s, 1, query, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
+    if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
+  }
   SS_HIP(hipSetDevice(s->device));
   static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
-  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + ((size_t)n_buckets + 1) * 8 + (size_t)n_buckets * 8;
+  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + ((size_t)n_buckets + 1) * 8 + (size_t)n_buckets * 8 + sizeof(ss_bm25_query);
   if (bytes > s->facet_ws_cap) {  // grow-only workspace (a hipMalloc / hipFree pair per call would synchronise the device)
     if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
     s->d_facet_ws = nullptr;
@@ -3226,6 +3255,7 @@ static int facet_count_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_
   unsigned long long* d_bits = d_total + 1;
   unsigned long long* d_counts = d_bits + groups;
   uint64_t* d_bounds = (uint64_t*)(d_counts + n_buckets + 1);
+  ss_bm25_query* d_sub = (ss_bm25_query*)(d_bounds + n_buckets);  // a tiered query's dense part
   int rc = SS_OK;
   if (hipMemcpyAsync(d_q, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
       hipMemsetAsync(d_total, 0, 8 + groups * 8 + ((size_t)n_buckets + 1) * 8, s->stream) != hipSuccess ||
@@ -3233,7 +3263,10 @@ static int facet_count_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_
        hipMemcpyAsync(d_bounds, range_lower_bounds, (size_t)n_buckets * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess))
     rc = SS_EDEVICE;
   if (rc == SS_OK)
-    rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream); });
+    rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() {
+      return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, query, d_q, d_sub, d_bits, d_total, s->stream, 1)
+                             : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream);
+    });
   if (rc == SS_OK) rc = ssi_facet_count(s, d_bits, s->bm_n_docs, facet_offset, facet_type, n_buckets, d_bounds, d_counts, point, s->stream);
   if (rc == SS_OK && (hipMemcpyAsync(out_counts, d_counts, ((size_t)n_buckets + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
                       (out_total && hipMemcpyAsync(out_total, d_total, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)))
@@ -3266,14 +3299,18 @@ static int facet_kth_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_fi
   bool has_and, has_or, all_probed, any_frequent;
   uint32_t nt_max, np_max;
   ShardLock g(s);
-  SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, query, s->stream));
-  SS_TRY(check_queries(s, 1, query, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
-  if (!all_probed || !s->d_probe) return SS_ENOTSUP;
+  BmTierPlan plan;  // (a query naming a sparse-tier term: bm25_match.h)
+  SS_TRY(tier_prepare(s, 1, query, &plan, s->stream));
+  if (!plan.any_tiered) {
+    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, query, s->stream));
+    SS_TRY(check_queries(s, 1, query, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
+    if (!all_probed || !s->d_probe) return SS_ENOTSUP;
+  }
   SS_HIP(hipSetDevice(s->device));
   static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
-  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + 256 * 8;
+  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + 256 * 8 + sizeof(ss_bm25_query);
   if (bytes > s->facet_ws_cap) {
     if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
     s->d_facet_ws = nullptr;
@@ -3286,9 +3323,13 @@ static int facet_kth_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_fi
   unsigned long long* d_total = (unsigned long long*)(ws + sizeof(ss_bm25_query));
   unsigned long long* d_bits = d_total + 1;
   unsigned long long* d_hist = d_bits + groups;
+  ss_bm25_query* d_sub = (ss_bm25_query*)(d_hist + 256);  // a tiered query's dense part
   SS_HIP(hipMemcpyAsync(d_q, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
   SS_HIP(hipMemsetAsync(d_total, 0, 8 + groups * 8, s->stream));
-  SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream); }));
+  SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
+    return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, query, d_q, d_sub, d_bits, d_total, s->stream, 1)
+                           : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream);
+  }));
   uint64_t total = 0;
   SS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipStreamSynchronize(s->stream));
@@ -3331,7 +3372,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                o_ac = o_as + al((size_t)CH * k * 4), o_cd = o_ac + al((size_t)CH * 4), o_cs = o_cd + al((size_t)CH * k * 4),
                o_cc = o_cs + al((size_t)CH * k * 4), o_at = o_cc + al((size_t)CH * 4), o_od = o_at + al((size_t)CH * 8),
                o_os = o_od + al((size_t)nq * k * 4), o_oc = o_os + al((size_t)nq * k * 4), o_ot = o_oc + al((size_t)nq * 4),
-               need = o_ot + al((size_t)nq * 8);
+               o_sub = o_ot + al((size_t)nq * 8), need = o_sub + al((size_t)CH * sizeof(ss_bm25_query));
   if (need > s->sort_ws_cap) {
     SS_HIP(hipStreamSynchronize(s->stream));
     if (s->d_sort_ws) (void)hipFree(s->d_sort_ws);
@@ -3346,18 +3387,28 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                      *d_xe = (unsigned long long*)(W + o_xe);
   SS_TRY(ensure_out(s, 1, k));
   constexpr int batched_off = 0;
+  std::vector<BmTierPlan> plans((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
   for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = queries + c0;
-    bool has_and, has_or, all_probed, any_frequent, phrase = false, any_filter = false, uniform = false, gated = false;
-    uint32_t nt_max, np_max, nn_max = 0;
-    SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qc, s->stream));
-    SS_TRY(check_queries(s, nb, qc, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
-    if (!all_probed || !s->d_probe || phrase) return SS_ENOTSUP;
+    bool has_and = false, has_or = false, all_probed = false, any_frequent = false, phrase = false, any_filter = false, uniform = false, gated = false;
+    uint32_t nt_max = 0, np_max = 0, nn_max = 0;
+    // a chunk that names a sparse-tier term: its match sets from both tiers (bm25_match.h), its two searches query by query below
+    // (bm25_search_host_queries routes each to bm25_search_tiered under the swapped exclusion bitmap); select and compose stay batched
+    BmTierPlan& plan = plans[c0 / CH];
+    SS_TRY(tier_prepare(s, nb, qc, &plan, s->stream));
+    if (!plan.any_tiered) {
+      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qc, s->stream));
+      SS_TRY(check_queries(s, nb, qc, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
+      if (!all_probed || !s->d_probe || phrase) return SS_ENOTSUP;
+    }
     SS_HIP(hipMemcpyAsync(d_q, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_match_bits(s, d_q, d_E, d_total, s->stream, nb); }));
+    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
+      return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, qc, d_q, (ss_bm25_query*)(W + o_sub), d_E, d_total, s->stream, nb)
+                             : ssi_bm25_match_bits(s, d_q, d_E, d_total, s->stream, nb);
+    }));
     SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, k, s->stream));
-    bool batched = !batched_off;
+    bool batched = !batched_off && !plan.any_tiered;
     for (int part = 0; part < 2 && batched; part++) {  // both searches as ONE batch each: every query under its own exclusion bitmap
       uint32_t* del = s->d_deleted;
       const uint64_t dw = s->deleted_words, nd = s->n_deleted;
