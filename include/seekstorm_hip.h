@@ -15,6 +15,8 @@
  *                       field_filter (1225-1237, 1397-1400), Precision::I8 records (vector_similarity.rs:1011-1016, 1754-1758)
  *   ss_bm25_search_filtered, ss_bm25_facet_count
  *                    <- facet_filter / query_facets of search_lexical_shard (add_result.rs:341-640)
+ *   ss_bm25_search_facets
+ *                    <- the same search returning ResultObject.facets beside its hits (add_result.rs:487-643, search.rs:3598-3760)
  *   ss_index_bin_*, ss_ref_decode_block*, ss_vec_upload_vector_bin*
  *                    <- readers of the shard files and in-RAM blocks (index.rs:3263-3740, vector.rs:1066-1094,
  *                       add_result.rs:2036-2293)
@@ -605,6 +607,29 @@ int ss_bm25_facet_kth_point(ss_shard* s, const ss_bm25_query* query, uint32_t n_
                             uint64_t* out_n_better, uint64_t* out_n_equal, uint64_t* out_total);
 int ss_facet_point_distances(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t facet_offset, const ss_facet_point* base,
                              uint64_t* out_values);
+
+/* A search WITH its query_facets, as ONE call for a batch (the crate's search(.., query_facets, ..) -> ResultObject.facets: facet_count,
+ * add_result.rs:487-643, bumps every requested facet for every counted doc; the shard finishes the maps, search.rs:3598-3760; the
+ * planner sums them over the shards, search.rs:1747-1870).  out_doc / out_score / out_count / out_total: exactly what
+ * ss_bm25_search_filtered writes for the same arguments (that entry's direct path runs -- never the lexical coalescer, whose answers are
+ * the same: deep pages k > SS_MAX_K and sparse-tier terms included;
+ * SS_RT_COUNT: the doc outputs may be NULL).  out_facet_counts [n_queries][sum_f (n_buckets[f] + 1)]: per query, facet after facet in
+ * the order given, the n_buckets[f] + 1 counters ss_bm25_facet_count[_point] writes for that query and facet (same bucket rule, the
+ * last slot = "other"); a facet's counters sum to the query's exact match count.  facet_offset / facet_type / n_buckets [n_facets];
+ * range_lower_bounds: the bounds of the numeric and Point facets back to back in facet order (string facets have none);
+ * bases [n_facets]: read for SS_FACET_POINT facets only, may be NULL without one.  All facets of all queries of a chunk of <= 64
+ * queries are counted by one kernel launch over the chunk's match sets; the facet filter's bitmap is built once per call.
+ * n_facets = 0: ss_bm25_search_filtered.  SS_EINVAL: more than SS_MAX_QUERY_FACETS facets, a type beyond SS_FACET_POINT, a Point facet
+ * without bases, bounds missing, n_buckets 0 or above 2^24.  SS_ESTATE: no facet records, or an offset beyond the record.
+ * SS_ENOTSUP -- for the whole call, outputs unspecified -- for the shapes ss_bm25_facet_count leaves to the caller (above: a phrase, a
+ * dense list without a probe row, and with a sparse term SS_OP_ALL_TERMS_FREQUENT or a union of several terms under a field filter);
+ * pool rows are dealt per chunk of <= 64 queries, so a chunk can be refused whose queries ss_bm25_facet_count serves one by one. */
+#define SS_MAX_QUERY_FACETS 16
+int ss_bm25_search_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* queries, uint32_t k, uint32_t result_type,
+                          uint32_t n_filters, const ss_facet_filter* filters,
+                          uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
+                          const uint64_t* range_lower_bounds, const ss_facet_point* bases,
+                          uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
 
 /* ------------------------------------------------------------------ vector image
  * rows: row-major [n_rows x dim] f32, already L2-normalised for cosine (vector.rs:585-596); the uploader of

@@ -48,6 +48,7 @@ class FacetFilterC(C.Structure):  # ss_facet_filter
 
 
 SS_MAX_FACET_FILTERS = 8
+SS_MAX_QUERY_FACETS = 16
 FACET_HI_INCLUSIVE, FACET_LO_EXCLUSIVE = 1, 2
 FACET_IDS_EXTERN = 0xFFFFFFFF
 FACET_TYPES = {"u8": 0, "u16": 1, "u32": 2, "u64": 3, "i8": 4, "i16": 5, "i32": 6, "i64": 7, "f32": 8, "f64": 9,
@@ -197,6 +198,8 @@ SYMBOLS = [
     ("ss_bm25_facet_kth_point", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                           C.c_uint64, u64p, u64p, u64p, u64p]),
     ("ss_facet_point_distances", C.c_int, [C.c_void_p, C.c_uint32, u32p, C.c_uint32, C.c_void_p, u64p]),
+    ("ss_bm25_search_facets", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                        C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
     ("ss_bm25_search_sharded", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     ("ss_rrf_merge_dev", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,

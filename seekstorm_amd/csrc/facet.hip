@@ -650,3 +650,177 @@ int ssi_facet_count(ss_shard* s, const unsigned long long* d_bits, uint64_t n_do
                     const uint64_t* d_bounds, unsigned long long* d_counts, hipStream_t st) {
   return ssi_facet_count(s, d_bits, n_docs, offset, type, n_buckets, d_bounds, d_counts, nullptr, st);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Facet counts of a BATCH: every requested facet of every query in ONE launch (ss_bm25_search_facets; query_facets of a search,
+// add_result.rs:487-643 bumps every facet for every counted doc).  blockIdx.y = the query, blockIdx.x = a slice of 256 * wpt words of
+// its match bitmap.  The slice's matches are COMPACTED onto the lanes: a popcount prefix over the slice's words (in LDS), then match i
+// of the slice is found by a binary search over the prefix and a rank select inside the word -- a 1 % match set keeps every lane
+// busy where one thread per 64-doc group would leave 99 % idle.  A matched doc's record is visited once for all its facets.
+// Counters are 32-bit LDS histograms (FM_LDS_COUNTERS words shared by the facets that fit, in facet order), flushed once per
+// workgroup with one 64-bit global atomic per non-zero counter; a facet of <= FM_AGGREGATE buckets adds lane-aggregated (one add per
+// distinct bucket of the wave).  A facet whose counters do not fit (string facets of many ids) counts straight into global memory:
+// its ids spread over many lines.  Bounds of the range facets are staged in LDS (the first FM_LDS_BOUNDS of them).
+// LDS: 4 KiB words + 2 KiB prefix + 8 KiB counters + 4 KiB bounds = 18 KiB: eight workgroups (32 waves) per CU.
+constexpr uint32_t FM_THREADS = 256, FM_MAX_WPT = 2, FM_LDS_COUNTERS = 2048, FM_LDS_BOUNDS = 512, FM_AGGREGATE = 16, FM_NO_LDS = 0xFFFFFFFFu;
+struct FacetMultiDesc {
+  uint32_t offset, type, n_buckets;
+  uint32_t bounds_begin;  // of its lower bounds inside the batch's bounds (range facets)
+  uint32_t cnt_begin;     // of its n_buckets + 1 counters inside a query's row
+  uint32_t lds_begin;     // of its LDS counters, FM_NO_LDS: counts in global memory
+  FacetPoint pt;
+};
+struct FacetMulti {
+  uint32_t n, lds_used, n_bounds, pad;
+  unsigned long long stride;  // counters per query
+  FacetMultiDesc f[SS_MAX_QUERY_FACETS];
+};
+
+// the bucket of one doc's value: facet_count_kernel's rule, word for word
+__device__ __forceinline__ uint32_t facet_bucket(const uint8_t* p, uint32_t stored_type, uint32_t n_buckets, const unsigned long long* bounds,
+                                                 const FacetPoint& pt) {
+  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
+  uint32_t type = stored_type;
+  unsigned long long v = facet_load(p, width[stored_type], type, pt);
+  if (type == SS_FACET_I8) v = (unsigned long long)(long long)(int8_t)v;      // sign-extend for the comparisons
+  else if (type == SS_FACET_I16) v = (unsigned long long)(long long)(int16_t)v;
+  else if (type == SS_FACET_I32) v = (unsigned long long)(long long)(int32_t)v;
+  if (type == SS_FACET_STRING16 || type == SS_FACET_STRING32) return v < n_buckets ? (uint32_t)v : n_buckets;
+  uint32_t lo = 0, hi = n_buckets;  // number of bounds <= v
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (facet_le(type, bounds[mid], v)) lo = mid + 1; else hi = mid;
+  }
+  return lo ? lo - 1 : n_buckets;  // below the first bound (or NaN): "other"
+}
+// position of the r-th (0-based) set bit of m; r < popcount(m)
+__device__ __forceinline__ uint32_t facet_select64(unsigned long long m, uint32_t r) {
+  uint32_t pos = 0, c = (uint32_t)__popc((uint32_t)m);
+  if (r >= c) { r -= c; m >>= 32; pos = 32; }
+  uint32_t x = (uint32_t)m;
+  c = (uint32_t)__popc(x & 0xFFFFu); if (r >= c) { r -= c; x >>= 16; pos += 16; }
+  c = (uint32_t)__popc(x & 0xFFu); if (r >= c) { r -= c; x >>= 8; pos += 8; }
+  c = (uint32_t)__popc(x & 0xFu); if (r >= c) { r -= c; x >>= 4; pos += 4; }
+  c = (uint32_t)__popc(x & 3u); if (r >= c) { r -= c; x >>= 2; pos += 2; }
+  if (r >= (x & 1u)) pos += 1;
+  return pos;
+}
+
+__global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned long long* __restrict__ bits, unsigned long long groups,
+                                                                 unsigned long long n_docs, const uint8_t* __restrict__ records,
+                                                                 uint32_t record_size, uint32_t wpt, const unsigned long long* __restrict__ bounds,
+                                                                 unsigned long long* __restrict__ counts, FacetMulti F) {
+  __shared__ unsigned long long s_word[FM_THREADS * FM_MAX_WPT];
+  __shared__ uint32_t s_pre[FM_THREADS * FM_MAX_WPT + 1];
+  __shared__ uint32_t s_wave[FM_THREADS / 64];
+  __shared__ uint32_t s_cnt[FM_LDS_COUNTERS];
+  __shared__ unsigned long long s_bounds[FM_LDS_BOUNDS];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t W = FM_THREADS * wpt;  // words of this slice (wpt <= FM_MAX_WPT)
+  const unsigned long long w0 = (unsigned long long)blockIdx.x * W;
+  bits += (size_t)blockIdx.y * groups;
+  counts += (size_t)blockIdx.y * F.stride;
+  unsigned long long mw[FM_MAX_WPT];
+  uint32_t c = 0;
+  for (uint32_t j = 0; j < FM_MAX_WPT; j++) {
+    mw[j] = 0ull;
+    if (j < wpt) {
+      const unsigned long long g = w0 + (unsigned long long)tid * wpt + j;
+      unsigned long long m = g < groups ? bits[g] : 0ull;
+      if (m && g * 64ull + 64ull > n_docs) m = g * 64ull >= n_docs ? 0ull : (m & ((1ull << (n_docs - g * 64ull)) - 1ull));  // no doc behind the last
+      mw[j] = m;
+      s_word[tid * wpt + j] = m;
+      c += (uint32_t)__popcll(m);
+    }
+  }
+  uint32_t inc = c;  // inclusive scan of the threads' match counts: inside the wave, then over the waves
+  for (uint32_t o = 1; o < 64u; o <<= 1) {
+    const uint32_t y = __shfl_up(inc, o);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63u) s_wave[wave] = inc;
+  __syncthreads();
+  uint32_t base = 0, T = 0;
+  for (uint32_t w = 0; w < FM_THREADS / 64; w++) { if (w < wave) base += s_wave[w]; T += s_wave[w]; }
+  if (T == 0) return;  // (the whole workgroup: nothing matched in this slice)
+  uint32_t e = base + inc - c;
+  for (uint32_t j = 0; j < FM_MAX_WPT; j++)
+    if (j < wpt) { s_pre[tid * wpt + j] = e; e += (uint32_t)__popcll(mw[j]); }
+  if (tid == 0) s_pre[W] = T;
+  for (uint32_t i = tid; i < F.lds_used; i += FM_THREADS) s_cnt[i] = 0u;
+  const uint32_t nb_lds = F.n_bounds < FM_LDS_BOUNDS ? F.n_bounds : FM_LDS_BOUNDS;
+  for (uint32_t i = tid; i < nb_lds; i += FM_THREADS) s_bounds[i] = bounds[i];
+  __syncthreads();
+  for (uint32_t i = tid; i < T; i += FM_THREADS) {
+    uint32_t lo = 0, hi = W;  // s_pre[lo] <= i < s_pre[hi]: the word that holds match i
+    while (hi - lo > 1u) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (s_pre[mid] <= i) lo = mid; else hi = mid;
+    }
+    const unsigned long long d = (w0 + lo) * 64ull + facet_select64(s_word[lo], i - s_pre[lo]);  // < n_docs: the words were masked
+    const uint8_t* rec = records + d * record_size;
+    for (uint32_t f = 0; f < F.n; f++) {
+      const FacetMultiDesc& D = F.f[f];
+      const unsigned long long* bnd = D.bounds_begin + D.n_buckets <= nb_lds ? s_bounds + D.bounds_begin : bounds + D.bounds_begin;
+      const uint32_t b = facet_bucket(rec + D.offset, D.type, D.n_buckets, bnd, D.pt);
+      if (D.n_buckets <= FM_AGGREGATE) {  // few buckets: one add per distinct bucket of the wave
+        unsigned long long todo = __ballot(1);
+        while (todo) {
+          const int leader = __builtin_ctzll(todo);
+          const uint32_t lb = (uint32_t)__shfl((int)b, leader);
+          const unsigned long long same = __ballot(b == lb) & todo;
+          if ((int)lane == leader) {
+            if (D.lds_begin != FM_NO_LDS) atomicAdd(&s_cnt[D.lds_begin + lb], (uint32_t)__popcll(same));
+            else atomicAdd(&counts[D.cnt_begin + lb], (unsigned long long)__popcll(same));
+          }
+          todo &= ~same;
+        }
+      } else if (D.lds_begin != FM_NO_LDS) {
+        atomicAdd(&s_cnt[D.lds_begin + b], 1u);
+      } else {
+        atomicAdd(&counts[D.cnt_begin + b], 1ull);
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t f = 0; f < F.n; f++) {
+    const FacetMultiDesc& D = F.f[f];
+    if (D.lds_begin == FM_NO_LDS) continue;
+    for (uint32_t i = tid; i <= D.n_buckets; i += FM_THREADS) {
+      const uint32_t v = s_cnt[D.lds_begin + i];
+      if (v) atomicAdd(&counts[D.cnt_begin + i], (unsigned long long)v);
+    }
+  }
+}
+
+// d_bits [nq][groups] match sets, d_bounds: the range facets' lower bounds back to back in facet order, d_counts [nq][sum_f (n_buckets[f] + 1)]
+// (zeroed by the caller).  The arguments were validated by the caller (types, bases, offsets inside the record).
+int ssi_facet_count_multi(ss_shard* s, uint32_t nq, const unsigned long long* d_bits, uint32_t n_facets, const uint32_t* offset, const uint32_t* type,
+                          const uint32_t* n_buckets, const ss_facet_point* bases, const uint64_t* d_bounds, unsigned long long* d_counts,
+                          hipStream_t st) {
+  if (nq == 0 || nq > 65535u || n_facets == 0 || n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
+  FacetMulti F;
+  memset(&F, 0, sizeof(F));
+  F.n = n_facets;
+  for (uint32_t f = 0; f < n_facets; f++) {
+    FacetMultiDesc& D = F.f[f];
+    D.offset = offset[f]; D.type = type[f]; D.n_buckets = n_buckets[f];
+    D.pt = FacetPoint{0, 0, 0};
+    if (type[f] == SS_FACET_POINT && facet_point_of(bases ? bases + f : nullptr, &D.pt) != SS_OK) return SS_EINVAL;
+    const bool strings = type[f] == SS_FACET_STRING16 || type[f] == SS_FACET_STRING32;
+    D.bounds_begin = F.n_bounds;
+    if (!strings) F.n_bounds += n_buckets[f];
+    D.cnt_begin = (uint32_t)F.stride;
+    F.stride += (unsigned long long)n_buckets[f] + 1ull;
+    D.lds_begin = FM_NO_LDS;
+    if (n_buckets[f] + 1u <= FM_LDS_COUNTERS - F.lds_used) { D.lds_begin = F.lds_used; F.lds_used += n_buckets[f] + 1u; }
+  }
+  const unsigned long long groups = (unsigned long long)s->bm_n_sub * (BM_SUB / 64);
+  // two words per thread unless that leaves the chip short of workgroups
+  const uint32_t wpt = ((groups + 2 * FM_THREADS - 1) / (2 * FM_THREADS)) * nq >= 2048u ? 2u : 1u;
+  const dim3 grid((unsigned)((groups + (unsigned long long)FM_THREADS * wpt - 1) / ((unsigned long long)FM_THREADS * wpt)), nq);
+  facet_multi_kernel<<<grid, FM_THREADS, 0, st>>>(d_bits, groups, (unsigned long long)s->bm_n_docs, s->d_facets, s->facet_record_size, wpt,
+                                                  (const unsigned long long*)d_bounds, d_counts, F);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}

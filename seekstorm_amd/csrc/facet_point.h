@@ -10,3 +10,7 @@ int ssi_facet_values(ss_shard* s, const uint32_t* d_docs, uint32_t n, uint32_t o
                      const ss_facet_point* point, hipStream_t st);
 int ssi_facet_count(ss_shard* s, const unsigned long long* d_bits, uint64_t n_docs, uint32_t offset, uint32_t type, uint32_t n_buckets,
                     const uint64_t* d_bounds, unsigned long long* d_counts, const ss_facet_point* point, hipStream_t st);
+// every facet of every query of a batch in one launch (facet.hip: "Facet counts of a BATCH")
+int ssi_facet_count_multi(ss_shard* s, uint32_t nq, const unsigned long long* d_bits, uint32_t n_facets, const uint32_t* offset, const uint32_t* type,
+                          const uint32_t* n_buckets, const ss_facet_point* bases, const uint64_t* d_bounds, unsigned long long* d_counts,
+                          hipStream_t st);

@@ -30,12 +30,13 @@
   } while (0)
 
 namespace {
-// runs `search` with the shard's tombstone bitmap replaced by the filter's exclusion bitmap (built on `st` first)
+// runs `search` with the shard's tombstone bitmap replaced by the filter's exclusion bitmap (built on `st` first; `prebuilt`: the caller
+// has built THESE filters' bitmap on `st` already and nothing has written d_filter_bits since -- ss_bm25_search_facets builds it once)
 template <typename F>
-int with_facet_filter(ss_shard* s, uint32_t n_filters, const ss_facet_filter* filters, hipStream_t st, F search) {
+int with_facet_filter(ss_shard* s, uint32_t n_filters, const ss_facet_filter* filters, hipStream_t st, F search, bool prebuilt = false) {
   if (n_filters == 0) return search();
   if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;  // a record for every doc of the lexical image
-  int rc = ssi_facet_build(s, n_filters, filters, st);
+  int rc = prebuilt ? SS_OK : ssi_facet_build(s, n_filters, filters, st);
   if (rc) return rc;
   uint32_t* del = s->d_deleted;
   const uint64_t words = s->deleted_words, n = s->n_deleted;
@@ -1465,7 +1466,7 @@ static int bm25_search_split_batch(ss_shard* s, uint32_t nq, const ss_bm25_query
 }
 
 static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
-                                    const ss_facet_filter* filters);
+                                    const ss_facet_filter* filters, bool filter_prebuilt = false);
 
 // A batch in which some query names a term of the SPARSE tier (bm25_sparse.hip).  Those queries are answered in two parts -- their
 // dense terms through the ordinary path (together with the batch's all-dense queries: one sub-batch), their sparse lists by the
@@ -1967,7 +1968,7 @@ static int bm25_shape_of(const ss_shard* s, const ss_bm25_query& Q, uint32_t kk,
 }
 
 static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
-                                    const ss_facet_filter* filters);
+                                    const ss_facet_filter* filters, bool filter_prebuilt);
 static int bm25_search_compose(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& composed);
 
 // *handled = false: every query is NATIVE (`*use` = the batch to run: q itself, or `norm` -- the copy with the dropped bits)
@@ -2049,9 +2050,9 @@ static int bm25_route_shapes(ss_shard* s, uint32_t nq, const ss_bm25_query* q, u
 
 // the search of ss_bm25_search_filtered / _sharded up to the device lists (s->d_out_*, on s->stream); caller holds s->mu
 static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
-                                    const ss_facet_filter* filters) {
+                                    const ss_facet_filter* filters, bool filter_prebuilt) {
   // (a facet filter: its exclusion bitmap stands in for the tombstones of everything below -- every kernel family reads the same one)
-  if (n_filters) return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return bm25_search_host_queries(s, nq, q, kk, rt, 0, nullptr); });
+  if (n_filters) return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return bm25_search_host_queries(s, nq, q, kk, rt, 0, nullptr); }, filter_prebuilt);
   std::vector<ss_bm25_query> norm;
   {
     bool handled = false;
@@ -2394,9 +2395,10 @@ static int bm25_answers_home(ss_shard* s, uint32_t nq, uint32_t kk, uint32_t* ou
   return SS_OK;
 }
 
-static int bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
-                              const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
-  ShardLock g(s);  // before check_queries: it reads the image's host-side tables (an upload replaces them)
+// (the caller holds the shard lock -- taken before check_queries: it reads the image's host-side tables, which an upload replaces)
+static int bm25_search_direct_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
+                                     const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
+                                     bool filter_prebuilt = false) {
   if (!s->d_post) return SS_ESTATE;
   const uint32_t kk = rt == SS_RT_COUNT ? 0 : k, kw = std::max<uint32_t>(kk, 1u);
   // by shape, like a coalesced batch (bm25_search_direct_lane): the queries that fit the one-launch path take it, the staged pipeline
@@ -2437,7 +2439,7 @@ static int bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, 
       memcpy(out_total, s->h_small + SM_H_TOTAL, (size_t)nq * sizeof(uint64_t));
       return SS_OK;
     }
-    SS_TRY(bm25_search_host_queries(s, nq, q, kk, rt, n_filters, filters));
+    SS_TRY(bm25_search_host_queries(s, nq, q, kk, rt, n_filters, filters, filter_prebuilt));
     return bm25_answers_home(s, nq, kk, out_doc, out_score, out_count, out_total);
   }
   // split: the staged part behind the launch on the same stream, its answers into rows [r0, nq) of a host copy in run order
@@ -2475,6 +2477,11 @@ static int bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, 
     out_total[i] = t_tot[r];
   }
   return SS_OK;
+}
+static int bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
+                              const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
+  ShardLock g(s);
+  return bm25_search_direct_locked(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
 }
 
 // the same for a coalesced batch on a lane: the shard mutex is held while the batch is ENQUEUED (queries from the lane's pinned staging,
@@ -3500,6 +3507,114 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
     out_total[i] = total;
   }
   return SS_OK;
+}
+
+// A search WITH its query_facets (search.rs:3598-3760 finishes what add_result.rs:487-643 counted beside the hits): the facet counts
+// of the whole batch are enqueued first -- per chunk of <= 64 queries one match-set build (both tiers) and ONE launch that counts every
+// facet of every query (facet.hip: "Facet counts of a BATCH") -- and the search itself runs behind them on the same stream, through
+// ss_bm25_search_filtered's direct path (bm25_search_direct_locked / bm25_search_deep_locked: that entry's answers, bit for bit; where
+// the lexical coalescer is on, that entry hands an unfiltered request to it -- this one never does, the answers are the same).  The
+// facet filter's bitmap is built once for all of it (`prebuilt`).  Waits: the search waits for its own answers (a deep page once per
+// pass), and by then the counters are done; their copy home into the caller's pageable array and the wait that ends it are the call's
+// second, short one -- the search paths own their waits, and the counters are not theirs to carry.  A workspace that has to grow waits
+// for the stream before it is freed, the first time only.
+static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t n_filters, const ss_facet_filter* filters,
+                               uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
+                               const uint64_t* range_lower_bounds, const ss_facet_point* bases, size_t n_bounds, size_t stride,
+                               std::vector<BmTierPlan>& plans, unsigned long long** d_counts_out) {
+  const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
+  const bool prebuilt = n_filters != 0;  // (the entry built the bitmap)
+  const uint32_t CH = std::min<uint32_t>(nq, 64u);  // (tier_prepare plans batches of <= 64, ssi_bm25_match_bits takes as many)
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_q = 0, o_sub = o_q + al((size_t)CH * sizeof(ss_bm25_query)), o_tot = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
+               o_bits = o_tot + al((size_t)CH * 8), o_bounds = o_bits + al((size_t)CH * groups * 8), o_cnt = o_bounds + al(n_bounds * 8),
+               need = o_cnt + al((size_t)nq * stride * 8);
+  if (need > s->facet_ws_cap) {  // grow-only workspace
+    SS_HIP(hipStreamSynchronize(s->stream));
+    if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
+    s->d_facet_ws = nullptr;
+    s->facet_ws_cap = 0;
+    SS_HIP(hipMalloc(&s->d_facet_ws, need));
+    s->facet_ws_cap = need;
+  }
+  char* W = (char*)s->d_facet_ws;
+  ss_bm25_query *d_q = (ss_bm25_query*)(W + o_q), *d_sub = (ss_bm25_query*)(W + o_sub);
+  unsigned long long *d_total = (unsigned long long*)(W + o_tot), *d_bits = (unsigned long long*)(W + o_bits), *d_counts = (unsigned long long*)(W + o_cnt);
+  uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
+  *d_counts_out = d_counts;
+  SS_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * stride * 8, s->stream));
+  if (n_bounds) SS_HIP(hipMemcpyAsync(d_bounds, range_lower_bounds, n_bounds * 8, hipMemcpyHostToDevice, s->stream));
+  plans.resize((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
+  for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
+    const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
+    const ss_bm25_query* qc = q + c0;
+    BmTierPlan& plan = plans[c0 / CH];  // (a chunk naming a sparse-tier term: bm25_match.h)
+    SS_TRY(tier_prepare(s, nb, qc, &plan, s->stream));
+    if (!plan.any_tiered) {
+      bool has_and, has_or, all_probed, any_frequent;
+      uint32_t nt_max, np_max;
+      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qc, s->stream));
+      SS_TRY(check_queries(s, nb, qc, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));  // (phrases: SS_ENOTSUP, as ss_bm25_facet_count)
+      if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
+    }
+    SS_HIP(hipMemcpyAsync(d_q, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+    SS_HIP(hipMemsetAsync(d_total, 0, (size_t)((char*)(d_bits + (size_t)nb * groups) - (char*)d_total), s->stream));
+    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
+      return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, qc, d_q, d_sub, d_bits, d_total, s->stream, nb)
+                             : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream, nb);
+    }, prebuilt));
+    SS_TRY(ssi_facet_count_multi(s, nb, d_bits, n_facets, facet_offset, facet_type, n_buckets, bases, d_bounds, d_counts + (size_t)c0 * stride, s->stream));
+  }
+  return SS_OK;
+}
+
+int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
+                          const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type,
+                          const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases, uint32_t* out_doc,
+                          float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts) {
+  if (n_facets == 0) return ss_bm25_search_filtered(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
+  if (!s || !q || !out_count || !out_total || !out_facet_counts || !facet_offset || !facet_type || !n_buckets) return SS_EINVAL;
+  if (rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
+  if (rt != SS_RT_COUNT && (k == 0 || !out_doc || !out_score)) return SS_EINVAL;
+  if (n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
+  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
+  size_t n_bounds = 0, stride = 0;
+  for (uint32_t f = 0; f < n_facets; f++) {
+    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
+    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
+    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) n_bounds += n_buckets[f];
+    stride += (size_t)n_buckets[f] + 1;
+  }
+  if (n_bounds && !range_lower_bounds) return SS_EINVAL;
+  if (!s->d_post) return SS_ESTATE;
+  if (nq == 0) return SS_OK;
+  for (uint32_t i = 0; i < nq; i++)
+    if (bm_q_op(q[i].op) == SS_OP_PHRASE) return SS_ENOTSUP;  // match sets hold no phrases (as ss_bm25_facet_count answers one)
+  ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
+  if (!s->d_post) return SS_ESTATE;
+  SS_HIP(hipSetDevice(s->device));
+  if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
+  for (uint32_t f = 0; f < n_facets; f++)
+    if ((uint64_t)facet_offset[f] + width[facet_type[f]] > s->facet_record_size) return SS_ESTATE;
+  std::vector<BmTierPlan> plans;
+  unsigned long long* d_counts = nullptr;
+  int rc = SS_OK;
+  if (n_filters) {  // one exclusion bitmap for the match sets and the search
+    rc = ssi_facet_build(s, n_filters, filters, s->stream);
+  }
+  if (rc == SS_OK)
+    rc = bm25_facets_enqueue(s, nq, q, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, n_bounds, stride,
+                             plans, &d_counts);
+  if (rc == SS_OK) {
+    // (the crate's offset + length is unbounded: a page deeper than SS_MAX_K results is answered in passes, as ss_bm25_search_filtered does)
+    if (rt != SS_RT_COUNT && k > SS_MAX_K)
+      rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); }, true);
+    else
+      rc = bm25_search_direct_locked(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total, true);
+  }
+  if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) rc = SS_EDEVICE;
+  if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (also on an error: the plans and the caller's arrays are being read)
+  return rc;
 }
 
 static int facet_values_impl(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t facet_offset, uint32_t facet_type,

@@ -38,6 +38,76 @@ static int write_out(const ResultObject& ro, uint32_t cap, uint64_t* out_doc, fl
   return (int)n;
 }
 
+// query facets cross this shim as text, one facet per line, tab-separated (labels hold neither tabs nor newlines):
+//   R <field> <offset> <SS_FACET_*> <range type 0 within | 1 above | 2 below> <base lat> <base lon> <unit> <prefix> <n> {<label> <bound bits>}
+//   S <field> <offset> <SS_FACET_*> <prefix> <length> <n> {<value of id>}
+//   T <field> <offset> <SS_FACET_*> <prefix> <length> <n sets> {<members of the set> {<member>}}
+// and facets come back as lines <field> <label> <count> (a facet without entries: <field> alone)
+static std::vector<std::string> split(const std::string& s, char sep) {
+  std::vector<std::string> out;
+  size_t at = 0;
+  for (;;) {
+    const size_t e = s.find(sep, at);
+    out.push_back(s.substr(at, e == std::string::npos ? e : e - at));
+    if (e == std::string::npos) break;
+    at = e + 1;
+  }
+  return out;
+}
+static bool parse_facets(const char* spec, std::vector<QueryFacet>* out) {
+  for (const std::string& line : split(spec ? spec : "", '\n')) {
+    if (line.empty()) continue;
+    const std::vector<std::string> t = split(line, '\t');
+    QueryFacet qf;
+    if (t.size() < 4) return false;
+    qf.field = t[1];
+    qf.facet_offset = (uint32_t)strtoul(t[2].c_str(), nullptr, 10);
+    qf.facet_type = (uint32_t)strtoul(t[3].c_str(), nullptr, 10);
+    if (t[0] == "R") {
+      if (t.size() < 10) return false;
+      qf.range_type = (RangeType)strtoul(t[4].c_str(), nullptr, 10);
+      qf.base = ss_facet_point{strtod(t[5].c_str(), nullptr), strtod(t[6].c_str(), nullptr), (uint32_t)strtoul(t[7].c_str(), nullptr, 10), 0};
+      qf.prefix = t[8];
+      const size_t n = strtoul(t[9].c_str(), nullptr, 10);
+      if (t.size() != 10 + 2 * n) return false;
+      for (size_t i = 0; i < n; i++) qf.ranges.emplace_back(t[10 + 2 * i], strtoull(t[11 + 2 * i].c_str(), nullptr, 10));
+    } else if (t[0] == "S" || t[0] == "T") {
+      if (t.size() < 7) return false;
+      qf.prefix = t[4];
+      qf.length = (uint32_t)strtoul(t[5].c_str(), nullptr, 10);
+      const size_t n = strtoul(t[6].c_str(), nullptr, 10);
+      size_t at = 7;
+      if (t[0] == "S") {
+        if (t.size() != 7 + n) return false;
+        qf.values.assign(t.begin() + 7, t.end());
+      } else {
+        qf.string_set = true;
+        for (size_t i = 0; i < n; i++) {
+          if (at >= t.size()) return false;
+          const size_t m = strtoul(t[at++].c_str(), nullptr, 10);
+          if (at + m > t.size()) return false;
+          qf.set_values.emplace_back(t.begin() + at, t.begin() + at + m);
+          at += m;
+        }
+      }
+    } else {
+      return false;
+    }
+    out->push_back(std::move(qf));
+  }
+  return true;
+}
+static int write_facets(const Facets& f, char* out, uint32_t cap) {
+  std::string s;
+  for (const auto& kv : f) {
+    if (kv.second.empty()) s += kv.first + "\n";
+    for (const auto& e : kv.second) s += kv.first + "\t" + e.first + "\t" + std::to_string(e.second) + "\n";
+  }
+  if (s.size() + 1 > cap) return SS_EINVAL;
+  memcpy(out, s.c_str(), s.size() + 1);
+  return (int)s.size();
+}
+
 extern "C" {
 
 float ssh_idf(uint64_t n_docs, uint64_t posting_count) { return idf(n_docs, posting_count); }
@@ -416,6 +486,34 @@ int ssh_index_search_lexical_batch(ssh_index* ix, uint32_t n, const uint32_t* te
     }
   }
   return err;
+}
+
+// finish_facets of every shard's raw counters (counts [n_shards][sum_f (n_buckets + 1)]), then merge_facets when merge != 0 (else
+// shard 0's map as finished); no device.  Returns the length of the text written, or a negative code.
+int ssh_facets_finish(const char* spec, uint32_t n_shards, const uint64_t* counts, uint32_t shard_number, int merge, uint32_t result_type,
+                      char* out, uint32_t cap) {
+  std::vector<QueryFacet> qf;
+  if (!parse_facets(spec, &qf) || n_shards == 0) return SS_EINVAL;
+  size_t stride = 0;
+  for (const QueryFacet& f : qf) stride += (size_t)f.n_buckets() + 1;
+  std::vector<Facets> maps;
+  for (uint32_t i = 0; i < n_shards; i++) maps.push_back(finish_facets(qf, counts + i * stride, shard_number));
+  return write_facets(merge ? merge_facets(qf, maps, (ResultType)result_type) : maps[0], out, cap);
+}
+
+// Index::search (SearchMode::Lexical) with query_facets; results as ssh_search writes them, ResultObject::facets as text into
+// out_facets (*facets_len = its length, or a negative code)
+int ssh_index_search_facets(ssh_index* ix, const uint32_t* terms, uint32_t n_terms, uint32_t query_type, uint32_t offset, uint32_t length,
+                            uint32_t result_type, uint32_t n_filters, const ss_facet_filter* filters, const char* spec, uint32_t cap,
+                            uint64_t* out_doc, float* out_score, uint64_t* out_meta, char* out_facets, uint32_t facets_cap, int* facets_len) {
+  std::vector<QueryFacet> qf;
+  if (!parse_facets(spec, &qf)) return SS_EINVAL;
+  std::vector<uint32_t> t(terms, terms + n_terms);
+  std::vector<ss_facet_filter> f(filters, filters + n_filters);
+  ResultObject ro = ix->index->search(t, nullptr, (QueryType)query_type, SearchMode::Lexical, offset, length, (ResultType)result_type, nullptr,
+                                      true, AnnMode(), {}, f, {}, {}, qf);
+  *facets_len = write_facets(ro.facets, out_facets, facets_cap);
+  return write_out(ro, cap, out_doc, out_score, nullptr, nullptr, nullptr, out_meta);
 }
 
 }  // extern "C"

@@ -343,9 +343,80 @@ bool Shard::mark_all_terms_frequent(ss_bm25_query* q, size_t top_k) const {
   return true;
 }
 
+Facets finish_facets(const std::vector<QueryFacet>& query_facets, const uint64_t* counts, size_t shard_number) {
+  Facets out;
+  const uint64_t cap = shard_number == 1 ? 0 : 0xFFFFFFFFull;  // facet_cap, search.rs:2466-2470
+  for (const QueryFacet& qf : query_facets) {
+    const uint32_t nb = qf.n_buckets();
+    const uint64_t* c = counts;
+    counts += (size_t)nb + 1;
+    std::vector<std::pair<uint32_t, uint64_t>> present;  // the crate's map: only what somebody counted into
+    for (uint32_t i = 0; i < nb; i++)
+      if (c[i]) present.emplace_back(i, c[i]);
+    Facet v;
+    if (qf.is_range()) {
+      if (qf.range_type == RangeType::CountAboveRange) {
+        uint64_t sum = 0;
+        for (size_t j = present.size(); j-- > 0;) { sum += present[j].second; present[j].second = sum; }
+      } else if (qf.range_type == RangeType::CountBelowRange) {
+        uint64_t sum = 0;
+        for (auto& e : present) { sum += e.second; e.second = sum; }
+      }
+      for (const auto& e : present) {
+        const std::string& label = qf.ranges[e.first].first;
+        if (qf.prefix.empty() || label.compare(0, qf.prefix.size(), qf.prefix) == 0) v.emplace_back(label, e.second);
+      }
+    } else {
+      if (qf.length == 0 || present.empty()) continue;
+      Facet pairs;
+      if (qf.string_set) {  // a set id's count goes to every member string (search.rs:3615-3637)
+        std::map<std::string, uint64_t> acc;
+        for (const auto& e : present)
+          for (const std::string& term : qf.set_values[e.first]) acc[term] += e.second;
+        pairs.assign(acc.begin(), acc.end());
+      } else {
+        for (const auto& e : present) pairs.emplace_back(qf.values[e.first], e.second);
+      }
+      std::stable_sort(pairs.begin(), pairs.end(), [](const auto& a, const auto& b) { return a.second > b.second; });
+      const uint64_t take = std::max<uint64_t>(qf.length, cap);
+      for (const auto& e : pairs) {
+        if (v.size() >= take) break;
+        if (qf.prefix.empty() || e.first.compare(0, qf.prefix.size(), qf.prefix) == 0) v.push_back(e);
+      }
+    }
+    if (!v.empty()) out[qf.field] = std::move(v);
+  }
+  return out;
+}
+
+Facets merge_facets(const std::vector<QueryFacet>& query_facets, const std::vector<Facets>& shard_maps, ResultType result_type) {
+  Facets out;
+  if (result_type == ResultType::Topk) return out;  // search.rs:1748
+  for (const QueryFacet& qf : query_facets) {
+    std::map<std::string, uint64_t> acc;
+    for (const Facets& m : shard_maps) {
+      auto it = m.find(qf.field);
+      if (it == m.end()) continue;
+      for (const auto& e : it->second) acc[e.first] += e.second;
+    }
+    Facet v(acc.begin(), acc.end());
+    std::stable_sort(v.begin(), v.end(), [](const auto& a, const auto& b) { return a.second > b.second; });
+    const size_t length = qf.is_range() ? 0xFFFFu : qf.length;
+    if (v.size() > length) v.resize(length);
+    out[qf.field] = std::move(v);
+  }
+  return out;
+}
+
 std::vector<ResultObject> Shard::search_lexical_batch(const std::vector<ss_bm25_query>& queries, size_t k,
                                                       ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
                                                       bool mark_frequent) {
+  return search_facets(queries, k, result_type, {}, facet_filter, 1, nullptr, mark_frequent);
+}
+
+std::vector<ResultObject> Shard::search_facets(const std::vector<ss_bm25_query>& queries, size_t k, ResultType result_type,
+                                               const std::vector<QueryFacet>& query_facets, const std::vector<ss_facet_filter>& facet_filter,
+                                               size_t shard_number, std::vector<uint64_t>* counts_out, bool mark_frequent) {
   const size_t nq = queries.size();
   std::vector<ResultObject> out(nq);
   if (nq == 0) return out;
@@ -366,13 +437,29 @@ std::vector<ResultObject> Shard::search_lexical_batch(const std::vector<ss_bm25_
     }
     if (!marked.empty()) qp = marked.data();
   }
-  const int rc = h_ ? ss_bm25_search_filtered(h_, (uint32_t)nq, qp, (uint32_t)k, (uint32_t)result_type,
-                                              (uint32_t)facet_filter.size(), facet_filter.empty() ? nullptr : facet_filter.data(),
-                                              doc.data(), score.data(), cnt.data(), tot.data())
+  // (no query facets: n_facets = 0 is ss_bm25_search_filtered)
+  const size_t nf = query_facets.size();
+  std::vector<uint32_t> f_off(nf), f_type(nf), f_nb(nf);
+  std::vector<uint64_t> bounds, counts;
+  std::vector<ss_facet_point> bases(nf);
+  size_t stride = 0;
+  for (size_t f = 0; f < nf; f++) {
+    const QueryFacet& qf = query_facets[f];
+    f_off[f] = qf.facet_offset; f_type[f] = qf.facet_type; f_nb[f] = qf.n_buckets(); bases[f] = qf.base;
+    if (qf.is_range())
+      for (const auto& r : qf.ranges) bounds.push_back(r.second);
+    stride += (size_t)f_nb[f] + 1;
+  }
+  counts.assign(nq * stride, 0);
+  const int rc = h_ ? ss_bm25_search_facets(h_, (uint32_t)nq, qp, (uint32_t)k, (uint32_t)result_type,
+                                            (uint32_t)facet_filter.size(), facet_filter.empty() ? nullptr : facet_filter.data(),
+                                            (uint32_t)nf, f_off.data(), f_type.data(), f_nb.data(), bounds.empty() ? nullptr : bounds.data(),
+                                            bases.data(), doc.data(), score.data(), cnt.data(), tot.data(), counts.data())
                     : (create_rc_ ? create_rc_ : SS_ESTATE);
   for (size_t q = 0; q < nq; q++) {
     ResultObject& ro = out[q];
     if (rc != SS_OK) { ro.last_error = rc; continue; }  // degrade to empty (search.rs:2461-2463)
+    if (nf) ro.facets = finish_facets(query_facets, counts.data() + q * stride, shard_number);
     const size_t n = result_type == ResultType::Count ? 0 : cnt[q];
     ro.results.resize(n);
     for (size_t i = 0; i < n; i++) {
@@ -387,6 +474,7 @@ std::vector<ResultObject> Shard::search_lexical_batch(const std::vector<ss_bm25_
     ro.result_count = n;
     ro.result_count_total = tot[q];
   }
+  if (counts_out) *counts_out = rc == SS_OK ? std::move(counts) : std::vector<uint64_t>();
   return out;
 }
 
@@ -685,8 +773,10 @@ int Shard::sorted_topk(const ss_bm25_query& q, const ResultSort* sorts, size_t n
 ResultObject Shard::search_lexical_shard(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset,
                                          size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
                                          const std::vector<uint32_t>& not_terms, const std::vector<uint16_t>& field_filter,
-                                         const std::vector<ResultSort>& result_sort) {
+                                         const std::vector<ResultSort>& result_sort, const std::vector<QueryFacet>& query_facets,
+                                         size_t shard_number) {
   ResultObject ro;
+  if (!query_facets.empty() && !result_sort.empty()) { ro.last_error = SS_EINVAL; return ro; }  // query_facets belong to searches by score
   // a union of several terms under a field filter goes down like any other query: per-term gating inside the scan kernels (<= 7
   // terms, round 3) or the reference's own sub-queries composed BEHIND the ABI (8 .. 10 terms, a sparse-tier term; round 6).
   {
@@ -701,7 +791,7 @@ ResultObject Shard::search_lexical_shard(const std::vector<uint32_t>& query_term
       ro.result_count_total = total;
       ro.result_count = ro.results.size();
     } else {
-      ro = std::move(search_lexical_batch({q}, offset + length, result_type, facet_filter)[0]);
+      ro = std::move(search_facets({q}, offset + length, result_type, query_facets, facet_filter, shard_number)[0]);
     }
   }
   if (offset) {  // drain offset (search.rs:3585-3593)
@@ -761,13 +851,15 @@ ResultObject Index::search(const std::vector<uint32_t>& query_terms, const float
                            SearchMode search_mode, size_t offset, size_t length, ResultType result_type,
                            const float* similarity_threshold, bool normalize_query, const AnnMode& ann_mode,
                            const std::vector<uint16_t>& vector_field_filter, const std::vector<ss_facet_filter>& facet_filter,
-                           const std::vector<uint32_t>& not_terms, const std::vector<uint16_t>& lexical_field_filter) {
+                           const std::vector<uint32_t>& not_terms, const std::vector<uint16_t>& lexical_field_filter,
+                           const std::vector<QueryFacet>& query_facets) {
   ResultObject ro;
   const size_t S = shards_.size();
   if (S == 0) return ro;
   const bool want_lex = (search_mode == SearchMode::Lexical || search_mode == SearchMode::Hybrid) && !query_terms.empty();
   const bool want_vec = (search_mode == SearchMode::Vector || search_mode == SearchMode::Hybrid) && query_vector != nullptr;
-  if (!comms_.empty() && want_lex && !want_vec && facet_filter.empty() && not_terms.empty() && lexical_field_filter.empty()) {
+  if (!query_facets.empty() && !want_lex) { ro.last_error = SS_EINVAL; return ro; }  // facets come from the lexical side: none to count
+  if (!comms_.empty() && want_lex && !want_vec && facet_filter.empty() && not_terms.empty() && lexical_field_filter.empty() && query_facets.empty()) {
     // shards on different GPUs (enable_device_exchange): every shard task searches its shard and the lists are exchanged and
     // merged on the devices over xGMI (ss_bm25_search_sharded) -- offset / length are applied to the merged list, as
     // search.rs:2109-2119 applies them after the gather
@@ -786,7 +878,7 @@ ResultObject Index::search(const std::vector<uint32_t>& query_terms, const float
   bool f32_images = true;
   for (const auto& sh : shards_) f32_images = f32_images && !sh->vectors_are_i8() && sh->dim() == qv.size();
   if (!comms_.empty() && want_vec && (want_lex || search_mode == SearchMode::Vector) && f32_images && ann_mode.kind == AnnMode::Kind::All &&
-      vector_field_filter.empty() && facet_filter.empty() && not_terms.empty() && lexical_field_filter.empty() &&
+      vector_field_filter.empty() && facet_filter.empty() && not_terms.empty() && lexical_field_filter.empty() && query_facets.empty() &&
       result_type != ResultType::Count && length > 0) {
     // Vector / Hybrid over shards on different GPUs: every shard task runs its searches at (0, offset + length), the lists travel
     // in ONE all-gather and are merged -- Hybrid: fused by RRF over the cross-shard concatenations -- on the devices
@@ -847,7 +939,7 @@ ResultObject Index::search(const std::vector<uint32_t>& query_terms, const float
   auto task = [&](size_t i) {
     Shard& sh = *shards_[i];
     if (want_lex) lex[i] = sh.search_lexical_shard(query_terms, query_type_default, 0, offset + length, result_type, facet_filter, not_terms,
-                                                   lexical_field_filter);
+                                                   lexical_field_filter, {}, query_facets, S);
     if (want_vec && qv.size() == sh.dim()) vec[i] = sh.search_vector_shard(qv.data(), offset + length, similarity_threshold, ann_mode, vector_field_filter);
   };
   if (S == 1) {
@@ -894,6 +986,11 @@ ResultObject Index::search(const std::vector<uint32_t>& query_terms, const float
           if (vd[j] == od[i]) { r.vector_score = vector_score_of(vs[j]); break; }
       }
     }
+  }
+  if (want_lex && !query_facets.empty()) {  // facets come from the lexical side (search.rs:1929-1939)
+    std::vector<Facets> maps;
+    for (size_t i = 0; i < S; i++) maps.push_back(lex[i].facets);
+    ro.facets = merge_facets(query_facets, maps, result_type);
   }
   ro.result_count = ro.results.size();
   return ro;

@@ -22,6 +22,7 @@
 
 #include <condition_variable>
 #include <future>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -58,9 +59,14 @@ struct Result {
   ResultSource source = ResultSource::Lexical;
 };
 
+// search.rs Facet: (label, count) pairs -- a string facet's values or a range facet's range labels
+using Facet = std::vector<std::pair<std::string, uint64_t>>;
+using Facets = std::map<std::string, Facet>;  // by the facet's field (search.rs:211 AHashMap<String, Facet>)
+
 // search.rs:186-213 (fields of this path)
 struct ResultObject {
   std::vector<Result> results;
+  Facets facets;                    // query_facets of the search (lexical side)
   uint64_t result_count = 0;        // = results.len()
   uint64_t result_count_total = 0;  // exact match count for Count / TopkCount; accepted pushes for vectors
   uint64_t observed_vector_count = 0;
@@ -102,6 +108,35 @@ std::vector<uint8_t> string_facet_rank_column(const uint8_t* records, uint64_t n
 // FacetFilter::Point (search.rs:852-859) as an ss_facet_filter: the distance to base inside [lo, hi), unit SS_POINT_KM / _MILES
 ss_facet_filter point_facet_filter(uint32_t facet_offset, const double base[2], double lo, double hi, uint32_t unit, uint32_t flags = 0);
 
+
+// search.rs QueryFacet + RangeType.  A RANGE facet (U8 .. F64, Timestamp = I64, Point): `ranges` = (label, lower bound as the value's
+// bits, f64 distance bits for Point) ascending, range_type, and for Point the base with its unit.  A STRING facet (String16/32;
+// string_set: StringSet16/32 over the same id column): the facet's values table by id (the crate's facets[i].values) -- `values`, or
+// `set_values` = the member strings of every set id --, prefix, length.
+enum class RangeType { CountWithinRange, CountAboveRange, CountBelowRange };
+struct QueryFacet {
+  std::string field;
+  uint32_t facet_offset = 0;
+  uint32_t facet_type = SS_FACET_U32;  // SS_FACET_*
+  std::vector<std::pair<std::string, uint64_t>> ranges;
+  RangeType range_type = RangeType::CountWithinRange;
+  ss_facet_point base = {0.0, 0.0, SS_POINT_KM, 0};
+  bool string_set = false;
+  std::vector<std::string> values;
+  std::vector<std::vector<std::string>> set_values;
+  std::string prefix;
+  uint32_t length = 0xFFFF;
+  bool is_range() const { return facet_type != SS_FACET_STRING16 && facet_type != SS_FACET_STRING32; }
+  uint32_t n_buckets() const { return (uint32_t)(is_range() ? ranges.size() : string_set ? set_values.size() : values.size()); }
+};
+// What a shard does to its raw counters before it answers (search.rs:3604-3760).  counts: facet after facet, n_buckets + 1 counters
+// each (the last one, "other", has no key in the crate's map).  Range facets: range_type over the ranges somebody fell into, listed
+// by range index; string facets: id -> string (a set id: every member string), count descending, prefix, take(max(length, cap)) with
+// cap = 0 for one shard and unlimited for several (facet_cap, search.rs:2466-2470).  length 0 or nothing counted: left out.
+Facets finish_facets(const std::vector<QueryFacet>& query_facets, const uint64_t* counts, size_t shard_number);
+// The planner's part (search.rs:1747-1870, 1929-1939, 2039-2048): the shards' maps summed by key, count descending, cut to the
+// facet's length (u16::MAX for range facets); every requested facet has an entry; ResultType::Topk: none at all.
+Facets merge_facets(const std::vector<QueryFacet>& query_facets, const std::vector<Facets>& shard_maps, ResultType result_type);
 
 // One shard image on one MI355X.
 class Shard {
@@ -174,7 +209,13 @@ class Shard {
   ResultObject search_lexical_shard(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset,
                                     size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter = {},
                                     const std::vector<uint32_t>& not_terms = {}, const std::vector<uint16_t>& field_filter = {},
-                                    const std::vector<ResultSort>& result_sort = {});
+                                    const std::vector<ResultSort>& result_sort = {}, const std::vector<QueryFacet>& query_facets = {},
+                                    size_t shard_number = 1);
+  // search_lexical_batch with the batch's query_facets in the same call (ss_bm25_search_facets): counts [n_queries][sum_f (n_buckets
+  // + 1)] raw counters, ResultObject::facets = finish_facets of each query's row (shard_number: of the index, for the crate's cap)
+  std::vector<ResultObject> search_facets(const std::vector<ss_bm25_query>& queries, size_t k, ResultType result_type,
+                                          const std::vector<QueryFacet>& query_facets, const std::vector<ss_facet_filter>& facet_filter = {},
+                                          size_t shard_number = 1, std::vector<uint64_t>* counts = nullptr, bool mark_frequent = true);
   // query_facets of one query (facet_count, add_result.rs:484-640): counts [n_buckets + 1], the last slot = outside the buckets.
   // String facets: n_buckets ids (bounds empty); numeric facets: the ranges' ascending lower bounds as the value's bits;
   // Point facets (facet_type SS_FACET_POINT): base + the lower bounds of the distance ranges as f64 bits.
@@ -257,7 +298,7 @@ class Index {
                       const float* similarity_threshold = nullptr, bool normalize_query = true,
                       const AnnMode& ann_mode = AnnMode(), const std::vector<uint16_t>& vector_field_filter = {},
                       const std::vector<ss_facet_filter>& facet_filter = {}, const std::vector<uint32_t>& not_terms = {},
-                      const std::vector<uint16_t>& lexical_field_filter = {});
+                      const std::vector<uint16_t>& lexical_field_filter = {}, const std::vector<QueryFacet>& query_facets = {});
 
  private:
   std::vector<std::shared_ptr<Shard>> shards_;

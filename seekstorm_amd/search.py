@@ -67,6 +67,7 @@ class ResultObject:  # search.rs:186-213
     observed_vector_count: int = 0
     observed_cluster_count: int = 0
     cpu_dispatch: bool = False  # SS_ENOTSUP: not an empty answer -- the reference's own dispatch block (search.rs:3374-3560) answers it
+    facets: dict = field(default_factory=dict)  # field -> [(label, count)] (search.rs:211 AHashMap<String, Facet>)
 
 
 SIMILARITY_NORMALIZATION_64_I8 = np.float32(1.0) / np.float32(16129.0)  # vector.rs:29
@@ -153,6 +154,87 @@ def threshold_raw(similarity_threshold, euclidean=False):
     if euclidean:
         return float(-np.float32(similarity_threshold))
     return float(((np.float32(similarity_threshold) * np.float32(2.0)) - np.float32(1.0)) / SIMILARITY_NORMALIZATION_64_I8)
+
+
+# ---- query_facets (search.rs:1747-1870, 2039-2048, 3598-3760).  A query facet is a dict:
+#   {"field", "offset", "type": "u8" .. "f64" | "point", "ranges": [(label, lower bound)], "range_type": "within" | "above" | "below"
+#    [, "base": (lat, lon), "unit": "km" | "miles"]}                                                   -- QueryFacet::U8 .. ::Point
+#   {"field", "offset", "type": "string16" | "string32", "values": [string of id 0, 1, ...], "prefix": "", "length": 10}
+#   {"field", "offset", "type": "stringset16" | "stringset32", "values": [[member strings of set id 0], ...], "prefix", "length"}
+U16_MAX = 0xFFFF
+FACET_CAP_ONE_SHARD, FACET_CAP_SHARDS = 0, 0xFFFFFFFF  # facet_cap, search.rs:2466-2470
+
+
+def _facet_is_range(qf):
+    return not qf["type"].startswith("string")
+
+
+def finish_facets(query_facets, counts, shard_number=1):
+    """What a shard does to its raw counters before it answers (search.rs:3604-3760).  counts[f]: the n_buckets + 1 counters of
+    facet f (the last one, "other", has no key in the crate's map and is dropped).  -> {field: [(label, count)]}.
+    Range facets: range_type applied over the ranges somebody fell into (the crate's map holds no others), listed by range index.
+    String facets: id -> string, count descending, prefix filter, take(max(length, cap)); cap = 0 for one shard, unlimited for several.
+    StringSet facets: a set id's count goes to every member string of the set first.  A facet of length 0 or without a count: left out.
+    (Among equal counts the crate's order is that of an unstable sort over a hash map: any.)"""
+    cap = FACET_CAP_ONE_SHARD if shard_number == 1 else FACET_CAP_SHARDS
+    out = {}
+    for qf, c in zip(query_facets, counts):
+        c = [int(x) for x in c]
+        nb = len(c) - 1
+        present = [(i, c[i]) for i in range(nb) if c[i]]
+        if _facet_is_range(qf):
+            if not present:
+                continue
+            rt = qf.get("range_type", "within")
+            if rt == "above":  # CountAboveRange: from the highest range down
+                run, acc = 0, {}
+                for i, n in reversed(present):
+                    run += n
+                    acc[i] = run
+                present = [(i, acc[i]) for i, _ in present]
+            elif rt == "below":
+                run, acc = 0, {}
+                for i, n in present:
+                    run += n
+                    acc[i] = run
+                present = [(i, acc[i]) for i, _ in present]
+            elif rt != "within":
+                raise ValueError("range_type: within | above | below")
+            prefix = qf.get("prefix", "")
+            v = [(qf["ranges"][i][0], n) for i, n in present if not prefix or qf["ranges"][i][0].startswith(prefix)]
+        else:
+            length = int(qf.get("length", U16_MAX))
+            if length == 0 or not present or not qf["values"]:
+                continue
+            if qf["type"].startswith("stringset"):
+                acc = {}
+                for i, n in present:
+                    for term in qf["values"][i]:
+                        acc[term] = acc.get(term, 0) + n
+                pairs = list(acc.items())
+            else:
+                pairs = [(qf["values"][i], n) for i, n in present]
+            pairs.sort(key=lambda e: -e[1])
+            prefix = qf.get("prefix", "")
+            v = [e for e in pairs if not prefix or e[0].startswith(prefix)][:max(length, cap)]
+        if v:
+            out[qf["field"]] = v
+    return out
+
+
+def merge_facets(query_facets, shard_maps, result_type=None):
+    """The planner's part (search.rs:1747-1870, 1929-1939, 2039-2048): the shards' maps summed by key, count descending, cut to the
+    facet's length (u16::MAX for range facets).  Every requested facet has an entry, an empty list if nobody counted into it;
+    ResultType.Topk: no facets at all (search.rs:1748)."""
+    if result_type is not None and int(result_type) == int(ResultType.Topk):
+        return {}
+    acc = {qf["field"]: ({}, U16_MAX if _facet_is_range(qf) else int(qf.get("length", U16_MAX))) for qf in query_facets}
+    for m in shard_maps:
+        for key, lst in m.items():
+            if key in acc:
+                for label, n in lst:
+                    acc[key][0][label] = acc[key][0].get(label, 0) + n
+    return {key: sorted(m.items(), key=lambda e: -e[1])[:length] for key, (m, length) in acc.items()}
 
 
 @dataclass(frozen=True)
@@ -1033,6 +1115,54 @@ class Shard:
                 "ss_bm25_search_filtered")
         return doc, score, cnt, tot
 
+    @staticmethod
+    def _facet_bounds(qf):
+        """a range facet's lower bounds in ss_facet_filter's bit form"""
+        lows = [b for _, b in qf["ranges"]]
+        if qf["type"] in ("f64", "point"):
+            return np.asarray(lows, np.float64).view(np.uint64).copy()
+        if qf["type"] == "f32":
+            return np.asarray(lows, np.float32).view(np.uint32).astype(np.uint64)
+        return np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in lows], np.uint64)
+
+    def search_lexical_facets(self, queries, k, query_facets, result_type=ResultType.TopkCount, facet_filter=None, reference_shortcuts=True):
+        """search_lexical_batch with the batch's query_facets in the same call (ss_bm25_search_facets): -> (doc, score, count, total,
+        counts_per_facet), counts_per_facet[f] = [n_queries][n_buckets + 1] raw counters of facet f (last column: "other"), what
+        finish_facets takes per query.  doc / score / count / total are search_lexical_batch's."""
+        if reference_shortcuts and result_type != ResultType.Count and not facet_filter and \
+                (self.lexical_field_count == 1 or self.fields_info()[1]):
+            queries = self.mark_all_terms_frequent(queries, k)
+        nq, nf_ = len(queries), len(query_facets)
+        kk = max(int(k), 1)
+        doc = np.full((nq, kk), N.SS_NO_DOC, np.uint32)
+        score = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.uint32)
+        tot = np.zeros(nq, np.uint64)
+        off = np.array([int(qf["offset"]) for qf in query_facets], np.uint32)
+        ty = np.array([N.FACET_TYPES[qf["type"].replace("stringset", "string")] for qf in query_facets], np.uint32)
+        bounds = [self._facet_bounds(qf) for qf in query_facets if _facet_is_range(qf)]
+        nb = np.array([len(qf["ranges"]) if _facet_is_range(qf) else len(qf["values"]) for qf in query_facets], np.uint32)
+        allb = np.concatenate(bounds) if bounds else None
+        bases = None
+        if any(qf["type"] == "point" for qf in query_facets):
+            bases = (N.FacetPointC * nf_)()
+            for i, qf in enumerate(query_facets):
+                if qf["type"] == "point":
+                    bases[i] = self._point(qf["base"], qf.get("unit", "km"))
+        stride = int(nb.astype(np.int64).sum()) + nf_
+        out = np.zeros((nq, stride), np.uint64)
+        farr, nf = self.facet_filters(facet_filter) if facet_filter else (None, 0)
+        N.check(N.lib().ss_bm25_search_facets(self._h, nq, queries.ctypes.data_as(C.c_void_p), int(k), int(result_type), nf,
+                                              None if farr is None else C.cast(farr, C.c_void_p), nf_, N.ptr(off, N.u32p), N.ptr(ty, N.u32p),
+                                              N.ptr(nb, N.u32p), N.ptr(allb, N.u64p), None if bases is None else C.cast(bases, C.c_void_p),
+                                              N.ptr(doc, N.u32p), N.ptr(score, N.f32p), N.ptr(cnt, N.u32p), N.ptr(tot, N.u64p),
+                                              N.ptr(out, N.u64p)), "ss_bm25_search_facets")
+        per, at = [], 0
+        for n in nb:
+            per.append(out[:, at:at + int(n) + 1])
+            at += int(n) + 1
+        return doc, score, cnt, tot, per
+
     def search_vector_batch(self, query_vectors, k, similarity_threshold=None, ann_mode=None, with_clusters=False,
                             field_filter=None, with_observed=False):
         """with_observed: -> (..., observed_cluster_count, observed_vector_count) per query (vector.rs:421, 1394, 1510)"""
@@ -1059,8 +1189,9 @@ class Shard:
     # ---- the reference's per-shard seams (one query)
     def search_lexical_shard(self, query_terms, query_type_default=QueryType.Union, offset=0, length=10,
                              result_type=ResultType.TopkCount, strict=False, not_terms=(), field_filter=None,
-                             facet_filter=None) -> ResultObject:
-        """search.rs:2427-2442: field_filter = indexed field ids, facet_filter = see facet_filters()"""
+                             facet_filter=None, query_facets=None, shard_number=1) -> ResultObject:
+        """search.rs:2427-2442: field_filter = indexed field ids, facet_filter = see facet_filters(), query_facets = see
+        finish_facets() (ResultObject.facets; shard_number: of the index, for the crate's facet_cap)"""
         ro = ResultObject()
         try:
             uniq = list(dict.fromkeys(int(t) for t in query_terms))
@@ -1069,9 +1200,15 @@ class Shard:
             # host-side composition below stays as a second route for the tests (compose_filtered_unions = True, <= 5 terms)
             if (field_filter and self.lexical_field_count > 1 and int(query_type_default) == int(QueryType.Union) and len(uniq) > 1
                     and self.compose_filtered_unions):
+                if query_facets:  # (outside the try: an argument error, whatever `strict`)
+                    raise NotImplementedError("query_facets with the host-side composition of a union under a field filter")
                 return self._union_with_field_filter(uniq, offset, length, result_type, not_terms, field_filter, facet_filter)
             q = self.make_queries([query_terms], query_type_default, [not_terms], field_filter=field_filter)
-            doc, score, cnt, tot = self.search_lexical_batch(q, offset + length, result_type, facet_filter=facet_filter)
+            if query_facets:
+                doc, score, cnt, tot, per = self.search_lexical_facets(q, offset + length, query_facets, result_type, facet_filter)
+                ro.facets = finish_facets(query_facets, [c[0] for c in per], shard_number)
+            else:
+                doc, score, cnt, tot = self.search_lexical_batch(q, offset + length, result_type, facet_filter=facet_filter)
         except Exception as e:
             if strict:
                 raise
@@ -1338,14 +1475,19 @@ class Index:
     def search(self, query_terms: Optional[Sequence[int]] = None, query_vector=None,
                query_type_default=QueryType.Union, search_mode=SearchMode.Lexical, offset=0, length=10,
                result_type=ResultType.TopkCount, similarity_threshold=None, normalize_query=True,
-               strict=False, not_terms=(), field_filter=None, facet_filter=None, ann_mode=None, result_sort=None) -> ResultObject:
+               strict=False, not_terms=(), field_filter=None, facet_filter=None, ann_mode=None, result_sort=None,
+               query_facets=None) -> ResultObject:
         """<IndexArc as Search>::search (search.rs:1134-1150): field_filter applies to both sides (lexical: several indexed
         fields; vector: records of the listed fields), facet_filter to the lexical side, ann_mode to the vector side.
         result_sort (SearchMode.Lexical; see Shard.search_lexical_sorted): every shard returns its best offset + length under
         the sort, the lists are merged under the same order across shards -- the facet values of the two docs, each read from its
-        own shard, then the score (result_ordering_root, min_heap.rs:56-300; search.rs:2088)"""
+        own shard, then the score (result_ordering_root, min_heap.rs:56-300; search.rs:2088).
+        query_facets (SearchMode.Lexical / Hybrid; see finish_facets): counted on the lexical side of every shard in the same call as
+        its hits, the shards' maps merged into ResultObject.facets (merge_facets)"""
         S = self.shard_number
         ro = ResultObject()
+        if query_facets and (result_sort or search_mode not in (SearchMode.Lexical, SearchMode.Hybrid) or not query_terms):
+            raise ValueError("query_facets apply to lexical and hybrid searches by score")
         if result_sort:
             if search_mode != SearchMode.Lexical or not query_terms:
                 raise ValueError("result_sort applies to lexical searches")
@@ -1374,11 +1516,14 @@ class Index:
         if want_vec and normalize_query:
             query_vector = normalize_f32(query_vector)  # search.rs:1464-1475 (Cosine, external inference)
         lex_d, lex_s, vec_d, vec_s = [], [], [], []
+        shard_maps = []
         for sh in self.shards:  # search.rs:1637-1743: each shard asked for (offset 0, length offset+length)
             lt = vt = 0
             if want_lex:
                 r = sh.search_lexical_shard(query_terms, query_type_default, 0, offset + length, result_type, strict,
-                                            not_terms, field_filter if sh.lexical_field_count > 1 else None, facet_filter)
+                                            not_terms, field_filter if sh.lexical_field_count > 1 else None, facet_filter,
+                                            query_facets, S)
+                shard_maps.append(r.facets)
                 lex_d += [x.doc_id * S + sh.shard_id for x in r.results]  # search.rs:1671
                 lex_s += [x.score for x in r.results]
                 lt = r.result_count_total
@@ -1394,5 +1539,7 @@ class Index:
         if result_type != ResultType.Count:
             d, s, src = merge_results(search_mode, (lex_d, lex_s), (vec_d, vec_s), offset, length)
             ro.results = [Result(int(a), float(b), ResultSource(int(c))) for a, b, c in zip(d, s, src)]
+        if query_facets:
+            ro.facets = merge_facets(query_facets, shard_maps, result_type)
         ro.result_count = len(ro.results)
         return ro
