@@ -17,6 +17,8 @@
  *                    <- facet_filter / query_facets of search_lexical_shard (add_result.rs:341-640)
  *   ss_bm25_search_facets
  *                    <- the same search returning ResultObject.facets beside its hits (add_result.rs:487-643, search.rs:3598-3760)
+ *   ss_docs_search   <- the empty query: the query_list_len == 0 arm of search_lexical_shard -> search_iterator_shard
+ *                       (search.rs:3374-3386, iterator.rs:316-358)
  *   ss_index_bin_*, ss_ref_decode_block*, ss_vec_upload_vector_bin*
  *                    <- readers of the shard files and in-RAM blocks (index.rs:3263-3740, vector.rs:1066-1094,
  *                       add_result.rs:2036-2293)
@@ -630,6 +632,31 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* 
                           uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
                           const uint64_t* range_lower_bounds, const ss_facet_point* bases,
                           uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
+
+/* The EMPTY query of a shard (the crate's search(.., enable_empty_query, ..) with no query string: search_iterator_shard,
+ * iterator.rs:316-358, reached from the query_list_len == 0 arm of search_lexical_shard, search.rs:3374-3386): every doc of the
+ * lexical image that is not tombstoned and passes the facet filters matches, nobody is scored (every score is 0.0, the interface
+ * carries none), and the order is the result sort's fields, then the DOC ID -- the larger id first (min_heap.rs:535-536, 1043-1044;
+ * doc_ascending != 0: the smaller first, what a trailing `_id` Ascending sort field asks for, min_heap.rs:580-585).
+ * out_doc [k]: the docs of rank [skip, skip + k) in that order; *out_count = their number = min(k, matches - skip); the slots beyond
+ * them are NOT written.  skip and k may be anything: by doc id alone (n_sorts = 0) a page of any depth is one pass over a bitmap of the
+ * docs; under a sort the ranks [0, skip + k) are found in passes of SS_MAX_K as ss_bm25_search_sorted finds a deep page.
+ * sorts: exactly ss_bm25_search_sorted's (numeric and Point fields, at most SS_MAX_SORT_FIELDS; -0.0 ties +0.0, NaN out of scope).
+ * The facet arguments and out_facet_counts [sum_f (n_buckets[f] + 1)]: ss_bm25_search_facets' for one query (n_facets = 0: none, the
+ * pointers may be NULL).
+ * result_type: SS_RT_COUNT -- no docs (out_doc may be NULL, *out_count = 0), *out_total and the facet counts exact;
+ * SS_RT_TOPKCOUNT -- docs, *out_total and the facet counts exact; SS_RT_TOPK -- the same docs; *out_total and the facet counts as
+ * ss_bm25_search_facets leaves them for SS_RT_TOPK: the counters are counted all the same, *out_total is only promised to be
+ * >= *out_count (the crate's Topk bumps neither, add_result.rs:226-230).
+ * SS_ESTATE: no lexical image; filters, sorts or facets without facet records for every doc of it.  SS_EINVAL: a result type, facet
+ * type or unit out of range, a string sort field, more than SS_MAX_SORT_FIELDS / SS_MAX_QUERY_FACETS / SS_MAX_FACET_FILTERS, an offset
+ * beyond the record, k = 0 with a result type that wants docs.  Never SS_ENOTSUP: no posting list is read, so probe rows, the sparse
+ * tier, the number of indexed fields and the probe budget make no difference. */
+int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t result_type, uint32_t doc_ascending,
+                   uint32_t n_sorts, const ss_result_sort* sorts, uint32_t n_filters, const ss_facet_filter* filters,
+                   uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
+                   const uint64_t* range_lower_bounds, const ss_facet_point* bases,
+                   uint32_t* out_doc, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
 
 /* ------------------------------------------------------------------ vector image
  * rows: row-major [n_rows x dim] f32, already L2-normalised for cosine (vector.rs:585-596); the uploader of

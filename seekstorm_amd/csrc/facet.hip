@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "facet_point.h"
+#include "bit_select.h"
 
 struct FacetFilters {
   uint32_t n;
@@ -528,7 +529,10 @@ __global__ void sort_excl_kernel(const unsigned long long* __restrict__ E, const
   if (g < groups) { ex_b[o] = ~B[o]; ex_e[o] = ~E[o]; }
 }
 // the answer of one query (blockIdx.x): list A (the docs of B with their scores, any order) ordered by (sort keys, score desc, doc asc),
-// then the first k - |A| of list C (the tie group of the last pivot, by score)
+// then the first k - |A| of list C (the tie group of the last pivot, by score).
+// BROWSE (the empty query, ss_docs_search: min_heap.rs:535-536, 1043-1044): nobody has a score -- a_score, c_score and out_score are not
+// read or written -- and the order after the sort keys is the doc id alone, 1 = the larger id first (the crate's default), 2 = the smaller.
+template <int BROWSE>
 __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __restrict__ a_doc, const float* __restrict__ a_score,
                                                             const uint32_t* __restrict__ a_cnt, const uint32_t* __restrict__ c_doc,
                                                             const float* __restrict__ c_score, const uint32_t* __restrict__ c_cnt,
@@ -541,13 +545,13 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
   __shared__ uint32_t dc[1024];
   __shared__ uint16_t perm[1024];
   const uint32_t i = threadIdx.x, q = blockIdx.x;
-  a_doc += (size_t)q * k; a_score += (size_t)q * k; c_doc += (size_t)q * k; c_score += (size_t)q * k;
-  out_doc += (size_t)q * k; out_score += (size_t)q * k;
+  a_doc += (size_t)q * k; c_doc += (size_t)q * k; out_doc += (size_t)q * k;
+  if (!BROWSE) { a_score += (size_t)q * k; c_score += (size_t)q * k; out_score += (size_t)q * k; }
   const uint32_t na = min(a_cnt[q] == 0xFFFFFFFFu ? 0u : a_cnt[q], k);
   const uint32_t nc = min(c_cnt[q] == 0xFFFFFFFFu ? 0u : c_cnt[q], k - na);
   perm[i] = (uint16_t)i;
   dc[i] = i < na ? a_doc[i] : 0xFFFFFFFFu;
-  sc[i] = i < na ? a_score[i] : -INFINITY;
+  sc[i] = BROWSE ? 0.f : (i < na ? a_score[i] : -INFINITY);
   for (uint32_t f = 0; f < (uint32_t)SS_MAX_SORT_FIELDS; f++) {
     unsigned long long kk = 0ull;
     if (i < na && f < F.n && dc[i] < n_facet_docs) {
@@ -564,8 +568,8 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
     if (!la) return a < b;
     for (uint32_t f = 0; f < F.n; f++)
       if (key[f][a] != key[f][b]) return key[f][a] > key[f][b];
-    if (sc[a] != sc[b]) return sc[a] > sc[b];
-    return dc[a] < dc[b];
+    if (!BROWSE && sc[a] != sc[b]) return sc[a] > sc[b];
+    return BROWSE == 1 ? dc[a] > dc[b] : dc[a] < dc[b];
   };
   for (uint32_t size = 2; size <= 1024u; size <<= 1)
     for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
@@ -577,14 +581,14 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
       }
       __syncthreads();
     }
-  if (i < na) { out_doc[i] = dc[perm[i]]; out_score[i] = sc[perm[i]]; }
-  else if (i < na + nc) { out_doc[i] = c_doc[i - na]; out_score[i] = c_score[i - na]; }
-  else if (i < k) { out_doc[i] = 0xFFFFFFFFu; out_score[i] = 0.f; }
+  if (i < na) { out_doc[i] = dc[perm[i]]; if (!BROWSE) out_score[i] = sc[perm[i]]; }
+  else if (i < na + nc) { out_doc[i] = c_doc[i - na]; if (!BROWSE) out_score[i] = c_score[i - na]; }
+  else if (i < k) { out_doc[i] = 0xFFFFFFFFu; if (!BROWSE) out_score[i] = 0.f; }
   if (i == 0) { out_count[q] = na + nc; out_total[q] = total[q]; }
 }
 
 // the device chain of nq queries up to the exclusion bitmaps (the caller then runs the two searches and ssi_sort_compose);
-// bit sets [nq][groups], d_total / d_state [nq], d_hist [nq][256]
+// bit sets [nq][groups], d_total / d_state [nq], d_hist [nq][256].  d_ex_b = nullptr: no exclusion bitmaps (ss_docs_search reads B and E)
 int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned long long* d_B, unsigned long long* d_ex_b, unsigned long long* d_ex_e,
                     const unsigned long long* d_total, unsigned long long* d_hist, void* d_state, uint32_t n_sorts, const ss_result_sort* sorts,
                     uint32_t k, hipStream_t st) {
@@ -612,16 +616,13 @@ int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned 
                                                sorts[f].descending ? 1u : 0u, state, pt);
     sort_level_end_kernel<<<nq, 64, 0, st>>>(state);
   }
-  sort_excl_kernel<<<grid, 256, 0, st>>>(d_E, d_B, d_ex_b, d_ex_e, groups);
+  if (d_ex_b) sort_excl_kernel<<<grid, 256, 0, st>>>(d_E, d_B, d_ex_b, d_ex_e, groups);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }
-// lists [nq][k], counts / totals / outputs per query
-int ssi_sort_compose(ss_shard* s, uint32_t nq, const uint32_t* a_doc, const float* a_score, const uint32_t* a_cnt, const uint32_t* c_doc,
-                     const float* c_score, const uint32_t* c_cnt, const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts,
-                     uint32_t k, uint32_t* out_doc, float* out_score, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
+static int sort_fields_dev(uint32_t n_sorts, const ss_result_sort* sorts, SortFieldsDev* out) {
   static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 0, 0, 8};
-  SortFieldsDev F;
+  SortFieldsDev& F = *out;
   memset(&F, 0, sizeof(F));
   F.n = n_sorts;
   for (uint32_t f = 0; f < n_sorts; f++) {
@@ -631,7 +632,31 @@ int ssi_sort_compose(ss_shard* s, uint32_t nq, const uint32_t* a_doc, const floa
       if (facet_point_of(&base, &F.pt[f]) != SS_OK) return SS_EINVAL;
     }
   }
-  sort_compose_kernel<<<nq, 1024, 0, st>>>(a_doc, a_score, a_cnt, c_doc, c_score, c_cnt, d_total, s->d_facets, s->facet_record_size,
+  return SS_OK;
+}
+// the browse order of ONE answer (ss_docs_search): list A by (sort keys, doc id), then the first k - |A| of list C; no scores
+int ssi_sort_compose_browse(ss_shard* s, const uint32_t* a_doc, const uint32_t* a_cnt, const uint32_t* c_doc, const uint32_t* c_cnt,
+                            const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k, bool doc_ascending,
+                            uint32_t* out_doc, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
+  if (k == 0 || k > 1024u) return SS_EINVAL;  // (one tuple per thread)
+  SortFieldsDev F;
+  if (sort_fields_dev(n_sorts, sorts, &F) != SS_OK) return SS_EINVAL;
+  if (doc_ascending)
+    sort_compose_kernel<2><<<1, 1024, 0, st>>>(a_doc, nullptr, a_cnt, c_doc, nullptr, c_cnt, d_total, s->d_facets, s->facet_record_size,
+                                                (unsigned long long)s->facet_docs, F, k, out_doc, nullptr, out_count, out_total);
+  else
+    sort_compose_kernel<1><<<1, 1024, 0, st>>>(a_doc, nullptr, a_cnt, c_doc, nullptr, c_cnt, d_total, s->d_facets, s->facet_record_size,
+                                                (unsigned long long)s->facet_docs, F, k, out_doc, nullptr, out_count, out_total);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+// lists [nq][k], counts / totals / outputs per query
+int ssi_sort_compose(ss_shard* s, uint32_t nq, const uint32_t* a_doc, const float* a_score, const uint32_t* a_cnt, const uint32_t* c_doc,
+                     const float* c_score, const uint32_t* c_cnt, const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts,
+                     uint32_t k, uint32_t* out_doc, float* out_score, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
+  SortFieldsDev F;
+  if (sort_fields_dev(n_sorts, sorts, &F) != SS_OK) return SS_EINVAL;
+  sort_compose_kernel<0><<<nq, 1024, 0, st>>>(a_doc, a_score, a_cnt, c_doc, c_score, c_cnt, d_total, s->d_facets, s->facet_record_size,
                                            (unsigned long long)s->facet_docs, F, k, out_doc, out_score, out_count, out_total);
   SS_HIP(hipGetLastError());
   return SS_OK;
@@ -693,19 +718,6 @@ __device__ __forceinline__ uint32_t facet_bucket(const uint8_t* p, uint32_t stor
   }
   return lo ? lo - 1 : n_buckets;  // below the first bound (or NaN): "other"
 }
-// position of the r-th (0-based) set bit of m; r < popcount(m)
-__device__ __forceinline__ uint32_t facet_select64(unsigned long long m, uint32_t r) {
-  uint32_t pos = 0, c = (uint32_t)__popc((uint32_t)m);
-  if (r >= c) { r -= c; m >>= 32; pos = 32; }
-  uint32_t x = (uint32_t)m;
-  c = (uint32_t)__popc(x & 0xFFFFu); if (r >= c) { r -= c; x >>= 16; pos += 16; }
-  c = (uint32_t)__popc(x & 0xFFu); if (r >= c) { r -= c; x >>= 8; pos += 8; }
-  c = (uint32_t)__popc(x & 0xFu); if (r >= c) { r -= c; x >>= 4; pos += 4; }
-  c = (uint32_t)__popc(x & 3u); if (r >= c) { r -= c; x >>= 2; pos += 2; }
-  if (r >= (x & 1u)) pos += 1;
-  return pos;
-}
-
 __global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned long long* __restrict__ bits, unsigned long long groups,
                                                                  unsigned long long n_docs, const uint8_t* __restrict__ records,
                                                                  uint32_t record_size, uint32_t wpt, const unsigned long long* __restrict__ bounds,

@@ -22,6 +22,7 @@
 #include "facet_point.h"
 #include "bm25_build.h"
 #include "bm25_match.h"
+#include "browse.h"
 
 #define SS_TRY(x)          \
   do {                     \
@@ -3615,6 +3616,146 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
   if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) rc = SS_EDEVICE;
   if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (also on an error: the plans and the caller's arrays are being read)
   return rc;
+}
+
+// The empty query of a shard (browse.hip; search_iterator_shard, iterator.rs:316-358).  Everything runs on s->stream: the match set of
+// "every live doc under the filter" (and its slice counts), the facet counts over it, and then either the page by doc id -- one scan
+// of the slice counts and one emit pass -- or, under a sort, ssi_sort_select over a copy of the match set, the two doc sets it leaves
+// listed by doc id and composed (facet.hip, the browse instances of the compose kernel); ranks beyond SS_MAX_K in passes, the docs of
+// the earlier passes cleared from the match set.  Waits: one, when skip + k <= SS_MAX_K (by doc id: k <= SS_MAX_K); else one for the
+// match count -- it bounds the passes and the copy home -- and one for the docs.
+int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t doc_ascending, uint32_t n_sorts, const ss_result_sort* sorts,
+                   uint32_t n_filters, const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type,
+                   const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases, uint32_t* out_doc,
+                   uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts) {
+  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
+  if (!s || !out_count || !out_total || rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
+  const bool want_docs = rt != SS_RT_COUNT;
+  if (want_docs && (k == 0 || !out_doc)) return SS_EINVAL;
+  if (n_sorts > SS_MAX_SORT_FIELDS || (n_sorts && !sorts) || n_filters > SS_MAX_FACET_FILTERS || (n_filters && !filters)) return SS_EINVAL;
+  for (uint32_t f = 0; f < n_sorts; f++)
+    if (sorts[f].facet_type > SS_FACET_POINT || sorts[f].facet_type == SS_FACET_STRING16 || sorts[f].facet_type == SS_FACET_STRING32) return SS_EINVAL;
+  if (n_facets > SS_MAX_QUERY_FACETS || (n_facets && (!facet_offset || !facet_type || !n_buckets || !out_facet_counts))) return SS_EINVAL;
+  size_t n_bounds = 0, stride = 0;
+  for (uint32_t f = 0; f < n_facets; f++) {
+    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
+    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
+    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) n_bounds += n_buckets[f];
+    stride += (size_t)n_buckets[f] + 1;
+  }
+  if (n_bounds && !range_lower_bounds) return SS_EINVAL;
+  ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
+  if (!s->d_post) return SS_ESTATE;
+  SS_HIP(hipSetDevice(s->device));
+  if ((n_sorts || n_filters || n_facets) && (!s->d_facets || s->facet_docs < s->bm_n_docs)) return SS_ESTATE;
+  for (uint32_t f = 0; f < n_sorts; f++)
+    if ((uint64_t)sorts[f].facet_offset + width[sorts[f].facet_type] > s->facet_record_size) return SS_EINVAL;
+  for (uint32_t f = 0; f < n_facets; f++)
+    if ((uint64_t)facet_offset[f] + width[facet_type[f]] > s->facet_record_size) return SS_EINVAL;
+  for (uint32_t f = 0; f < n_filters; f++)
+    if (filters[f].type > SS_FACET_POINT || (uint64_t)filters[f].offset + width[filters[f].type] > s->facet_record_size) return SS_EINVAL;
+
+  const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64), n_slices = browse_slices(groups), n_docs = s->bm_n_docs;
+  const bool sorted = want_docs && n_sorts != 0, descending = doc_ascending == 0;
+  if (groups == 0 || n_docs == 0) {  // an image without docs
+    *out_count = 0;
+    *out_total = 0;
+    if (n_facets) memset(out_facet_counts, 0, stride * 8);
+    return SS_OK;
+  }
+  // ranks wanted: [skip, skip + k) of at most n_docs matches; a sorted page finds the ranks before it too
+  const uint64_t reach = skip > UINT64_MAX - k ? UINT64_MAX : skip + k;
+  const uint64_t out_cap = !want_docs ? 0 : sorted ? std::min<uint64_t>(reach, n_docs) : std::min<uint64_t>(k, n_docs);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // head: [0] matches, [1] matches left to a sorted pass, [2] the compose kernel's copy; [3] as uint32: page / list A / list C / composed counts
+  const size_t o_head = 0, o_M = o_head + al(64), o_scnt = o_M + al(groups * 8), o_sbeg = o_scnt + al(n_slices * 4),
+               o_E = o_sbeg + al(n_slices * 8), o_B = o_E + (sorted ? al(groups * 8) : 0), o_hist = o_B + (sorted ? al(groups * 8) : 0),
+               o_state = o_hist + (sorted ? al(256 * 8) : 0), o_a = o_state + (sorted ? al(64) : 0), o_c = o_a + (sorted ? al(SS_MAX_K * 4) : 0),
+               o_out = o_c + (sorted ? al(SS_MAX_K * 4) : 0), o_bounds = o_out + al(out_cap * 4), o_cnt = o_bounds + al(n_bounds * 8),
+               need = o_cnt + al(stride * 8);
+  if (need > s->facet_ws_cap) {  // grow-only workspace
+    SS_HIP(hipStreamSynchronize(s->stream));
+    if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
+    s->d_facet_ws = nullptr;
+    s->facet_ws_cap = 0;
+    SS_HIP(hipMalloc(&s->d_facet_ws, need));
+    s->facet_ws_cap = need;
+  }
+  char* W = (char*)s->d_facet_ws;
+  unsigned long long *d_head = (unsigned long long*)(W + o_head), *d_M = (unsigned long long*)(W + o_M), *d_sbeg = (unsigned long long*)(W + o_sbeg),
+                     *d_E = (unsigned long long*)(W + o_E), *d_B = (unsigned long long*)(W + o_B), *d_counts = (unsigned long long*)(W + o_cnt);
+  uint32_t *d_scnt = (uint32_t*)(W + o_scnt), *d_n = (uint32_t*)(d_head + 3), *d_a = (uint32_t*)(W + o_a), *d_c = (uint32_t*)(W + o_c),
+           *d_out = (uint32_t*)(W + o_out);
+  uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
+  SS_HIP(hipMemsetAsync(d_head, 0, 64, s->stream));
+  if (n_facets) SS_HIP(hipMemsetAsync(d_counts, 0, stride * 8, s->stream));
+  if (n_bounds) SS_HIP(hipMemcpyAsync(d_bounds, range_lower_bounds, n_bounds * 8, hipMemcpyHostToDevice, s->stream));
+  int rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_browse_bits(s, d_M, d_scnt, d_head, s->stream); });
+  if (rc == SS_OK && n_facets)
+    rc = ssi_facet_count_multi(s, 1, d_M, n_facets, facet_offset, facet_type, n_buckets, bases, d_bounds, d_counts, s->stream);
+  uint64_t total = 0;
+  uint32_t count = 0, h_doc[SS_MAX_K];  // (h_doc: a shallow page's docs on their way home)
+  auto hip_ok = [&](hipError_t e) { if (e != hipSuccess && rc == SS_OK) rc = e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE; return rc == SS_OK; };
+  if (rc == SS_OK && want_docs && !sorted) {
+    rc = ssi_browse_select(s, d_M, descending, skip, k, d_scnt, d_sbeg, true, d_out, d_n, s->stream);
+    if (rc == SS_OK && k <= SS_MAX_K) {  // a shallow page: the docs come home with the counts, one wait
+      if (hip_ok(hipMemcpyAsync(&total, d_head, 8, hipMemcpyDeviceToHost, s->stream)) &&
+          hip_ok(hipMemcpyAsync(&count, d_n, 4, hipMemcpyDeviceToHost, s->stream)) &&
+          hip_ok(hipMemcpyAsync(h_doc, d_out, (size_t)out_cap * 4, hipMemcpyDeviceToHost, s->stream)) &&
+          hip_ok(hipStreamSynchronize(s->stream))) {
+        count = (uint32_t)std::min<uint64_t>(count, out_cap);
+        memcpy(out_doc, h_doc, (size_t)count * 4);
+      }
+    } else if (rc == SS_OK) {
+      if (hip_ok(hipMemcpyAsync(&total, d_head, 8, hipMemcpyDeviceToHost, s->stream)) &&
+          hip_ok(hipMemcpyAsync(&count, d_n, 4, hipMemcpyDeviceToHost, s->stream)) && hip_ok(hipStreamSynchronize(s->stream))) {
+        count = (uint32_t)std::min<uint64_t>(count, out_cap);
+        if (count) hip_ok(hipMemcpyAsync(out_doc, d_out, (size_t)count * 4, hipMemcpyDeviceToHost, s->stream));
+      }
+    }
+  } else if (rc == SS_OK && sorted) {
+    uint64_t n_rank = out_cap;  // ranks [0, n_rank) are found; known to exist once the match count is home
+    const bool deep = reach > SS_MAX_K;
+    if (deep) {
+      if (hip_ok(hipMemcpyAsync(&total, d_head, 8, hipMemcpyDeviceToHost, s->stream))) hip_ok(hipStreamSynchronize(s->stream));
+      n_rank = total > skip ? std::min<uint64_t>(n_rank, total) : 0;  // (nobody at rank skip: no pass at all)
+    }
+    if (rc == SS_OK) hip_ok(hipMemcpyAsync(d_head + 1, d_head, 8, hipMemcpyDeviceToDevice, s->stream));
+    for (uint64_t got = 0; rc == SS_OK && got < n_rank;) {
+      const uint32_t kk = (uint32_t)std::min<uint64_t>(SS_MAX_K, n_rank - got);
+      if (!hip_ok(hipMemcpyAsync(d_E, d_M, groups * 8, hipMemcpyDeviceToDevice, s->stream))) break;
+      rc = ssi_sort_select(s, 1, d_E, d_B, nullptr, nullptr, d_head + 1, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, kk, s->stream);
+      // list A: all of B (fewer than kk docs); list C: the best kk of the last pivot's tie group by doc id, of which the compose takes kk - |A|
+      if (rc == SS_OK) rc = ssi_browse_select(s, d_B, descending, 0, kk, d_scnt, d_sbeg, false, d_a, d_n + 1, s->stream);
+      if (rc == SS_OK) rc = ssi_browse_select(s, d_E, descending, 0, kk, d_scnt, d_sbeg, false, d_c, d_n + 2, s->stream);
+      if (rc == SS_OK)
+        rc = ssi_sort_compose_browse(s, d_a, d_n + 1, d_c, d_n + 2, d_head, n_sorts, sorts, kk, !descending, d_out + got, d_n + 3, d_head + 2, s->stream);
+      if (rc == SS_OK && got + kk < n_rank) rc = ssi_browse_clear(s, d_M, d_out + got, kk, d_head + 1, s->stream);  // (deep: every pass is full)
+      got += kk;
+    }
+    if (rc == SS_OK && deep) {
+      count = n_rank > skip ? (uint32_t)(n_rank - skip) : 0u;
+      if (count) hip_ok(hipMemcpyAsync(out_doc, d_out + skip, (size_t)count * 4, hipMemcpyDeviceToHost, s->stream));
+    } else if (rc == SS_OK) {  // one pass of skip + k <= SS_MAX_K ranks: the composed count says how many exist
+      uint32_t n = 0;
+      if (hip_ok(hipMemcpyAsync(&total, d_head, 8, hipMemcpyDeviceToHost, s->stream)) &&
+          (n_rank == 0 || (hip_ok(hipMemcpyAsync(&n, d_n + 3, 4, hipMemcpyDeviceToHost, s->stream)) &&
+                           hip_ok(hipMemcpyAsync(h_doc, d_out, (size_t)n_rank * 4, hipMemcpyDeviceToHost, s->stream)))) &&
+          hip_ok(hipStreamSynchronize(s->stream))) {
+        n = (uint32_t)std::min<uint64_t>(n, n_rank);
+        count = n > skip ? n - (uint32_t)skip : 0u;
+        memcpy(out_doc, h_doc + (count ? skip : 0), (size_t)count * 4);
+      }
+    }
+  } else if (rc == SS_OK) {
+    hip_ok(hipMemcpyAsync(&total, d_head, 8, hipMemcpyDeviceToHost, s->stream));
+  }
+  if (rc == SS_OK && n_facets) hip_ok(hipMemcpyAsync(out_facet_counts, d_counts, stride * 8, hipMemcpyDeviceToHost, s->stream));
+  if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (also on an error: the caller's arrays are being read)
+  if (rc != SS_OK) return rc;
+  *out_count = count;
+  *out_total = total;
+  return SS_OK;
 }
 
 static int facet_values_impl(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t facet_offset, uint32_t facet_type,

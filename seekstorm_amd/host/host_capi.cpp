@@ -516,4 +516,33 @@ int ssh_index_search_facets(ssh_index* ix, const uint32_t* terms, uint32_t n_ter
   return write_out(ro, cap, out_doc, out_score, nullptr, nullptr, nullptr, out_meta);
 }
 
+// Index::search with enable_empty_query and no terms (SearchMode::Lexical): the empty query.  sorts as ssh_index_search_sorted takes
+// them; id_sort: 0 = no `_id` / `_score` entry, 1 / 2 = a trailing `_id` entry descending / ascending, 3 / 4 = a trailing `_score`
+// entry descending / ascending.  spec may be NULL or empty (no query_facets).  Results and facets as ssh_index_search_facets writes them.
+int ssh_index_search_empty(ssh_index* ix, uint32_t offset, uint32_t length, uint32_t result_type, uint32_t n_filters, const ss_facet_filter* filters,
+                           const ssh_result_sort* sorts, uint32_t n_sorts, uint32_t id_sort, const char* spec, uint32_t cap, uint64_t* out_doc,
+                           float* out_score, uint64_t* out_meta, char* out_facets, uint32_t facets_cap, int* facets_len) {
+  std::vector<QueryFacet> qf;
+  if (!parse_facets(spec, &qf) || id_sort > 4) return SS_EINVAL;
+  std::vector<ResultSort> rs(n_sorts);
+  for (uint32_t i = 0; i < n_sorts; i++) {
+    rs[i].facet_offset = sorts[i].facet_offset;
+    rs[i].facet_type = sorts[i].facet_type;
+    rs[i].descending = sorts[i].descending != 0;
+    rs[i].base[0] = sorts[i].base[0];
+    rs[i].base[1] = sorts[i].base[1];
+  }
+  if (id_sort) {
+    ResultSort last;
+    last.field = id_sort <= 2 ? ResultSort::Field::Id : ResultSort::Field::Score;
+    last.descending = id_sort == 1 || id_sort == 3;
+    rs.push_back(last);
+  }
+  if (!ix->index) ix->index.reset(new Index(ix->shards));
+  ResultObject ro = ix->index->search({}, nullptr, QueryType::Union, SearchMode::Lexical, offset, length, (ResultType)result_type, nullptr, true,
+                                      AnnMode(), {}, std::vector<ss_facet_filter>(filters, filters + n_filters), {}, {}, qf, true, rs);
+  *facets_len = write_facets(ro.facets, out_facets, facets_cap);
+  return write_out(ro, cap, out_doc, out_score, nullptr, nullptr, nullptr, out_meta);
+}
+
 }  // extern "C"

@@ -651,6 +651,56 @@ ss_facet_filter bits_filter(uint32_t offset, uint32_t type, uint64_t lo, uint64_
 }
 }  // namespace
 
+ResultObject Shard::search_docs(size_t k, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
+                                const std::vector<ResultSort>& result_sort, const std::vector<QueryFacet>& query_facets, bool doc_ascending,
+                                uint64_t skip, size_t shard_number) {
+  ResultObject ro;
+  if (!h_) { ro.last_error = create_rc_ ? create_rc_ : SS_ESTATE; return ro; }
+  std::vector<ss_result_sort> rs;
+  for (size_t f = 0; f < result_sort.size(); f++) {
+    const ResultSort& sf = result_sort[f];
+    if (sf.field != ResultSort::Field::Facet) {  // `_id` / `_score`: the last entry only
+      if (f + 1 != result_sort.size()) { ro.last_error = SS_EINVAL; return ro; }
+      if (sf.field == ResultSort::Field::Id) doc_ascending = !sf.descending;
+      break;
+    }
+    rs.push_back(ss_result_sort{sf.facet_offset, sf.facet_type, sf.descending ? 1u : 0u, 0, sf.base[0], sf.base[1]});
+  }
+  const size_t nf = query_facets.size();
+  std::vector<uint32_t> f_off(nf), f_type(nf), f_nb(nf);
+  std::vector<uint64_t> bounds;
+  std::vector<ss_facet_point> bases(nf);
+  size_t stride = 0;
+  for (size_t f = 0; f < nf; f++) {
+    const QueryFacet& qf = query_facets[f];
+    f_off[f] = qf.facet_offset; f_type[f] = qf.facet_type; f_nb[f] = qf.n_buckets(); bases[f] = qf.base;
+    if (qf.is_range())
+      for (const auto& r : qf.ranges) bounds.push_back(r.second);
+    stride += (size_t)f_nb[f] + 1;
+  }
+  std::vector<uint64_t> counts(stride, 0);
+  std::vector<uint32_t> doc(std::max<size_t>(k, 1));
+  uint32_t cnt = 0;
+  uint64_t tot = 0;
+  const int rc = ss_docs_search(h_, skip, (uint32_t)k, (uint32_t)result_type, doc_ascending ? 1u : 0u, (uint32_t)rs.size(),
+                                rs.empty() ? nullptr : rs.data(), (uint32_t)facet_filter.size(), facet_filter.empty() ? nullptr : facet_filter.data(),
+                                (uint32_t)nf, f_off.data(), f_type.data(), f_nb.data(), bounds.empty() ? nullptr : bounds.data(), bases.data(),
+                                doc.data(), &cnt, &tot, counts.data());
+  if (rc != SS_OK) { ro.last_error = rc; return ro; }  // degrade to empty (search.rs:2461-2463)
+  if (nf) ro.facets = finish_facets(query_facets, counts.data(), shard_number);
+  ro.results.resize(cnt);
+  for (size_t i = 0; i < cnt; i++) {
+    Result& r = ro.results[i];
+    r.doc_id = doc[i];
+    r.shard_id = shard_id_;
+    r.level_id = (uint32_t)(r.doc_id >> 16);
+    r.source = ResultSource::Lexical;
+  }
+  ro.result_count = cnt;
+  ro.result_count_total = tot;
+  return ro;
+}
+
 int Shard::sort_keys(const std::vector<uint32_t>& doc_ids, const ResultSort& sf, std::vector<uint64_t>* keys) {
   keys->assign(doc_ids.size(), 0);
   if (doc_ids.empty()) return SS_OK;
@@ -846,16 +896,84 @@ ResultObject Index::search_lexical_sorted(const std::vector<uint32_t>& query_ter
   return ro;
 }
 
+ResultObject Index::search_empty(size_t offset, size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
+                                 const std::vector<ResultSort>& result_sort, const std::vector<QueryFacet>& query_facets) {
+  ResultObject ro;
+  const size_t S = shards_.size(), k = offset + length;
+  const bool want_docs = result_type != ResultType::Count && k != 0;
+  auto global = [&](Result r, const Shard& sh) {
+    r.doc_id = r.doc_id * S + sh.shard_id();  // search.rs:1671
+    return r;
+  };
+  if (facet_filter.empty() && query_facets.empty() &&
+      (result_sort.empty() || (result_sort.size() == 1 && result_sort[0].field != ResultSort::Field::Facet))) {
+    const bool ascending = !result_sort.empty() && !result_sort[0].descending;
+    std::vector<Result> all;
+    for (size_t i = 0; i < S; i++) {
+      ro.result_count_total += shards_[i]->indexed_doc_count();  // (tombstoned docs included: iterator.rs:381, 410)
+      if (!want_docs) continue;
+      ResultObject part = shards_[i]->search_docs(k, ResultType::Topk, {}, {}, {}, ascending);
+      if (part.last_error != SS_OK) { ro.last_error = part.last_error; continue; }  // a failing shard degrades to empty
+      for (const Result& r : part.results) all.push_back(global(r, *shards_[i]));
+    }
+    std::sort(all.begin(), all.end(), [&](const Result& a, const Result& b) { return ascending ? a.doc_id < b.doc_id : a.doc_id > b.doc_id; });
+    for (size_t j = offset; j < all.size() && j < k; j++) ro.results.push_back(all[j]);
+    ro.result_count = ro.results.size();
+    return ro;
+  }
+  std::vector<ResultSort> fields = result_sort;
+  bool ascending = false;
+  for (size_t f = 0; f < fields.size(); f++)
+    if (fields[f].field != ResultSort::Field::Facet && f + 1 != fields.size()) { ro.last_error = SS_EINVAL; return ro; }
+  if (!fields.empty() && fields.back().field != ResultSort::Field::Facet) {
+    if (fields.back().field == ResultSort::Field::Id) ascending = !fields.back().descending;
+    fields.pop_back();
+  }
+  struct Row { std::vector<uint64_t> keys; Result r; };
+  std::vector<Row> rows;
+  std::vector<Facets> maps;
+  for (size_t i = 0; i < S; i++) {
+    Shard& sh = *shards_[i];
+    ResultObject part = sh.search_docs(k, want_docs ? result_type : ResultType::Count, facet_filter, fields, query_facets, ascending, 0, S);
+    if (part.last_error != SS_OK) { ro.last_error = part.last_error; continue; }
+    ro.result_count_total += part.result_count_total;
+    if (!query_facets.empty()) maps.push_back(std::move(part.facets));
+    std::vector<uint32_t> docs(part.results.size());
+    for (size_t j = 0; j < docs.size(); j++) docs[j] = (uint32_t)part.results[j].doc_id;
+    std::vector<std::vector<uint64_t>> keys(fields.size());
+    bool ok = true;
+    for (size_t f = 0; f < fields.size() && ok; f++) ok = sh.sort_keys(docs, fields[f], &keys[f]) == SS_OK;
+    if (!ok) { ro.last_error = SS_EDEVICE; continue; }
+    for (size_t j = 0; j < docs.size(); j++) {
+      Row row;
+      for (size_t f = 0; f < fields.size(); f++) row.keys.push_back(keys[f][j]);
+      row.r = global(part.results[j], sh);
+      rows.push_back(std::move(row));
+    }
+  }
+  std::sort(rows.begin(), rows.end(), [&](const Row& a, const Row& b) {
+    for (size_t f = 0; f < a.keys.size(); f++)
+      if (a.keys[f] != b.keys[f]) return a.keys[f] > b.keys[f];
+    return ascending ? a.r.doc_id < b.r.doc_id : a.r.doc_id > b.r.doc_id;
+  });
+  for (size_t j = offset; want_docs && j < rows.size() && j < k; j++) ro.results.push_back(rows[j].r);
+  if (!query_facets.empty()) ro.facets = merge_facets(query_facets, maps, result_type);
+  ro.result_count = ro.results.size();
+  return ro;
+}
+
 // ------------------------------------------------------------------ Index::search
 ResultObject Index::search(const std::vector<uint32_t>& query_terms, const float* query_vector, QueryType query_type_default,
                            SearchMode search_mode, size_t offset, size_t length, ResultType result_type,
                            const float* similarity_threshold, bool normalize_query, const AnnMode& ann_mode,
                            const std::vector<uint16_t>& vector_field_filter, const std::vector<ss_facet_filter>& facet_filter,
                            const std::vector<uint32_t>& not_terms, const std::vector<uint16_t>& lexical_field_filter,
-                           const std::vector<QueryFacet>& query_facets) {
+                           const std::vector<QueryFacet>& query_facets, bool enable_empty_query, const std::vector<ResultSort>& result_sort) {
   ResultObject ro;
   const size_t S = shards_.size();
   if (S == 0) return ro;
+  if (enable_empty_query && query_terms.empty() && search_mode == SearchMode::Lexical && query_vector == nullptr)
+    return search_empty(offset, length, result_type, facet_filter, result_sort, query_facets);
   const bool want_lex = (search_mode == SearchMode::Lexical || search_mode == SearchMode::Hybrid) && !query_terms.empty();
   const bool want_vec = (search_mode == SearchMode::Vector || search_mode == SearchMode::Hybrid) && query_vector != nullptr;
   if (!query_facets.empty() && !want_lex) { ro.last_error = SS_EINVAL; return ro; }  // facets come from the lexical side: none to count

@@ -92,11 +92,14 @@ float vector_score_of(float raw_dot);                           // vector.rs:149
 
 // search.rs ResultSort: one sort field of a lexical search -- a numeric facet (its offset inside the facet.bin record and its
 // SS_FACET_* type) ascending or descending, or a Point facet (type SS_FACET_POINT) by its distance to `base` (lat, lon).
+// The empty query (Index::search with enable_empty_query, Shard::search_docs) also takes the crate's `_id` and `_score` fields, as
+// the LAST entry only: field = Id orders by doc id in the entry's direction (min_heap.rs:580-585), Score is a no-op (every score 0.0).
 struct ResultSort {
   uint32_t facet_offset = 0;
   uint32_t facet_type = SS_FACET_U32;
   bool descending = false;
   double base[2] = {0.0, 0.0};
+  enum class Field { Facet, Id, Score } field = Field::Facet;
 };
 // Result sort by a String16 / String32 facet (min_heap.rs:860-897, 939-976: the STRINGS of the two docs' value ids are compared,
 // Rust String order = byte-wise UTF-8).  The device sorts numbers: append one derived u32 column to the facet.bin records before
@@ -211,6 +214,12 @@ class Shard {
                                     const std::vector<uint32_t>& not_terms = {}, const std::vector<uint16_t>& field_filter = {},
                                     const std::vector<ResultSort>& result_sort = {}, const std::vector<QueryFacet>& query_facets = {},
                                     size_t shard_number = 1);
+  // The EMPTY query of this shard (ss_docs_search; search_iterator_shard, iterator.rs:316-358): every doc that is not tombstoned
+  // and passes facet_filter, scores 0.0, ordered by result_sort's facet fields and then the doc id (the larger first; doc_ascending:
+  // the smaller first) -- the docs of rank [skip, skip + k).  facets = finish_facets(query_facets) for shard_number shards.
+  ResultObject search_docs(size_t k, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter = {},
+                           const std::vector<ResultSort>& result_sort = {}, const std::vector<QueryFacet>& query_facets = {},
+                           bool doc_ascending = false, uint64_t skip = 0, size_t shard_number = 1);
   // search_lexical_batch with the batch's query_facets in the same call (ss_bm25_search_facets): counts [n_queries][sum_f (n_buckets
   // + 1)] raw counters, ResultObject::facets = finish_facets of each query's row (shard_number: of the index, for the crate's cap)
   std::vector<ResultObject> search_facets(const std::vector<ss_bm25_query>& queries, size_t k, ResultType result_type,
@@ -298,7 +307,16 @@ class Index {
                       const float* similarity_threshold = nullptr, bool normalize_query = true,
                       const AnnMode& ann_mode = AnnMode(), const std::vector<uint16_t>& vector_field_filter = {},
                       const std::vector<ss_facet_filter>& facet_filter = {}, const std::vector<uint32_t>& not_terms = {},
-                      const std::vector<uint16_t>& lexical_field_filter = {}, const std::vector<QueryFacet>& query_facets = {});
+                      const std::vector<uint16_t>& lexical_field_filter = {}, const std::vector<QueryFacet>& query_facets = {},
+                      bool enable_empty_query = false, const std::vector<ResultSort>& result_sort = {});
+  // search() with enable_empty_query, SearchMode::Lexical and no terms (result_sort is read on this path only; lexical_field_filter
+  // plays no part).  Index path -- no facet_filter, no query_facets, result_sort empty or ONE Id / Score entry (search.rs:1413-1432,
+  // search_iterator_index, iterator.rs:360-413): global ids from the largest down (up iff that entry is ascending), tombstoned docs
+  // skipped, offset / length applied, result_count_total = the indexed doc count, tombstoned docs included.  Shard path -- anything
+  // else (search.rs:3374-3386 on every shard, k = offset + length): ids local * S + shard, rows merged by (sort keys, global doc id
+  // in the tie direction), totals summed, facets merged.
+  ResultObject search_empty(size_t offset, size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
+                            const std::vector<ResultSort>& result_sort, const std::vector<QueryFacet>& query_facets);
 
  private:
   std::vector<std::shared_ptr<Shard>> shards_;

@@ -928,11 +928,9 @@ class Shard:
                 "ss_facet_point_distances")
         return out.view(np.float64)
 
-    def search_lexical_sorted_batch(self, queries, result_sort, k, facet_filter=None):
-        """a BATCH of queries under result_sort = [(facet offset, type, descending[, base])] (numeric facets, Point facets by
-        simplified_distance to base = (lat, lon)): ss_bm25_search_sorted -- the pivots of every sort field are found on the device, two
-        searches under exclusion bitmaps and a compose kernel per query, one synchronisation per call.
-        -> (doc [nq][k], score [nq][k], count [nq], total [nq])"""
+    @staticmethod
+    def _result_sorts(result_sort):
+        """result_sort = [(facet offset, type, descending[, base])] -> (n, ss_result_sort array)"""
         n = len(result_sort)
         arr = (N.ResultSortC * max(n, 1))()
         for i, sf in enumerate(result_sort):
@@ -942,6 +940,14 @@ class Shard:
                 arr[i].facet_type, arr[i].base_lat, arr[i].base_lon = N.FACET_TYPES["point"], float(sf[3][0]), float(sf[3][1])
             else:
                 arr[i].facet_type = N.FACET_TYPES[ty]
+        return n, arr
+
+    def search_lexical_sorted_batch(self, queries, result_sort, k, facet_filter=None):
+        """a BATCH of queries under result_sort = [(facet offset, type, descending[, base])] (numeric facets, Point facets by
+        simplified_distance to base = (lat, lon)): ss_bm25_search_sorted -- the pivots of every sort field are found on the device, two
+        searches under exclusion bitmaps and a compose kernel per query, one synchronisation per call.
+        -> (doc [nq][k], score [nq][k], count [nq], total [nq])"""
+        n, arr = self._result_sorts(result_sort)
         q = np.ascontiguousarray(queries)
         nq, kk = len(q), int(k)
         doc = np.full((nq, kk), N.SS_NO_DOC, np.uint32)
@@ -1125,6 +1131,76 @@ class Shard:
             return np.asarray(lows, np.float32).view(np.uint32).astype(np.uint64)
         return np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in lows], np.uint64)
 
+    @classmethod
+    def _query_facet_args(cls, query_facets):
+        """query_facets (see finish_facets) -> the facet arrays of ss_bm25_search_facets / ss_docs_search:
+        (offsets, types, n_buckets, range lower bounds back to back or None, bases or None, counters per query)"""
+        nf_ = len(query_facets)
+        off = np.array([int(qf["offset"]) for qf in query_facets], np.uint32)
+        ty = np.array([N.FACET_TYPES[qf["type"].replace("stringset", "string")] for qf in query_facets], np.uint32)
+        bounds = [cls._facet_bounds(qf) for qf in query_facets if _facet_is_range(qf)]
+        nb = np.array([len(qf["ranges"]) if _facet_is_range(qf) else len(qf["values"]) for qf in query_facets], np.uint32)
+        allb = np.concatenate(bounds) if bounds else None
+        bases = None
+        if any(qf["type"] == "point" for qf in query_facets):
+            bases = (N.FacetPointC * nf_)()
+            for i, qf in enumerate(query_facets):
+                if qf["type"] == "point":
+                    bases[i] = cls._point(qf["base"], qf.get("unit", "km"))
+        return off, ty, nb, allb, bases, int(nb.astype(np.int64).sum()) + nf_
+
+    def search_docs(self, k, result_type=ResultType.TopkCount, facet_filter=None, result_sort=None, query_facets=None, doc_ascending=False,
+                    skip=0):
+        """The EMPTY query of this shard (ss_docs_search; search_iterator_shard, iterator.rs:316-358): every doc that is not tombstoned and
+        passes facet_filter matches, every score is 0.0, and the order is result_sort's fields, then the doc id -- the larger id first,
+        the smaller first with doc_ascending.  -> (doc ids of rank [skip, skip + k), count, total, facets); facets = finish_facets of
+        query_facets for ONE shard ({} without query_facets; raw counters: search_docs_raw).
+        result_sort = [(facet offset, type, descending[, base])] as search_lexical_sorted_batch takes; its LAST entry may be the marker
+        ("_id", descending) -- the crate's sort by the `_id` field (min_heap.rs:580-585) -- which is not a facet: it sets doc_ascending =
+        not descending and is dropped; ("_score", descending) as the last entry is dropped too (every score is 0.0).  Anywhere else
+        either marker raises ValueError."""
+        doc, cnt, tot, per = self.search_docs_raw(k, result_type, facet_filter, result_sort, query_facets, doc_ascending, skip)
+        return doc, cnt, tot, finish_facets(query_facets, per, 1) if query_facets else {}
+
+    @staticmethod
+    def split_id_sort(result_sort, doc_ascending=False):
+        """result_sort with a trailing ("_id" | "_score", descending) marker -> (the facet sort fields, doc_ascending)"""
+        sorts = list(result_sort or [])
+        if sorts and isinstance(sorts[-1][0], str):
+            name, desc = sorts[-1][0], sorts[-1][-1]
+            if name not in ("_id", "_score"):
+                raise ValueError("result_sort: a facet is named by its offset; the markers are \"_id\" and \"_score\"")
+            if name == "_id":
+                doc_ascending = not desc
+            sorts = sorts[:-1]
+        if any(isinstance(sf[0], str) for sf in sorts):
+            raise ValueError("result_sort: \"_id\" / \"_score\" only as the last entry")
+        return sorts, bool(doc_ascending)
+
+    def search_docs_raw(self, k, result_type=ResultType.TopkCount, facet_filter=None, result_sort=None, query_facets=None,
+                        doc_ascending=False, skip=0):
+        """search_docs with the raw counters: -> (doc ids, count, total, [counters of facet f: n_buckets + 1, the last = "other"])"""
+        sorts, asc = self.split_id_sort(result_sort, doc_ascending)
+        n, arr = self._result_sorts(sorts)
+        kk = int(k)
+        doc = np.full(max(kk, 1), N.SS_NO_DOC, np.uint32)
+        cnt, tot = C.c_uint32(0), C.c_uint64(0)
+        farr, nf = self.facet_filters(facet_filter) if facet_filter else (None, 0)
+        nqf = len(query_facets) if query_facets else 0
+        off = ty = nb = allb = bases = out = None
+        if nqf:
+            off, ty, nb, allb, bases, stride = self._query_facet_args(query_facets)
+            out = np.zeros(stride, np.uint64)
+        N.check(N.lib().ss_docs_search(self._h, int(skip), kk, int(result_type), 1 if asc else 0, n, C.cast(arr, C.c_void_p) if n else None, nf,
+                                       None if farr is None else C.cast(farr, C.c_void_p), nqf, N.ptr(off, N.u32p), N.ptr(ty, N.u32p),
+                                       N.ptr(nb, N.u32p), N.ptr(allb, N.u64p), None if bases is None else C.cast(bases, C.c_void_p),
+                                       N.ptr(doc, N.u32p), C.byref(cnt), C.byref(tot), N.ptr(out, N.u64p)), "ss_docs_search")
+        per, at = [], 0
+        for b in (nb if nqf else []):
+            per.append(out[at:at + int(b) + 1])
+            at += int(b) + 1
+        return doc[:cnt.value].copy(), int(cnt.value), int(tot.value), per
+
     def search_lexical_facets(self, queries, k, query_facets, result_type=ResultType.TopkCount, facet_filter=None, reference_shortcuts=True):
         """search_lexical_batch with the batch's query_facets in the same call (ss_bm25_search_facets): -> (doc, score, count, total,
         counts_per_facet), counts_per_facet[f] = [n_queries][n_buckets + 1] raw counters of facet f (last column: "other"), what
@@ -1138,18 +1214,7 @@ class Shard:
         score = np.zeros((nq, kk), np.float32)
         cnt = np.zeros(nq, np.uint32)
         tot = np.zeros(nq, np.uint64)
-        off = np.array([int(qf["offset"]) for qf in query_facets], np.uint32)
-        ty = np.array([N.FACET_TYPES[qf["type"].replace("stringset", "string")] for qf in query_facets], np.uint32)
-        bounds = [self._facet_bounds(qf) for qf in query_facets if _facet_is_range(qf)]
-        nb = np.array([len(qf["ranges"]) if _facet_is_range(qf) else len(qf["values"]) for qf in query_facets], np.uint32)
-        allb = np.concatenate(bounds) if bounds else None
-        bases = None
-        if any(qf["type"] == "point" for qf in query_facets):
-            bases = (N.FacetPointC * nf_)()
-            for i, qf in enumerate(query_facets):
-                if qf["type"] == "point":
-                    bases[i] = self._point(qf["base"], qf.get("unit", "km"))
-        stride = int(nb.astype(np.int64).sum()) + nf_
+        off, ty, nb, allb, bases, stride = self._query_facet_args(query_facets)
         out = np.zeros((nq, stride), np.uint64)
         farr, nf = self.facet_filters(facet_filter) if facet_filter else (None, 0)
         N.check(N.lib().ss_bm25_search_facets(self._h, nq, queries.ctypes.data_as(C.c_void_p), int(k), int(result_type), nf,
@@ -1476,16 +1541,22 @@ class Index:
                query_type_default=QueryType.Union, search_mode=SearchMode.Lexical, offset=0, length=10,
                result_type=ResultType.TopkCount, similarity_threshold=None, normalize_query=True,
                strict=False, not_terms=(), field_filter=None, facet_filter=None, ann_mode=None, result_sort=None,
-               query_facets=None) -> ResultObject:
+               query_facets=None, enable_empty_query=False) -> ResultObject:
         """<IndexArc as Search>::search (search.rs:1134-1150): field_filter applies to both sides (lexical: several indexed
         fields; vector: records of the listed fields), facet_filter to the lexical side, ann_mode to the vector side.
         result_sort (SearchMode.Lexical; see Shard.search_lexical_sorted): every shard returns its best offset + length under
         the sort, the lists are merged under the same order across shards -- the facet values of the two docs, each read from its
         own shard, then the score (result_ordering_root, min_heap.rs:56-300; search.rs:2088).
         query_facets (SearchMode.Lexical / Hybrid; see finish_facets): counted on the lexical side of every shard in the same call as
-        its hits, the shards' maps merged into ResultObject.facets (merge_facets)"""
+        its hits, the shards' maps merged into ResultObject.facets (merge_facets).
+        enable_empty_query (the crate's argument, default False: nothing changes): SearchMode.Lexical with no query terms lists the
+        docs instead of raising or returning nothing -- see _search_empty; in result_sort the `_id` / `_score` fields are spelt
+        ("_id", descending) / ("_score", descending), as the last entry only (Shard.search_docs).  Vector and Hybrid searches
+        without terms are not touched by the flag."""
         S = self.shard_number
         ro = ResultObject()
+        if enable_empty_query and not query_terms and search_mode == SearchMode.Lexical and query_vector is None:
+            return self._search_empty(offset, length, result_type, facet_filter, result_sort, query_facets)
         if query_facets and (result_sort or search_mode not in (SearchMode.Lexical, SearchMode.Hybrid) or not query_terms):
             raise ValueError("query_facets apply to lexical and hybrid searches by score")
         if result_sort:
@@ -1539,6 +1610,57 @@ class Index:
         if result_type != ResultType.Count:
             d, s, src = merge_results(search_mode, (lex_d, lex_s), (vec_d, vec_s), offset, length)
             ro.results = [Result(int(a), float(b), ResultSource(int(c))) for a, b, c in zip(d, s, src)]
+        if query_facets:
+            ro.facets = merge_facets(query_facets, shard_maps, result_type)
+        ro.result_count = len(ro.results)
+        return ro
+
+    def _search_empty(self, offset, length, result_type, facet_filter, result_sort, query_facets) -> ResultObject:
+        """The empty query (search.rs:1413-1432 and 3374-3386).  field_filter plays no part.
+        Index path -- no facet_filter, no query_facets, result_sort empty or ONE ("_id" | "_score", descending) entry
+        (search_iterator_index, iterator.rs:360-413): global doc ids from the largest down (from the smallest up iff that one entry is
+        ascending), tombstoned docs skipped, `offset` live docs skipped and `length` taken, every score 0.0, and result_count_total =
+        the indexed doc count, tombstoned docs INCLUDED (the crate's own figure, reproduced).
+        Shard path -- everything else (search_iterator_shard on every shard, k = offset + length): local ids remapped to
+        local * S + shard, rows merged by (the sort keys, each doc's read from its own shard, then the global doc id in the tie
+        direction), totals summed over the shards' live matches, facets through merge_facets."""
+        S = self.shard_number
+        ro = ResultObject()
+        sorts = list(result_sort or [])
+        k = int(offset) + int(length)
+        if not facet_filter and not query_facets and (not sorts or (len(sorts) == 1 and sorts[0][0] in ("_id", "_score"))):
+            ascending = bool(sorts) and not sorts[0][-1]
+            ro.result_count_total = sum(int(sh.indexed_doc_count) for sh in self.shards)
+            if int(result_type) != int(ResultType.Count) and k:
+                ids = []
+                for sh in self.shards:
+                    d, _, _, _ = sh.search_docs(k, ResultType.Topk, doc_ascending=ascending)
+                    ids += [int(x) * S + sh.shard_id for x in d]
+                ids.sort(reverse=not ascending)
+                ro.results = [Result(g, 0.0, ResultSource.Lexical) for g in ids[offset:offset + length]]
+            ro.result_count = len(ro.results)
+            return ro
+        fsorts, ascending = Shard.split_id_sort(sorts)
+        rows, shard_maps = [], []
+        want_docs = int(result_type) != int(ResultType.Count) and k
+        for sh in self.shards:
+            d, _, tot, per = sh.search_docs_raw(k, result_type if want_docs else ResultType.Count, facet_filter, fsorts, query_facets, ascending)
+            ro.result_count_total += tot
+            if query_facets:
+                shard_maps.append(finish_facets(query_facets, per, S))
+            keys = []
+            for sf in fsorts:
+                if sf[1] == "point":
+                    vals, ty = sh.facet_point_distances(d, sf[0], sf[3], "sortkey").view(np.uint64), "f64"
+                else:
+                    vals, ty = sh.facet_values(d, sf[0], sf[1]), sf[1]
+                keys.append([Shard._facet_order_key(x, ty, sf[2]) for x in vals])
+            for i in range(len(d)):
+                g = int(d[i]) * S + sh.shard_id
+                rows.append((tuple(-kk[i] for kk in keys), g if ascending else -g, g))
+        rows.sort()
+        if want_docs:
+            ro.results = [Result(g, 0.0, ResultSource.Lexical) for _, _, g in rows[offset:offset + length]]
         if query_facets:
             ro.facets = merge_facets(query_facets, shard_maps, result_type)
         ro.result_count = len(ro.results)
