@@ -467,7 +467,8 @@ typedef struct {
  * order, only listed ones under SS_OP_FIELD_FILTER; the score sums all fields of the unique terms.  Host-pointer batches may mix
  * phrase queries with others (run as two sub-batches inside the library, answers back in the callers' order); a DEVICE-resident
  * batch (ss_bm25_search_dev) holds phrase queries only (ops_mask bit 4).  NOT terms work with phrases as with every query type
- * (add_result.rs:3440-3497; ABI v4): a doc found in a NOT list is no match. */
+ * (add_result.rs:3440-3497; ABI v4): a doc found in a NOT list is no match.  The entries that walk match sets -- ss_bm25_facet_count,
+ * ss_bm25_facet_kth, ss_bm25_search_sorted, ss_bm25_search_facets -- answer phrases too (below). */
 
 /* Batched BM25 search.  Outputs: out_doc/out_score [n_queries*k], out_count [n_queries] (= results.len()),
  * out_total [n_queries] (= result_count_total: exact match count for Count/TopkCount). */
@@ -557,9 +558,12 @@ int ss_bm25_search_filtered_dev(ss_shard* s, uint32_t n_queries, const ss_bm25_q
  * bound).  *out_total (may be NULL) = the match count.  The match set is read from the probe index's bit records:
  * SS_ENOTSUP if a dense list of the query has no probe row (ss_bm25_term_probed).  Terms of the SPARSE tier
  * (ss_bm25_append_sparse[_fields]), scored or NOT, are answered too: their lists are merged into the bit records' match set on
- * the device.  Left to the caller's own path (SS_ENOTSUP) when the query names a sparse term: phrases, SS_OP_ALL_TERMS_FREQUENT,
- * unions of several terms under a field filter.  The same holds for ss_bm25_facet_kth, ss_bm25_search_sorted and the *_point
- * entries below. */
+ * the device.  Left to the caller's own path (SS_ENOTSUP) when the query names a sparse term: SS_OP_ALL_TERMS_FREQUENT,
+ * unions of several terms under a field filter.  PHRASES are answered, on either tier: the match set of the phrase's unique terms as
+ * an intersection is refined by the position check on the device.  SS_ENOTSUP for a phrase on an image without positions (or naming a
+ * sparse term on a tier without them; ss_bm25_search answers SS_ESTATE there), on several indexed fields without merged lists, and for a
+ * phrase ss_bm25_search refuses as well (a place naming unique term SS_MAX_PHRASE or later; more than 6 unique terms with a sparse one).
+ * The same holds for ss_bm25_facet_kth, ss_bm25_search_sorted and the *_point entries below. */
 int ss_bm25_facet_count(ss_shard* s, const ss_bm25_query* query, uint32_t n_filters, const ss_facet_filter* filters,
                         uint32_t facet_offset, uint32_t facet_type, uint32_t n_buckets, const uint64_t* range_lower_bounds,
                         uint64_t* out_counts, uint64_t* out_total);
@@ -586,7 +590,8 @@ int ss_facet_values(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t f
  * (strictly better than a pivot at some field) and the tie group of the last pivot --, which two ordinary searches under exclusion
  * bitmaps turn into scored lists and a compose kernel orders by (field 1, ..., field n, score desc, doc asc).  The host only
  * launches: one synchronisation per call.  n_sorts <= SS_MAX_SORT_FIELDS numeric or Point fields (n_sorts = 0: by score alone);
- * every list of every query needs a probe row (SS_ENOTSUP otherwise, as for ss_bm25_facet_kth); no phrase queries.
+ * every list of every query needs a probe row (SS_ENOTSUP otherwise, as for ss_bm25_facet_kth); phrase queries are answered as
+ * ss_bm25_facet_count answers them (a chunk of <= 64 queries that holds one runs its two searches query by query).
  * out_doc / out_score [n_queries][k], out_count [n_queries], out_total [n_queries] = all matches of the query.
  * -0.0 and +0.0 tie in a sort field (partial_cmp, min_heap.rs:807-830); a pivot at zero comes back as +0.0.  NaN in a sort field has
  * no reference order and is out of scope. */
@@ -623,8 +628,10 @@ int ss_facet_point_distances(ss_shard* s, uint32_t n, const uint32_t* doc_ids, u
  * queries are counted by one kernel launch over the chunk's match sets; the facet filter's bitmap is built once per call.
  * n_facets = 0: ss_bm25_search_filtered.  SS_EINVAL: more than SS_MAX_QUERY_FACETS facets, a type beyond SS_FACET_POINT, a Point facet
  * without bases, bounds missing, n_buckets 0 or above 2^24.  SS_ESTATE: no facet records, or an offset beyond the record.
- * SS_ENOTSUP -- for the whole call, outputs unspecified -- for the shapes ss_bm25_facet_count leaves to the caller (above: a phrase, a
- * dense list without a probe row, and with a sparse term SS_OP_ALL_TERMS_FREQUENT or a union of several terms under a field filter);
+ * Phrases are answered, alone or mixed with other queries in the batch, as ss_bm25_facet_count answers them.
+ * SS_ENOTSUP -- for the whole call, outputs unspecified -- for the shapes ss_bm25_facet_count leaves to the caller (above: a phrase
+ * without the positions or merged lists it needs, a dense list without a probe row, and with a sparse term SS_OP_ALL_TERMS_FREQUENT or
+ * a union of several terms under a field filter);
  * pool rows are dealt per chunk of <= 64 queries, so a chunk can be refused whose queries ss_bm25_facet_count serves one by one. */
 #define SS_MAX_QUERY_FACETS 16
 int ss_bm25_search_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* queries, uint32_t k, uint32_t result_type,

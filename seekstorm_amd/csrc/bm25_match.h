@@ -26,3 +26,15 @@ int ssi_bm25_tier_plan(const ss_shard* s, uint32_t nq, const ss_bm25_query* q, B
 // probe row (the caller ran ssi_bm25_ensure_probe_rows first).
 int ssi_bm25_match_bits_tiered(ss_shard* s, const BmTierPlan& plan, const ss_bm25_query* h_q, const ss_bm25_query* d_q, ss_bm25_query* d_sub,
                                unsigned long long* d_bits, unsigned long long* d_total, hipStream_t st, uint32_t nq);
+
+// PHRASES (bm25_phrase_bits.hip).  The match set of a phrase = the match set of its INTERSECTION FORM (ssi_bm25_phrase_stage: the same
+// terms and NOT terms, no field-filter bits -- a phrase reads the merged lists, its filter is a test on positions), built by the
+// calls above, then refined: ssi_bm25_phrase_refine clears every doc of d_bits [nq][n_sub * BM_SUB / 64] whose positions do not carry
+// the phrase and takes it off d_total [nq].  d_q: the batch as the caller gave it, on the device; its queries that are no phrases are
+// left alone.  ssi_bm25_phrase_check: SS_OK when the refine can answer the phrase on this image; SS_ENOTSUP for what stays with the
+// caller's own path -- no positions in the image (or in the sparse tier, for a phrase naming a sparse term), several indexed fields
+// without merged lists, a phrase the search refuses as well (a place naming unique term SS_MAX_PHRASE or later; more than 6 unique terms
+// with a sparse one among them); SS_EINVAL for a malformed phrase.
+int ssi_bm25_phrase_check(const ss_shard* s, const ss_bm25_query& q);
+void ssi_bm25_phrase_stage(const ss_bm25_query& q, ss_bm25_query* out);
+int ssi_bm25_phrase_refine(ss_shard* s, const ss_bm25_query* d_q, unsigned long long* d_bits, unsigned long long* d_total, hipStream_t st, uint32_t nq);

@@ -3224,6 +3224,40 @@ static int tier_prepare(ss_shard* s, uint32_t nq, const ss_bm25_query* q, BmTier
   return SS_OK;
 }
 
+// PHRASES in such a batch (bm25_phrase_bits.hip): a phrase's match set is the match set of its intersection form, refined by its
+// positions.  match_stage_phrases checks every phrase of the chunk against the image -- under the shard lock, before anything is staged;
+// SS_ENOTSUP for what stays with the caller's own path -- and writes the chunk with its phrases in intersection
+// form into mc->staged.  A chunk without a phrase leaves it empty: form() is then the caller's own array and every call below is the
+// one such a chunk has always taken.  The staged forms are read by asynchronous copies: a MatchChunk lives until the call's synchronisation.
+struct MatchChunk {
+  BmTierPlan tier;
+  std::vector<ss_bm25_query> staged;
+  bool any_phrase() const { return !staged.empty(); }
+  const ss_bm25_query* form(const ss_bm25_query* qc) const { return staged.empty() ? qc : staged.data(); }
+};
+static int match_stage_phrases(const ss_shard* s, uint32_t nb, const ss_bm25_query* qc, MatchChunk* mc) {
+  mc->staged.clear();
+  bool any = false;
+  for (uint32_t i = 0; i < nb; i++)
+    if (bm_q_op(qc[i].op) == SS_OP_PHRASE) {
+      SS_TRY(ssi_bm25_phrase_check(s, qc[i]));
+      any = true;
+    }
+  if (!any) return SS_OK;
+  mc->staged.assign(qc, qc + nb);
+  for (uint32_t i = 0; i < nb; i++)
+    if (bm_q_op(qc[i].op) == SS_OP_PHRASE) ssi_bm25_phrase_stage(qc[i], &mc->staged[i]);
+  return SS_OK;
+}
+// the match sets of a prepared chunk: qf / d_q = its form() on the host / the device, d_ph = the chunk as the caller gave it, on the
+// device (read only when it holds a phrase)
+static int match_bits_chunk(ss_shard* s, const MatchChunk& mc, const ss_bm25_query* qf, const ss_bm25_query* d_q, ss_bm25_query* d_sub,
+                            const ss_bm25_query* d_ph, unsigned long long* d_bits, unsigned long long* d_total, hipStream_t st, uint32_t nb) {
+  SS_TRY(mc.tier.any_tiered ? ssi_bm25_match_bits_tiered(s, mc.tier, qf, d_q, d_sub, d_bits, d_total, st, nb)
+                            : ssi_bm25_match_bits(s, d_q, d_bits, d_total, st, nb));
+  return mc.any_phrase() ? ssi_bm25_phrase_refine(s, d_ph, d_bits, d_total, st, nb) : SS_OK;
+}
+
 // Facet counts of ONE query (query_facets / facet_count, add_result.rs:484-640): histogram of a facet over the query's match
 // set (after NOT terms, tombstones and the facet filter).  out_counts [n_buckets + 1]: a string facet's ids 0 .. n_buckets-1,
 // or the numeric ranges given by their ascending lower bounds; the last slot collects what falls outside.
@@ -3238,18 +3272,21 @@ static int facet_count_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_
   bool has_and, has_or, all_probed, any_frequent;
   uint32_t nt_max, np_max;
   ShardLock g(s);
-  BmTierPlan plan;  // (a query naming a sparse-tier term: bm25_match.h)
-  SS_TRY(tier_prepare(s, 1, query, &plan, s->stream));
+  MatchChunk mc;  // (a phrase: its intersection form, refined; a query naming a sparse-tier term: bm25_match.h)
+  SS_TRY(match_stage_phrases(s, 1, query, &mc));
+  const ss_bm25_query* qf = mc.form(query);
+  BmTierPlan& plan = mc.tier;
+  SS_TRY(tier_prepare(s, 1, qf, &plan, s->stream));
   if (!plan.any_tiered) {
-    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, query, s->stream));
-    SS_TRY(check_queries(s, 1, query, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
+    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, qf, s->stream));
+    SS_TRY(check_queries(s, 1, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
     if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
   }
   SS_HIP(hipSetDevice(s->device));
   static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
-  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + ((size_t)n_buckets + 1) * 8 + (size_t)n_buckets * 8 + sizeof(ss_bm25_query);
+  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + ((size_t)n_buckets + 1) * 8 + (size_t)n_buckets * 8 + 2 * sizeof(ss_bm25_query);
   if (bytes > s->facet_ws_cap) {  // grow-only workspace (a hipMalloc / hipFree pair per call would synchronise the device)
     if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
     s->d_facet_ws = nullptr;
@@ -3264,17 +3301,16 @@ static int facet_count_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_
   unsigned long long* d_counts = d_bits + groups;
   uint64_t* d_bounds = (uint64_t*)(d_counts + n_buckets + 1);
   ss_bm25_query* d_sub = (ss_bm25_query*)(d_bounds + n_buckets);  // a tiered query's dense part
+  ss_bm25_query* d_ph = d_sub + 1;                                 // a phrase as the caller gave it (d_q holds its intersection form)
   int rc = SS_OK;
-  if (hipMemcpyAsync(d_q, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+  if (hipMemcpyAsync(d_q, qf, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
+      (mc.any_phrase() && hipMemcpyAsync(d_ph, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream) != hipSuccess) ||
       hipMemsetAsync(d_total, 0, 8 + groups * 8 + ((size_t)n_buckets + 1) * 8, s->stream) != hipSuccess ||
       (!string_facet &&
        hipMemcpyAsync(d_bounds, range_lower_bounds, (size_t)n_buckets * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess))
     rc = SS_EDEVICE;
   if (rc == SS_OK)
-    rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() {
-      return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, query, d_q, d_sub, d_bits, d_total, s->stream, 1)
-                             : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream);
-    });
+    rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return match_bits_chunk(s, mc, qf, d_q, d_sub, d_ph, d_bits, d_total, s->stream, 1); });
   if (rc == SS_OK) rc = ssi_facet_count(s, d_bits, s->bm_n_docs, facet_offset, facet_type, n_buckets, d_bounds, d_counts, point, s->stream);
   if (rc == SS_OK && (hipMemcpyAsync(out_counts, d_counts, ((size_t)n_buckets + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
                       (out_total && hipMemcpyAsync(out_total, d_total, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)))
@@ -3307,18 +3343,21 @@ static int facet_kth_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_fi
   bool has_and, has_or, all_probed, any_frequent;
   uint32_t nt_max, np_max;
   ShardLock g(s);
-  BmTierPlan plan;  // (a query naming a sparse-tier term: bm25_match.h)
-  SS_TRY(tier_prepare(s, 1, query, &plan, s->stream));
+  MatchChunk mc;  // (a phrase: its intersection form, refined; a query naming a sparse-tier term: bm25_match.h)
+  SS_TRY(match_stage_phrases(s, 1, query, &mc));
+  const ss_bm25_query* qf = mc.form(query);
+  BmTierPlan& plan = mc.tier;
+  SS_TRY(tier_prepare(s, 1, qf, &plan, s->stream));
   if (!plan.any_tiered) {
-    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, query, s->stream));
-    SS_TRY(check_queries(s, 1, query, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
+    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, qf, s->stream));
+    SS_TRY(check_queries(s, 1, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
     if (!all_probed || !s->d_probe) return SS_ENOTSUP;
   }
   SS_HIP(hipSetDevice(s->device));
   static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
-  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + 256 * 8 + sizeof(ss_bm25_query);
+  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + 256 * 8 + 2 * sizeof(ss_bm25_query);
   if (bytes > s->facet_ws_cap) {
     if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
     s->d_facet_ws = nullptr;
@@ -3332,12 +3371,11 @@ static int facet_kth_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_fi
   unsigned long long* d_bits = d_total + 1;
   unsigned long long* d_hist = d_bits + groups;
   ss_bm25_query* d_sub = (ss_bm25_query*)(d_hist + 256);  // a tiered query's dense part
-  SS_HIP(hipMemcpyAsync(d_q, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+  ss_bm25_query* d_ph = d_sub + 1;                         // a phrase as the caller gave it (d_q holds its intersection form)
+  SS_HIP(hipMemcpyAsync(d_q, qf, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+  if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
   SS_HIP(hipMemsetAsync(d_total, 0, 8 + groups * 8, s->stream));
-  SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
-    return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, query, d_q, d_sub, d_bits, d_total, s->stream, 1)
-                           : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream);
-  }));
+  SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() { return match_bits_chunk(s, mc, qf, d_q, d_sub, d_ph, d_bits, d_total, s->stream, 1); }));
   uint64_t total = 0;
   SS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipStreamSynchronize(s->stream));
@@ -3380,7 +3418,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                o_ac = o_as + al((size_t)CH * k * 4), o_cd = o_ac + al((size_t)CH * 4), o_cs = o_cd + al((size_t)CH * k * 4),
                o_cc = o_cs + al((size_t)CH * k * 4), o_at = o_cc + al((size_t)CH * 4), o_od = o_at + al((size_t)CH * 8),
                o_os = o_od + al((size_t)nq * k * 4), o_oc = o_os + al((size_t)nq * k * 4), o_ot = o_oc + al((size_t)nq * 4),
-               o_sub = o_ot + al((size_t)nq * 8), need = o_sub + al((size_t)CH * sizeof(ss_bm25_query));
+               o_sub = o_ot + al((size_t)nq * 8), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)), need = o_ph + al((size_t)CH * sizeof(ss_bm25_query));
   if (need > s->sort_ws_cap) {
     SS_HIP(hipStreamSynchronize(s->stream));
     if (s->d_sort_ws) (void)hipFree(s->d_sort_ws);
@@ -3395,7 +3433,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                      *d_xe = (unsigned long long*)(W + o_xe);
   SS_TRY(ensure_out(s, 1, k));
   constexpr int batched_off = 0;
-  std::vector<BmTierPlan> plans((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
+  std::vector<MatchChunk> plans((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
   for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = queries + c0;
@@ -3403,20 +3441,25 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
     uint32_t nt_max = 0, np_max = 0, nn_max = 0;
     // a chunk that names a sparse-tier term: its match sets from both tiers (bm25_match.h), its two searches query by query below
     // (bm25_search_host_queries routes each to bm25_search_tiered under the swapped exclusion bitmap); select and compose stay batched
-    BmTierPlan& plan = plans[c0 / CH];
-    SS_TRY(tier_prepare(s, nb, qc, &plan, s->stream));
+    // a chunk that holds a phrase: match sets of the intersection forms, refined (bm25_phrase_bits.hip); its two searches query by
+    // query as well -- the ordinary search answers a phrase under the swapped bitmap and routes it to its own kernel family
+    MatchChunk& mc = plans[c0 / CH];
+    SS_TRY(match_stage_phrases(s, nb, qc, &mc));
+    const ss_bm25_query* qf = mc.form(qc);
+    BmTierPlan& plan = mc.tier;
+    SS_TRY(tier_prepare(s, nb, qf, &plan, s->stream));
     if (!plan.any_tiered) {
-      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qc, s->stream));
-      SS_TRY(check_queries(s, nb, qc, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
+      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qf, s->stream));
+      SS_TRY(check_queries(s, nb, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
       if (!all_probed || !s->d_probe || phrase) return SS_ENOTSUP;
     }
-    SS_HIP(hipMemcpyAsync(d_q, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
-      return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, qc, d_q, (ss_bm25_query*)(W + o_sub), d_E, d_total, s->stream, nb)
-                             : ssi_bm25_match_bits(s, d_q, d_E, d_total, s->stream, nb);
-    }));
+    ss_bm25_query* d_ph = (ss_bm25_query*)(W + o_ph);
+    SS_HIP(hipMemcpyAsync(d_q, qf, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+    if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream,
+                             [&]() { return match_bits_chunk(s, mc, qf, d_q, (ss_bm25_query*)(W + o_sub), d_ph, d_E, d_total, s->stream, nb); }));
     SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, k, s->stream));
-    bool batched = !batched_off && !plan.any_tiered;
+    bool batched = !batched_off && !plan.any_tiered && !mc.any_phrase();
     for (int part = 0; part < 2 && batched; part++) {  // both searches as ONE batch each: every query under its own exclusion bitmap
       uint32_t* del = s->d_deleted;
       const uint64_t dw = s->deleted_words, nd = s->n_deleted;
@@ -3522,12 +3565,13 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
 static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t n_filters, const ss_facet_filter* filters,
                                uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
                                const uint64_t* range_lower_bounds, const ss_facet_point* bases, size_t n_bounds, size_t stride,
-                               std::vector<BmTierPlan>& plans, unsigned long long** d_counts_out) {
+                               std::vector<MatchChunk>& plans, unsigned long long** d_counts_out) {
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
   const bool prebuilt = n_filters != 0;  // (the entry built the bitmap)
   const uint32_t CH = std::min<uint32_t>(nq, 64u);  // (tier_prepare plans batches of <= 64, ssi_bm25_match_bits takes as many)
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_q = 0, o_sub = o_q + al((size_t)CH * sizeof(ss_bm25_query)), o_tot = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
+  const size_t o_q = 0, o_sub = o_q + al((size_t)CH * sizeof(ss_bm25_query)), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
+               o_tot = o_ph + al((size_t)CH * sizeof(ss_bm25_query)),
                o_bits = o_tot + al((size_t)CH * 8), o_bounds = o_bits + al((size_t)CH * groups * 8), o_cnt = o_bounds + al(n_bounds * 8),
                need = o_cnt + al((size_t)nq * stride * 8);
   if (need > s->facet_ws_cap) {  // grow-only workspace
@@ -3539,7 +3583,7 @@ static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q,
     s->facet_ws_cap = need;
   }
   char* W = (char*)s->d_facet_ws;
-  ss_bm25_query *d_q = (ss_bm25_query*)(W + o_q), *d_sub = (ss_bm25_query*)(W + o_sub);
+  ss_bm25_query *d_q = (ss_bm25_query*)(W + o_q), *d_sub = (ss_bm25_query*)(W + o_sub), *d_ph = (ss_bm25_query*)(W + o_ph);
   unsigned long long *d_total = (unsigned long long*)(W + o_tot), *d_bits = (unsigned long long*)(W + o_bits), *d_counts = (unsigned long long*)(W + o_cnt);
   uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
   *d_counts_out = d_counts;
@@ -3549,21 +3593,23 @@ static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q,
   for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = q + c0;
-    BmTierPlan& plan = plans[c0 / CH];  // (a chunk naming a sparse-tier term: bm25_match.h)
-    SS_TRY(tier_prepare(s, nb, qc, &plan, s->stream));
+    MatchChunk& mc = plans[c0 / CH];  // (a chunk holding a phrase: bm25_phrase_bits.hip; naming a sparse-tier term: bm25_match.h)
+    SS_TRY(match_stage_phrases(s, nb, qc, &mc));
+    const ss_bm25_query* qf = mc.form(qc);
+    BmTierPlan& plan = mc.tier;
+    SS_TRY(tier_prepare(s, nb, qf, &plan, s->stream));
     if (!plan.any_tiered) {
       bool has_and, has_or, all_probed, any_frequent;
       uint32_t nt_max, np_max;
-      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qc, s->stream));
-      SS_TRY(check_queries(s, nb, qc, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));  // (phrases: SS_ENOTSUP, as ss_bm25_facet_count)
+      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qf, s->stream));
+      SS_TRY(check_queries(s, nb, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
       if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
     }
-    SS_HIP(hipMemcpyAsync(d_q, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+    SS_HIP(hipMemcpyAsync(d_q, qf, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+    if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
     SS_HIP(hipMemsetAsync(d_total, 0, (size_t)((char*)(d_bits + (size_t)nb * groups) - (char*)d_total), s->stream));
-    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
-      return plan.any_tiered ? ssi_bm25_match_bits_tiered(s, plan, qc, d_q, d_sub, d_bits, d_total, s->stream, nb)
-                             : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream, nb);
-    }, prebuilt));
+    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream,
+                             [&]() { return match_bits_chunk(s, mc, qf, d_q, d_sub, d_ph, d_bits, d_total, s->stream, nb); }, prebuilt));
     SS_TRY(ssi_facet_count_multi(s, nb, d_bits, n_facets, facet_offset, facet_type, n_buckets, bases, d_bounds, d_counts + (size_t)c0 * stride, s->stream));
   }
   return SS_OK;
@@ -3589,15 +3635,13 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
   if (n_bounds && !range_lower_bounds) return SS_EINVAL;
   if (!s->d_post) return SS_ESTATE;
   if (nq == 0) return SS_OK;
-  for (uint32_t i = 0; i < nq; i++)
-    if (bm_q_op(q[i].op) == SS_OP_PHRASE) return SS_ENOTSUP;  // match sets hold no phrases (as ss_bm25_facet_count answers one)
   ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
   if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
   for (uint32_t f = 0; f < n_facets; f++)
     if ((uint64_t)facet_offset[f] + width[facet_type[f]] > s->facet_record_size) return SS_ESTATE;
-  std::vector<BmTierPlan> plans;
+  std::vector<MatchChunk> plans;
   unsigned long long* d_counts = nullptr;
   int rc = SS_OK;
   if (n_filters) {  // one exclusion bitmap for the match sets and the search

@@ -208,7 +208,8 @@ class Shard {
 
   // the reference's per-shard seams (one query)
   // not_terms: the "-term" operands; field_filter: indexed field ids (a union of several terms under it is answered through
-  // the reference's own sub-queries, union.rs:1168-1479); result_sort: Vec<ResultSort> over numeric and Point facets
+  // the reference's own sub-queries, union.rs:1168-1479); result_sort: Vec<ResultSort> over numeric and Point facets.
+  // result_sort and query_facets work with QueryType::Phrase as well: the library builds a phrase's match set on the device
   ResultObject search_lexical_shard(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset,
                                     size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter = {},
                                     const std::vector<uint32_t>& not_terms = {}, const std::vector<uint16_t>& field_filter = {},
@@ -221,13 +222,15 @@ class Shard {
                            const std::vector<ResultSort>& result_sort = {}, const std::vector<QueryFacet>& query_facets = {},
                            bool doc_ascending = false, uint64_t skip = 0, size_t shard_number = 1);
   // search_lexical_batch with the batch's query_facets in the same call (ss_bm25_search_facets): counts [n_queries][sum_f (n_buckets
-  // + 1)] raw counters, ResultObject::facets = finish_facets of each query's row (shard_number: of the index, for the crate's cap)
+  // + 1)] raw counters, ResultObject::facets = finish_facets of each query's row (shard_number: of the index, for the crate's cap).
+  // The batch may hold phrase queries, alone or mixed with unions and intersections.
   std::vector<ResultObject> search_facets(const std::vector<ss_bm25_query>& queries, size_t k, ResultType result_type,
                                           const std::vector<QueryFacet>& query_facets, const std::vector<ss_facet_filter>& facet_filter = {},
                                           size_t shard_number = 1, std::vector<uint64_t>* counts = nullptr, bool mark_frequent = true);
   // query_facets of one query (facet_count, add_result.rs:484-640): counts [n_buckets + 1], the last slot = outside the buckets.
   // String facets: n_buckets ids (bounds empty); numeric facets: the ranges' ascending lower bounds as the value's bits;
   // Point facets (facet_type SS_FACET_POINT): base + the lower bounds of the distance ranges as f64 bits.
+  // Unions, intersections and phrases, on either tier (a phrase on an image without positions: SS_ENOTSUP).
   // order keys of docs under one sort field: larger = better (the facet's stored value mapped to an unsigned integer that orders
   // like it, complemented for an ascending sort; Point facets: by simplified_distance to the field's base)
   int sort_keys(const std::vector<uint32_t>& doc_ids, const ResultSort& field, std::vector<uint64_t>* keys);
@@ -291,7 +294,7 @@ class Index {
   // search() for SearchMode::Lexical with result_sort: every shard returns its best offset + length under the sort
   // (Shard::search_lexical_shard with result_sort), the lists are merged under the same order across shards -- the facet
   // values of the two docs, each read from its own shard, then the score (result_ordering_root, min_heap.rs:56-300;
-  // search.rs:2088) --, then offset / length.  Global ids, totals summed.
+  // search.rs:2088) --, then offset / length.  Global ids, totals summed.  Any query type, QueryType::Phrase included.
   ResultObject search_lexical_sorted(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset, size_t length,
                                      const std::vector<ResultSort>& result_sort, const std::vector<ss_facet_filter>& facet_filter = {},
                                      const std::vector<uint32_t>& not_terms = {});
@@ -301,7 +304,7 @@ class Index {
   // One host thread per shard (the reference spawns one task per shard, search.rs:1637-1743); each shard is asked for
   // (offset 0, length offset+length) (search.rs:1658-1659); ids become local * S + shard (search.rs:1671);
   // totals are summed, Hybrid takes max(lexical, vector) per shard (search.rs:1919-1921); merge / RRF / sort /
-  // offset / truncate through ss_merge_results (search.rs:1875-2119).
+  // offset / truncate through ss_merge_results (search.rs:1875-2119).  query_facets and result_sort apply to phrases too.
   ResultObject search(const std::vector<uint32_t>& query_terms, const float* query_vector, QueryType query_type_default,
                       SearchMode search_mode, size_t offset, size_t length, ResultType result_type,
                       const float* similarity_threshold = nullptr, bool normalize_query = true,

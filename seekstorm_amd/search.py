@@ -896,7 +896,7 @@ class Shard:
     def facet_kth(self, query, facet_offset, facet_type, descending, k, facet_filter=None, base=None):
         """the pivot of a result sort: (stored bits of the k-th best value among the query's matches, matches strictly better,
         matches equal, all matches) -- ss_bm25_facet_kth; a Point facet (base = (lat, lon)): the f64 bits of the k-th best
-        simplified_distance to the base -- ss_bm25_facet_kth_point"""
+        simplified_distance to the base -- ss_bm25_facet_kth_point.  Any query facet_count takes, phrases included."""
         farr, nf = self.facet_filters(facet_filter) if facet_filter else (None, 0)
         q = np.ascontiguousarray(query[:1])
         v, nb, ne, tot = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -945,7 +945,8 @@ class Shard:
     def search_lexical_sorted_batch(self, queries, result_sort, k, facet_filter=None):
         """a BATCH of queries under result_sort = [(facet offset, type, descending[, base])] (numeric facets, Point facets by
         simplified_distance to base = (lat, lon)): ss_bm25_search_sorted -- the pivots of every sort field are found on the device, two
-        searches under exclusion bitmaps and a compose kernel per query, one synchronisation per call.
+        searches under exclusion bitmaps and a compose kernel per query, one synchronisation per call.  Phrase queries are answered,
+        alone or mixed with others (a chunk of 64 queries holding one runs its searches query by query).
         -> (doc [nq][k], score [nq][k], count [nq], total [nq])"""
         n, arr = self._result_sorts(result_sort)
         q = np.ascontiguousarray(queries)
@@ -961,7 +962,8 @@ class Shard:
         return doc, score, cnt, tot
 
     def search_lexical_sorted(self, query, result_sort, k, facet_filter=None):
-        """ONE query (a 1-element make_queries array) under result_sort -> (doc ids, scores, total): ss_bm25_search_sorted"""
+        """ONE query (a 1-element make_queries array, any query type: phrases too) under result_sort -> (doc ids, scores, total):
+        ss_bm25_search_sorted"""
         if len(result_sort) > N.SS_MAX_SORT_FIELDS:
             return self.search_lexical_sorted_composed(query, result_sort, k, facet_filter)
         doc, score, cnt, tot = self.search_lexical_sorted_batch(query[:1], result_sort, k, facet_filter)
@@ -1030,7 +1032,8 @@ class Shard:
         """query_facets of one query (facet_count, add_result.rs:484-640): histogram of the facet over the match set.
         String facets: n_buckets ids; numeric facets: ascending lower bounds of the ranges; Point facets (QueryFacet::Point):
         base = (lat, lon), unit, and the lower bounds of the DISTANCE ranges.  -> (counts [n_buckets], docs outside the
-        buckets, match count)"""
+        buckets, match count).  Unions, intersections and phrases, on either tier; a phrase needs the positions in the image (and in
+        the sparse tier when it names a sparse term): SeekStormHipError SS_ENOTSUP without them."""
         if facet_type == "point":
             bounds = np.asarray(range_lower_bounds, np.float64).view(np.uint64).copy()
             nb = len(bounds)
@@ -1204,7 +1207,8 @@ class Shard:
     def search_lexical_facets(self, queries, k, query_facets, result_type=ResultType.TopkCount, facet_filter=None, reference_shortcuts=True):
         """search_lexical_batch with the batch's query_facets in the same call (ss_bm25_search_facets): -> (doc, score, count, total,
         counts_per_facet), counts_per_facet[f] = [n_queries][n_buckets + 1] raw counters of facet f (last column: "other"), what
-        finish_facets takes per query.  doc / score / count / total are search_lexical_batch's."""
+        finish_facets takes per query.  doc / score / count / total are search_lexical_batch's.  The batch may hold phrase queries,
+        alone or mixed with unions and intersections."""
         if reference_shortcuts and result_type != ResultType.Count and not facet_filter and \
                 (self.lexical_field_count == 1 or self.fields_info()[1]):
             queries = self.mark_all_terms_frequent(queries, k)
@@ -1548,7 +1552,8 @@ class Index:
         the sort, the lists are merged under the same order across shards -- the facet values of the two docs, each read from its
         own shard, then the score (result_ordering_root, min_heap.rs:56-300; search.rs:2088).
         query_facets (SearchMode.Lexical / Hybrid; see finish_facets): counted on the lexical side of every shard in the same call as
-        its hits, the shards' maps merged into ResultObject.facets (merge_facets).
+        its hits, the shards' maps merged into ResultObject.facets (merge_facets).  Both work with query_type_default = Phrase: the
+        shards count and sort a phrase's matches on the device.
         enable_empty_query (the crate's argument, default False: nothing changes): SearchMode.Lexical with no query terms lists the
         docs instead of raising or returning nothing -- see _search_empty; in result_sort the `_id` / `_score` fields are spelt
         ("_id", descending) / ("_score", descending), as the last entry only (Shard.search_docs).  Vector and Hybrid searches
