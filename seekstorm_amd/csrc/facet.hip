@@ -167,8 +167,7 @@ int ssi_facet_build(ss_shard* s, uint32_t n_filters, const ss_facet_filter* filt
   uint64_t set_words = 0, set_begin[SS_MAX_FACET_FILTERS] = {0}, set_bits[SS_MAX_FACET_FILTERS] = {0};
   for (uint32_t i = 0; i < n_filters; i++) {
     const ss_facet_filter& f = filters[i];
-    static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
-    if (f.type > SS_FACET_POINT || f.offset + width[f.type] > s->facet_record_size) return SS_EINVAL;
+    if (f.type > SS_FACET_POINT || f.offset + ssi_facet_width(f.type) > s->facet_record_size) return SS_EINVAL;
     const bool strings = f.type == SS_FACET_STRING16 || f.type == SS_FACET_STRING32;
     if (strings && f.n_values > 8 && f.n_values != SS_FACET_IDS_EXTERN) return SS_EINVAL;
     F.f[i] = f;
@@ -346,13 +345,12 @@ __global__ void facet_radix_kernel(const unsigned long long* __restrict__ bits, 
 int ssi_facet_kth(ss_shard* s, const unsigned long long* d_bits, uint64_t n_docs, uint64_t n_matches, uint32_t offset, uint32_t type,
                   bool descending, uint64_t k, unsigned long long* d_hist, uint64_t* value_bits, uint64_t* n_better, uint64_t* n_equal,
                   const ss_facet_point* point, hipStream_t st) {
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 0, 0, 8};
   if (type == SS_FACET_STRING16 || type == SS_FACET_STRING32) return SS_ENOTSUP;  // they sort by their strings, which live in the host's facet.json
   FacetPoint pt{0, 0, 0};
   if (type == SS_FACET_POINT && facet_point_of(point, &pt) != SS_OK) return SS_EINVAL;  // the key is the f64 distance
   *n_better = 0; *n_equal = 0; *value_bits = 0;
   if (n_matches == 0) return SS_OK;
-  const uint32_t key_bits = 8u * width[type];
+  const uint32_t key_bits = 8u * ssi_facet_width(type);
   uint64_t want = std::min<uint64_t>(k, n_matches);  // rank (1-based) still to be found inside the current prefix
   unsigned long long prefix = 0;
   const uint64_t groups = (n_docs + 63) / 64;
@@ -388,14 +386,13 @@ __global__ void facet_values_kernel(const uint8_t* __restrict__ records, uint32_
 // point == nullptr: the stored bits (a Point facet's Morton code); with a point: the f64 distance to it
 int ssi_facet_values(ss_shard* s, const uint32_t* d_docs, uint32_t n, uint32_t offset, uint32_t type, unsigned long long* d_out,
                      const ss_facet_point* point, hipStream_t st) {
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   FacetPoint pt{0, 0, 0};
   uint32_t load_as = type;
   if (type == SS_FACET_POINT) {
     if (!point) load_as = SS_FACET_U64;
     else if (facet_point_of(point, &pt) != SS_OK) return SS_EINVAL;
   }
-  if (n) facet_values_kernel<<<(n + 255) / 256, 256, 0, st>>>(s->d_facets, s->facet_record_size, offset, width[type], d_docs, n,
+  if (n) facet_values_kernel<<<(n + 255) / 256, 256, 0, st>>>(s->d_facets, s->facet_record_size, offset, ssi_facet_width(type), d_docs, n,
                                                                (unsigned long long)s->facet_docs, d_out, load_as, pt);
   SS_HIP(hipGetLastError());
   return SS_OK;
@@ -592,7 +589,6 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
 int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned long long* d_B, unsigned long long* d_ex_b, unsigned long long* d_ex_e,
                     const unsigned long long* d_total, unsigned long long* d_hist, void* d_state, uint32_t n_sorts, const ss_result_sort* sorts,
                     uint32_t k, hipStream_t st) {
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 0, 0, 8};
   const unsigned long long n_docs = s->bm_n_docs, groups = (unsigned long long)s->bm_n_sub * (BM_SUB / 64);
   const dim3 grid((unsigned)((groups + 255) / 256), nq);
   SortState* state = (SortState*)d_state;
@@ -605,7 +601,7 @@ int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned 
       const ss_facet_point base{sorts[f].base_lat, sorts[f].base_lon, SS_POINT_SORTKEY, 0};
       if (facet_point_of(&base, &pt) != SS_OK) return SS_EINVAL;
     }
-    const uint32_t key_bits = 8u * width[type];
+    const uint32_t key_bits = 8u * ssi_facet_width(type);
     sort_level_begin_kernel<<<nq, 256, 0, st>>>(state, d_hist);
     for (uint32_t b = 0; b < key_bits / 8u; b++) {
       sort_radix_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, s->d_facets, s->facet_record_size, sorts[f].facet_offset, type, key_bits,
@@ -621,12 +617,11 @@ int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned 
   return SS_OK;
 }
 static int sort_fields_dev(uint32_t n_sorts, const ss_result_sort* sorts, SortFieldsDev* out) {
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 0, 0, 8};
   SortFieldsDev& F = *out;
   memset(&F, 0, sizeof(F));
   F.n = n_sorts;
   for (uint32_t f = 0; f < n_sorts; f++) {
-    F.offset[f] = sorts[f].facet_offset; F.type[f] = sorts[f].facet_type; F.bytes[f] = width[sorts[f].facet_type]; F.desc[f] = sorts[f].descending ? 1u : 0u;
+    F.offset[f] = sorts[f].facet_offset; F.type[f] = sorts[f].facet_type; F.bytes[f] = ssi_facet_width(sorts[f].facet_type); F.desc[f] = sorts[f].descending ? 1u : 0u;
     if (sorts[f].facet_type == SS_FACET_POINT) {
       const ss_facet_point base{sorts[f].base_lat, sorts[f].base_lon, SS_POINT_SORTKEY, 0};
       if (facet_point_of(&base, &F.pt[f]) != SS_OK) return SS_EINVAL;

@@ -3,6 +3,13 @@
 #pragma once
 #include "ss_common.h"
 
+// bytes a facet of `type` (<= SS_FACET_POINT, checked by the caller) takes in the record; a Point is its 8-byte Morton code.  (The
+// sorts never read a string's: they refuse string facets first.)  The kernels keep their own device-side tables.
+inline uint32_t ssi_facet_width(uint32_t type) {
+  static const uint8_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
+  return width[type];
+}
+
 int ssi_facet_kth(ss_shard* s, const unsigned long long* d_bits, uint64_t n_docs, uint64_t n_matches, uint32_t offset, uint32_t type,
                   bool descending, uint64_t k, unsigned long long* d_hist, uint64_t* value_bits, uint64_t* n_better, uint64_t* n_equal,
                   const ss_facet_point* point, hipStream_t st);

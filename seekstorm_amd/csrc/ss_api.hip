@@ -14,6 +14,7 @@
 #include <iterator>
 #include <memory>
 #include <new>
+#include <type_traits>
 #include <unordered_map>
 
 #include "ss_common.h"
@@ -31,6 +32,41 @@
   } while (0)
 
 namespace {
+// The shard's exclusion bitmap (d_deleted / deleted_words / n_deleted: its tombstones, as a rule) replaced by another one for the life
+// of the object; n_deleted = 1 says "some doc may be excluded": the kernels take their filtered instantiations.  per_query() /
+// vec_stride(): the bitmap is one of `words` words PER QUERY of the lexical / vector batch in flight; both flags are restored with the
+// bitmap and otherwise left as they stand (0 outside such a batch: no guard nests inside one).  The caller holds the shard lock.
+struct ExclSwap {
+  ss_shard* s;
+  uint32_t* del; uint64_t dw, nd; uint32_t pq, stride;
+  ExclSwap(ss_shard* s_, uint32_t* bits, uint64_t words)
+      : s(s_), del(s_->d_deleted), dw(s_->deleted_words), nd(s_->n_deleted), pq(s_->del_per_query), stride(s_->vec_del_stride) {
+    s->d_deleted = bits; s->deleted_words = words; s->n_deleted = 1;
+  }
+  ExclSwap(const ExclSwap&) = delete;
+  ~ExclSwap() { s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd; s->del_per_query = pq; s->vec_del_stride = stride; }
+  void per_query() { s->del_per_query = 1; }
+  void vec_stride(uint32_t words) { s->vec_del_stride = words; }
+};
+
+// Grow-only device workspace: *ptr holds at least `need` units (bytes behind a void*, elements else); a hipMalloc / hipFree pair per
+// call would synchronise the device.  Growing waits for s->stream first -- work still queued may read the old block --, frees it and
+// allocates `alloc` units (where a caller keeps slack against the next growth).  hipFree waits for the device anyway, so the explicit
+// wait costs the call sites that had none nothing, and the steady state (need <= *cap) does not touch the device at all.  On
+// failure *ptr = nullptr and *cap = 0.
+template <typename T>
+int reserve(ss_shard* s, T** ptr, size_t* cap, size_t need, size_t alloc = 0) {
+  if (need <= *cap) return SS_OK;
+  alloc = std::max(alloc, need);
+  SS_HIP(hipStreamSynchronize(s->stream));
+  if (*ptr) (void)hipFree(*ptr);
+  *ptr = nullptr;
+  *cap = 0;
+  SS_HIP(hipMalloc((void**)ptr, alloc * sizeof(std::conditional_t<std::is_void<T>::value, char, T>)));
+  *cap = alloc;
+  return SS_OK;
+}
+
 // runs `search` with the shard's tombstone bitmap replaced by the filter's exclusion bitmap (built on `st` first; `prebuilt`: the caller
 // has built THESE filters' bitmap on `st` already and nothing has written d_filter_bits since -- ss_bm25_search_facets builds it once)
 template <typename F>
@@ -39,14 +75,8 @@ int with_facet_filter(ss_shard* s, uint32_t n_filters, const ss_facet_filter* fi
   if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;  // a record for every doc of the lexical image
   int rc = prebuilt ? SS_OK : ssi_facet_build(s, n_filters, filters, st);
   if (rc) return rc;
-  uint32_t* del = s->d_deleted;
-  const uint64_t words = s->deleted_words, n = s->n_deleted;
-  s->d_deleted = s->d_filter_bits;
-  s->deleted_words = (s->facet_docs + 31) / 32;
-  s->n_deleted = 1;  // "some doc may be excluded": the kernels take their filtered instantiations
-  rc = search();
-  s->d_deleted = del; s->deleted_words = words; s->n_deleted = n;
-  return rc;
+  ExclSwap sw(s, s->d_filter_bits, (s->facet_docs + 31) / 32);
+  return search();
 }
 }  // namespace
 
@@ -336,15 +366,9 @@ static int ensure_out(ss_shard* s, size_t nq, size_t k) {
   return SS_OK;
 }
 
-// grow-only device staging of host-pointer queries (a hipMalloc / hipFree pair per call would synchronise the device)
+// device staging of host-pointer queries
 static int ensure_qstage(ss_shard* s, size_t bytes) {
-  if (bytes <= s->qstage_cap) return SS_OK;
-  if (s->d_qstage) (void)hipFree(s->d_qstage);
-  s->d_qstage = nullptr;
-  s->qstage_cap = 0;
-  SS_HIP(hipMalloc(&s->d_qstage, bytes));
-  s->qstage_cap = bytes;
-  return SS_OK;
+  return reserve(s, &s->d_qstage, &s->qstage_cap, bytes);
 }
 
 // ------------------------------------------------------------------ BM25
@@ -1561,13 +1585,7 @@ static int bm25_search_tiered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, 
   const size_t o_q = 0, o_dr = o_q + al((size_t)ns * sizeof(ss_bm25_query)), o_sr = o_dr + al((size_t)nq * 4), o_keys = o_sr + al((size_t)nq * 4),
                o_ext = o_keys + al((size_t)ns * 64 * KPL * 8), o_doc = o_ext + al((size_t)ns * 8), o_sc = o_doc + al((size_t)nq * kw * 4),
                o_cnt = o_sc + al((size_t)nq * kw * 4), o_tot = o_cnt + al((size_t)nq * 4), o_seed = o_tot + al((size_t)nq * 8), need = o_seed + al((size_t)nd * 4 + 4);
-  if (need > s->tier_ws_cap) {
-    SS_HIP(hipStreamSynchronize(s->stream));
-    if (s->d_tier_ws) (void)hipFree(s->d_tier_ws);
-    s->d_tier_ws = nullptr; s->tier_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_tier_ws, need * 2));
-    s->tier_ws_cap = need * 2;
-  }
+  SS_TRY(reserve(s, &s->d_tier_ws, &s->tier_ws_cap, need, need * 2));
   char* W = (char*)s->d_tier_ws;
   // the host vectors are read by synchronous copies (they may die with this frame) -- which do not wait for the stream: a tiered
   // search still queued (the device-pointer entry point returns early, bm25_search_tiered_excl runs several) reads this workspace.
@@ -1620,19 +1638,8 @@ static int bm25_search_tiered_excl(ss_shard* s, uint32_t nq, const ss_bm25_query
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t h_doc = 0, h_sc = h_doc + al((size_t)n_sp * kw * 4), h_cnt = h_sc + al((size_t)n_sp * kw * 4), h_tot = h_cnt + al((size_t)n_sp * 4),
                h_need = h_tot + al((size_t)n_sp * 8);
-  if (h_need > s->tier_hold_cap || words > s->excl_words_cap) SS_HIP(hipStreamSynchronize(s->stream));
-  if (h_need > s->tier_hold_cap) {
-    if (s->d_tier_hold) (void)hipFree(s->d_tier_hold);
-    s->d_tier_hold = nullptr; s->tier_hold_cap = 0;
-    SS_HIP(hipMalloc(&s->d_tier_hold, h_need * 2));
-    s->tier_hold_cap = h_need * 2;
-  }
-  if (words > s->excl_words_cap) {
-    if (s->d_excl_bits) (void)hipFree(s->d_excl_bits);
-    s->d_excl_bits = nullptr; s->excl_words_cap = 0;
-    SS_HIP(hipMalloc(&s->d_excl_bits, words * 4));
-    s->excl_words_cap = words;
-  }
+  SS_TRY(reserve(s, &s->d_tier_hold, &s->tier_hold_cap, h_need, h_need * 2));
+  SS_TRY(reserve(s, &s->d_excl_bits, &s->excl_words_cap, words));
   char* H = (char*)s->d_tier_hold;
   std::vector<ss_bm25_query> rest(q, q + nq);
   for (uint32_t j = 0; j < n_sp; j++) {
@@ -1650,12 +1657,10 @@ static int bm25_search_tiered_excl(ss_shard* s, uint32_t nq, const ss_bm25_query
     rest[special[j]] = R;  // keeps the row's place in the batch below; its answer is overwritten
     const bool had = s->n_deleted != 0;
     SS_TRY(ssi_bm25_sparse_excl_bits(s, had ? s->d_deleted : nullptr, had ? (uint32_t)s->deleted_words : 0u, lists, n_lists, s->d_excl_bits, (uint32_t)words, s->stream));
-    uint32_t* del = s->d_deleted;
-    const uint64_t dw = s->deleted_words, nd = s->n_deleted;
-    s->d_deleted = s->d_excl_bits; s->deleted_words = words; s->n_deleted = 1;
-    const int rc = bm25_search_host_queries(s, 1, &R, kk, rt, 0, nullptr);
-    s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd;
-    if (rc != SS_OK) return rc;
+    {
+      ExclSwap sw(s, s->d_excl_bits, words);
+      SS_TRY(bm25_search_host_queries(s, 1, &R, kk, rt, 0, nullptr));
+    }
     if (nq == 1) return SS_OK;  // the answer stands in row 0 already
     if (kk) {
       SS_HIP(hipMemcpyAsync(H + h_doc + (size_t)j * kw * 4, s->d_out_doc, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
@@ -1738,19 +1743,8 @@ static int bm25_search_gated_scan_rule(ss_shard* s, const ss_bm25_query& Q, uint
   const size_t groups = (size_t)s->bm_n_sub * (BM_SUB / 64), words = ((size_t)s->bm_n_docs + 31) / 32;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t o_q = 0, o_tot = o_q + al(64 * sizeof(ss_bm25_query)), o_sets = o_tot + al(64 * 8), need = o_sets + al(2 * (size_t)n * groups * 8);
-  if (need > s->gate_ws_cap || words > s->excl_words_cap) SS_HIP(hipStreamSynchronize(s->stream));
-  if (need > s->gate_ws_cap) {
-    if (s->d_gate_ws) (void)hipFree(s->d_gate_ws);
-    s->d_gate_ws = nullptr; s->gate_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_gate_ws, need));
-    s->gate_ws_cap = need;
-  }
-  if (words > s->excl_words_cap) {
-    if (s->d_excl_bits) (void)hipFree(s->d_excl_bits);
-    s->d_excl_bits = nullptr; s->excl_words_cap = 0;
-    SS_HIP(hipMalloc(&s->d_excl_bits, words * 4));
-    s->excl_words_cap = words;
-  }
+  SS_TRY(reserve(s, &s->d_gate_ws, &s->gate_ws_cap, need));
+  SS_TRY(reserve(s, &s->d_excl_bits, &s->excl_words_cap, words));
   char* W = (char*)s->d_gate_ws;
   if (nd2) {
     SS_HIP(hipMemcpy(W + o_q, subs.data(), subs.size() * sizeof(ss_bm25_query), hipMemcpyHostToDevice));  // (synchronous: `subs` is a local)
@@ -1766,12 +1760,8 @@ static int bm25_search_gated_scan_rule(ss_shard* s, const ss_bm25_query& Q, uint
   *a_cnt = 0; *a_tot = 0;
   if (kk && rt != SS_RT_COUNT) {
     {
-      uint32_t* del = s->d_deleted;
-      const uint64_t dw = s->deleted_words, nd = s->n_deleted;
-      s->d_deleted = s->d_excl_bits; s->deleted_words = words; s->n_deleted = 1;
-      const int rc = bm25_search_host_queries(s, 1, &U, kk, SS_RT_TOPK, 0, nullptr);
-      s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd;
-      if (rc != SS_OK) return rc;
+      ExclSwap sw(s, s->d_excl_bits, words);
+      SS_TRY(bm25_search_host_queries(s, 1, &U, kk, SS_RT_TOPK, 0, nullptr));
     }
     SS_HIP(hipStreamSynchronize(s->stream));
     SS_HIP(hipMemcpy(a_doc, s->d_out_doc, (size_t)kw * 4, hipMemcpyDeviceToHost));
@@ -2007,12 +1997,7 @@ static int bm25_route_shapes(ss_shard* s, uint32_t nq, const ss_bm25_query* q, u
   const size_t o_q = 0, o_perm = o_q + al((size_t)nq * sizeof(ss_bm25_query)), o_doc = o_perm + al((size_t)nq * 4), o_sc = o_doc + al((size_t)nq * kw * 4),
                o_cnt = o_sc + al((size_t)nq * kw * 4), o_tot = o_cnt + al((size_t)nq * 4), need = o_tot + al((size_t)nq * 8);
   SS_HIP(hipStreamSynchronize(s->stream));  // the workspace may still be read by the batch before; the copies below are synchronous
-  if (need > s->route_ws_cap) {
-    if (s->d_route_ws) (void)hipFree(s->d_route_ws);
-    s->d_route_ws = nullptr; s->route_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_route_ws, need * 2));
-    s->route_ws_cap = need * 2;
-  }
+  SS_TRY(reserve(s, &s->d_route_ws, &s->route_ws_cap, need, need * 2));
   char* W = (char*)s->d_route_ws;
   std::vector<ss_bm25_query> sub;
   std::vector<uint32_t> perm;
@@ -2903,27 +2888,6 @@ __global__ void peel_max_kernel(const uint32_t* __restrict__ v, unsigned long lo
   if ((threadIdx.x & 63u) == 0) atomicMax(out, m);
 }
 
-namespace {
-// the shard's exclusion bitmap replaced by the peel bitmap for the life of the object (the caller holds the shard lock)
-struct PeelSwap {
-  ss_shard* s;
-  uint32_t* del; uint64_t dw, nd; uint32_t stride;
-  PeelSwap(ss_shard* s_, uint32_t* bits, uint64_t words, uint32_t vec_stride) : s(s_), del(s_->d_deleted), dw(s_->deleted_words), nd(s_->n_deleted), stride(s_->vec_del_stride) {
-    s->d_deleted = bits; s->deleted_words = words; s->n_deleted = 1; s->vec_del_stride = vec_stride;
-  }
-  ~PeelSwap() { s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd; s->vec_del_stride = stride; }
-};
-int peel_ensure(ss_shard* s, size_t dwords) {
-  if (dwords <= s->peel_words_cap) return SS_OK;
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (s->d_peel_bits) (void)hipFree(s->d_peel_bits);
-  s->d_peel_bits = nullptr; s->peel_words_cap = 0;
-  SS_HIP(hipMalloc(&s->d_peel_bits, dwords * sizeof(uint32_t)));
-  s->peel_words_cap = dwords;
-  return SS_OK;
-}
-}  // namespace
-
 // lexical: query by query (each pass is a single-query search of the ordinary paths).  Caller holds the shard lock; a facet filter's
 // bitmap already stands in s->d_deleted (with_facet_filter).
 static int bm25_search_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,
@@ -2931,7 +2895,7 @@ static int bm25_search_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query
   const uint32_t base_words = s->n_deleted ? (uint32_t)s->deleted_words : 0u;
   const uint32_t words = std::max<uint32_t>((uint32_t)(((uint64_t)s->bm_n_docs + 31) / 32), base_words);
   SS_HIP(hipSetDevice(s->device));
-  SS_TRY(peel_ensure(s, words));
+  SS_TRY(reserve(s, &s->d_peel_bits, &s->peel_words_cap, words));
   const uint32_t* base = s->n_deleted ? s->d_deleted : nullptr;
   std::vector<uint32_t> h_doc(SS_MAX_K);
   std::vector<float> h_score(SS_MAX_K);
@@ -2943,7 +2907,7 @@ static int bm25_search_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query
     peel_init_kernel<<<std::min<uint32_t>(1024u, (words + 255u) / 256u), 256, 0, s->stream>>>(s->d_peel_bits, words, 1, base, base_words);
     SS_HIP(hipGetLastError());
     {
-      PeelSwap sw(s, s->d_peel_bits, words, 0);
+      ExclSwap sw(s, s->d_peel_bits, words);
       for (uint32_t pass = 0; got < k; pass++) {
         const uint32_t kk = std::min<uint32_t>(SS_MAX_K, k - got);
         SS_TRY(bm25_search_host_queries(s, 1, q + i, kk, pass == 0 ? rt : (uint32_t)SS_RT_TOPK, 0, nullptr));
@@ -3007,7 +2971,7 @@ static int vec_search_deep_locked(ss_shard* s, uint32_t nq, const void* queries,
   const uint32_t base_words = s->n_deleted ? (uint32_t)s->deleted_words : 0u;
   const uint32_t words = std::max<uint32_t>((uint32_t)((doc_bound + 31) / 32), base_words);
   const uint32_t G = (uint32_t)std::min<size_t>(nq, SS_VEC_BATCH);
-  SS_TRY(peel_ensure(s, (size_t)words * G));
+  SS_TRY(reserve(s, &s->d_peel_bits, &s->peel_words_cap, (size_t)words * G));
   const uint32_t* base = s->n_deleted ? s->d_deleted : nullptr;
   const uint32_t ocw = (mode && (mode->flags & SS_ANN_REPORT_OBSERVED)) ? 3u : 1u;
   std::vector<uint32_t> h_doc((size_t)G * SS_MAX_K), h_count(G), got(G);
@@ -3019,7 +2983,8 @@ static int vec_search_deep_locked(ss_shard* s, uint32_t nq, const void* queries,
     SS_HIP(hipGetLastError());
     std::fill(got.begin(), got.end(), 0u);
     std::fill(dry.begin(), dry.end(), (uint8_t)0);
-    PeelSwap sw(s, s->d_peel_bits, words, words);
+    ExclSwap sw(s, s->d_peel_bits, words);
+    sw.vec_stride(words);
     for (uint32_t pass = 0;; pass++) {
       uint32_t* d_ncl = nullptr;
       SS_TRY(vec_search_host_lists(s, nb, (const char*)queries + (size_t)g0 * s->dim * elem, elem, query_scale ? query_scale + g0 : nullptr, SS_MAX_K, thr, mode,
@@ -3249,13 +3214,66 @@ static int match_stage_phrases(const ss_shard* s, uint32_t nb, const ss_bm25_que
     if (bm_q_op(qc[i].op) == SS_OP_PHRASE) ssi_bm25_phrase_stage(qc[i], &mc->staged[i]);
   return SS_OK;
 }
-// the match sets of a prepared chunk: qf / d_q = its form() on the host / the device, d_ph = the chunk as the caller gave it, on the
-// device (read only when it holds a phrase)
-static int match_bits_chunk(ss_shard* s, const MatchChunk& mc, const ss_bm25_query* qf, const ss_bm25_query* d_q, ss_bm25_query* d_sub,
-                            const ss_bm25_query* d_ph, unsigned long long* d_bits, unsigned long long* d_total, hipStream_t st, uint32_t nb) {
-  SS_TRY(mc.tier.any_tiered ? ssi_bm25_match_bits_tiered(s, mc.tier, qf, d_q, d_sub, d_bits, d_total, st, nb)
-                            : ssi_bm25_match_bits(s, d_q, d_bits, d_total, st, nb));
-  return mc.any_phrase() ? ssi_bm25_phrase_refine(s, d_ph, d_bits, d_total, st, nb) : SS_OK;
+// what check_queries says of a chunk nothing of which is tiered: the arguments of the sorted entry's batched ssi_bm25_search
+struct MatchBatchInfo {
+  bool has_and = false, has_or = false, all_probed = false, any_frequent = false, any_filter = false, uniform = false, gated = false;
+  uint32_t nt_max = 0, np_max = 0, nn_max = 0;
+};
+// THE MATCH-SET STEP of a chunk of nb <= 64 queries, in two halves, because an entry's own refusals (its facet record, its workspace)
+// come between them and the order of the refusals is part of the ABI.  match_prepare, on the host: the phrases staged, the tiers
+// planned, and -- where nothing is tiered -- the probe rows ensured and the chunk passed through check_queries; SS_ENOTSUP for a list
+// without bit records (the match set comes from the probe index).  `info`: the sorted entry runs the chunk's batched search itself and
+// takes check_queries' findings, a union under a field filter among them; without `info` check_queries refuses such a union
+// (SS_ENOTSUP), as it always has for the other entries.  match_enqueue, on s->stream: the chunk's form to d_q (and the chunk as given
+// to d_ph when it holds a phrase), then under the facet filter's bitmap the match sets of both tiers and the phrases' refine.  d_total
+// and d_bits are the caller's to clear: the layouts differ.
+static int match_prepare(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, MatchChunk* mc, MatchBatchInfo* info = nullptr) {
+  SS_TRY(match_stage_phrases(s, nb, qc, mc));
+  const ss_bm25_query* qf = mc->form(qc);
+  SS_TRY(tier_prepare(s, nb, qf, &mc->tier, s->stream));
+  if (mc->tier.any_tiered) return SS_OK;
+  MatchBatchInfo local, &b = info ? *info : local;
+  bool phrase = false;
+  SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qf, s->stream));
+  SS_TRY(check_queries(s, nb, qf, &b.has_and, &b.has_or, &b.nt_max, &b.np_max, &b.all_probed, &b.any_frequent, &phrase, &b.any_filter, &b.uniform,
+                       info ? &b.gated : nullptr, &b.nn_max));
+  return b.all_probed && s->d_probe && !phrase ? SS_OK : SS_ENOTSUP;
+}
+static int match_enqueue(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, const MatchChunk& mc, uint32_t n_filters, const ss_facet_filter* filters,
+                         bool prebuilt, ss_bm25_query* d_q, ss_bm25_query* d_sub, ss_bm25_query* d_ph, unsigned long long* d_bits,
+                         unsigned long long* d_total) {
+  const ss_bm25_query* qf = mc.form(qc);
+  SS_HIP(hipMemcpyAsync(d_q, qf, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+  if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+  return with_facet_filter(s, n_filters, filters, s->stream, [&]() {
+    SS_TRY(mc.tier.any_tiered ? ssi_bm25_match_bits_tiered(s, mc.tier, qf, d_q, d_sub, d_bits, d_total, s->stream, nb)
+                              : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream, nb));
+    return mc.any_phrase() ? ssi_bm25_phrase_refine(s, d_ph, d_bits, d_total, s->stream, nb) : SS_OK;
+  }, prebuilt);
+}
+
+// ONE query's match set, as ss_bm25_facet_count and ss_bm25_facet_kth build it: the query prepared, then the facet's place in the record
+// checked, then the workspace [query][total][match words][`extra` bytes of the caller's][dense part of a tiered query][phrase as given].
+// The caller holds the shard lock, clears d_total / d_bits and calls match_enqueue; `mc` lives until its synchronisation.
+struct OneMatch {
+  MatchChunk mc;
+  ss_bm25_query *d_q, *d_sub, *d_ph;
+  unsigned long long *d_total, *d_bits;  // d_bits [groups]; the caller's bytes follow
+  uint64_t groups;
+};
+static int one_match_prepare(ss_shard* s, const ss_bm25_query* query, uint32_t facet_offset, uint32_t facet_type, size_t extra, OneMatch* m) {
+  SS_TRY(match_prepare(s, 1, query, &m->mc));
+  SS_HIP(hipSetDevice(s->device));
+  if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + ssi_facet_width(facet_type) > s->facet_record_size) return SS_ESTATE;
+  m->groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
+  SS_TRY(reserve(s, &s->d_facet_ws, &s->facet_ws_cap, sizeof(ss_bm25_query) + 8 + m->groups * 8 + extra + 2 * sizeof(ss_bm25_query)));
+  char* ws = (char*)s->d_facet_ws;
+  m->d_q = (ss_bm25_query*)ws;
+  m->d_total = (unsigned long long*)(ws + sizeof(ss_bm25_query));
+  m->d_bits = m->d_total + 1;
+  m->d_sub = (ss_bm25_query*)((char*)(m->d_bits + m->groups) + extra);
+  m->d_ph = m->d_sub + 1;
+  return SS_OK;
 }
 
 // Facet counts of ONE query (query_facets / facet_count, add_result.rs:484-640): histogram of a facet over the query's match
@@ -3269,51 +3287,20 @@ static int facet_count_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_
   if (facet_type > SS_FACET_POINT || (!string_facet && !range_lower_bounds)) return SS_EINVAL;
   if (facet_type == SS_FACET_POINT && (!point || point->unit > SS_POINT_MILES)) return SS_EINVAL;
   if (!s->d_post) return SS_ESTATE;
-  bool has_and, has_or, all_probed, any_frequent;
-  uint32_t nt_max, np_max;
   ShardLock g(s);
-  MatchChunk mc;  // (a phrase: its intersection form, refined; a query naming a sparse-tier term: bm25_match.h)
-  SS_TRY(match_stage_phrases(s, 1, query, &mc));
-  const ss_bm25_query* qf = mc.form(query);
-  BmTierPlan& plan = mc.tier;
-  SS_TRY(tier_prepare(s, 1, qf, &plan, s->stream));
-  if (!plan.any_tiered) {
-    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, qf, s->stream));
-    SS_TRY(check_queries(s, 1, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
-    if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
-  }
-  SS_HIP(hipSetDevice(s->device));
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
-  if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
-  const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
-  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + ((size_t)n_buckets + 1) * 8 + (size_t)n_buckets * 8 + 2 * sizeof(ss_bm25_query);
-  if (bytes > s->facet_ws_cap) {  // grow-only workspace (a hipMalloc / hipFree pair per call would synchronise the device)
-    if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
-    s->d_facet_ws = nullptr;
-    s->facet_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_facet_ws, bytes));
-    s->facet_ws_cap = bytes;
-  }
-  char* ws = (char*)s->d_facet_ws;
-  ss_bm25_query* d_q = (ss_bm25_query*)ws;
-  unsigned long long* d_total = (unsigned long long*)(ws + sizeof(ss_bm25_query));
-  unsigned long long* d_bits = d_total + 1;
-  unsigned long long* d_counts = d_bits + groups;
+  OneMatch m;
+  SS_TRY(one_match_prepare(s, query, facet_offset, facet_type, ((size_t)n_buckets + 1) * 8 + (size_t)n_buckets * 8, &m));
+  unsigned long long* d_counts = m.d_bits + m.groups;
   uint64_t* d_bounds = (uint64_t*)(d_counts + n_buckets + 1);
-  ss_bm25_query* d_sub = (ss_bm25_query*)(d_bounds + n_buckets);  // a tiered query's dense part
-  ss_bm25_query* d_ph = d_sub + 1;                                 // a phrase as the caller gave it (d_q holds its intersection form)
   int rc = SS_OK;
-  if (hipMemcpyAsync(d_q, qf, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream) != hipSuccess ||
-      (mc.any_phrase() && hipMemcpyAsync(d_ph, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream) != hipSuccess) ||
-      hipMemsetAsync(d_total, 0, 8 + groups * 8 + ((size_t)n_buckets + 1) * 8, s->stream) != hipSuccess ||
+  if (hipMemsetAsync(m.d_total, 0, 8 + m.groups * 8 + ((size_t)n_buckets + 1) * 8, s->stream) != hipSuccess ||
       (!string_facet &&
        hipMemcpyAsync(d_bounds, range_lower_bounds, (size_t)n_buckets * 8, hipMemcpyHostToDevice, s->stream) != hipSuccess))
     rc = SS_EDEVICE;
-  if (rc == SS_OK)
-    rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return match_bits_chunk(s, mc, qf, d_q, d_sub, d_ph, d_bits, d_total, s->stream, 1); });
-  if (rc == SS_OK) rc = ssi_facet_count(s, d_bits, s->bm_n_docs, facet_offset, facet_type, n_buckets, d_bounds, d_counts, point, s->stream);
+  if (rc == SS_OK) rc = match_enqueue(s, 1, query, m.mc, n_filters, filters, false, m.d_q, m.d_sub, m.d_ph, m.d_bits, m.d_total);
+  if (rc == SS_OK) rc = ssi_facet_count(s, m.d_bits, s->bm_n_docs, facet_offset, facet_type, n_buckets, d_bounds, d_counts, point, s->stream);
   if (rc == SS_OK && (hipMemcpyAsync(out_counts, d_counts, ((size_t)n_buckets + 1) * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-                      (out_total && hipMemcpyAsync(out_total, d_total, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)))
+                      (out_total && hipMemcpyAsync(out_total, m.d_total, 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)))
     rc = SS_EDEVICE;
   if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;
   return rc;
@@ -3340,47 +3327,17 @@ static int facet_kth_impl(ss_shard* s, const ss_bm25_query* query, uint32_t n_fi
   if (facet_type == SS_FACET_STRING16 || facet_type == SS_FACET_STRING32) return SS_ENOTSUP;
   if (facet_type == SS_FACET_POINT && (!point || point->unit > SS_POINT_MILES)) return SS_EINVAL;
   if (!s->d_post) return SS_ESTATE;
-  bool has_and, has_or, all_probed, any_frequent;
-  uint32_t nt_max, np_max;
   ShardLock g(s);
-  MatchChunk mc;  // (a phrase: its intersection form, refined; a query naming a sparse-tier term: bm25_match.h)
-  SS_TRY(match_stage_phrases(s, 1, query, &mc));
-  const ss_bm25_query* qf = mc.form(query);
-  BmTierPlan& plan = mc.tier;
-  SS_TRY(tier_prepare(s, 1, qf, &plan, s->stream));
-  if (!plan.any_tiered) {
-    SS_TRY(ssi_bm25_ensure_probe_rows(s, 1, qf, s->stream));
-    SS_TRY(check_queries(s, 1, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
-    if (!all_probed || !s->d_probe) return SS_ENOTSUP;
-  }
-  SS_HIP(hipSetDevice(s->device));
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
-  if (!s->d_facets || s->facet_docs < s->bm_n_docs || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
-  const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
-  const size_t bytes = sizeof(ss_bm25_query) + 8 + groups * 8 + 256 * 8 + 2 * sizeof(ss_bm25_query);
-  if (bytes > s->facet_ws_cap) {
-    if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
-    s->d_facet_ws = nullptr;
-    s->facet_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_facet_ws, bytes));
-    s->facet_ws_cap = bytes;
-  }
-  char* ws = (char*)s->d_facet_ws;
-  ss_bm25_query* d_q = (ss_bm25_query*)ws;
-  unsigned long long* d_total = (unsigned long long*)(ws + sizeof(ss_bm25_query));
-  unsigned long long* d_bits = d_total + 1;
-  unsigned long long* d_hist = d_bits + groups;
-  ss_bm25_query* d_sub = (ss_bm25_query*)(d_hist + 256);  // a tiered query's dense part
-  ss_bm25_query* d_ph = d_sub + 1;                         // a phrase as the caller gave it (d_q holds its intersection form)
-  SS_HIP(hipMemcpyAsync(d_q, qf, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-  if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, query, sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-  SS_HIP(hipMemsetAsync(d_total, 0, 8 + groups * 8, s->stream));
-  SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() { return match_bits_chunk(s, mc, qf, d_q, d_sub, d_ph, d_bits, d_total, s->stream, 1); }));
+  OneMatch m;
+  SS_TRY(one_match_prepare(s, query, facet_offset, facet_type, 256 * 8, &m));
+  unsigned long long* d_hist = m.d_bits + m.groups;
+  SS_HIP(hipMemsetAsync(m.d_total, 0, 8 + m.groups * 8, s->stream));
+  SS_TRY(match_enqueue(s, 1, query, m.mc, n_filters, filters, false, m.d_q, m.d_sub, m.d_ph, m.d_bits, m.d_total));
   uint64_t total = 0;
-  SS_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s->stream));
+  SS_HIP(hipMemcpyAsync(&total, m.d_total, 8, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipStreamSynchronize(s->stream));
   if (out_total) *out_total = total;
-  return ssi_facet_kth(s, d_bits, s->bm_n_docs, total, facet_offset, facet_type, descending != 0, k, d_hist, out_value, out_n_better,
+  return ssi_facet_kth(s, m.d_bits, s->bm_n_docs, total, facet_offset, facet_type, descending != 0, k, d_hist, out_value, out_n_better,
                        out_n_equal, point, s->stream);
 }
 int ss_bm25_facet_kth(ss_shard* s, const ss_bm25_query* query, uint32_t n_filters, const ss_facet_filter* filters,
@@ -3403,12 +3360,11 @@ int ss_bm25_facet_kth_point(ss_shard* s, const ss_bm25_query* query, uint32_t n_
 static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
                                      uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                                      uint64_t* out_total) {
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
   if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
   for (uint32_t f = 0; f < n_sorts; f++)
-    if (sorts[f].facet_offset + width[sorts[f].facet_type] > s->facet_record_size) return SS_ESTATE;
+    if (sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
   const uint32_t CH = std::min<uint32_t>(nq, 64u);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -3419,13 +3375,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                o_cc = o_cs + al((size_t)CH * k * 4), o_at = o_cc + al((size_t)CH * 4), o_od = o_at + al((size_t)CH * 8),
                o_os = o_od + al((size_t)nq * k * 4), o_oc = o_os + al((size_t)nq * k * 4), o_ot = o_oc + al((size_t)nq * 4),
                o_sub = o_ot + al((size_t)nq * 8), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)), need = o_ph + al((size_t)CH * sizeof(ss_bm25_query));
-  if (need > s->sort_ws_cap) {
-    SS_HIP(hipStreamSynchronize(s->stream));
-    if (s->d_sort_ws) (void)hipFree(s->d_sort_ws);
-    s->d_sort_ws = nullptr; s->sort_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_sort_ws, need));
-    s->sort_ws_cap = need;
-  }
+  SS_TRY(reserve(s, &s->d_sort_ws, &s->sort_ws_cap, need));
   char* W = (char*)s->d_sort_ws;
   ss_bm25_query* d_q = (ss_bm25_query*)(W + o_q);
   unsigned long long* d_total = (unsigned long long*)(W + o_tot);
@@ -3437,49 +3387,32 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
   for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = queries + c0;
-    bool has_and = false, has_or = false, all_probed = false, any_frequent = false, phrase = false, any_filter = false, uniform = false, gated = false;
-    uint32_t nt_max = 0, np_max = 0, nn_max = 0;
     // a chunk that names a sparse-tier term: its match sets from both tiers (bm25_match.h), its two searches query by query below
     // (bm25_search_host_queries routes each to bm25_search_tiered under the swapped exclusion bitmap); select and compose stay batched
     // a chunk that holds a phrase: match sets of the intersection forms, refined (bm25_phrase_bits.hip); its two searches query by
     // query as well -- the ordinary search answers a phrase under the swapped bitmap and routes it to its own kernel family
     MatchChunk& mc = plans[c0 / CH];
-    SS_TRY(match_stage_phrases(s, nb, qc, &mc));
-    const ss_bm25_query* qf = mc.form(qc);
-    BmTierPlan& plan = mc.tier;
-    SS_TRY(tier_prepare(s, nb, qf, &plan, s->stream));
-    if (!plan.any_tiered) {
-      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qf, s->stream));
-      SS_TRY(check_queries(s, nb, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
-      if (!all_probed || !s->d_probe || phrase) return SS_ENOTSUP;
-    }
-    ss_bm25_query* d_ph = (ss_bm25_query*)(W + o_ph);
-    SS_HIP(hipMemcpyAsync(d_q, qf, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-    if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream,
-                             [&]() { return match_bits_chunk(s, mc, qf, d_q, (ss_bm25_query*)(W + o_sub), d_ph, d_E, d_total, s->stream, nb); }));
+    MatchBatchInfo b;
+    SS_TRY(match_prepare(s, nb, qc, &mc, &b));
+    SS_TRY(match_enqueue(s, nb, qc, mc, n_filters, filters, false, d_q, (ss_bm25_query*)(W + o_sub), (ss_bm25_query*)(W + o_ph), d_E, d_total));
     SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, k, s->stream));
-    bool batched = !batched_off && !plan.any_tiered && !mc.any_phrase();
+    bool batched = !batched_off && !mc.tier.any_tiered && !mc.any_phrase();
     for (int part = 0; part < 2 && batched; part++) {  // both searches as ONE batch each: every query under its own exclusion bitmap
-      uint32_t* del = s->d_deleted;
-      const uint64_t dw = s->deleted_words, nd = s->n_deleted;
-      s->d_deleted = (uint32_t*)(part == 0 ? d_xb : d_xe); s->deleted_words = groups * 2; s->n_deleted = 1; s->del_per_query = 1;
+      ExclSwap sw(s, (uint32_t*)(part == 0 ? d_xb : d_xe), groups * 2);
+      sw.per_query();
       const int rc = ssi_bm25_search(s, nb, d_q, k, SS_RT_TOPK, (uint32_t*)(W + (part == 0 ? o_ad : o_cd)), (float*)(W + (part == 0 ? o_as : o_cs)),
-                                     (uint32_t*)(W + (part == 0 ? o_ac : o_cc)), (uint64_t*)(W + o_at), has_and, has_or, nt_max, np_max, all_probed,
-                                     s->stream, any_frequent, false, any_filter, uniform, gated, nn_max);
-      s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd; s->del_per_query = 0;
+                                     (uint32_t*)(W + (part == 0 ? o_ac : o_cc)), (uint64_t*)(W + o_at), b.has_and, b.has_or, b.nt_max, b.np_max,
+                                     b.all_probed, s->stream, b.any_frequent, false, b.any_filter, b.uniform, b.gated, b.nn_max);
       if (rc == SS_ENOTSUP && part == 0) batched = false;  // not the pruned kernel's batch: query by query below
       else if (rc != SS_OK) return rc;
     }
     if (!batched) {
       for (uint32_t i = 0; i < nb; i++)
         for (int part = 0; part < 2; part++) {
-          uint32_t* del = s->d_deleted;
-          const uint64_t dw = s->deleted_words, nd = s->n_deleted;
-          s->d_deleted = (uint32_t*)((part == 0 ? d_xb : d_xe) + (size_t)i * groups); s->deleted_words = groups * 2; s->n_deleted = 1;
-          const int rc = bm25_search_host_queries(s, 1, qc + i, k, SS_RT_TOPK, 0, nullptr);
-          s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd;
-          if (rc != SS_OK) return rc;
+          {
+            ExclSwap sw(s, (uint32_t*)((part == 0 ? d_xb : d_xe) + (size_t)i * groups), groups * 2);
+            SS_TRY(bm25_search_host_queries(s, 1, qc + i, k, SS_RT_TOPK, 0, nullptr));
+          }
           SS_HIP(hipMemcpyAsync(W + (part == 0 ? o_ad : o_cd) + (size_t)i * k * 4, s->d_out_doc, (size_t)k * 4, hipMemcpyDeviceToDevice, s->stream));
           SS_HIP(hipMemcpyAsync(W + (part == 0 ? o_as : o_cs) + (size_t)i * k * 4, s->d_out_score, (size_t)k * 4, hipMemcpyDeviceToDevice, s->stream));
           SS_HIP(hipMemcpyAsync(W + (part == 0 ? o_ac : o_cc) + (size_t)i * 4, s->d_out_count, 4, hipMemcpyDeviceToDevice, s->stream));
@@ -3504,7 +3437,6 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   if (n_sorts == 0) return ss_bm25_search_filtered(s, nq, queries, k, SS_RT_TOPKCOUNT, n_filters, filters, out_doc, out_score, out_count, out_total);
   if (!sorts) return SS_EINVAL;
   if (n_sorts > SS_MAX_SORT_FIELDS) return SS_ENOTSUP;
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   for (uint32_t f = 0; f < n_sorts; f++) {
     if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
     if (sorts[f].facet_type == SS_FACET_STRING16 || sorts[f].facet_type == SS_FACET_STRING32) return SS_ENOTSUP;  // by their strings: the host's rank column
@@ -3518,7 +3450,7 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   SS_HIP(hipSetDevice(s->device));
   const uint32_t base_words = s->n_deleted ? (uint32_t)s->deleted_words : 0u;
   const uint32_t words = std::max<uint32_t>((uint32_t)(((uint64_t)s->bm_n_docs + 31) / 32), base_words);
-  SS_TRY(peel_ensure(s, words));
+  SS_TRY(reserve(s, &s->d_peel_bits, &s->peel_words_cap, words));
   const uint32_t* base = s->n_deleted ? s->d_deleted : nullptr;
   std::vector<uint32_t> h_doc(SS_MAX_K);
   std::vector<float> h_score(SS_MAX_K);
@@ -3527,7 +3459,7 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
     uint64_t total = 0;
     peel_init_kernel<<<std::min<uint32_t>(1024u, (words + 255u) / 256u), 256, 0, s->stream>>>(s->d_peel_bits, words, 1, base, base_words);
     SS_HIP(hipGetLastError());
-    PeelSwap sw(s, s->d_peel_bits, words, 0);
+    ExclSwap sw(s, s->d_peel_bits, words);
     for (uint32_t pass = 0; got < k; pass++) {
       const uint32_t kk = std::min<uint32_t>(SS_MAX_K, k - got);
       uint32_t c = 0;
@@ -3553,6 +3485,19 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   return SS_OK;
 }
 
+// The query-facet arrays of ss_bm25_search_facets / ss_docs_search (their null checks are the callers'): every type, bucket count and
+// Point base -> *n_bounds = the lower bounds of the range facets, back to back; *stride = the counters of one query
+static int check_query_facets(uint32_t n_facets, const uint32_t* facet_type, const uint32_t* n_buckets, const ss_facet_point* bases, size_t* n_bounds,
+                              size_t* stride) {
+  for (uint32_t f = 0; f < n_facets; f++) {
+    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
+    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
+    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) *n_bounds += n_buckets[f];
+    *stride += (size_t)n_buckets[f] + 1;
+  }
+  return SS_OK;
+}
+
 // A search WITH its query_facets (search.rs:3598-3760 finishes what add_result.rs:487-643 counted beside the hits): the facet counts
 // of the whole batch are enqueued first -- per chunk of <= 64 queries one match-set build (both tiers) and ONE launch that counts every
 // facet of every query (facet.hip: "Facet counts of a BATCH") -- and the search itself runs behind them on the same stream, through
@@ -3574,14 +3519,7 @@ static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q,
                o_tot = o_ph + al((size_t)CH * sizeof(ss_bm25_query)),
                o_bits = o_tot + al((size_t)CH * 8), o_bounds = o_bits + al((size_t)CH * groups * 8), o_cnt = o_bounds + al(n_bounds * 8),
                need = o_cnt + al((size_t)nq * stride * 8);
-  if (need > s->facet_ws_cap) {  // grow-only workspace
-    SS_HIP(hipStreamSynchronize(s->stream));
-    if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
-    s->d_facet_ws = nullptr;
-    s->facet_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_facet_ws, need));
-    s->facet_ws_cap = need;
-  }
+  SS_TRY(reserve(s, &s->d_facet_ws, &s->facet_ws_cap, need));
   char* W = (char*)s->d_facet_ws;
   ss_bm25_query *d_q = (ss_bm25_query*)(W + o_q), *d_sub = (ss_bm25_query*)(W + o_sub), *d_ph = (ss_bm25_query*)(W + o_ph);
   unsigned long long *d_total = (unsigned long long*)(W + o_tot), *d_bits = (unsigned long long*)(W + o_bits), *d_counts = (unsigned long long*)(W + o_cnt);
@@ -3594,22 +3532,9 @@ static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q,
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = q + c0;
     MatchChunk& mc = plans[c0 / CH];  // (a chunk holding a phrase: bm25_phrase_bits.hip; naming a sparse-tier term: bm25_match.h)
-    SS_TRY(match_stage_phrases(s, nb, qc, &mc));
-    const ss_bm25_query* qf = mc.form(qc);
-    BmTierPlan& plan = mc.tier;
-    SS_TRY(tier_prepare(s, nb, qf, &plan, s->stream));
-    if (!plan.any_tiered) {
-      bool has_and, has_or, all_probed, any_frequent;
-      uint32_t nt_max, np_max;
-      SS_TRY(ssi_bm25_ensure_probe_rows(s, nb, qf, s->stream));
-      SS_TRY(check_queries(s, nb, qf, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent));
-      if (!all_probed || !s->d_probe) return SS_ENOTSUP;  // the match set comes from the probe index's bit records
-    }
-    SS_HIP(hipMemcpyAsync(d_q, qf, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
-    if (mc.any_phrase()) SS_HIP(hipMemcpyAsync(d_ph, qc, (size_t)nb * sizeof(ss_bm25_query), hipMemcpyHostToDevice, s->stream));
+    SS_TRY(match_prepare(s, nb, qc, &mc));
     SS_HIP(hipMemsetAsync(d_total, 0, (size_t)((char*)(d_bits + (size_t)nb * groups) - (char*)d_total), s->stream));
-    SS_TRY(with_facet_filter(s, n_filters, filters, s->stream,
-                             [&]() { return match_bits_chunk(s, mc, qf, d_q, d_sub, d_ph, d_bits, d_total, s->stream, nb); }, prebuilt));
+    SS_TRY(match_enqueue(s, nb, qc, mc, n_filters, filters, prebuilt, d_q, d_sub, d_ph, d_bits, d_total));
     SS_TRY(ssi_facet_count_multi(s, nb, d_bits, n_facets, facet_offset, facet_type, n_buckets, bases, d_bounds, d_counts + (size_t)c0 * stride, s->stream));
   }
   return SS_OK;
@@ -3624,14 +3549,8 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
   if (rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
   if (rt != SS_RT_COUNT && (k == 0 || !out_doc || !out_score)) return SS_EINVAL;
   if (n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   size_t n_bounds = 0, stride = 0;
-  for (uint32_t f = 0; f < n_facets; f++) {
-    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
-    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
-    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) n_bounds += n_buckets[f];
-    stride += (size_t)n_buckets[f] + 1;
-  }
+  SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
   if (n_bounds && !range_lower_bounds) return SS_EINVAL;
   if (!s->d_post) return SS_ESTATE;
   if (nq == 0) return SS_OK;
@@ -3640,7 +3559,7 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
   SS_HIP(hipSetDevice(s->device));
   if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
   for (uint32_t f = 0; f < n_facets; f++)
-    if ((uint64_t)facet_offset[f] + width[facet_type[f]] > s->facet_record_size) return SS_ESTATE;
+    if ((uint64_t)facet_offset[f] + ssi_facet_width(facet_type[f]) > s->facet_record_size) return SS_ESTATE;
   std::vector<MatchChunk> plans;
   unsigned long long* d_counts = nullptr;
   int rc = SS_OK;
@@ -3672,7 +3591,6 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t
                    uint32_t n_filters, const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type,
                    const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases, uint32_t* out_doc,
                    uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts) {
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   if (!s || !out_count || !out_total || rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
   const bool want_docs = rt != SS_RT_COUNT;
   if (want_docs && (k == 0 || !out_doc)) return SS_EINVAL;
@@ -3681,23 +3599,18 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t
     if (sorts[f].facet_type > SS_FACET_POINT || sorts[f].facet_type == SS_FACET_STRING16 || sorts[f].facet_type == SS_FACET_STRING32) return SS_EINVAL;
   if (n_facets > SS_MAX_QUERY_FACETS || (n_facets && (!facet_offset || !facet_type || !n_buckets || !out_facet_counts))) return SS_EINVAL;
   size_t n_bounds = 0, stride = 0;
-  for (uint32_t f = 0; f < n_facets; f++) {
-    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
-    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
-    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) n_bounds += n_buckets[f];
-    stride += (size_t)n_buckets[f] + 1;
-  }
+  SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
   if (n_bounds && !range_lower_bounds) return SS_EINVAL;
   ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
   if ((n_sorts || n_filters || n_facets) && (!s->d_facets || s->facet_docs < s->bm_n_docs)) return SS_ESTATE;
   for (uint32_t f = 0; f < n_sorts; f++)
-    if ((uint64_t)sorts[f].facet_offset + width[sorts[f].facet_type] > s->facet_record_size) return SS_EINVAL;
+    if ((uint64_t)sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_EINVAL;
   for (uint32_t f = 0; f < n_facets; f++)
-    if ((uint64_t)facet_offset[f] + width[facet_type[f]] > s->facet_record_size) return SS_EINVAL;
+    if ((uint64_t)facet_offset[f] + ssi_facet_width(facet_type[f]) > s->facet_record_size) return SS_EINVAL;
   for (uint32_t f = 0; f < n_filters; f++)
-    if (filters[f].type > SS_FACET_POINT || (uint64_t)filters[f].offset + width[filters[f].type] > s->facet_record_size) return SS_EINVAL;
+    if (filters[f].type > SS_FACET_POINT || (uint64_t)filters[f].offset + ssi_facet_width(filters[f].type) > s->facet_record_size) return SS_EINVAL;
 
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64), n_slices = browse_slices(groups), n_docs = s->bm_n_docs;
   const bool sorted = want_docs && n_sorts != 0, descending = doc_ascending == 0;
@@ -3717,14 +3630,7 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t
                o_state = o_hist + (sorted ? al(256 * 8) : 0), o_a = o_state + (sorted ? al(64) : 0), o_c = o_a + (sorted ? al(SS_MAX_K * 4) : 0),
                o_out = o_c + (sorted ? al(SS_MAX_K * 4) : 0), o_bounds = o_out + al(out_cap * 4), o_cnt = o_bounds + al(n_bounds * 8),
                need = o_cnt + al(stride * 8);
-  if (need > s->facet_ws_cap) {  // grow-only workspace
-    SS_HIP(hipStreamSynchronize(s->stream));
-    if (s->d_facet_ws) (void)hipFree(s->d_facet_ws);
-    s->d_facet_ws = nullptr;
-    s->facet_ws_cap = 0;
-    SS_HIP(hipMalloc(&s->d_facet_ws, need));
-    s->facet_ws_cap = need;
-  }
+  SS_TRY(reserve(s, &s->d_facet_ws, &s->facet_ws_cap, need));
   char* W = (char*)s->d_facet_ws;
   unsigned long long *d_head = (unsigned long long*)(W + o_head), *d_M = (unsigned long long*)(W + o_M), *d_sbeg = (unsigned long long*)(W + o_sbeg),
                      *d_E = (unsigned long long*)(W + o_E), *d_B = (unsigned long long*)(W + o_B), *d_counts = (unsigned long long*)(W + o_cnt);
@@ -3806,9 +3712,8 @@ static int facet_values_impl(ss_shard* s, uint32_t n, const uint32_t* doc_ids, u
                              const ss_facet_point* point, uint64_t* out_values) {
   if (!s || (n && (!doc_ids || !out_values)) || facet_type > SS_FACET_POINT) return SS_EINVAL;
   if (point && point->unit > SS_POINT_MILES) return SS_EINVAL;
-  static const uint32_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   ShardLock g(s);
-  if (!s->d_facets || facet_offset + width[facet_type] > s->facet_record_size) return SS_ESTATE;
+  if (!s->d_facets || facet_offset + ssi_facet_width(facet_type) > s->facet_record_size) return SS_ESTATE;
   if (n == 0) return SS_OK;
   SS_HIP(hipSetDevice(s->device));
   SS_TRY(ensure_qstage(s, (size_t)n * 12));
