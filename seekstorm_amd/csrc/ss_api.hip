@@ -22,6 +22,7 @@
 #include "ss_threads.h"
 #include "facet_point.h"
 #include "bm25_build.h"
+#include "bm25_image.h"
 #include "bm25_match.h"
 #include "browse.h"
 
@@ -77,6 +78,37 @@ int with_facet_filter(ss_shard* s, uint32_t n_filters, const ss_facet_filter* fi
   if (rc) return rc;
   ExclSwap sw(s, s->d_filter_bits, (s->facet_docs + 31) / 32);
   return search();
+}
+
+// the postings of n_terms lists (CSR): offs non-decreasing; inside a list docs ascending and in [lo, hi), no tf of 0 (lists in parallel)
+bool postings_ok(uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, uint64_t lo, uint64_t hi) {
+  for (uint32_t t = 0; t < n_terms; t++)
+    if (offs[t + 1] < offs[t]) return false;
+  std::atomic<int> bad{0};
+  ss_parallel_for(n_terms, 64, [&](size_t a, size_t b, unsigned) {
+    for (size_t t = a; t < b; t++)
+      for (uint64_t j = offs[t]; j < offs[t + 1]; j++)
+        if (docs[j] < lo || docs[j] >= hi || tfs[j] == 0 || (j > offs[t] && docs[j] <= docs[j - 1])) { bad.store(1); return; }
+  });
+  return !bad.load();
+}
+
+// The positions a `_positions` upload needs are exactly sum(tf), and there: asked BEFORE anything is built or read, since the walk over
+// the postings indexes the positions by the running sum of the tfs.
+bool positions_needed(const uint64_t* offs, uint32_t n_terms, const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
+  if (!offs || n_terms == 0 || (offs[n_terms] && !tfs)) return false;
+  uint64_t need = 0;
+  for (uint64_t j = offs[0]; j < offs[n_terms]; j++) need += tfs[j];
+  return need == n_positions && (!need || positions);
+}
+
+// a commit brings the next level or replaces the last one (a re-commit); only the last level may be partial; doc ids stay under 2^32
+template <class Levels>
+int level_rules(uint32_t level, uint32_t n_level_docs, const Levels& levels) {
+  if (level > levels.size() || level + 1 < levels.size()) return SS_EINVAL;
+  if (level >= 1 && levels[level - 1].n_docs != 65536u) return SS_EINVAL;
+  if ((uint64_t)level * 65536u + n_level_docs > 0xFFFFFFFFull) return SS_ENOTSUP;
+  return SS_OK;
 }
 }  // namespace
 
@@ -229,8 +261,7 @@ static void free_vec(ss_shard* s) {
   s->ann_ev = nullptr; s->ann_ev_set = false; s->ann_ev_stream = nullptr;
 }
 static void free_raw_levels(ss_shard* s) {
-  for (ss_raw_level& L : s->raw)
-    for (void* p : {(void*)L.d_off, (void*)L.d_doc, (void*)L.d_tf, (void*)L.d_npos, (void*)L.d_prel, (void*)L.d_tpos, (void*)L.d_pos}) if (p) (void)hipFree(p);
+  for (ss_raw_level& L : s->raw) raw_level_free(L);
   s->raw.clear();
   s->h_doclen.clear();
   s->raw_f.clear();
@@ -239,11 +270,8 @@ static void free_raw_levels(ss_shard* s) {
 // keep_tier: the dense image goes (a commit swaps in its successor), the sparse tier stays
 static void free_bm25(ss_shard* s, bool keep_tier = false) {
   free_raw_levels(s);
-  void* ptrs[] = {s->d_post, s->d_term_base, s->d_sub_off, s->d_comp, s->d_probe, s->d_probe_z, s->d_probe_row, s->d_umax, s->d_submax, s->d_boost, s->d_pos, s->d_pos32, s->d_pos_off, s->d_pos_base,
-                  s->d_doclen};
-  for (void* p : ptrs) if (p) { s->blocks.drop(p); (void)hipFree(p); }
+  bm_image_arrays(s, [&](auto*& p) { if (p) { s->blocks.drop(p); (void)hipFree(p); } });
   s->blocks.clear_idle();
-  s->d_doclen = nullptr;
   ssi_bm25_drop_kth(s);
   if (!keep_tier) {
     for (void* p : {(void*)s->d_sp_base, (void*)s->d_sp_post, (void*)s->d_sp_pos, (void*)s->d_sp_pos_end}) if (p) (void)hipFree(p);
@@ -251,11 +279,7 @@ static void free_bm25(ss_shard* s, bool keep_tier = false) {
     s->d_sp_pos = nullptr; s->d_sp_pos_end = nullptr; s->sp_pos_n = 0; s->sp_pos_elem = 0;
     ssi_bm25_sparse_levels_drop(s);
   }
-  s->d_post = nullptr; s->d_term_base = nullptr; s->d_sub_off = nullptr; s->d_comp = nullptr;
-  s->probe_pool_begin = 0; s->probe_pool_rows = 0; s->pool_list.clear(); s->pool_tick.clear();
-  s->d_probe = nullptr; s->d_probe_z = nullptr; s->d_probe_row = nullptr; s->h_probe_row.clear(); s->bm_probe_rows = 0; s->d_umax = nullptr; s->d_submax = nullptr; s->d_pos = nullptr; s->d_pos32 = nullptr; s->d_pos_off = nullptr; s->d_pos_base = nullptr;
-  s->bm_n_docs = 0; s->bm_n_terms = 0; s->bm_n_sub = 0; s->bm_n_post = 0; s->bm_n_fields = 1; s->bm_merged = false; s->d_boost = nullptr;
-  s->h_df.clear(); s->h_df_real.clear(); s->h_boost.clear(); s->bm_n_post_pad = 0; s->bm_partmax = false;
+  bm_image_clear_fields(s);
 }
 
 int ss_shard_destroy(ss_shard* s) {
@@ -379,17 +403,11 @@ int ss_bm25_upload(ss_shard* s, uint64_t n_docs, const uint8_t* doclen, uint32_t
 
 int ss_bm25_upload_positions(ss_shard* s, uint64_t n_docs, const uint8_t* doclen, uint32_t n_terms, const uint64_t* offs,
                              const uint32_t* docs, const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
-  if (n_positions && !positions) return SS_EINVAL;
-  // the positions array must hold exactly sum(tf) entries -- checked BEFORE anything is built or read: the walk over the
-  // postings indexes it by the running sum of the tfs
-  if (!offs || n_terms == 0) return SS_EINVAL;
-  if (offs[n_terms] && !tfs) return SS_EINVAL;
-  uint64_t need = 0;
-  for (uint64_t j = offs[0]; j < offs[n_terms]; j++) need += tfs[j];
-  if (need != n_positions || (need && !positions)) return SS_EINVAL;
-  int rc = ssi_bm25_upload(s, n_docs, doclen, n_terms, offs, docs, tfs, 0);
-  if (rc) return rc;
-  return ssi_bm25_attach_positions(s, offs, docs, tfs, positions, n_positions);
+  if (!positions_needed(offs, n_terms, tfs, positions, n_positions)) return SS_EINVAL;
+  return ss_guard([&]() -> int {
+    SS_TRY(ssi_bm25_upload(s, n_docs, doclen, n_terms, offs, docs, tfs, 0));
+    return ssi_bm25_attach_positions(s, offs, docs, tfs, positions, n_positions);
+  }, SS_ENOMEM, SS_EDEVICE);
 }
 
 }  // extern "C"
@@ -409,15 +427,7 @@ static int bm25_upload_device_build(ss_shard* s, const uint8_t* doclen, const ui
                                     uint64_t positions_sum) {
   const uint32_t nt = s->bm_n_terms;
   const uint64_t nd = s->bm_n_docs, np = offs[nt] - offs[0];
-  for (uint32_t t = 0; t < nt; t++)
-    if (offs[t + 1] < offs[t]) return SS_EINVAL;
-  std::atomic<int> bad{0};
-  ss_parallel_for(nt, 64, [&](size_t a, size_t b, unsigned) {
-    for (size_t t = a; t < b; t++)
-      for (uint64_t j = offs[t]; j < offs[t + 1]; j++)
-        if (docs[j] >= nd || tfs[j] == 0 || (j > offs[t] && docs[j] <= docs[j - 1])) { bad.store(1); return; }
-  });
-  if (bad.load()) return SS_EINVAL;
+  if (!postings_ok(nt, offs, docs, tfs, 0, nd)) return SS_EINVAL;
   ss_raw_level L;
   L.n_docs = 0; L.n_terms = nt; L.n_post = np;
   if (positions_sum) L.psum = positions_sum;
@@ -426,23 +436,10 @@ static int bm25_upload_device_build(ss_shard* s, const uint8_t* doclen, const ui
     ss_parallel_for(nd, 1u << 20, [&](size_t a, size_t b, unsigned w) { uint64_t c = 0; for (size_t d = a; d < b; d++) c += ss_byte4_to_int(doclen[d]); part[w] += c; });
     for (uint64_t c : part) L.psum += c;
   }
-  auto drop = [&]() { for (void* p : {(void*)L.d_off, (void*)L.d_doc, (void*)L.d_tf}) if (p) (void)hipFree(p); };
-#define SS_HIP_D(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { drop(); return e_ == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE; } } while (0)
-  std::vector<uint64_t> rel((size_t)nt + 1);
-  for (uint32_t t = 0; t <= nt; t++) rel[t] = offs[t] - offs[0];
-  SS_HIP_D(hipMalloc(&L.d_off, rel.size() * sizeof(uint64_t)));
-  SS_HIP_D(hipMalloc(&L.d_doc, std::max<uint64_t>(np, 1) * sizeof(uint32_t)));
-  SS_HIP_D(hipMalloc(&L.d_tf, std::max<uint64_t>(np, 1) * sizeof(uint16_t)));
-  SS_HIP_D(hipMemcpyAsync(L.d_off, rel.data(), rel.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream));
-  if (np) {
-    SS_HIP_D(hipMemcpyAsync(L.d_doc, docs + offs[0], np * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-    SS_HIP_D(hipMemcpyAsync(L.d_tf, tfs + offs[0], np * sizeof(uint16_t), hipMemcpyHostToDevice, s->stream));
-  }
-  SS_HIP_D(hipStreamSynchronize(s->stream));
-#undef SS_HIP_D
+  SS_TRY(raw_level_upload(L, offs, docs, tfs, nt, nullptr, s->stream));
   std::vector<ss_raw_level> one{L};
   const int rc = ssi_bm25_rebuild_from_raw(s, one, nt, doclen, nd, s, s->stream, true);
-  drop();
+  raw_level_free(L);
   return rc;
 }
 
@@ -486,11 +483,7 @@ int ss_bm25_upload_fields(ss_shard* s, uint64_t n_docs, uint32_t n_fields, const
 int ss_bm25_upload_fields_positions(ss_shard* s, uint64_t n_docs, uint32_t n_fields, const uint8_t* doclen, const float* boost,
                                     uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
                                     const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
-  if (!offs || n_terms == 0) return SS_EINVAL;
-  if (offs[n_terms] && !tfs) return SS_EINVAL;
-  uint64_t need = 0;  // checked before anything is built or read, as in ss_bm25_upload_positions
-  for (uint64_t j = offs[0]; j < offs[n_terms]; j++) need += tfs[j];
-  if (need != n_positions || (need && !positions)) return SS_EINVAL;
+  if (!positions_needed(offs, n_terms, tfs, positions, n_positions)) return SS_EINVAL;
   return ss_guard([&] { return ssi_bm25_upload_fields_positions(s, n_docs, n_fields, doclen, boost, n_terms, offs, docs, fields, tfs, 0, positions, n_positions); },
                   SS_ENOMEM, SS_EDEVICE);
 }
@@ -685,9 +678,7 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
     // (a re-committed level only grows, commit.rs:204-206; a shrinking one would leave the tier's postings of the level pointing
     // past the image until ss_bm25_append_sparse_level replaces them)
     if (s->sp_n && level < s->raw.size() && n_level_docs < s->raw[level].n_docs) return SS_ENOTSUP;
-    if (level > s->raw.size() || level + 1 < s->raw.size()) return SS_EINVAL;  // append the next level, or replace the last one (a re-commit)
-    if (level >= 1 && s->raw[level - 1].n_docs != 65536u) return SS_EINVAL;    // only the last level may be partial
-    if ((uint64_t)level * 65536u + n_level_docs > 0xFFFFFFFFull) return SS_ENOTSUP;
+    SS_TRY(level_rules(level, n_level_docs, s->raw));
     nt_old = s->raw.empty() ? 0u : s->bm_n_terms;
     if (n_terms < nt_old) return SS_EINVAL;                    // the vocabulary only grows; new terms get the next ids
     if (level > 0 && (s->raw[0].d_tpos != nullptr) != with_pos) return SS_EINVAL;  // positions for every level of an image, or for none
@@ -696,17 +687,7 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   }
   // validation: docs of a term ascending and inside the level
   const uint64_t d_lo = (uint64_t)level * 65536u, d_hi = d_lo + n_level_docs;
-  for (uint32_t t = 0; t < n_terms; t++)
-    if (offs[t + 1] < offs[t]) return SS_EINVAL;
-  {
-    std::atomic<int> bad{0};
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++)
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++)
-          if (docs[j] < d_lo || docs[j] >= d_hi || tfs[j] == 0 || (j > offs[t] && docs[j] <= docs[j - 1])) { bad.store(1); return; }
-    });
-    if (bad.load()) return SS_EINVAL;
-  }
+  if (!postings_ok(n_terms, offs, docs, tfs, d_lo, d_hi)) return SS_EINVAL;
   ss_raw_level L;
   L.n_docs = n_level_docs; L.n_terms = n_terms; L.n_post = offs[n_terms] - offs[0];
   for (uint32_t d = 0; d < n_level_docs; d++) L.psum += ss_byte4_to_int(level_doclen[d]);
@@ -746,38 +727,14 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   hipStream_t bst = nullptr;
   std::unique_ptr<ss_shard> img(new ss_shard);
   auto fail = [&](int rc) {
-    for (void* p : {(void*)L.d_off, (void*)L.d_doc, (void*)L.d_tf, (void*)L.d_npos, (void*)L.d_prel, (void*)L.d_tpos, (void*)L.d_pos}) if (p) (void)hipFree(p);
-    void* ip[] = {img->d_post, img->d_term_base, img->d_sub_off, img->d_comp, img->d_probe, img->d_probe_z, img->d_probe_row, img->d_umax, img->d_submax, img->d_doclen,
-                  img->d_pos, img->d_pos_off, img->d_pos_base};
-    for (void* p : ip) if (p && !s->blocks.release(p)) (void)hipFree(p);
+    raw_level_free(L);
+    bm_image_arrays(img.get(), [&](auto*& p) { if (p && !s->blocks.release(p)) (void)hipFree(p); });
     if (bst) (void)hipStreamDestroy(bst);
     return rc;
   };
-#define SS_HIP_F(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(e_ == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE); } while (0)
-  SS_HIP_F(hipStreamCreateWithFlags(&bst, hipStreamNonBlocking));
-  std::vector<uint64_t> rel((size_t)n_terms + 1);
-  for (uint32_t t = 0; t <= n_terms; t++) rel[t] = offs[t] - offs[0];
-  SS_HIP_F(hipMalloc(&L.d_off, rel.size() * sizeof(uint64_t)));
-  SS_HIP_F(hipMalloc(&L.d_doc, std::max<uint64_t>(L.n_post, 1) * sizeof(uint32_t)));
-  SS_HIP_F(hipMalloc(&L.d_tf, std::max<uint64_t>(L.n_post, 1) * sizeof(uint16_t)));
-  SS_HIP_F(hipMemcpyAsync(L.d_off, rel.data(), rel.size() * sizeof(uint64_t), hipMemcpyHostToDevice, bst));
-  if (L.n_post) {
-    SS_HIP_F(hipMemcpyAsync(L.d_doc, docs + offs[0], L.n_post * sizeof(uint32_t), hipMemcpyHostToDevice, bst));
-    SS_HIP_F(hipMemcpyAsync(L.d_tf, tfs + offs[0], L.n_post * sizeof(uint16_t), hipMemcpyHostToDevice, bst));
-  }
-  if (with_pos) {
-    SS_HIP_F(hipMalloc(&L.d_npos, std::max<uint64_t>(L.n_post, 1) * sizeof(uint16_t)));
-    SS_HIP_F(hipMalloc(&L.d_prel, std::max<uint64_t>(L.n_post, 1) * sizeof(uint32_t)));
-    SS_HIP_F(hipMalloc(&L.d_tpos, h_tpos.size() * sizeof(uint64_t)));
-    SS_HIP_F(hipMalloc(&L.d_pos, std::max<uint64_t>(n_positions, 1) * sizeof(uint16_t)));
-    if (L.n_post) {
-      SS_HIP_F(hipMemcpyAsync(L.d_npos, h_npos.data(), L.n_post * sizeof(uint16_t), hipMemcpyHostToDevice, bst));
-      SS_HIP_F(hipMemcpyAsync(L.d_prel, h_prel.data(), L.n_post * sizeof(uint32_t), hipMemcpyHostToDevice, bst));
-    }
-    SS_HIP_F(hipMemcpyAsync(L.d_tpos, h_tpos.data(), h_tpos.size() * sizeof(uint64_t), hipMemcpyHostToDevice, bst));
-    if (n_positions) SS_HIP_F(hipMemcpyAsync(L.d_pos, positions, n_positions * sizeof(uint16_t), hipMemcpyHostToDevice, bst));
-  }
-  SS_HIP_F(hipStreamSynchronize(bst));  // (rel dies with this frame; the caller's arrays are free again)
+  if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return fail(e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE);
+  const raw_level_positions pos{h_npos.data(), h_prel.data(), h_tpos.data(), positions, n_positions};
+  if (const int rc_up = raw_level_upload(L, offs, docs, tfs, n_terms, with_pos ? &pos : nullptr, bst)) return fail(rc_up);
   levels.push_back(L);
   doclen.insert(doclen.end(), level_doclen, level_doclen + n_level_docs);
   const auto t_build = std::chrono::steady_clock::now();
@@ -800,33 +757,19 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
     std::vector<ss_raw_level> keep(s->raw.begin(), s->raw.begin() + level);
     s->raw.clear();  // (free_bm25 must not release the levels that stay)
     {  // the old image's arrays go back to the block pool: the next commit builds into them
-      void** op[] = {(void**)&s->d_post, (void**)&s->d_term_base, (void**)&s->d_sub_off, (void**)&s->d_comp, (void**)&s->d_probe, (void**)&s->d_probe_z,
-                     (void**)&s->d_probe_row, (void**)&s->d_umax, (void**)&s->d_submax, (void**)&s->d_doclen, (void**)&s->d_pos, (void**)&s->d_pos_off,
-                     (void**)&s->d_pos_base};
       s->blocks.gen++;
-      for (void** pp : op) if (*pp && s->blocks.release(*pp)) *pp = nullptr;
+      bm_image_arrays(s, [&](auto*& p) { if (p && s->blocks.release(p)) p = nullptr; });  // (d_boost, d_pos32: null in an image built by levels)
       std::vector<ss_block_pool::Idle> idle;
       idle.swap(s->blocks.idle);   // (free_bm25 clears the idle list: these stay)
       free_bm25(s, /*keep_tier=*/true);
       s->blocks.idle.swap(idle);
       s->blocks.trim(3);
     }
-    if (replace)
-      for (void* p : {(void*)replaced.d_off, (void*)replaced.d_doc, (void*)replaced.d_tf, (void*)replaced.d_npos, (void*)replaced.d_prel, (void*)replaced.d_tpos,
-                      (void*)replaced.d_pos})
-        if (p) (void)hipFree(p);
+    if (replace) raw_level_free(replaced);
     keep.push_back(L);
     s->raw.swap(keep);
     s->h_doclen.swap(doclen);
-    s->bm_n_docs = img->bm_n_docs; s->bm_n_terms = img->bm_n_terms; s->bm_n_sub = img->bm_n_sub; s->bm_n_fields = 1; s->bm_merged = false;
-    s->bm_n_post = img->bm_n_post; s->bm_n_post_pad = img->bm_n_post_pad; s->bm_avgdl = img->bm_avgdl; s->bm_partmax = img->bm_partmax;
-    s->d_post = img->d_post; s->d_term_base = img->d_term_base; s->d_sub_off = img->d_sub_off; s->d_comp = img->d_comp;
-    s->d_probe = img->d_probe; s->d_probe_z = img->d_probe_z; s->d_probe_row = img->d_probe_row; s->d_umax = img->d_umax; s->d_submax = img->d_submax;
-    s->d_doclen = img->d_doclen;
-    s->d_pos = img->d_pos; s->d_pos_off = img->d_pos_off; s->d_pos_base = img->d_pos_base;
-    s->h_df.swap(img->h_df); s->h_probe_row.swap(img->h_probe_row); s->bm_probe_rows = img->bm_probe_rows;
-    s->probe_pool_begin = img->probe_pool_begin; s->probe_pool_rows = img->probe_pool_rows; s->pool_list.swap(img->pool_list); s->pool_tick.swap(img->pool_tick);
-    s->pool_clock = 0;
+    bm_image_take(s, img.get());
     if (s->sp_n) {  // the average length moved: the sparse postings' codes follow (their docs of this level: ss_bm25_append_sparse_level)
       rc_recode = ssi_bm25_sparse_levels_recode(s, s->stream);
       if (rc_recode == SS_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc_recode = SS_EDEVICE;
@@ -834,7 +777,6 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
     s->raw_last_rebuild_ms = rebuild_ms;
     s->raw_last_append_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
-#undef SS_HIP_F
   // the dense image is swapped in either way; a sparse tier that could not follow the new average length would score its terms with
   // the old one: the caller hears about it, and commits again or rebuilds
   (void)hipStreamDestroy(bst);
@@ -858,13 +800,12 @@ int ss_bm25_append_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_do
       if ((s->d_post || !s->raw.empty()) && s->raw_f.empty()) return SS_ESTATE;  // an image that was not built this way
       if (s->sp_n) return SS_ENOTSUP;                                            // (a sparse tier beside it: upload + ss_bm25_append_sparse_fields)
       if (!s->raw_f.empty() && s->raw_f_fields != n_fields) return SS_EINVAL;
-      if (level > s->raw_f.size() || level + 1 < s->raw_f.size()) return SS_EINVAL;  // append the next level, or replace the last one
-      if (level >= 1 && s->raw_f[level - 1].n_docs != 65536u) return SS_EINVAL;      // only the last level may be partial
-      if ((uint64_t)level * 65536u + n_level_docs > 0xFFFFFFFFull) return SS_ENOTSUP;
+      SS_TRY(level_rules(level, n_level_docs, s->raw_f));
       if (!s->raw_f.empty() && n_terms < s->raw_f.back().n_terms && level == s->raw_f.size()) return SS_EINVAL;  // the vocabulary only grows
       levels.assign(s->raw_f.begin(), s->raw_f.begin() + level);
     }
     const uint64_t d_lo = (uint64_t)level * 65536u, d_hi = d_lo + n_level_docs;
+    // (not postings_ok: a doc's entries follow each other field by field; their order is ssi_bm25_upload_fields' to judge)
     for (uint32_t t = 0; t < n_terms; t++)
       if (offs[t + 1] < offs[t]) return SS_EINVAL;
     for (uint64_t j = offs[0]; j < offs[n_terms]; j++)
@@ -1054,58 +995,51 @@ int ss_bm25_term_df(ss_shard* s, uint32_t n, const uint32_t* terms, uint64_t* df
 int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
                                 const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
   if (!s || !offs || n_lists == 0 || (offs[n_lists] > offs[0] && (!docs || !tfs))) return SS_EINVAL;
-  ShardLock g(s);
-  if (s->raw.empty()) return SS_ESTATE;  // an image that grows level by level (ss_bm25_append_level)
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays the level replaces
-  return ssi_bm25_append_sparse_level(s, level, n_lists, offs, docs, tfs, npos, positions, n_positions);
+  return ss_guard([&]() -> int {
+    ShardLock g(s);
+    if (s->raw.empty()) return SS_ESTATE;  // an image that grows level by level (ss_bm25_append_level)
+    SS_HIP(hipSetDevice(s->device));
+    SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays the level replaces
+    return ssi_bm25_append_sparse_level(s, level, n_lists, offs, docs, tfs, npos, positions, n_positions);
+  }, SS_ENOMEM, SS_EDEVICE);
+}
+// Whole lists of rare terms behind the tier's: with_fields = entries (doc, field, tf) of an image with several indexed fields -- said
+// apart from `fields`, which postings present must bring then --; with_positions = the entry brings positions (none at all: still
+// a tier that carries them).  The first new list's term id continues behind the dense terms and the lists the tier holds.
+static int append_sparse(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, bool with_fields, const uint8_t* fields,
+                         const uint16_t* tfs, bool with_positions, const uint16_t* positions, uint64_t n_positions, const uint16_t* npos,
+                         uint32_t* first_term_id_out) {
+  if (!s || !offs || (n_lists && offs[n_lists] > offs[0] && (!docs || (with_fields && !fields) || !tfs)) || (with_positions && n_positions && !positions))
+    return SS_EINVAL;
+  return ss_guard([&]() -> int {
+    static const uint16_t none = 0;
+    if (with_positions && !positions) positions = &none;
+    ShardLock g(s);
+    SS_HIP(hipSetDevice(s->device));
+    SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays an append replaces
+    const uint32_t first = s->bm_n_terms / std::max<uint32_t>(s->bm_n_fields, 1) + s->sp_n;
+    SS_TRY(with_fields ? ssi_bm25_append_sparse_fields(s, n_lists, offs, docs, fields, tfs, positions, n_positions, npos)
+                       : ssi_bm25_append_sparse(s, n_lists, offs, docs, tfs, positions, n_positions, npos));
+    if (first_term_id_out) *first_term_id_out = first;
+    return SS_OK;
+  }, SS_ENOMEM, SS_EDEVICE);
 }
 int ss_bm25_append_sparse(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
                           uint32_t* first_term_id_out) {
-  if (!s || !offs || (n_lists && offs[n_lists] > offs[0] && (!docs || !tfs))) return SS_EINVAL;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays an append replaces
-  const uint32_t first = s->bm_n_terms + s->sp_n;
-  SS_TRY(ssi_bm25_append_sparse(s, n_lists, offs, docs, tfs));
-  if (first_term_id_out) *first_term_id_out = first;
-  return SS_OK;
+  return append_sparse(s, n_lists, offs, docs, false, nullptr, tfs, false, nullptr, 0, nullptr, first_term_id_out);
 }
 int ss_bm25_append_sparse_fields(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
                                  const uint16_t* tfs, uint32_t* first_term_id_out) {
-  if (!s || !offs || (n_lists && offs[n_lists] > offs[0] && (!docs || !fields || !tfs))) return SS_EINVAL;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays an append replaces
-  const uint32_t first = s->bm_n_terms / std::max<uint32_t>(s->bm_n_fields, 1) + s->sp_n;
-  SS_TRY(ssi_bm25_append_sparse_fields(s, n_lists, offs, docs, fields, tfs));
-  if (first_term_id_out) *first_term_id_out = first;
-  return SS_OK;
+  return append_sparse(s, n_lists, offs, docs, true, fields, tfs, false, nullptr, 0, nullptr, first_term_id_out);
 }
 int ss_bm25_append_sparse_positions(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
                                     const uint16_t* positions, uint64_t n_positions, const uint16_t* npos, uint32_t* first_term_id_out) {
-  if (!s || !offs || (n_lists && offs[n_lists] > offs[0] && (!docs || !tfs)) || (n_positions && !positions)) return SS_EINVAL;
-  static const uint16_t none = 0;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays an append replaces
-  const uint32_t first = s->bm_n_terms + s->sp_n;
-  SS_TRY(ssi_bm25_append_sparse(s, n_lists, offs, docs, tfs, positions ? positions : &none, n_positions, npos));
-  if (first_term_id_out) *first_term_id_out = first;
-  return SS_OK;
+  return append_sparse(s, n_lists, offs, docs, false, nullptr, tfs, true, positions, n_positions, npos, first_term_id_out);
 }
 int ss_bm25_append_sparse_fields_positions(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
                                            const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions, const uint16_t* npos,
                                            uint32_t* first_term_id_out) {
-  if (!s || !offs || (n_lists && offs[n_lists] > offs[0] && (!docs || !fields || !tfs)) || (n_positions && !positions)) return SS_EINVAL;
-  static const uint16_t none = 0;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays an append replaces
-  const uint32_t first = s->bm_n_terms / std::max<uint32_t>(s->bm_n_fields, 1) + s->sp_n;
-  SS_TRY(ssi_bm25_append_sparse_fields(s, n_lists, offs, docs, fields, tfs, positions ? positions : &none, n_positions, npos));
-  if (first_term_id_out) *first_term_id_out = first;
-  return SS_OK;
+  return append_sparse(s, n_lists, offs, docs, true, fields, tfs, true, positions, n_positions, npos, first_term_id_out);
 }
 int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, uint64_t* bytes) {
   if (!s) return SS_EINVAL;
