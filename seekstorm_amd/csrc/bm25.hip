@@ -5,6 +5,11 @@
 #include <cstdlib>
 
 #include "bm25_dev.h"
+#include "bm25_pack.h"
+
+#ifndef PB_STAGED_KTHB
+#define PB_STAGED_KTHB 0  // (bm25_probe.hip)
+#endif
 
 
 // ---------------------------------------------------------------- merge of partition-local lists (bitonic in LDS)
@@ -151,14 +156,37 @@ constexpr uint32_t BM_CLAIM_AND = 1u, BM_CLAIM_OR = 2u, BM_CLAIM_PROBED = 4u, BM
 constexpr uint32_t BM_CLAIM_FILTER = 32u;  // some query of the batch carries a field filter (variants sized for term x field lists)
 constexpr uint32_t BM_CLAIM_UNIFORM = 64u;  // every query has exactly np_claim terms (the 16-bit scan's intersection instance)
 constexpr uint32_t BM_CLAIM_GATED = 128u;   // some query is a UNION of several terms under a field filter (exact counts then come from the scan)
-__global__ void bm_expand_kernel(const ss_bm25_query* __restrict__ q, bm_vquery* __restrict__ vq, uint32_t nq, uint32_t n_lists,
-                                 const unsigned long long* __restrict__ term_base, const float* __restrict__ boost,
-                                 unsigned long long* __restrict__ total, uint32_t* __restrict__ tau, uint32_t claim,
-                                 uint32_t n_vterms, const uint32_t* __restrict__ probe_row, uint32_t merged, uint32_t keep_tau = 0u,
-                                 const float* __restrict__ kthw = nullptr, uint32_t kth_sel = 3u,
-                                 unsigned long long* __restrict__ best_slots = nullptr, uint32_t best_P = 0u, uint32_t best_KS = 0u) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nq) return;
+// The two forms a batch arrives in: the public queries as they are (device-resident batches, phrase batches), or packed by the host
+// (bm25_pack.h: a host-pointer batch without phrase queries -- the upload is a ninth of the full form's for three-term queries).
+struct BmQFull {
+  const ss_bm25_query* q;
+  __device__ uint32_t n_terms() const { return q->n_terms; }
+  __device__ uint32_t op() const { return q->op; }
+  __device__ uint32_t term(uint32_t t) const { return q->term[t]; }
+  __device__ float idf(uint32_t t) const { return q->idf[t]; }
+  __device__ uint32_t phrase_len() const { return q->phrase_len; }
+  __device__ uint8_t phrase_seq(uint32_t j) const { return q->phrase_seq[j]; }
+  __device__ bool holds(uint32_t) const { return true; }
+};
+struct BmQPacked {
+  const uint32_t* p;
+  uint32_t W;
+  __device__ uint32_t n_terms() const { return p[0]; }
+  __device__ uint32_t op() const { return p[1]; }
+  __device__ uint32_t term(uint32_t t) const { return p[BM_PACK_HDR + t]; }
+  __device__ float idf(uint32_t t) const { return __uint_as_float(p[BM_PACK_HDR + W + t]); }
+  __device__ uint32_t phrase_len() const { return 0u; }   // (a batch with a phrase query travels in the full form)
+  __device__ uint8_t phrase_seq(uint32_t) const { return 0; }
+  __device__ bool holds(uint32_t n) const { return n <= W; }  // a query of more terms than the stride has slots: malformed
+};
+
+// one query: tau line, total and the expanded query V (the kernel's LDS staging)
+template <class QV>
+__device__ __forceinline__ void bm_expand_one(const QV Q, bm_vquery& V, uint32_t i, uint32_t n_lists, const unsigned long long* __restrict__ term_base,
+                              const float* __restrict__ boost, unsigned long long* __restrict__ total, uint32_t* __restrict__ tau,
+                              uint32_t claim, uint32_t n_vterms, const uint32_t* __restrict__ probe_row, uint32_t merged, uint32_t keep_tau,
+                              const float* __restrict__ kthw, uint32_t kth_sel, unsigned long long* __restrict__ best_slots, uint32_t best_P,
+                              uint32_t best_KS) {
   // rank 0 of every partition's list doubles as the partition's BEST-SO-FAR key while the many-list scan runs (bm25_scan16m_kernel
   // derives the query's threshold from the k-th largest of them): they start from "none"
   if (best_slots)
@@ -166,44 +194,42 @@ __global__ void bm_expand_kernel(const ss_bm25_query* __restrict__ q, bm_vquery*
   total[i] = 0ull;                      // per-query match count and shared threshold start from zero (no separate memset launch)
   if (!keep_tau) tau[(size_t)i * BM_TAU_STRIDE] = 0u;  // (keep_tau: an experiment -- the same batch again with the thresholds it ended on)
                                                        // (a union without exclusions raises it to its seed at the end of the expansion)
-  const ss_bm25_query& Q = q[i];  // (read in place: a local copy indexed at run time would live in scratch)
-  bm_vquery& V = vq[i];  // written in place: a local copy indexed at run time would live in scratch
-  const uint32_t np = Q.n_terms, n_not = bm_q_nnot(Q.op);
+  const uint32_t np = Q.n_terms(), n_not = bm_q_nnot(Q.op());
   const uint32_t n_fields = n_lists - (merged ? 1u : 0u);                      // indexed fields
-  const uint32_t filt = n_fields > 1 ? bm_q_field_filter(Q.op) : 0u;
-  const bool q_is_phrase = bm_q_op(Q.op) == SS_OP_PHRASE;
+  const uint32_t filt = n_fields > 1 ? bm_q_field_filter(Q.op()) : 0u;
+  const bool q_is_phrase = bm_q_op(Q.op()) == SS_OP_PHRASE;
   const bool use_merged = merged != 0u && (filt == 0u || q_is_phrase);         // this query reads the merged lists only (a phrase always:
                                                                                // its filter is a test on the positions' field bits)
   const uint32_t f_begin = use_merged ? n_lists - 1u : 0u, f_end = use_merged ? n_lists : n_fields;  // the lists of a term it reads
   const uint32_t eff_fields = use_merged ? 1u : n_fields;                      // ... as how many fields the rules below see them
   {
     const uint32_t nt_claim = (claim >> 8) & 0xFFu, np_claim = (claim >> 16) & 0xFFu, ff = filt;
-    bool bad = np == 0 || np + n_not > (uint32_t)SS_MAX_QUERY_TERMS || (np + n_not) * eff_fields > (uint32_t)BM_MAX_VTERMS;
+    bool bad = np == 0 || np + n_not > (uint32_t)SS_MAX_QUERY_TERMS || !Q.holds(np + n_not) || (np + n_not) * eff_fields > (uint32_t)BM_MAX_VTERMS;
     bad |= ff != 0u && merged != 0u && !q_is_phrase && !(claim & BM_CLAIM_FILTER);  // the variants were sized for one list per term
     bad |= np + n_not > nt_claim || np > np_claim;
     bad |= (claim & BM_CLAIM_UNIFORM) != 0u && np != np_claim;
     bad |= n_not != 0 && nt_claim == np_claim;  // nt == np declares a batch without NOT terms (unfiltered kernel variants)
-    const bool q_and = ((bm_q_op(Q.op) == SS_OP_INTERSECTION || bm_q_op(Q.op) == SS_OP_PHRASE) && np > 1) || ff != 0u;
-    const bool q_gated = ff != 0u && bm_q_op(Q.op) == SS_OP_UNION && np > 1;  // a union under a field filter: BM_AND_GATED
+    const bool q_and = ((bm_q_op(Q.op()) == SS_OP_INTERSECTION || bm_q_op(Q.op()) == SS_OP_PHRASE) && np > 1) || ff != 0u;
+    const bool q_gated = ff != 0u && bm_q_op(Q.op()) == SS_OP_UNION && np > 1;  // a union under a field filter: BM_AND_GATED
     bad |= q_gated && (np > 7u || !(claim & BM_CLAIM_GATED));
     bad |= q_and && !(claim & BM_CLAIM_AND);
     bad |= !q_and && np > 1 && !(claim & BM_CLAIM_OR);
     // a phrase batch holds phrase queries only (one indexed field or merged lists, no NOT terms, 2 .. SS_MAX_PHRASE words naming the unique terms)
-    const bool q_phrase = bm_q_op(Q.op) == SS_OP_PHRASE;
-    bad |= bm_q_op(Q.op) > (uint32_t)SS_OP_PHRASE || q_phrase != ((claim & BM_CLAIM_PHRASE) != 0u);
+    const bool q_phrase = bm_q_op(Q.op()) == SS_OP_PHRASE;
+    bad |= bm_q_op(Q.op()) > (uint32_t)SS_OP_PHRASE || q_phrase != ((claim & BM_CLAIM_PHRASE) != 0u);
     if (q_phrase) {
-      bad |= (n_lists != 1 && merged == 0u) || Q.phrase_len < 2u || Q.phrase_len > (uint32_t)SS_MAX_PHRASE || np > 6u;
+      bad |= (n_lists != 1 && merged == 0u) || Q.phrase_len() < 2u || Q.phrase_len() > (uint32_t)SS_MAX_PHRASE || np > 6u;
       // (a word place inside an n-gram key carries SS_PHRASE_SKIP; the key's other component terms are scored, not placed)
-      bad |= Q.phrase_seq[0] >= np;
-      for (uint32_t j = 1; j < (uint32_t)SS_MAX_PHRASE && j < Q.phrase_len; j++) bad |= Q.phrase_seq[j] >= np && Q.phrase_seq[j] != SS_PHRASE_SKIP;
+      bad |= Q.phrase_seq(0) >= np;
+      for (uint32_t j = 1; j < (uint32_t)SS_MAX_PHRASE && j < Q.phrase_len(); j++) bad |= Q.phrase_seq(j) >= np && Q.phrase_seq(j) != SS_PHRASE_SKIP;
     }
-    bad |= bm_q_all_frequent(Q.op) && bm_q_op(Q.op) == SS_OP_INTERSECTION && np > 1 && ff == 0u && !(claim & BM_CLAIM_FREQ);
+    bad |= bm_q_all_frequent(Q.op()) && bm_q_op(Q.op()) == SS_OP_INTERSECTION && np > 1 && ff == 0u && !(claim & BM_CLAIM_FREQ);
     if (!bad)
       for (uint32_t t = 0; t < np + n_not; t++) {
-        bad |= Q.term[t] >= n_vterms / n_lists;
+        bad |= Q.term(t) >= n_vterms / n_lists;
         if (!bad && (claim & BM_CLAIM_PROBED) && probe_row)
           for (uint32_t f = f_begin; f < f_end; f++) {
-            const uint32_t v = Q.term[t] * n_lists + f;
+            const uint32_t v = Q.term(t) * n_lists + f;
             bad |= probe_row[v] == BM_NO_PROBE_ROW && term_base[v + 1] != term_base[v];
           }
       }
@@ -219,15 +245,15 @@ __global__ void bm_expand_kernel(const ss_bm25_query* __restrict__ q, bm_vquery*
   }
   // field_filter (several indexed fields): every term must occur in a listed field (add_result.rs:3124-3136) -- an
   // intersection whose match bits only the listed fields' lists may set; a single filtered term is an intersection of one
-  const bool is_and = ((bm_q_op(Q.op) == SS_OP_INTERSECTION || bm_q_op(Q.op) == SS_OP_PHRASE) && np > 1) || filt != 0u;
+  const bool is_and = ((bm_q_op(Q.op()) == SS_OP_INTERSECTION || bm_q_op(Q.op()) == SS_OP_PHRASE) && np > 1) || filt != 0u;
   const bool mask = np <= 8;  // 9-10 terms (single field only, checked on the host): count instead of bits
   // all_terms_frequent (intersection.rs:198-209): the caller saw N > 256 k and df >= N / 2 for every term.  One field and
   // <= 7 terms (bit 7 of the match byte becomes the "some tf < 10" mark; the host refuses the rest).
   // (several indexed fields: over the merged lists only -- a field filter switches the shortcut off, add_result.rs:3116)
-  const bool freq = bm_q_all_frequent(Q.op) && bm_q_op(Q.op) == SS_OP_INTERSECTION && np > 1 && np <= 7 && (n_lists == 1 || (use_merged && filt == 0u));
+  const bool freq = bm_q_all_frequent(Q.op()) && bm_q_op(Q.op()) == SS_OP_INTERSECTION && np > 1 && np <= 7 && (n_lists == 1 || (use_merged && filt == 0u));
   // a UNION of several terms under a field filter (ss_common.h BM_AND_GATED): a term's listed fields first -- their postings add
   // and set the term's bit --, then its unlisted fields, which add only where the bit is set
-  const bool gated = filt != 0u && bm_q_op(Q.op) == SS_OP_UNION && np > 1;
+  const bool gated = filt != 0u && bm_q_op(Q.op()) == SS_OP_UNION && np > 1;
   uint32_t n = 0, n_scored = 0;
   for (uint32_t t = 0; t < np + n_not; t++) {
     if (t == np) n_scored = n;
@@ -235,12 +261,12 @@ __global__ void bm_expand_kernel(const ss_bm25_query* __restrict__ q, bm_vquery*
       for (uint32_t f = f_begin; f < f_end; f++) {
         const bool listed = !filt || ((filt >> f) & 1u);
         if (gated && t < np && listed != (pass == 0)) continue;
-        const uint32_t v = Q.term[t] * n_lists + f;
+        const uint32_t v = Q.term(t) * n_lists + f;
         // a term without postings in a field contributes nothing there (one list per term: kept, the zero-length list is harmless)
         if (eff_fields > 1 && term_base[v + 1] == term_base[v]) continue;
         if (n >= (uint32_t)BM_MAX_VTERMS) break;
         V.term[n] = v;
-        V.idf[n] = t < np ? (n_lists > 1 ? boost[f] * Q.idf[t] : Q.idf[t]) : 0.f;  // weight * plo.idf, add_result.rs:1253-1261
+        V.idf[n] = t < np ? (n_lists > 1 ? boost[f] * Q.idf(t) : Q.idf(t)) : 0.f;  // weight * plo.idf, add_result.rs:1253-1261
         if (gated && t < np) V.and_val[n] = (uint8_t)((listed ? 0u : 0x80u) | (1u << t));
         else V.and_val[n] = (is_and && t < np && listed) ? (uint8_t)(mask ? (1u << t) : 0xFFu) : (uint8_t)0;
         V.group[n] = (uint8_t)t;
@@ -249,13 +275,13 @@ __global__ void bm_expand_kernel(const ss_bm25_query* __restrict__ q, bm_vquery*
   }
   if (n_not == 0) n_scored = n;
   V.n_terms = n_scored;
-  V.op = (filt ? (uint32_t)SS_OP_INTERSECTION : np > 1 ? (bm_q_op(Q.op) == SS_OP_PHRASE ? (uint32_t)SS_OP_INTERSECTION : bm_q_op(Q.op)) : (uint32_t)SS_OP_UNION) |
+  V.op = (filt ? (uint32_t)SS_OP_INTERSECTION : np > 1 ? (bm_q_op(Q.op()) == SS_OP_PHRASE ? (uint32_t)SS_OP_INTERSECTION : bm_q_op(Q.op())) : (uint32_t)SS_OP_UNION) |
          ((n - n_scored) << 8);
   V.n_groups = np;
   V.and_target = gated ? (1u | BM_AND_GATED | (np > 2 ? BM_AND_TOUCH : 0u)) : is_and ? ((mask ? (1u << np) - 1u : np) | (freq ? BM_AND_FREQ : 0u)) : 0u;
   for (uint32_t j = n; j < (uint32_t)BM_MAX_VTERMS; j++) { V.term[j] = 0; V.idf[j] = 0.f; V.and_val[j] = 0; V.group[j] = 0xFF; }
-  V.phrase_len = bm_q_op(Q.op) == SS_OP_PHRASE ? Q.phrase_len : 0u;
-  for (int j = 0; j < SS_MAX_PHRASE; j++) V.phrase_seq[j] = Q.phrase_seq[j];
+  V.phrase_len = bm_q_op(Q.op()) == SS_OP_PHRASE ? Q.phrase_len() : 0u;
+  for (int j = 0; j < SS_MAX_PHRASE; j++) V.phrase_seq[j] = Q.phrase_seq(j);
   V.phrase_fields = (q_is_phrase && filt) ? filt : 0xFFFFFFFFu;
   // threshold seed (bm_kth_kernel): a union -- every list adds to the score of a doc that holds it -- with nothing that could take a
   // doc away again (the caller passes kthw only when no tombstone / filter bitmap is in force; NOT terms, field filters, a phrase's position test --
@@ -265,6 +291,37 @@ __global__ void bm_expand_kernel(const ss_bm25_query* __restrict__ q, bm_vquery*
     for (uint32_t j = 0; j < n; j++) seed = fmaxf(seed, V.idf[j] * kthw[(size_t)V.term[j] * 4u + kth_sel]);
     tau[(size_t)i * BM_TAU_STRIDE] = __float_as_uint(seed);
   }
+}
+
+// One thread expands one query into the block's LDS staging (written at run-time indices: registers would spill to scratch, global
+// memory took ~100 dependent narrow stores per thread -- 20 us per 1000 queries); the block's bm_vquery records are contiguous in vq
+// and leave in 16-byte stores.
+constexpr uint32_t BM_EXPAND_THREADS = 64u;
+static_assert(sizeof(bm_vquery) % 4 == 0 && (BM_EXPAND_THREADS * sizeof(bm_vquery)) % 16 == 0, "a block's records: whole 16-byte words");
+template <bool PACKED>
+__global__ void __launch_bounds__(BM_EXPAND_THREADS) bm_expand_kernel(const void* __restrict__ q, uint32_t packed_w, bm_vquery* __restrict__ vq, uint32_t nq, uint32_t n_lists,
+                                 const unsigned long long* __restrict__ term_base, const float* __restrict__ boost,
+                                 unsigned long long* __restrict__ total, uint32_t* __restrict__ tau, uint32_t claim,
+                                 uint32_t n_vterms, const uint32_t* __restrict__ probe_row, uint32_t merged, uint32_t keep_tau = 0u,
+                                 const float* __restrict__ kthw = nullptr, uint32_t kth_sel = 3u,
+                                 unsigned long long* __restrict__ best_slots = nullptr, uint32_t best_P = 0u, uint32_t best_KS = 0u) {
+  __shared__ __attribute__((aligned(16))) bm_vquery sv[BM_EXPAND_THREADS];
+  const uint32_t i0 = blockIdx.x * BM_EXPAND_THREADS, i = i0 + threadIdx.x;
+  if (i < nq) {
+    if constexpr (PACKED)
+      bm_expand_one(BmQPacked{(const uint32_t*)q + (size_t)i * bm_pack_stride(packed_w), packed_w}, sv[threadIdx.x], i, n_lists, term_base, boost,
+                    total, tau, claim, n_vterms, probe_row, merged, keep_tau, kthw, kth_sel, best_slots, best_P, best_KS);
+    else
+      bm_expand_one(BmQFull{(const ss_bm25_query*)q + i}, sv[threadIdx.x], i, n_lists, term_base, boost, total, tau, claim, n_vterms, probe_row,
+                    merged, keep_tau, kthw, kth_sel, best_slots, best_P, best_KS);
+  }
+  __syncthreads();
+  // records [i0, i0 + n_here) of vq: vq + i0 is 16-byte aligned (hipMalloc, and a block's records are whole 16-byte words)
+  const uint32_t n_here = min(BM_EXPAND_THREADS, nq - i0), dwords = n_here * (uint32_t)(sizeof(bm_vquery) / 4u);
+  const uint4* src4 = (const uint4*)sv;
+  uint4* dst4 = (uint4*)(vq + i0);
+  for (uint32_t w = threadIdx.x; w < dwords / 4u; w += BM_EXPAND_THREADS) dst4[w] = src4[w];
+  for (uint32_t w = (dwords & ~3u) + threadIdx.x; w < dwords; w += BM_EXPAND_THREADS) ((uint32_t*)(vq + i0))[w] = ((const uint32_t*)sv)[w];
 }
 
 // a threshold seed from outside the batch's own lists (ss_common.h d_ext_seed): the query's shared threshold starts at least there
@@ -367,7 +424,7 @@ int ssi_bm25_match_bits(ss_shard* s, const ss_bm25_query* d_q, unsigned long lon
     W.vq_cap = 64 * sizeof(bm_vquery);
   }
   uint32_t* tau = (uint32_t*)(d_bits);  // the expansion zeroes one threshold line per query: scratch, overwritten below
-  bm_expand_kernel<<<1, 128, 0, st>>>(d_q, (bm_vquery*)W.d_vq, nq, s->bm_n_fields, (const unsigned long long*)s->d_term_base,
+  bm_expand_kernel<false><<<1, BM_EXPAND_THREADS, 0, st>>>(d_q, 0u, (bm_vquery*)W.d_vq, nq, s->bm_n_fields, (const unsigned long long*)s->d_term_base,
                                       s->d_boost, d_total, tau, BM_CLAIM_AND | BM_CLAIM_OR | BM_CLAIM_FREQ | BM_CLAIM_FILTER | (0xFFu << 8) | (0xFEu << 16),
                                       s->bm_n_terms, nullptr, s->bm_merged ? 1u : 0u);  // the host entry point validated the query
   BmParams p{};
@@ -425,7 +482,7 @@ int ssi_bm25_merge_lists(u64* bufA, u64* bufB, uint32_t nq, uint32_t P, uint32_t
 int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t k, uint32_t rt, uint32_t* d_out_doc,
                     float* d_out_score, uint32_t* d_out_count, uint64_t* d_out_total, bool has_and, bool has_or,
                     uint32_t nt_max, uint32_t np_max, bool all_probed, hipStream_t st, bool any_frequent, bool phrase, bool any_field_filter,
-                    bool uniform_terms, bool any_gated, uint32_t nn_max) {
+                    bool uniform_terms, bool any_gated, uint32_t nn_max, uint32_t packed_w) {
   if (!s->d_post) return SS_ESTATE;
   if (nq == 0) return SS_OK;
   if (k > SS_MAX_K) return SS_EINVAL;
@@ -483,7 +540,9 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   // imbalance is gone and fewer, longer assignments win again: 1.08 ms at 8 partitions per query, 1.10 at 10 / 12, 1.11 at 16, 1.15 at
   // 24 (tools/probes/psweep.sh).  Workgroups made of the partitions of ONE query instead of 8 queries of one partition were tried as
   // well (profiles/r3_map_sweep.log): no better, for the pruned kernel neither.)
-  constexpr bool staged_kthb = true;  // (only read by builds with -DPB_STAGED_KTHB=1)
+  // the probe kernel reads rank 0 of its partitions' lists as best-so-far keys only in builds with -DPB_STAGED_KTHB=1 (bm25_probe.hip,
+  // a measurement switch): only then does the expansion zero them -- the kernel writes every rank of every list itself
+  constexpr bool staged_kthb = PB_STAGED_KTHB != 0;
   const bool scan16m = scan16 && (np_max > 6 || (np_max > 4 && KPL == 2));  // the many-list instance (its waves share their best keys)
   const uint32_t resident = (pruned || phrase) ? 6144u : scan16 ? 4096u : 2048u, rounds = (pruned || phrase) ? 4u : 2u;
   uint32_t P = (rounds * resident) / nq;
@@ -540,12 +599,20 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
                          (any_frequent ? BM_CLAIM_FREQ : 0u) | (any_field_filter ? BM_CLAIM_FILTER : 0u) | (uniform_terms ? BM_CLAIM_UNIFORM : 0u) | (any_gated ? BM_CLAIM_GATED : 0u) |
                          (std::min(nt_max / F, 255u) << 8) |
                          (std::min(np_max / F, 255u) << 16);
-  bm_expand_kernel<<<(nq + 127) / 128, 128, 0, st>>>(d_q, (bm_vquery*)W.d_vq, nq, s->bm_n_fields,
-                                                    (const unsigned long long*)s->d_term_base, s->d_boost, total, tau, claim,
-                                                    s->bm_n_terms, s->d_probe_row, s->bm_merged ? 1u : 0u,
-                                                    0u /* keep_tau: the ceiling experiment of round 3, tools/probes/tau_ceiling.py */,
-                                                    (s->n_deleted || s->del_per_query || k == 0) ? nullptr : s->d_kthw, bm_kth_sel(k),
-                                                    (scan16m || (pruned && staged_kthb)) ? bufA : nullptr, P, KS);
+  {
+    const float* seeds = (s->n_deleted || s->del_per_query || k == 0) ? nullptr : s->d_kthw;
+    u64* best = (scan16m || (pruned && staged_kthb)) ? bufA : nullptr;
+    const uint32_t grid = (nq + BM_EXPAND_THREADS - 1u) / BM_EXPAND_THREADS;
+    const uint32_t keep_tau = 0u;  // (the ceiling experiment of round 3, tools/probes/tau_ceiling.py)
+    if (packed_w)
+      bm_expand_kernel<true><<<grid, BM_EXPAND_THREADS, 0, st>>>(d_q, packed_w, (bm_vquery*)W.d_vq, nq, s->bm_n_fields, (const unsigned long long*)s->d_term_base,
+                                                                s->d_boost, total, tau, claim, s->bm_n_terms, s->d_probe_row, s->bm_merged ? 1u : 0u, keep_tau,
+                                                                seeds, bm_kth_sel(k), best, P, KS);
+    else
+      bm_expand_kernel<false><<<grid, BM_EXPAND_THREADS, 0, st>>>(d_q, 0u, (bm_vquery*)W.d_vq, nq, s->bm_n_fields, (const unsigned long long*)s->d_term_base,
+                                                                 s->d_boost, total, tau, claim, s->bm_n_terms, s->d_probe_row, s->bm_merged ? 1u : 0u, keep_tau,
+                                                                 seeds, bm_kth_sel(k), best, P, KS);
+  }
 
   if (s->d_ext_seed && s->ext_seed_n == nq && k) {  // (a sub-batch the tiered search split further runs without: its rows moved)
     bm_ext_seed_kernel<<<(nq + 255) / 256, 256, 0, st>>>(s->d_ext_seed, nq, tau);

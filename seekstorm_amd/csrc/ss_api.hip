@@ -24,6 +24,7 @@
 #include "bm25_build.h"
 #include "bm25_image.h"
 #include "bm25_match.h"
+#include "bm25_pack.h"
 #include "browse.h"
 
 #define SS_TRY(x)          \
@@ -1051,11 +1052,21 @@ int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, ui
   return SS_OK;
 }
 
+// What the pass over a batch that is about to be uploaded collects besides its verdict (bm25_search_host_queries): the batch in the packed
+// form (bm25_pack.h; given up when a phrase query turns up -- those need phrase_seq / phrase_len), and the postings its scored terms
+// name in all (the pruned kernel's partition rule, ss_common.h bm_batch_postings).
+struct bm_batch_sink {
+  bm_packer pack;
+  const std::vector<uint64_t>* df = nullptr;  // postings per public term
+  uint64_t postings = 0;
+};
+
 // nt_max: largest n_terms + NOT terms of the batch (what the scan kernels are specialised on); np_max: largest n_terms
 // any_filter: some query carries a field filter (on an image with merged lists the others read one list per term)
+// sink: filled with every query that passed, in the same pass
 static int check_queries(const ss_shard* s, uint32_t nq, const ss_bm25_query* q, bool* has_and, bool* has_or, uint32_t* nt_max,
                          uint32_t* np_max, bool* all_probed, bool* any_frequent, bool* phrase = nullptr, bool* any_filter = nullptr,
-                         bool* uniform = nullptr, bool* gated = nullptr, uint32_t* nn_max = nullptr) {
+                         bool* uniform = nullptr, bool* gated = nullptr, uint32_t* nn_max = nullptr, bm_batch_sink* sink = nullptr) {
   uint32_t n_phrase = 0, np_min = 0xFFFFFFFFu, most_not = 0;
   bool some_gated = false;
   const uint32_t L = s->bm_n_fields, RF = bm_real_fields(s);  // lists per term, indexed fields
@@ -1129,6 +1140,12 @@ static int check_queries(const ss_shard* s, uint32_t nq, const ss_bm25_query* q,
     np_min = std::min(np_min, q[i].n_terms);
     any_not |= n_not != 0;
     most_not = std::max(most_not, n_not);
+    if (sink) {
+      if (op == SS_OP_PHRASE) sink->pack.give_up();
+      else sink->pack.add(q[i], all);
+      for (uint32_t t = 0; t < q[i].n_terms; t++)
+        if (q[i].term[t] < sink->df->size()) sink->postings += (*sink->df)[q[i].term[t]];
+    }
   }
   if (nn_max) *nn_max = most_not;  // the most NOT terms any query of the batch has (nt_max - np_max says only that there are some)
   if (uniform) *uniform = np_min == *np_max;  // every query with the same number of terms
@@ -1991,10 +2008,15 @@ static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_quer
   }
   SS_TRY(ssi_bm25_ensure_probe_rows(s, nq, q, s->stream));
   if (nq > 1) {  // phrase queries have a kernel of their own: a batch that mixes them with others runs as two, answers back in place
-    std::vector<uint8_t> is_phrase(nq);
+    // (this count stays a pass of its own in front of check_queries: a mixed batch is split BEFORE that pass could refuse it, and each
+    // half then reports its own errors -- folding it would change which code a batch with two faults returns)
     uint32_t n_phrase = 0;
-    for (uint32_t i = 0; i < nq; i++) n_phrase += (is_phrase[i] = bm_q_op(q[i].op) == SS_OP_PHRASE ? 1 : 0);
-    if (n_phrase != 0 && n_phrase != nq) return bm25_search_split_batch(s, nq, q, kk, rt, n_filters, filters, is_phrase, n_phrase);
+    for (uint32_t i = 0; i < nq; i++) n_phrase += bm_q_op(q[i].op) == SS_OP_PHRASE ? 1u : 0u;
+    if (n_phrase != 0 && n_phrase != nq) {
+      std::vector<uint8_t> is_phrase(nq);
+      for (uint32_t i = 0; i < nq; i++) is_phrase[i] = bm_q_op(q[i].op) == SS_OP_PHRASE ? 1 : 0;
+      return bm25_search_split_batch(s, nq, q, kk, rt, n_filters, filters, is_phrase, n_phrase);
+    }
   }
   if (nq > 1 && s->bm_probe_rows != 0 && s->bm_probe_rows < s->bm_n_terms) {  // rationed probe rows: a mixed batch runs as two
     std::vector<uint8_t> probed(nq);
@@ -2008,49 +2030,47 @@ static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_quer
       return bm25_search_split_batch(s, nq, q, kk, rt, n_filters, filters, probed, n_probed);
     }
   }
+  // One pass validates the batch, packs it into the pinned staging and sums its postings: the staging is made ready first.  It is sized
+  // for the full form, which no packed batch exceeds (bm25_pack.h).
+  SS_HIP(hipSetDevice(s->device));
+  const size_t qbytes = (size_t)nq * sizeof(ss_bm25_query);
+  if (qbytes > s->h_bq_cap) {
+    if (s->bq_ev_set) SS_HIP(hipEventSynchronize(s->bq_ev));
+    if (s->h_bq) (void)hipHostFree(s->h_bq);
+    s->h_bq = nullptr; s->h_bq_cap = 0;
+    const size_t cap = std::max<size_t>(qbytes * 2, 64u << 10);
+    SS_HIP(hipHostMalloc(&s->h_bq, cap, hipHostMallocDefault));
+    s->h_bq_cap = cap;
+  }
+  if (!s->bq_ev) SS_HIP(hipEventCreateWithFlags(&s->bq_ev, hipEventDisableTiming));
+  if (s->bq_ev_set) SS_HIP(hipEventSynchronize(s->bq_ev));  // (the copy of the batch before: long done unless the stream is backed up)
+  bm_batch_sink sink;
+  sink.pack.dst = (uint32_t*)s->h_bq;
+  sink.pack.cap_dwords = s->h_bq_cap / sizeof(uint32_t);
+  sink.df = s->bm_n_fields > 1 ? &s->h_df_real : &s->h_df;
   bool has_and = false, has_or = false;
   uint32_t nt_max = 0, np_max = 0, nn_max = 0;
   bool all_probed = false, any_frequent = false, phrase = false, any_filter = false, uniform = false, gated = false;
-  SS_TRY(check_queries(s, nq, q, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
-  SS_HIP(hipSetDevice(s->device));
+  SS_TRY(check_queries(s, nq, q, &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max, &sink));
   SS_TRY(ensure_out(s, nq, std::max<uint32_t>(kk, 1)));
-  if ((size_t)nq * sizeof(ss_bm25_query) > s->bq_cap) {
+  if (qbytes > s->bq_cap) {
     if (s->d_bq) (void)hipFree(s->d_bq);
     s->d_bq = nullptr; s->bq_cap = 0;
-    SS_HIP(hipMalloc(&s->d_bq, (size_t)nq * sizeof(ss_bm25_query)));
-    s->bq_cap = (size_t)nq * sizeof(ss_bm25_query);
+    SS_HIP(hipMalloc(&s->d_bq, qbytes));
+    s->bq_cap = qbytes;
   }
-  {
-    const size_t qbytes = (size_t)nq * sizeof(ss_bm25_query);
-    if (qbytes > s->h_bq_cap) {
-      if (s->bq_ev_set) SS_HIP(hipEventSynchronize(s->bq_ev));
-      if (s->h_bq) (void)hipHostFree(s->h_bq);
-      s->h_bq = nullptr; s->h_bq_cap = 0;
-      const size_t cap = std::max<size_t>(qbytes * 2, 64u << 10);
-      SS_HIP(hipHostMalloc(&s->h_bq, cap, hipHostMallocDefault));
-      s->h_bq_cap = cap;
-    }
-    if (!s->bq_ev) SS_HIP(hipEventCreateWithFlags(&s->bq_ev, hipEventDisableTiming));
-    if (s->bq_ev_set) SS_HIP(hipEventSynchronize(s->bq_ev));  // (the copy of the batch before: long done unless the stream is backed up)
-    memcpy(s->h_bq, q, qbytes);
-    SS_HIP(hipMemcpyAsync(s->d_bq, s->h_bq, qbytes, hipMemcpyHostToDevice, s->stream));
-    SS_HIP(hipEventRecord(s->bq_ev, s->stream));
-    s->bq_ev_set = true;
-  }
-  {  // the batch's weight, for the pruned kernel's partition rule: the host has the queries in hand here
-    uint64_t sum = 0;
-    const bool mf = s->bm_n_fields > 1;
-    for (uint32_t i = 0; i < nq; i++)
-      for (uint32_t t = 0; t < q[i].n_terms && t < (uint32_t)SS_MAX_QUERY_TERMS; t++) {
-        const uint32_t term = q[i].term[t];
-        if (mf) { if (term < s->h_df_real.size()) sum += s->h_df_real[term]; }
-        else if (term < s->h_df.size()) sum += s->h_df[term];
-      }
-    s->bm_batch_postings = sum / nq;
-  }
+  // the packed batch (a ninth of the full form's bytes for three-term queries), or -- a phrase batch -- the queries as they are
+  const uint32_t packed_w = sink.pack.ok && sink.pack.n == nq ? sink.pack.W : 0u;
+  const size_t up_bytes = packed_w ? bm_pack_bytes(nq, packed_w) : qbytes;
+  if (!packed_w) memcpy(s->h_bq, q, qbytes);
+  SS_HIP(hipMemcpyAsync(s->d_bq, s->h_bq, up_bytes, hipMemcpyHostToDevice, s->stream));
+  SS_HIP(hipEventRecord(s->bq_ev, s->stream));
+  s->bq_ev_set = true;
+  s->bm_batch_postings = sink.postings / nq;  // the batch's weight, for the pruned kernel's partition rule
   const int rc_search = with_facet_filter(s, n_filters, filters, s->stream, [&]() {
     return ssi_bm25_search(s, nq, (const ss_bm25_query*)s->d_bq, kk, rt, s->d_out_doc, s->d_out_score, s->d_out_count,
-                           s->d_out_total, has_and, has_or, nt_max, np_max, all_probed, s->stream, any_frequent, phrase, any_filter, uniform, gated, nn_max);
+                           s->d_out_total, has_and, has_or, nt_max, np_max, all_probed, s->stream, any_frequent, phrase, any_filter, uniform, gated, nn_max,
+                           packed_w);
   });
   s->bm_batch_postings = 0;
   return rc_search;
@@ -2328,7 +2348,7 @@ static int bm25_search_direct_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
   uint32_t n_fit = nq;
   bool split = false;
   // (a rationed vocabulary: one pass over the whole batch deals the pool's rows -- no split)
-  // (a call of more than SM_H_QUERIES queries is the staged pipeline's whole: its fixed cost is spread thin there -- 1000 C2 queries 0.70 ms --
+  // (a call of more than SM_H_QUERIES queries is the staged pipeline's whole: its fixed cost is spread thin there -- 1000 C2 queries 0.67 ms --
   // where launches of 64 cost 0.1 ms each)
   if (kk && nq > 1 && nq <= SM_H_QUERIES && n_filters == 0 && !(s->bm_probe_rows != 0 && s->bm_probe_rows < s->bm_n_terms)) {
     ss_small_shape sh{};
