@@ -364,10 +364,28 @@ int ss_bm25_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, con
  * inside a term, doc ids inside the level, and level_doclen [n_fields][n_level_docs] as ss_bm25_upload_fields takes them.  The levels are
  * kept on the host and the image is rebuilt by the multi-field builder -- a commit costs what an upload of the shard costs (the
  * one-field form rebuilds on the device); the answers afterwards are those of ONE ss_bm25_upload_fields of all levels, bit for bit.
- * n_fields and boost must stay the same from level to level.  No sparse tier beside it (SS_ENOTSUP), no positions yet. */
+ * n_fields and boost must stay the same from level to level.  No sparse tier beside it (SS_ENOTSUP), no positions; a refused rebuild
+ * leaves no image.  Kept for compatibility: ss_bm25_commit_level_fields below supersedes it. */
 int ss_bm25_append_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen,
                                 const float* boost, uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
                                 const uint16_t* tfs);
+/* ... the same seam with the levels kept IN HBM and the image rebuilt ON THE DEVICE, positions included (additive in ABI v7; it supersedes
+ * ss_bm25_append_level_fields, which stays for compatibility).  Entries, level rules, n_fields (2..8), boosts and the growing vocabulary as
+ * above; positions = every entry's in the caller's order, ascending inside an entry, tf of them each or npos[i] (npos may be NULL) as
+ * for ss_bm25_append_level_positions; positions == NULL: an image without positions.  Every level brings positions or none does, and
+ * n_fields and boost stay the same (SS_EINVAL).  A commit costs the level's bytes over PCIe, one host pass over the LEVEL's entries and a
+ * device-side rebuild of per-field lists, merged lists, probe rows and position arrays from the levels' postings; the answers afterwards
+ * are those of ONE ss_bm25_upload_fields[_positions] of all levels, bit for bit.  The new image is built beside the serving one and
+ * swapped in under one lock together with the level list: a refused or failed commit leaves image and levels as they were, and commits
+ * of one shard are serialised.  Refusals, before anything is touched: SS_ESTATE on an image built another way (a whole-image upload,
+ * ss_bm25_append_level, ss_bm25_append_level_fields -- which in turn answers SS_ESTATE on levels committed here); SS_ENOTSUP beside a
+ * sparse tier, for a posting weight the code cannot hold (the WEIGHT RANGE above), for a term with 2^32 positions or more over all
+ * levels, and for positions on a corpus whose boosts keep the merged lists from being built (such a corpus commits without positions,
+ * as ss_bm25_upload_fields uploads it). */
+int ss_bm25_commit_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen /* [n_fields][n_level_docs] */,
+                                const float* boost, uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
+                                const uint16_t* tfs, const uint16_t* npos /* may be NULL: tf */, const uint16_t* positions /* NULL: an image without positions */,
+                                uint64_t n_positions);
 /* ... with the postings' POSITIONS, so that phrase queries work on an image that grows by commits: positions = every posting's in CSR
  * order (ascending inside a posting), tf of them each, or npos[i] where that is not the tf (npos may be NULL) -- the component terms of
  * an n-gram key, whose own positions stand behind its FIRST component's postings (ss_bm25_upload_index_bin_positions).  Every level of

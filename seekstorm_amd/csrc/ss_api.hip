@@ -261,12 +261,33 @@ static void free_vec(ss_shard* s) {
   if (s->ann_ev) (void)hipEventDestroy(s->ann_ev);
   s->ann_ev = nullptr; s->ann_ev_set = false; s->ann_ev_stream = nullptr;
 }
+extern "C++" {
+// the levels of ss_bm25_commit_level_fields, beside their shards (bm25_image.h ss_mf_levels)
+static std::mutex g_mf_mu;
+static std::map<const ss_shard*, std::unique_ptr<ss_mf_levels>> g_mf;
+ss_mf_levels* ssi_mf_levels(const ss_shard* s, bool create) {
+  std::lock_guard<std::mutex> g(g_mf_mu);
+  auto it = g_mf.find(s);
+  if (it != g_mf.end()) return it->second.get();
+  if (!create) return nullptr;
+  return (g_mf[s] = std::make_unique<ss_mf_levels>()).get();
+}
+void ssi_mf_levels_drop(const ss_shard* s) {
+  std::lock_guard<std::mutex> g(g_mf_mu);
+  g_mf.erase(s);
+}
+}  // extern "C++"
 static void free_raw_levels(ss_shard* s) {
   for (ss_raw_level& L : s->raw) raw_level_free(L);
   s->raw.clear();
   s->h_doclen.clear();
   s->raw_f.clear();
   s->raw_f_fields = 0;
+  if (ss_mf_levels* M = ssi_mf_levels(s, false)) {
+    for (ss_raw_level_mf& L : M->raw) raw_level_mf_free(L);
+    M->raw.clear();
+    M->boost.clear();
+  }
 }
 // keep_tier: the dense image goes (a commit swaps in its successor), the sparse tier stays
 static void free_bm25(ss_shard* s, bool keep_tier = false) {
@@ -332,6 +353,7 @@ int ss_shard_destroy(ss_shard* s) {
     if (st) (void)hipStreamSynchronize(st);
   free_vec(s);
   free_bm25(s);
+  ssi_mf_levels_drop(s);
   for (void* p_ : {(void*)s->d_vq, (void*)s->d_vdoc, (void*)s->d_vscore, (void*)s->d_vcount, (void*)s->d_vtotal}) if (p_) (void)hipFree(p_);
   void* ptrs[] = {s->d_qstage, s->d_out_doc, s->d_out_score, s->d_out_count, s->d_out_total, s->d_bq, s->d_deleted, s->d_facets, s->d_filter_bits, s->d_facet_ws, s->d_pool_stage, s->d_tier_ws, s->d_tier_hold, s->d_excl_bits, s->d_sort_ws, s->d_route_ws, s->d_peel_bits, s->d_gate_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -727,35 +749,38 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   }
   hipStream_t bst = nullptr;
   std::unique_ptr<ss_shard> img(new ss_shard);
-  auto fail = [&](int rc) {
+  auto undo = [&]() {
     raw_level_free(L);
     bm_image_arrays(img.get(), [&](auto*& p) { if (p && !s->blocks.release(p)) (void)hipFree(p); });
-    if (bst) (void)hipStreamDestroy(bst);
-    return rc;
   };
-  if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return fail(e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE);
+  CommitUndo<decltype(undo)> own{undo, bst};
+  if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
   const raw_level_positions pos{h_npos.data(), h_prel.data(), h_tpos.data(), positions, n_positions};
-  if (const int rc_up = raw_level_upload(L, offs, docs, tfs, n_terms, with_pos ? &pos : nullptr, bst)) return fail(rc_up);
+  if (const int rc_up = raw_level_upload(L, offs, docs, tfs, n_terms, with_pos ? &pos : nullptr, bst)) return rc_up;
   levels.push_back(L);
   doclen.insert(doclen.end(), level_doclen, level_doclen + n_level_docs);
   const auto t_build = std::chrono::steady_clock::now();
   int rc = ssi_bm25_rebuild_from_raw(s, levels, n_terms, doclen.data(), doclen.size(), img.get(), bst);
-  if (rc) return fail(rc);
+  if (rc) return rc;
   const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
   int rc_recode = SS_OK;
   {  // the swap: searches in flight finish on the old image, whose arrays are then released
     ShardLock g(s);
-    if (level > s->raw.size() || level + 1 < s->raw.size()) return fail(SS_ESTATE);  // another commit got in between (the caller's write lock forbids it)
+    if (level > s->raw.size() || level + 1 < s->raw.size()) return SS_ESTATE;  // another commit got in between (the caller's write lock forbids it)
     (void)hipStreamSynchronize(s->stream);
     for (auto& kv : s->bm_ws) (void)hipStreamSynchronize(kv.first);
     if (s->sp_n) {  // the sparse postings under the new average length: a weight the code cannot hold refuses the commit before anything changes
       const int rc_check = ssi_bm25_sparse_levels_check(s, img.get(), bst);
-      if (rc_check) return fail(rc_check);
+      if (rc_check) return rc_check;
     }
     ss_raw_level replaced;
     const bool replace = level < s->raw.size();
     if (replace) replaced = s->raw[level];
-    std::vector<ss_raw_level> keep(s->raw.begin(), s->raw.begin() + level);
+    std::vector<ss_raw_level> keep;
+    keep.reserve((size_t)level + 1);
+    keep.assign(s->raw.begin(), s->raw.begin() + level);
+    keep.push_back(L);
+    own.taken = true;  // from here on the level and the image are the shard's
     s->raw.clear();  // (free_bm25 must not release the levels that stay)
     {  // the old image's arrays go back to the block pool: the next commit builds into them
       s->blocks.gen++;
@@ -767,7 +792,6 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
       s->blocks.trim(3);
     }
     if (replace) raw_level_free(replaced);
-    keep.push_back(L);
     s->raw.swap(keep);
     s->h_doclen.swap(doclen);
     bm_image_take(s, img.get());
@@ -780,7 +804,6 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   }
   // the dense image is swapped in either way; a sparse tier that could not follow the new average length would score its terms with
   // the old one: the caller hears about it, and commits again or rebuilds
-  (void)hipStreamDestroy(bst);
   return rc_recode;
 }
 
@@ -864,10 +887,102 @@ int ss_bm25_append_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_do
   }, SS_ENOMEM, SS_EDEVICE);
 }
 
+// ... with the levels in HBM and the image rebuilt ON THE DEVICE (ssi_bm25_rebuild_from_raw_fields), positions included: the shape of
+// append_level_impl.  The host makes one pass over the level's own entries (mf_level.h), the level goes up on a stream of the commit's
+// own, the image is built beside the serving one from the block pool and swapped in under ONE lock section together with the level
+// list.  Whatever fails before the swap frees what this call allocated; the shard answers as before.
+static_assert(MF_OK == SS_OK && MF_EINVAL == SS_EINVAL && MF_ENOTSUP == SS_ENOTSUP && MF_POS_FIELD_SHIFT == BM_POS_FIELD_SHIFT, "mf_level.h");
+static int commit_level_fields_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost,
+                                    uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields, const uint16_t* tfs,
+                                    const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
+  if (!s || !level_doclen || !offs || n_terms == 0 || n_level_docs == 0 || n_level_docs > 65536u || n_fields < 2 || n_fields > 8) return SS_EINVAL;
+  if (offs[n_terms] && (!docs || !fields || !tfs)) return SS_EINVAL;
+  if (n_positions && !positions) return SS_EINVAL;
+  const bool with_pos = positions != nullptr;
+  const auto t_begin = std::chrono::steady_clock::now();
+  ss_mf_levels* const M = ssi_mf_levels(s, true);
+  std::lock_guard<std::mutex> commits(M->commit_mu);  // commits of one shard: one after the other
+  SS_HIP(hipSetDevice(s->device));
+  std::vector<float> b(n_fields, 1.0f);
+  if (boost) b.assign(boost, boost + n_fields);
+  std::vector<ss_raw_level_mf> levels;
+  {
+    ShardLock g(s);
+    if (s->sp_n) return SS_ENOTSUP;  // (the sparse tier beside a committed multi-field image: not built)
+    if ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()) return SS_ESTATE;  // an image that was not built this way
+    if (!M->raw.empty() && M->raw[0].n_fields != n_fields) return SS_EINVAL;
+    SS_TRY(level_rules(level, n_level_docs, M->raw));
+    if (level > 0 && n_terms < M->raw[level - 1].n_terms) return SS_EINVAL;                    // the vocabulary only grows
+    if (level > 0 && (M->raw[0].d_tpos != nullptr) != with_pos) return SS_EINVAL;             // positions for every level of an image, or for none
+    if (level > 0 && memcmp(M->boost.data(), b.data(), n_fields * sizeof(float)) != 0) return SS_EINVAL;  // ... and the same boosts
+    levels.assign(M->raw.begin(), M->raw.begin() + level);
+  }
+  mf_level_host H;
+  SS_TRY(mf_level_prepare(level, n_level_docs, n_fields, n_terms, offs, docs, fields, tfs, npos, positions, n_positions, &H));
+  ss_raw_level_mf L;
+  for (uint64_t d = 0; d < (uint64_t)n_fields * n_level_docs; d++) L.psum += ss_byte4_to_int(level_doclen[d]);
+  hipStream_t bst = nullptr;
+  std::unique_ptr<ss_shard> img(new ss_shard);
+  auto undo = [&]() {
+    raw_level_mf_free(L);
+    bm_image_arrays(img.get(), [&](auto*& p) { if (p && !s->blocks.release(p)) (void)hipFree(p); });
+  };
+  CommitUndo<decltype(undo)> own{undo, bst};
+  if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
+  if (const int rc_up = raw_level_mf_upload(L, H, level_doclen, bst)) return rc_up;
+  levels.push_back(L);  // (a copy of the handles: `L` stays the owner until the swap)
+  const auto t_build = std::chrono::steady_clock::now();
+  const int rc = ssi_bm25_rebuild_from_raw_fields(s, levels, n_fields, b.data(), img.get(), bst);
+  if (rc) return rc;
+  const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+  {  // the swap: searches in flight finish on the old image, whose arrays are then released
+    ShardLock g(s);
+    if (level > M->raw.size() || level + 1 < M->raw.size() || s->sp_n || ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()))
+      return SS_ESTATE;  // an upload got in between
+    (void)hipStreamSynchronize(s->stream);
+    for (auto& kv : s->bm_ws) (void)hipStreamSynchronize(kv.first);
+    ss_raw_level_mf replaced;
+    const bool replace = level < M->raw.size();
+    if (replace) replaced = M->raw[level];
+    std::vector<ss_raw_level_mf> keep;
+    keep.reserve((size_t)level + 1);
+    keep.assign(M->raw.begin(), M->raw.begin() + level);
+    keep.push_back(L);
+    M->boost = b;
+    own.taken = true;  // from here on the level and the image are the shard's
+    M->raw.clear();  // (free_bm25 must not release the levels that stay)
+    {  // the old image's arrays go back to the block pool: the next commit builds into them
+      s->blocks.gen++;
+      bm_image_arrays(s, [&](auto*& p) { if (p && s->blocks.release(p)) p = nullptr; });
+      std::vector<ss_block_pool::Idle> idle;
+      idle.swap(s->blocks.idle);   // (free_bm25 clears the idle list: these stay)
+      free_bm25(s);
+      s->blocks.idle.swap(idle);
+      s->blocks.trim(3);
+    }
+    if (replace) raw_level_mf_free(replaced);
+    M->raw.swap(keep);
+    bm_image_take_fields(s, img.get());
+    s->raw_last_rebuild_ms = rebuild_ms;
+    s->raw_last_append_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+  return SS_OK;
+}
+int ss_bm25_commit_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost,
+                                uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields, const uint16_t* tfs,
+                                const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
+  return ss_guard([&] { return commit_level_fields_impl(s, level, n_level_docs, n_fields, level_doclen, boost, n_terms, offs, docs, fields, tfs, npos,
+                                                        positions, n_positions); }, SS_ENOMEM, SS_EDEVICE);
+}
+
 int ss_bm25_incremental_info(ss_shard* s, uint32_t* n_levels, uint64_t* raw_bytes, double* last_append_ms, double* last_rebuild_ms) {
   if (!s) return SS_EINVAL;
   ShardLock g(s);
   uint64_t b = 0;
+  if (const ss_mf_levels* M = ssi_mf_levels(s, false)) {
+    for (const ss_raw_level_mf& L : M->raw) b += raw_level_mf_bytes(L);
+    if (n_levels && !M->raw.empty()) { *n_levels = (uint32_t)M->raw.size(); n_levels = nullptr; }
+  }
   for (const ss_raw_level_f& L : s->raw_f) b += L.off.size() * 8u + L.doc.size() * 7u + L.doclen.size();
   if (n_levels && !s->raw_f.empty()) { *n_levels = (uint32_t)s->raw_f.size(); n_levels = nullptr; }
   for (const ss_raw_level& L : s->raw)

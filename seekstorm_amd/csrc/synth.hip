@@ -4,6 +4,7 @@
 #include "ss_common.h"
 #include "ss_threads.h"
 #include "bm25_build.h"
+#include "bm25_image.h"
 #include "sparse_levels.h"
 
 #include <chrono>
@@ -701,6 +702,372 @@ int ssi_bm25_rebuild_from_raw(const ss_shard* s, const std::vector<ss_raw_level>
   if (trace)
     fprintf(stderr, "[append] docs %llu postings %llu: setup+copies %.2f ms, count+scan %.2f, alloc post+probe %.2f, fill %.2f, maxima rule %.2f\n",
             (unsigned long long)nd, (unsigned long long)npost, ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, now()));
+#undef SS_HIP_C
+  cleanup();
+  return SS_OK;
+}
+
+// ---------------------------------------------------------------- ... of SEVERAL indexed fields (ss_bm25_commit_level_fields)
+// What ssi_bm25_upload_fields + ssi_bm25_build_from_host_merged + ssi_bm25_upload_positions_fields do on the host, over the levels kept in
+// HBM (ss_raw_level_mf).  Virtual term v = t * L + f, L = fields + merged: list f < fields reads the level's (term, field) CSR, the
+// merged list the term CSR.  Every global index derives from (v, sub-block) and the CSR bounds of the sub-block's level.
+struct MfLevelDev {
+  const unsigned long long* foff; const uint32_t* fdoc; const uint16_t* ftf;
+  const unsigned long long* moff; const uint32_t* mdoc; const uint16_t* mtf;
+  const uint32_t* pos; const uint32_t* mnpos; const uint32_t* mprel; const unsigned long long* tpos;  // positions (or null)
+  uint32_t n_terms, pad;
+};
+constexpr uint32_t MF_LEVEL_SHIFT = 16u - (uint32_t)BM_SUB_LOG2;  // a level = 65 536 docs = 16 sub-blocks
+// the postings of list f of term t inside sub-block sb: [lo, hi) of Lv.fdoc (f < RF) or Lv.mdoc (the merged list)
+__device__ __forceinline__ void mf_segment(const MfLevelDev& Lv, uint32_t RF, uint32_t t, uint32_t f, uint32_t sb, u64* lo_out, u64* hi_out) {
+  if (t >= Lv.n_terms) { *lo_out = 0; *hi_out = 0; return; }
+  const bool mg = f >= RF;
+  const uint32_t* __restrict__ doc = mg ? Lv.mdoc : Lv.fdoc;
+  const u64 a = mg ? Lv.moff[t] : Lv.foff[(u64)t * RF + f], b = mg ? Lv.moff[t + 1] : Lv.foff[(u64)t * RF + f + 1];
+  const uint32_t d0 = sb << BM_SUB_LOG2, d1 = d0 + (uint32_t)BM_SUB;
+  u64 lo = a, hi = b;
+  while (lo < hi) { const u64 m = (lo + hi) >> 1; if (doc[m] < d0) lo = m + 1; else hi = m; }
+  const u64 first = lo;
+  hi = b;
+  while (lo < hi) { const u64 m = (lo + hi) >> 1; if (doc[m] < d1) lo = m + 1; else hi = m; }
+  *lo_out = first; *hi_out = lo;
+}
+// one thread per (v, sub-block): the segment's size in 16-byte units (shifted by one for the exclusive scan) and the list's df
+__global__ void mf_count_kernel(const MfLevelDev* __restrict__ levels, uint32_t RF, uint32_t L, uint32_t nv, uint32_t n_sub,
+                                uint32_t* __restrict__ sub, u64* __restrict__ df) {
+  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (u64)nv * n_sub) return;
+  const uint32_t v = (uint32_t)(i / n_sub), sb = (uint32_t)(i % n_sub);
+  u64 lo, hi;
+  mf_segment(levels[sb >> MF_LEVEL_SHIFT], RF, v / L, v % L, sb, &lo, &hi);
+  const uint32_t n = (uint32_t)(hi - lo);
+  sub[(size_t)v * (n_sub + 1) + sb + 1] = (n + 3u) >> 2;
+  if (n) atomicAdd(&df[v], (u64)n);
+}
+// the merged weight of an entry, as the host builder forms it: sum_f boost_f * (tf (K + 1) / (tf + comp[len_f])) over the fields that
+// hold the doc, fields ascending, every step rounded to f32; *lt10: the tf of the lowest such field < 10
+__device__ __forceinline__ float mf_merged_weight(const uint16_t* __restrict__ tf_e, uint32_t RF, const uint8_t* __restrict__ doclen, u64 n_docs,
+                                                  uint32_t d, const float* __restrict__ comp, const float* __restrict__ boost, float k1, uint32_t* lt10) {
+  float w = 0.f;
+  bool any = false;
+  *lt10 = 0u;
+  for (uint32_t f = 0; f < RF; f++) {
+    const uint32_t tf = tf_e[f];
+    if (!tf) continue;
+    const float tt = (float)tf;
+    const float part = ss_fmul(boost[f], __fdiv_rn(ss_fmul(tt, k1), ss_fadd(tt, comp[doclen[(u64)f * n_docs + d]])));
+    w = any ? ss_fadd(w, part) : part;
+    if (!any) *lt10 = tf < 10u ? 1u : 0u;
+    any = true;
+  }
+  return w;
+}
+// one wave per (term, sub-block) over the merged entries: the largest and the smallest merged weight of the image (positive floats
+// order like their bit patterns) -> range[0] / range[1]; the host picks the merged lists' scale from them
+__global__ void mf_range_kernel(const MfLevelDev* __restrict__ levels, uint32_t RF, uint32_t n_terms, uint32_t n_sub, const uint8_t* __restrict__ doclen,
+                                u64 n_docs, const float* __restrict__ comp, const float* __restrict__ boost, float k1, uint32_t* __restrict__ range) {
+  const int lane = threadIdx.x & 63;
+  const u64 gw = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (gw >= (u64)n_terms * n_sub) return;
+  const uint32_t t = (uint32_t)(gw / n_sub), sb = (uint32_t)(gw % n_sub);
+  const MfLevelDev Lv = levels[sb >> MF_LEVEL_SHIFT];
+  u64 lo, hi;
+  mf_segment(Lv, RF, t, RF, sb, &lo, &hi);
+  if (lo == hi) return;
+  uint32_t mx = 0u, mn = 0xFFFFFFFFu;
+  for (u64 i = lo + (u64)lane; i < hi; i += 64u) {
+    uint32_t lt10;
+    const uint32_t b = __float_as_uint(mf_merged_weight(Lv.mtf + i * RF, RF, doclen, n_docs, Lv.mdoc[i], comp, boost, k1, &lt10));
+    mx = max(mx, b); mn = min(mn, b);
+  }
+  for (int o = 32; o > 0; o >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, o)); mn = min(mn, (uint32_t)__shfl_xor((int)mn, o)); }
+  if (lane == 0) { atomicMax(&range[0], mx); atomicMin(&range[1], mn); }
+}
+// one wave per (v, sub-block), as raw_fill_kernel: packed postings + NULL padding, the probe row's bit records and ranks, the segment's
+// and the list's largest weight, the count of weights the code cannot hold.  A field list codes tf and the length byte of ITS plane of
+// doclen [fields][n_docs]; a merged list codes weight / mscale, and where flagged[v] carries "tf of the lowest field < 10" in bit 0.
+__global__ void mf_fill_kernel(const MfLevelDev* __restrict__ levels, uint32_t RF, uint32_t L, uint32_t nv, uint32_t n_sub,
+                               const uint8_t* __restrict__ doclen, u64 n_docs, const float* __restrict__ comp, const float* __restrict__ boost, float k1,
+                               float mscale, const uint32_t* __restrict__ sub, const u64* __restrict__ term_base, uint32_t* __restrict__ post,
+                               uint2* __restrict__ probe, uint32_t* __restrict__ probe_z, const uint32_t* __restrict__ probe_row,
+                               uint32_t* __restrict__ umax_bits, float* __restrict__ submax, const uint8_t* __restrict__ flagged,
+                               uint32_t* __restrict__ n_uncodable) {
+  __shared__ unsigned long long masks[4][BM_SUB / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const u64 gw = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (gw >= (u64)nv * n_sub) return;
+  const uint32_t v = (uint32_t)(gw / n_sub), sb = (uint32_t)(gw % n_sub);
+  const uint32_t t = v / L, f = v % L;
+  const bool mg = f >= RF;
+  const MfLevelDev Lv = levels[sb >> MF_LEVEL_SHIFT];
+  u64 lo, hi;
+  mf_segment(Lv, RF, t, f, sb, &lo, &hi);
+  const uint32_t seg0 = sub[(size_t)v * (n_sub + 1) + sb] * 4u;
+  const u64 base = term_base[v] * 4ull + seg0;
+  const bool flg = flagged[v] != 0;
+  const bool have_row = probe && probe_row[v] != BM_NO_PROBE_ROW;
+  masks[w][lane] = 0ull;
+  __builtin_amdgcn_wave_barrier();
+  const uint8_t* __restrict__ dl = doclen + (u64)(mg ? 0u : f) * n_docs;
+  float wmax = 0.f;
+  uint32_t n_bad = 0;
+  for (u64 i = lo + (u64)lane; i < hi; i += 64u) {
+    uint32_t d, code;
+    float wgt;
+    if (mg) {
+      d = Lv.mdoc[i];
+      uint32_t lt10;
+      wgt = __fdiv_rn(mf_merged_weight(Lv.mtf + i * RF, RF, doclen, n_docs, d, comp, boost, k1, &lt10), mscale);
+      code = bm_wcode(wgt);
+      if (flg) code = (code & ~1u) | lt10;
+    } else {
+      d = Lv.fdoc[i];
+      const float tt = (float)Lv.ftf[i];
+      wgt = __fdiv_rn(ss_fmul(tt, k1), ss_fadd(tt, comp[dl[d]]));  // bm_weight_exact
+      code = bm_wcode(wgt);
+    }
+    n_bad += bm_w_codable(wgt) ? 0u : 1u;
+    const uint32_t din = d & (uint32_t)(BM_SUB - 1);
+    post[base + (i - lo)] = bm_pack(din, code);
+    wmax = fmaxf(wmax, bm_wdecode(code));
+    if (have_row) atomicOr(&masks[w][din >> 6], 1ull << (din & 63u));
+  }
+  const uint32_t n = (uint32_t)(hi - lo);
+  if ((uint32_t)lane < ((4u - (n & 3u)) & 3u)) post[base + n + lane] = 0u;  // NULL padding
+  for (int o = 32; o > 0; o >>= 1) wmax = fmaxf(wmax, __shfl_xor(wmax, o));
+  if (__any(n_bad != 0u)) {
+    for (int o = 32; o > 0; o >>= 1) n_bad += __shfl_xor(n_bad, o);
+    if (lane == 0) atomicAdd(n_uncodable, n_bad);
+  }
+  if (lane == 0) {
+    submax[(size_t)v * n_sub + sb] = wmax;
+    if (wmax > 0.f) atomicMax(&umax_bits[v], __float_as_uint(wmax));
+  }
+  if (have_row) {
+    __builtin_amdgcn_wave_barrier();
+    const unsigned long long m = masks[w][lane];
+    uint32_t run = (uint32_t)__popcll(m);
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(run, o); if (lane >= o) run += x; }
+    run -= (uint32_t)__popcll(m);
+    const size_t gi = ((size_t)probe_row[v] * n_sub + sb) * (BM_SUB / 64) + (uint32_t)lane;
+    probe[gi] = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+    probe_z[gi] = seg0 + run;
+  }
+}
+// ---- positions: the u32 forms of raw_pos_total / copy / off over the MERGED lists.  d_pos32 = every term's tagged positions, level after
+// level; d_pos_off = per slot of the merged list the running end; d_pos_base of all L lists of a term = the term's start.
+__global__ void mf_pos_total_kernel(const MfLevelDev* __restrict__ levels, uint32_t n_levels, uint32_t n_terms, u64* __restrict__ tot,
+                                    u64* __restrict__ lstart) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_terms) return;
+  u64 c = 0;
+  for (uint32_t l = 0; l < n_levels; l++) {
+    lstart[(size_t)t * n_levels + l] = c;
+    if (t < levels[l].n_terms) c += levels[l].tpos[t + 1] - levels[l].tpos[t];
+  }
+  tot[t] = c;
+}
+__global__ void mf_pos_base_kernel(const u64* __restrict__ tstart, uint32_t L, uint32_t nv, u64* __restrict__ pos_base) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v > nv) return;
+  pos_base[v] = tstart[v / L];  // (v = nv: the terms' total)
+}
+__global__ void mf_pos_copy_kernel(const MfLevelDev* __restrict__ levels, uint32_t n_levels, uint32_t n_terms, const u64* __restrict__ tstart,
+                                   const u64* __restrict__ lstart, uint32_t* __restrict__ pos) {
+  const uint32_t t = blockIdx.x, l = blockIdx.y;
+  if (t >= n_terms || l >= n_levels || t >= levels[l].n_terms) return;
+  const u64 a = levels[l].tpos[t], b = levels[l].tpos[t + 1];
+  if (a == b) return;
+  const u64 at = tstart[t] + lstart[(size_t)t * n_levels + l];
+  const uint32_t* __restrict__ src = levels[l].pos + a;
+  for (u64 i = threadIdx.x; i < b - a; i += blockDim.x) pos[at + i] = src[i];
+}
+__global__ void mf_pos_off_kernel(const MfLevelDev* __restrict__ levels, uint32_t n_levels, uint32_t RF, uint32_t L, uint32_t n_terms, uint32_t n_sub,
+                                  const uint32_t* __restrict__ sub, const u64* __restrict__ term_base, const u64* __restrict__ lstart,
+                                  uint32_t* __restrict__ pos_off) {
+  const int lane = threadIdx.x & 63;
+  const u64 gw = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (gw >= (u64)n_terms * n_sub) return;
+  const uint32_t t = (uint32_t)(gw / n_sub), sb = (uint32_t)(gw % n_sub), v = t * L + RF;
+  const uint32_t li = sb >> MF_LEVEL_SHIFT;
+  const MfLevelDev Lv = levels[li];
+  u64 lo, hi;
+  mf_segment(Lv, RF, t, RF, sb, &lo, &hi);
+  u64 start = lstart[(size_t)t * n_levels + li];  // positions of the term before this segment: earlier levels' + earlier entries of this one
+  const uint32_t seg0 = sub[(size_t)v * (n_sub + 1) + sb] * 4u, seg1 = sub[(size_t)v * (n_sub + 1) + sb + 1] * 4u;
+  const u64 base = term_base[v] * 4ull + seg0;
+  const uint32_t n = (uint32_t)(hi - lo);
+  if (n) start += Lv.mprel[lo];  // (an empty segment stores nothing: seg1 == seg0)
+  u64 run = start;
+  for (uint32_t i0 = 0; i0 < n; i0 += 64u) {
+    const uint32_t i = i0 + (uint32_t)lane;
+    uint32_t inc = i < n ? Lv.mnpos[lo + i] : 0u;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(inc, o); if (lane >= o) inc += x; }
+    if (i < n) pos_off[base + i] = (uint32_t)(run + inc);
+    run += (u64)__shfl(inc, 63);
+  }
+  const uint32_t pad = seg1 - seg0 - n;  // NULL padding slots of the segment (0 .. 3)
+  if ((uint32_t)lane < pad) pos_off[base + n + lane] = (uint32_t)run;
+}
+
+int ssi_bm25_rebuild_from_raw_fields(const ss_shard* s, const std::vector<ss_raw_level_mf>& levels, uint32_t n_fields, const float* boost, ss_shard* img,
+                                     hipStream_t st) {
+  const uint32_t RF = n_fields, nl = (uint32_t)levels.size();
+  if (nl == 0 || RF < 2 || RF > 8) return SS_EINVAL;
+  u64 nd = 0, psum = 0, nent = 0, n_positions = 0;
+  uint32_t nt = 0;
+  const bool with_pos = levels[0].d_tpos != nullptr;
+  for (const ss_raw_level_mf& Lv : levels) {
+    if (Lv.n_fields != RF || (Lv.d_tpos != nullptr) != with_pos) return SS_EINVAL;  // positions for every level or for none
+    nd += Lv.n_docs; psum += Lv.psum; nent += Lv.n_ent; n_positions += Lv.n_pos; nt = std::max(nt, Lv.n_terms);
+  }
+  if (nd == 0 || nt == 0) return SS_EINVAL;
+  const uint32_t ns = (uint32_t)((nd + BM_SUB - 1) >> BM_SUB_LOG2);
+  std::vector<float> b(RF, 1.0f);
+  if (boost) b.assign(boost, boost + RF);
+  bool merged = true;  // (ssi_bm25_upload_fields' rule)
+  for (float x : b) merged = merged && x > 0.f && x < 1e30f;
+  img->device = s->device;
+  img->probe_budget = s->probe_budget;
+  img->pool = const_cast<ss_block_pool*>(&s->blocks);  // (the caller serialises commits: nobody else touches the pool meanwhile)
+  img->bm_n_docs = nd; img->bm_n_sub = ns; img->bm_n_post = nent;
+  img->bm_avgdl = (float)psum / (float)nd;  // commit.rs:318-319, all fields (index.rs:5848)
+  std::vector<MfLevelDev> lv(nl);
+  for (uint32_t i = 0; i < nl; i++) {
+    const ss_raw_level_mf& Lv = levels[i];
+    lv[i] = MfLevelDev{(const unsigned long long*)Lv.d_foff, Lv.d_fdoc, Lv.d_ftf, (const unsigned long long*)Lv.d_moff, Lv.d_mdoc, Lv.d_mtf,
+                       Lv.d_pos, Lv.d_mnpos, Lv.d_mprel, (const unsigned long long*)Lv.d_tpos, Lv.n_terms, 0u};
+  }
+  MfLevelDev* d_lv = nullptr;
+  u64 *d_tot = nullptr, *d_df = nullptr, *d_ptot = nullptr, *d_lstart = nullptr, *d_tstart = nullptr;
+  uint8_t* d_flg = nullptr;
+  uint32_t *d_bad = nullptr, *d_range = nullptr;
+  float* d_b = nullptr;
+  auto cleanup = [&]() {
+    for (void* p : {(void*)d_lv, (void*)d_tot, (void*)d_df, (void*)d_ptot, (void*)d_lstart, (void*)d_tstart, (void*)d_flg, (void*)d_bad, (void*)d_range, (void*)d_b})
+      if (p) (void)hipFree(p);
+  };
+#define SS_HIP_C(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { cleanup(); return e_ == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE; } } while (0)
+  SS_HIP_C(hipMalloc(&d_lv, lv.size() * sizeof(MfLevelDev)));
+  SS_HIP_C(hipMemcpyAsync(d_lv, lv.data(), lv.size() * sizeof(MfLevelDev), hipMemcpyHostToDevice, st));
+  SS_HIP_C(img_malloc(img, &img->d_doclen, (size_t)RF * nd));
+  for (uint32_t f = 0; f < RF; f++) {  // [fields][n_docs] from the levels' own planes
+    u64 at = 0;
+    for (const ss_raw_level_mf& Lv : levels) {
+      SS_HIP_C(hipMemcpyAsync(img->d_doclen + (size_t)f * nd + at, Lv.d_doclen + (size_t)f * Lv.n_docs, Lv.n_docs, hipMemcpyDeviceToDevice, st));
+      at += Lv.n_docs;
+    }
+  }
+  SS_HIP_C(img_malloc(img, &img->d_comp, SS_COMP_N * sizeof(float)));
+  float comp[SS_COMP_N];
+  fill_comp(img->bm_avgdl, comp);
+  SS_HIP_C(hipMemcpyAsync(img->d_comp, comp, sizeof(comp), hipMemcpyHostToDevice, st));
+  SS_HIP_C(hipMalloc(&d_b, RF * sizeof(float)));
+  SS_HIP_C(hipMemcpyAsync(d_b, b.data(), RF * sizeof(float), hipMemcpyHostToDevice, st));
+  const volatile float k1 = 1.2f + 1.0f;  // (K + 1) as bm_weight_exact forms it
+  const u64 tpairs = (u64)nt * ns;
+  if (tpairs + 3 > 0xFFFFFFFFull * 4ull) { cleanup(); return SS_ENOTSUP; }
+  float mscale = 1.0f;
+  if (merged) {  // the merged weights' span decides whether the image gets merged lists, and their scale (ssi_bm25_build_from_host_merged)
+    const uint32_t init[2] = {0u, 0xFFFFFFFFu};
+    SS_HIP_C(hipMalloc(&d_range, sizeof(init)));
+    SS_HIP_C(hipMemcpyAsync(d_range, init, sizeof(init), hipMemcpyHostToDevice, st));
+    mf_range_kernel<<<(uint32_t)((tpairs + 3) / 4), 256, 0, st>>>(d_lv, RF, nt, ns, img->d_doclen, nd, img->d_comp, d_b, k1, d_range);
+    SS_HIP_C(hipGetLastError());
+    uint32_t r[2];
+    SS_HIP_C(hipMemcpyAsync(r, d_range, sizeof(r), hipMemcpyDeviceToHost, st));
+    SS_HIP_C(hipStreamSynchronize(st));
+    if (r[1] != 0xFFFFFFFFu) {  // (an image without a single entry keeps the scale 1)
+      const float wmax = bm_u2f(r[0]), wmin = bm_u2f(r[1]);
+      int e = 0;
+      (void)std::frexp(wmax / 3.99f, &e);
+      mscale = std::ldexp(1.0f, e);
+      if (wmin / mscale < 6.2e-5f) { merged = false; mscale = 1.0f; }  // SS_MERGED_RANGE: this image gets no merged lists
+    }
+  }
+  if (!merged && with_pos) { cleanup(); return SS_ENOTSUP; }  // (ssi_bm25_upload_positions_fields: no phrase path without merged lists)
+  const uint32_t L = RF + (merged ? 1u : 0u);
+  if ((u64)nt * L > 0x7FFFFFFFull) { cleanup(); return SS_ENOTSUP; }
+  const uint32_t nv = nt * L;
+  const u64 pairs = (u64)nv * ns;
+  if (pairs + 3 > 0xFFFFFFFFull * 4ull) { cleanup(); return SS_ENOTSUP; }
+  img->bm_n_terms = nv; img->bm_n_fields = L; img->bm_merged = merged;
+  SS_HIP_C(hipMalloc(&d_tot, (size_t)nv * sizeof(u64)));
+  SS_HIP_C(hipMalloc(&d_df, (size_t)nv * sizeof(u64)));
+  SS_HIP_C(hipMemsetAsync(d_df, 0, (size_t)nv * sizeof(u64), st));
+  const size_t rows = (size_t)nv * (ns + 1);
+  SS_HIP_C(img_malloc(img, &img->d_sub_off, (rows + ns + 1) * sizeof(uint32_t)));  // + one all-zero row (absent terms)
+  SS_HIP_C(hipMemsetAsync(img->d_sub_off + rows, 0, ((size_t)ns + 1) * sizeof(uint32_t), st));
+  SS_HIP_C(img_malloc(img, &img->d_term_base, ((size_t)nv + 1) * sizeof(u64)));
+  mf_count_kernel<<<(uint32_t)((pairs + 255) / 256), 256, 0, st>>>(d_lv, RF, L, nv, ns, img->d_sub_off, d_df);
+  lex_scan_rows_kernel<<<nv, 1024, 0, st>>>(img->d_sub_off, ns, d_tot);
+  lex_scan_terms_kernel<<<1, 64, 0, st>>>(d_tot, (u64*)img->d_term_base, nv);
+  SS_HIP_C(hipGetLastError());
+  SS_HIP_C(hipStreamSynchronize(st));
+  std::vector<u64> tot(nv);
+  img->h_df.resize(nv);
+  SS_HIP_C(hipMemcpy(tot.data(), d_tot, (size_t)nv * sizeof(u64), hipMemcpyDeviceToHost));
+  SS_HIP_C(hipMemcpy(img->h_df.data(), d_df, (size_t)nv * sizeof(u64), hipMemcpyDeviceToHost));
+  u64 units = 0;
+  for (uint32_t v = 0; v < nv; v++) {
+    if (tot[v] >= (1ull << 28)) { cleanup(); return SS_ENOTSUP; }  // a term's segment offsets must stay below 4 GB
+    units += tot[v];
+  }
+  int rc = alloc_post(img, units);
+  if (rc) { cleanup(); return rc; }
+  rc = alloc_probe(img, st);
+  if (rc) { cleanup(); return rc; }
+  std::vector<uint8_t> flg(nv, 0);
+  if (merged)
+    for (uint32_t v = L - 1; v < nv; v += L) flg[v] = bm_merged_list_flagged(img, img->h_df[v]) ? 1 : 0;
+  SS_HIP_C(hipMalloc(&d_flg, nv));
+  SS_HIP_C(hipMemcpyAsync(d_flg, flg.data(), nv, hipMemcpyHostToDevice, st));
+  SS_HIP_C(hipMalloc(&d_bad, sizeof(uint32_t)));
+  SS_HIP_C(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), st));
+  mf_fill_kernel<<<(uint32_t)((pairs + 3) / 4), 256, 0, st>>>(d_lv, RF, L, nv, ns, img->d_doclen, nd, img->d_comp, d_b, k1, mscale, img->d_sub_off,
+                                                             (const u64*)img->d_term_base, img->d_post, img->d_probe, img->d_probe_z, img->d_probe_row,
+                                                             (uint32_t*)img->d_umax, img->d_submax, d_flg, d_bad);
+  SS_HIP_C(hipGetLastError());
+  if (with_pos) {
+    SS_HIP_C(hipMalloc(&d_ptot, (size_t)nt * sizeof(u64)));
+    SS_HIP_C(hipMalloc(&d_lstart, (size_t)nt * nl * sizeof(u64)));
+    SS_HIP_C(hipMalloc(&d_tstart, ((size_t)nt + 1) * sizeof(u64)));
+    SS_HIP_C(img_malloc(img, &img->d_pos_base, ((size_t)nv + 1) * sizeof(u64)));
+    SS_HIP_C(img_malloc(img, &img->d_pos32, (size_t)std::max<u64>(n_positions, 1) * sizeof(uint32_t)));
+    SS_HIP_C(img_malloc(img, &img->d_pos_off, ((size_t)img->bm_n_post_pad + 8) * sizeof(uint32_t)));
+    SS_HIP_C(hipMemsetAsync(img->d_pos_off, 0, ((size_t)img->bm_n_post_pad + 8) * sizeof(uint32_t), st));  // (the field lists' slots: phrases read the merged lists)
+    mf_pos_total_kernel<<<(nt + 255) / 256, 256, 0, st>>>(d_lv, nl, nt, d_ptot, d_lstart);
+    lex_scan_terms_kernel<<<1, 64, 0, st>>>(d_ptot, d_tstart, nt);
+    mf_pos_base_kernel<<<nv / 256 + 1, 256, 0, st>>>(d_tstart, L, nv, (u64*)img->d_pos_base);
+    mf_pos_copy_kernel<<<dim3(nt, nl), 256, 0, st>>>(d_lv, nl, nt, d_tstart, d_lstart, img->d_pos32);
+    mf_pos_off_kernel<<<(uint32_t)((tpairs + 3) / 4), 256, 0, st>>>(d_lv, nl, RF, L, nt, ns, img->d_sub_off, (const u64*)img->d_term_base, d_lstart,
+                                                                   img->d_pos_off);
+    SS_HIP_C(hipGetLastError());
+  }
+  SS_HIP_C(hipStreamSynchronize(st));
+  uint32_t n_bad = 0;
+  SS_HIP_C(hipMemcpy(&n_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (n_bad) { cleanup(); return SS_ENOTSUP; }  // weights the code cannot hold: never clamped
+  if (with_pos) {  // d_pos_off counts from the term's start in 32 bits, over ALL levels (ssi_bm25_upload_positions_fields refuses the same)
+    std::vector<u64> ptot(nt);
+    SS_HIP_C(hipMemcpy(ptot.data(), d_ptot, (size_t)nt * sizeof(u64), hipMemcpyDeviceToHost));
+    for (uint32_t t = 0; t < nt; t++)
+      if (ptot[t] >= (1ull << 32)) { cleanup(); return SS_ENOTSUP; }
+  }
+  if (!merged) {  // the length bytes stay with images that have merged lists only, as in the one-shot builder
+    if (!img->pool || !img->pool->release(img->d_doclen)) (void)hipFree(img->d_doclen);
+    img->d_doclen = nullptr;
+  }
+  rc = bm_decide_partmax_dev(img);
+  if (rc) { cleanup(); return rc; }
+  std::vector<float> bb = b;
+  if (merged) bb.push_back(mscale);  // the merged list's "boost" gives the scale back through idf
+  SS_HIP_C(img_malloc(img, &img->d_boost, bb.size() * sizeof(float)));
+  SS_HIP_C(hipMemcpy(img->d_boost, bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice));
+  img->h_boost = bb;
+  img->h_df_real.assign(nt, 0);
+  for (const ss_raw_level_mf& Lv : levels)
+    for (uint32_t t = 0; t < Lv.n_terms; t++) img->h_df_real[t] += Lv.h_mdf[t];
 #undef SS_HIP_C
   cleanup();
   return SS_OK;
