@@ -379,7 +379,7 @@ int ss_bm25_append_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_do
  * swapped in under one lock together with the level list: a refused or failed commit leaves image and levels as they were, and commits
  * of one shard are serialised.  Refusals, before anything is touched: SS_ESTATE on an image built another way (a whole-image upload,
  * ss_bm25_append_level, ss_bm25_append_level_fields -- which in turn answers SS_ESTATE on levels committed here); SS_ENOTSUP beside a
- * sparse tier, for a posting weight the code cannot hold (the WEIGHT RANGE above), for a term with 2^32 positions or more over all
+ * sparse tier of whole lists (one of levels: ss_bm25_commit_sparse_level_fields below), for a posting weight the code cannot hold (the WEIGHT RANGE above), for a term with 2^32 positions or more over all
  * levels, and for positions on a corpus whose boosts keep the merged lists from being built (such a corpus commits without positions,
  * as ss_bm25_upload_fields uploads it). */
 int ss_bm25_commit_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen /* [n_fields][n_level_docs] */,
@@ -404,6 +404,31 @@ int ss_bm25_append_level_positions(ss_shard* s, uint32_t level, uint32_t n_level
  * (ss_bm25_append_sparse) takes no levels, and this one no whole lists (SS_ESTATE).  SS_EINVAL leaves the tier as it was. */
 int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs /*[n_lists+1]*/, const uint32_t* doc_ids,
                                 const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions);
+/* ... on an image of SEVERAL INDEXED FIELDS whose levels came through ss_bm25_commit_level_fields: after the dense commit of `level`
+ * (the level the dense image committed last), the entries (doc, field, tf) of the RARE terms in that level, sorted by (doc, field)
+ * inside a list, doc ids inside the level, tf >= 1, field < n_fields.  List i continues sparse list i (term id = dense terms + i);
+ * n_lists >= the tier's current lists -- the further ones are new terms.  Positions come per entry, ascending inside an entry, tf of
+ * them each or npos[e]; every level of the tier brings positions exactly when the image's levels carry them.  The first call creates
+ * the tier; a level the tier has seen already is REPLACED (the re-commit of a partial level: first ss_bm25_commit_level_fields with
+ * the same level, then this); levels without rare postings may be skipped.  The tier keeps ONE merged posting per (term, doc), as
+ * ss_bm25_append_sparse_fields does -- weight = the sum over the doc's fields of boost_f * tf_f (K+1) / (tf_f + comp[len_f]) over the
+ * merged lists' scale, the fields' mask beside the code --, and beside it the tf of every field (2 * n_fields bytes, 0 = absent):
+ * all its postings are re-coded on the device after every commit, as avgdl and the merged scale move.  Positions are kept
+ * field-tagged in 32 bits, so phrases and field filters may name the tier's terms.  Beside such a tier ss_bm25_commit_level_fields
+ * keeps n_terms at the dense count (new terms start rare) and never shrinks a re-committed level (SS_ENOTSUP otherwise), checks the
+ * tier's postings under the new image before the swap (SS_ENOTSUP: a weight the code cannot hold, or an image that comes out without
+ * merged lists; image, levels and tier stay) and re-codes the tier after it; a failed re-code after the swap is returned.
+ * Returns: SS_EINVAL -- a null shard / offsets / array, n_lists 0 or below the tier's count, `level` not the last committed level or
+ * older than the tier's last, offsets descending, a doc outside the level, tf 0, field >= n_fields, entries not ascending by
+ * (doc, field), docs not behind the list's last, positions not ascending inside an entry, the counts' sum != n_positions, positions
+ * on an image without or none on an image with; SS_ESTATE -- no image, an image built another way (a whole-image upload,
+ * ss_bm25_append_level[_fields]), a tier of whole lists (ss_bm25_append_sparse_fields; that entry in turn answers SS_ESTATE on a
+ * tier of levels); SS_ENOTSUP -- an image without merged lists (boosts too far apart), a weight outside the code's range (never
+ * clamped), 2^32 positions or more of one list in one level; SS_ENOMEM / SS_EDEVICE.  Every refusal leaves the tier exactly as it was:
+ * the new arrays are built beside the serving ones and swapped under the shard lock once the device is idle. */
+int ss_bm25_commit_sparse_level_fields(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs /*[n_lists+1]*/, const uint32_t* docs,
+                                       const uint8_t* fields, const uint16_t* tfs, const uint16_t* npos /* may be NULL: tf */,
+                                       const uint16_t* positions /* NULL: none */, uint64_t n_positions);
 int ss_bm25_incremental_info(ss_shard* s, uint32_t* n_levels, uint64_t* raw_bytes, double* last_append_ms, double* last_rebuild_ms);
 /* Search strategy.  AUTO: requests with <= 4 scored terms and k <= 128 take the PRUNED path (the reference's block-max /
  * sub-query pruning, intersection.rs:2224-2233, union.rs:1355-1405, as MaxScore over a probe index: only essential /

@@ -2,10 +2,15 @@
 // A commit changes the shard's average document length, and with it every BM25 weight (commit.rs recomputes bm25_component_cache): the
 // tier therefore keeps the tf of every sparse posting beside its (code | doc) word and re-codes the postings on the device after a
 // commit.  That state -- the tf array and the per-list starts of the positions pool -- lives beside the shard, keyed by it.
+// One indexed field: one tf per posting, u16 positions.  Several (ss_bm25_commit_level_fields + ss_bm25_commit_sparse_level_fields): one
+// merged posting per (term, doc) with a ROW of tfs, one per field (0 = absent), field-tagged u32 positions; the re-coding then follows the
+// merged lists' scale as well as the average length.
 #pragma once
 #include "ss_common.h"
 
 bool ssi_bm25_sparse_levels_has(const ss_shard* s);
+// the tf row of its postings: 0 = no such tier, 1 = one indexed field, else the indexed fields of ssi_bm25_commit_sparse_level_fields
+uint32_t ssi_bm25_sparse_levels_fields(const ss_shard* s);
 void ssi_bm25_sparse_levels_drop(const ss_shard* s);
 // every sparse posting's code again from its tf, the image's d_doclen and d_comp (after a commit moved the average length)
 // (SS_ENOTSUP: a weight the code cannot hold, bm_w_codable)
@@ -18,3 +23,9 @@ int ssi_bm25_sparse_levels_check(ss_shard* s, const ss_shard* img, hipStream_t s
 // replaced.  Caller holds s->mu, the device is idle.
 int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
                                  const uint16_t* npos, const uint16_t* positions, uint64_t n_positions);
+// ... of an image with SEVERAL indexed fields whose levels came through ss_bm25_commit_level_fields: entries (doc, field, tf) sorted by
+// (doc, field) inside a list; the tier keeps one merged posting per (list, doc) with the tf of every field beside it (mf_sparse_level.h),
+// positions field-tagged in 32 bits.  SS_ESTATE: no such image, or a tier of whole lists; SS_ENOTSUP: an image without merged lists, a
+// weight the code cannot hold.  Caller holds s->mu, the device is idle.
+int ssi_bm25_commit_sparse_level_fields(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
+                                        const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions);

@@ -908,7 +908,11 @@ static int commit_level_fields_impl(ss_shard* s, uint32_t level, uint32_t n_leve
   std::vector<ss_raw_level_mf> levels;
   {
     ShardLock g(s);
-    if (s->sp_n) return SS_ENOTSUP;  // (the sparse tier beside a committed multi-field image: not built)
+    // a tier of whole lists (ss_bm25_append_sparse_fields) keeps no tfs and cannot follow a commit.  A tier of levels
+    // (ss_bm25_commit_sparse_level_fields) numbers its terms behind the dense ones: new terms start rare; a re-committed level only grows
+    // (a shrinking one would leave the tier's postings of the level pointing past the image)
+    if (s->sp_n && (ssi_bm25_sparse_levels_fields(s) != n_fields || n_terms != s->bm_n_terms / s->bm_n_fields)) return SS_ENOTSUP;
+    if (s->sp_n && level < M->raw.size() && n_level_docs < M->raw[level].n_docs) return SS_ENOTSUP;
     if ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()) return SS_ESTATE;  // an image that was not built this way
     if (!M->raw.empty() && M->raw[0].n_fields != n_fields) return SS_EINVAL;
     SS_TRY(level_rules(level, n_level_docs, M->raw));
@@ -935,12 +939,20 @@ static int commit_level_fields_impl(ss_shard* s, uint32_t level, uint32_t n_leve
   const int rc = ssi_bm25_rebuild_from_raw_fields(s, levels, n_fields, b.data(), img.get(), bst);
   if (rc) return rc;
   const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+  int rc_recode = SS_OK;
   {  // the swap: searches in flight finish on the old image, whose arrays are then released
     ShardLock g(s);
-    if (level > M->raw.size() || level + 1 < M->raw.size() || s->sp_n || ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()))
+    const bool tier = s->sp_n != 0;
+    if (level > M->raw.size() || level + 1 < M->raw.size() || (tier && ssi_bm25_sparse_levels_fields(s) != n_fields) ||
+        ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()))
       return SS_ESTATE;  // an upload got in between
     (void)hipStreamSynchronize(s->stream);
     for (auto& kv : s->bm_ws) (void)hipStreamSynchronize(kv.first);
+    if (tier) {  // the sparse postings under the new lengths, boosts and merged scale: refused before anything changes, never clamped
+      if (!img->bm_merged) return SS_ENOTSUP;  // (an image without merged lists has no tier)
+      const int rc_check = ssi_bm25_sparse_levels_check(s, img.get(), bst);
+      if (rc_check) return rc_check;
+    }
     ss_raw_level_mf replaced;
     const bool replace = level < M->raw.size();
     if (replace) replaced = M->raw[level];
@@ -956,17 +968,21 @@ static int commit_level_fields_impl(ss_shard* s, uint32_t level, uint32_t n_leve
       bm_image_arrays(s, [&](auto*& p) { if (p && s->blocks.release(p)) p = nullptr; });
       std::vector<ss_block_pool::Idle> idle;
       idle.swap(s->blocks.idle);   // (free_bm25 clears the idle list: these stay)
-      free_bm25(s);
+      free_bm25(s, /*keep_tier=*/tier);
       s->blocks.idle.swap(idle);
       s->blocks.trim(3);
     }
     if (replace) raw_level_mf_free(replaced);
     M->raw.swap(keep);
     bm_image_take_fields(s, img.get());
+    if (tier) {  // avgdl and the merged scale moved: the sparse postings' codes follow (their docs of this level: ss_bm25_commit_sparse_level_fields)
+      rc_recode = ssi_bm25_sparse_levels_recode(s, s->stream);
+      if (rc_recode == SS_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc_recode = SS_EDEVICE;
+    }
     s->raw_last_rebuild_ms = rebuild_ms;
     s->raw_last_append_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
   }
-  return SS_OK;
+  return rc_recode;  // (the dense image is swapped in either way, as in append_level_impl: the caller hears that the tier could not follow)
 }
 int ss_bm25_commit_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost,
                                 uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields, const uint16_t* tfs,
@@ -1119,6 +1135,18 @@ int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, c
     return ssi_bm25_append_sparse_level(s, level, n_lists, offs, docs, tfs, npos, positions, n_positions);
   }, SS_ENOMEM, SS_EDEVICE);
 }
+// ... of an image with several indexed fields whose levels came through ss_bm25_commit_level_fields (include/seekstorm_hip.h)
+int ss_bm25_commit_sparse_level_fields(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
+                                       const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
+  if (!s || !offs || n_lists == 0 || (offs[n_lists] > offs[0] && (!docs || !fields || !tfs)) || (n_positions && !positions)) return SS_EINVAL;
+  return ss_guard([&]() -> int {
+    ShardLock g(s);
+    if (!s->d_post) return SS_ESTATE;
+    SS_HIP(hipSetDevice(s->device));
+    SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays the level replaces
+    return ssi_bm25_commit_sparse_level_fields(s, level, n_lists, offs, docs, fields, tfs, npos, positions, n_positions);
+  }, SS_ENOMEM, SS_EDEVICE);
+}
 // Whole lists of rare terms behind the tier's: with_fields = entries (doc, field, tf) of an image with several indexed fields -- said
 // apart from `fields`, which postings present must bring then --; with_positions = the entry brings positions (none at all: still
 // a tier that carries them).  The first new list's term id continues behind the dense terms and the lists the tier holds.
@@ -1163,7 +1191,8 @@ int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, ui
   const uint64_t np = s->h_sp_base.empty() ? 0 : s->h_sp_base.back();
   if (n_lists) *n_lists = s->sp_n;
   if (n_postings) *n_postings = np;
-  if (bytes) *bytes = np * (ssi_bm25_sparse_levels_has(s) ? 10 : 8) + ((uint64_t)s->sp_n + 1) * 8;  // (a tier of levels keeps the tfs)
+  const uint32_t tf_row = ssi_bm25_sparse_levels_fields(s);  // (a tier of levels keeps the tf of every indexed field beside a posting)
+  if (bytes) *bytes = np * (8 + 2 * (uint64_t)tf_row) + ((uint64_t)s->sp_n + 1) * 8;
   return SS_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "bm25_build.h"
 #include "bm25_image.h"
 #include "sparse_levels.h"
+#include "mf_sparse_level.h"
 
 #include <chrono>
 #include <cmath>
@@ -1280,7 +1281,8 @@ static int sparse_install(ss_shard* s, uint32_t n_lists, const std::vector<u64>&
 // ---------------------------------------------------------------- the sparse tier level by level (sparse_levels.h)
 namespace {
 struct SparseLevels {
-  uint16_t* d_tf = nullptr;    // [sparse postings] the tf behind every posting's code
+  uint16_t* d_tf = nullptr;    // [sparse postings][n_fields] the tf behind every posting's code (several fields: a row per posting, 0 = absent)
+  uint32_t n_fields = 1;       // 1: a tier of ssi_bm25_append_sparse_level; the indexed fields of ssi_bm25_commit_sparse_level_fields
   std::vector<uint64_t> h_pbase;    // [sp_n + 1] first position of every list in d_sp_pos (a tier with positions)
   int64_t last_level = -1;          // the level the last call brought (a re-commit of it replaces what it brought) ...
   std::vector<uint32_t> h_last_n, h_last_pos;  // ... per list: its postings / positions of that level, the lists' tails
@@ -1288,22 +1290,27 @@ struct SparseLevels {
 std::mutex g_spl_mu;
 std::unordered_map<const ss_shard*, SparseLevels> g_spl;
 
+// P: an element of the positions pool (uint16_t: one indexed field; uint32_t: field-tagged, several)
+template <class P>
 struct SpExtend {
   const uint64_t* old_base; uint32_t n_old; const uint64_t* new_base; uint32_t n_lists;
   const uint64_t* old_post; const uint16_t* old_tf; uint64_t* new_post; uint16_t* new_tf;
   const uint64_t* lvl_off; const uint32_t* lvl_doc; const uint16_t* lvl_tf;
+  uint32_t F;  // tfs per posting (old_tf / new_tf / lvl_tf: rows of F)
   const uint32_t* drop_n; const uint32_t* drop_p;  // a replaced level: the postings / positions at every old list's tail that go (or nullptr)
   const uint64_t* old_pbase; const uint64_t* new_pbase; const uint64_t* old_pend; uint64_t* new_pend;  // positions (new_pend == nullptr: a tier without)
-  const uint16_t* old_pool; uint16_t* new_pool; const uint32_t* lvl_pend; const uint64_t* lvl_pbase; const uint16_t* lvl_pool;
-  uint32_t n_docs; uint32_t* bad;
+  const P* old_pool; P* new_pool; const uint32_t* lvl_pend; const uint64_t* lvl_pbase; const P* lvl_pool;
+  uint32_t d_lo, n_docs; uint32_t* bad;  // the level's docs lie in [d_lo, n_docs)
 };
 }  // namespace
-// one wave per list: the list's old postings (and their positions) to their new places, the level's behind them
-__global__ void __launch_bounds__(256) sp_extend_kernel(SpExtend A) {
+// one wave per list: the list's old postings (with their tf rows and positions) to their new places, the level's behind them
+template <class P>
+__global__ void __launch_bounds__(256) sp_extend_kernel(SpExtend<P> A) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint64_t i64 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> 6;
   if (i64 >= A.n_lists) return;
   const uint32_t i = (uint32_t)i64;
+  const uint64_t F = A.F;
   const bool was = i < A.n_old;
   const uint64_t ob = was ? A.old_base[i] : 0ull, no = was ? A.old_base[i + 1] - ob - (A.drop_n ? A.drop_n[i] : 0u) : 0ull;
   const uint64_t nb = A.new_base[i], lo = A.lvl_off[i], nn = A.lvl_off[i + 1] - lo;
@@ -1312,17 +1319,22 @@ __global__ void __launch_bounds__(256) sp_extend_kernel(SpExtend A) {
   const uint64_t npb = pos ? A.new_pbase[i] : 0ull;
   for (uint64_t j = lane; j < no; j += 64u) {
     A.new_post[nb + j] = A.old_post[ob + j];
-    A.new_tf[nb + j] = A.old_tf[ob + j];
     if (pos) A.new_pend[nb + j] = npb + (A.old_pend[ob + j] - opb);
   }
+  for (uint64_t j = lane; j < no * F; j += 64u) A.new_tf[nb * F + j] = A.old_tf[ob * F + j];
   for (uint64_t j = lane; j < nn; j += 64u) {
     const uint32_t d = A.lvl_doc[lo + j];
-    bool ok = d < A.n_docs && A.lvl_tf[lo + j] != 0;
+    uint32_t any_tf = 0u;
+    for (uint64_t f = 0; f < F; f++) {
+      const uint16_t t = A.lvl_tf[(lo + j) * F + f];
+      any_tf |= t;
+      A.new_tf[(nb + no + j) * F + f] = t;
+    }
+    bool ok = d >= A.d_lo && d < A.n_docs && any_tf != 0u;
     if (j > 0) ok = ok && d > A.lvl_doc[lo + j - 1];
     else if (no) ok = ok && d > (uint32_t)A.old_post[ob + no - 1];  // behind everything the list holds
     if (!ok) atomicOr(A.bad, 1u);
-    A.new_post[nb + no + j] = (uint64_t)d;  // (its code: sp_recode_kernel)
-    A.new_tf[nb + no + j] = A.lvl_tf[lo + j];
+    A.new_post[nb + no + j] = (uint64_t)d;  // (its code: sp_recode_kernel / sp_recode_fields_kernel)
     if (pos) A.new_pend[nb + no + j] = npb + opn + A.lvl_pend[lo + j];
   }
   if (pos) {
@@ -1351,10 +1363,40 @@ __global__ void __launch_bounds__(256) sp_recode_kernel(uint64_t* __restrict__ p
     if ((threadIdx.x & 63u) == 0u) atomicAdd(n_uncodable, n_bad);
   }
 }
+// ... of a tier of SEVERAL indexed fields: the merged posting's weight from its tf row [RF] -- the operations of mf_merged_weight, what
+// mf_fill_kernel gives a dense merged posting and the host loop of ssi_bm25_append_sparse_fields a sparse one --, divided by the merged
+// lists' scale; the code carries the mask of the fields that hold the term at BM_SP_FIELD_SHIFT.  The refusal is that host loop's own
+// (never clamped); write = false only counts.
+__global__ void __launch_bounds__(256) sp_recode_fields_kernel(uint64_t* __restrict__ post, const uint16_t* __restrict__ tf, uint64_t n, uint32_t RF,
+                                                               const uint8_t* __restrict__ doclen, uint32_t n_docs, const float* __restrict__ comp,
+                                                               const float* __restrict__ boost, float k1, float mscale,
+                                                               uint32_t* __restrict__ n_uncodable, int write) {
+  uint32_t n_bad = 0;
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256u) {
+    const uint32_t d = (uint32_t)post[p];
+    if (d >= n_docs) continue;  // (never read a length byte past the image)
+    const uint16_t* __restrict__ row = tf + p * RF;
+    uint32_t lt10, fmask = 0u;
+    const float w = mf_merged_weight(row, RF, doclen, n_docs, d, comp, boost, k1, &lt10);
+    for (uint32_t f = 0; f < RF; f++) fmask |= row[f] ? 1u << f : 0u;
+    const float q = __fdiv_rn(w, mscale);
+    n_bad += (!(w > 0.f) || q < 6.2e-5f || q >= 4.0f) ? 1u : 0u;
+    if (write) post[p] = ((uint64_t)(bm_wcode(q) | (fmask << BM_SP_FIELD_SHIFT)) << 32) | d;
+  }
+  if (__any(n_bad != 0u)) {
+    for (int o = 32; o > 0; o >>= 1) n_bad += __shfl_xor(n_bad, o);
+    if ((threadIdx.x & 63u) == 0u) atomicAdd(n_uncodable, n_bad);
+  }
+}
 
 bool ssi_bm25_sparse_levels_has(const ss_shard* s) {
   std::lock_guard<std::mutex> g(g_spl_mu);
   return g_spl.find(s) != g_spl.end();
+}
+uint32_t ssi_bm25_sparse_levels_fields(const ss_shard* s) {
+  std::lock_guard<std::mutex> g(g_spl_mu);
+  auto it = g_spl.find(s);
+  return it == g_spl.end() ? 0u : it->second.n_fields;
 }
 void ssi_bm25_sparse_levels_drop(const ss_shard* s) {
   std::lock_guard<std::mutex> g(g_spl_mu);
@@ -1363,26 +1405,25 @@ void ssi_bm25_sparse_levels_drop(const ss_shard* s) {
   if (it->second.d_tf) (void)hipFree(it->second.d_tf);
   g_spl.erase(it);
 }
-// write = false: counts only, against the given length bytes and component cache (a commit's new image, before it is swapped in)
-static int sparse_levels_recode(ss_shard* s, hipStream_t st, const uint8_t* doclen, uint64_t n_docs, const float* comp, bool write) {
-  uint16_t* d_tf = nullptr;
-  {
-    std::lock_guard<std::mutex> g(g_spl_mu);
-    auto it = g_spl.find(s);
-    if (it == g_spl.end()) return SS_OK;
-    d_tf = it->second.d_tf;
-  }
-  const uint64_t n = s->h_sp_base.empty() ? 0 : s->h_sp_base.back();
+// the codes of n postings (post, tf rows of F) under the length bytes, component cache -- and, several fields, boosts and merged scale --
+// of `img`; write = false: counts only (a commit's new image, before it is swapped in).  SS_ENOTSUP: a weight the code cannot hold, or
+// an image of several fields without merged lists
+static int sp_recode_run(uint64_t* post, const uint16_t* tf, uint64_t n, uint32_t F, const ss_shard* img, hipStream_t st, bool write) {
   if (!n) return SS_OK;
-  if (!s->d_sp_post || !d_tf || !doclen || !comp) return SS_ESTATE;
+  if (F > 1 && (!img->bm_merged || bm_real_fields(img) != F || img->h_boost.size() != (size_t)F + 1)) return SS_ENOTSUP;
+  if (!post || !tf || !img->d_doclen || !img->d_comp || (F > 1 && !img->d_boost)) return SS_ESTATE;
   uint32_t* d_bad = nullptr;
   SS_HIP(hipMalloc(&d_bad, sizeof(uint32_t)));
   uint32_t n_bad = 0;
   hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(uint32_t), st);
   const volatile float k1 = 1.2f + 1.0f;  // (K + 1) as bm_weight_exact forms it
   if (e == hipSuccess) {
-    sp_recode_kernel<<<(uint32_t)std::min<uint64_t>((n + 255) / 256, 65536), 256, 0, st>>>(s->d_sp_post, d_tf, n, doclen, (uint32_t)n_docs, comp, k1,
-                                                                                           d_bad, write ? 1 : 0);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, 65536);
+    if (F == 1)
+      sp_recode_kernel<<<grid, 256, 0, st>>>(post, tf, n, img->d_doclen, (uint32_t)img->bm_n_docs, img->d_comp, k1, d_bad, write ? 1 : 0);
+    else
+      sp_recode_fields_kernel<<<grid, 256, 0, st>>>(post, tf, n, F, img->d_doclen, (uint32_t)img->bm_n_docs, img->d_comp, img->d_boost, k1,
+                                                    img->h_boost[F], d_bad, write ? 1 : 0);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpyAsync(&n_bad, d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, st);
@@ -1391,17 +1432,180 @@ static int sparse_levels_recode(ss_shard* s, hipStream_t st, const uint8_t* docl
   if (e != hipSuccess) return SS_EDEVICE;
   return n_bad ? SS_ENOTSUP : SS_OK;
 }
-int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st) {
-  return sparse_levels_recode(s, st, s->d_doclen, s->bm_n_docs, s->d_comp, true);
+// ... of the serving tier
+static int sparse_levels_recode(ss_shard* s, hipStream_t st, const ss_shard* img, bool write) {
+  uint16_t* d_tf = nullptr;
+  uint32_t F = 1;
+  {
+    std::lock_guard<std::mutex> g(g_spl_mu);
+    auto it = g_spl.find(s);
+    if (it == g_spl.end()) return SS_OK;
+    d_tf = it->second.d_tf;
+    F = it->second.n_fields;
+  }
+  return sp_recode_run(s->d_sp_post, d_tf, s->h_sp_base.empty() ? 0 : s->h_sp_base.back(), F, img, st, write);
 }
-int ssi_bm25_sparse_levels_check(ss_shard* s, const ss_shard* img, hipStream_t st) {
-  return sparse_levels_recode(s, st, img->d_doclen, img->bm_n_docs, img->d_comp, false);
+int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st) { return sparse_levels_recode(s, st, s, true); }
+int ssi_bm25_sparse_levels_check(ss_shard* s, const ss_shard* img, hipStream_t st) { return sparse_levels_recode(s, st, img, false); }
+
+// What a level brings to the tier, however many fields: list i's postings off[i] .. off[i + 1] (from 0) of doc / tf (rows of F); with
+// positions, per posting the END of its positions counted from its list's first of the level (pend), the lists' first positions in the
+// level's pool (pbase [n_lists + 1]) and the pool itself (elements of sp_level_install's P).
+namespace {
+struct SpLevelIn {
+  uint32_t F;
+  const uint64_t* off; const uint32_t* doc; const uint16_t* tf;
+  bool with_pos; const uint32_t* pend; const uint64_t* pbase; const void* pool; uint64_t n_positions;
+  uint64_t d_lo;
+};
+// the tier's level state as a call finds it: SS_EINVAL for a level older than the tier's last; drop_n / drop_p = what a replaced level brought
+int sp_level_state(const ss_shard* s, uint32_t level, uint32_t n_old, bool with_pos, std::vector<uint32_t>* drop_n, std::vector<uint32_t>* drop_p,
+                   std::vector<uint64_t>* old_pbase) {
+  std::lock_guard<std::mutex> g(g_spl_mu);
+  auto it = g_spl.find(s);
+  if (it != g_spl.end()) {
+    if ((int64_t)level < it->second.last_level) return SS_EINVAL;
+    if ((int64_t)level == it->second.last_level) { *drop_n = it->second.h_last_n; *drop_p = it->second.h_last_pos; }
+    *old_pbase = it->second.h_pbase;
+  }
+  if (!drop_n->empty() && (drop_n->size() != n_old || (with_pos && drop_p->size() != n_old))) return SS_ESTATE;
+  return SS_OK;
+}
+}  // namespace
+// The new tier beside the serving one (sp_extend_kernel), its codes under the image's weights (never clamped: SS_ENOTSUP), then the swap.
+// Whatever fails leaves the tier exactly as it was.  Caller holds s->mu, the device is idle.
+template <class P>
+static int sp_level_install(ss_shard* s, uint32_t level, uint32_t n_lists, const SpLevelIn& in, const std::vector<uint32_t>& drop_n,
+                            const std::vector<uint32_t>& drop_p, std::vector<uint64_t> old_pbase) {
+  const uint32_t n_old = s->sp_n, F = in.F;
+  const bool with_pos = in.with_pos, replace = !drop_n.empty();
+  const uint64_t n_new = in.off[n_lists], n_positions = in.n_positions;
+  // the new starts of the lists (postings; positions)
+  std::vector<uint64_t> base((size_t)n_lists + 1, 0), pbase;
+  uint64_t dropped_p = 0;
+  for (uint32_t i = 0; i < n_lists; i++) {
+    uint64_t had = i < n_old ? s->h_sp_base[i + 1] - s->h_sp_base[i] : 0ull;
+    if (replace && i < n_old) { if (drop_n[i] > had) return SS_ESTATE; had -= drop_n[i]; }
+    base[i + 1] = base[i] + had + (in.off[i + 1] - in.off[i]);
+  }
+  if (with_pos) {
+    if (old_pbase.size() != (size_t)n_old + 1) { if (n_old) return SS_ESTATE; old_pbase.assign(1, 0); }
+    pbase.assign((size_t)n_lists + 1, 0);
+    for (uint32_t i = 0; i < n_lists; i++) {
+      uint64_t had = i < n_old ? old_pbase[i + 1] - old_pbase[i] : 0ull;
+      if (replace && i < n_old) { if (drop_p[i] > had) return SS_ESTATE; had -= drop_p[i]; dropped_p += drop_p[i]; }
+      pbase[i + 1] = pbase[i] + had + (in.pbase[i + 1] - in.pbase[i]);
+    }
+    if (pbase[n_lists] != s->sp_pos_n - dropped_p + n_positions) return SS_ESTATE;
+  }
+  // device: the new arrays, the level's staging
+  std::vector<void*> owned;
+  auto dalloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
+    owned.push_back(p);
+    return p;
+  };
+  auto drop_all = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
+  auto up = [&](void* d, const void* h, size_t bytes) { return bytes == 0 || hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+  const uint64_t tot = base[n_lists];
+  uint64_t* nbase = (uint64_t*)dalloc(base.size() * 8);
+  uint64_t* npost = (uint64_t*)dalloc((size_t)tot * 8);
+  uint16_t* ntf = (uint16_t*)dalloc((size_t)tot * F * 2);
+  uint64_t* d_lvl_off = (uint64_t*)dalloc(((size_t)n_lists + 1) * 8);
+  uint32_t* d_lvl_doc = (uint32_t*)dalloc((size_t)n_new * 4);
+  uint16_t* d_lvl_tf = (uint16_t*)dalloc((size_t)n_new * F * 2);
+  uint32_t* d_bad = (uint32_t*)dalloc(4);
+  uint32_t *d_drop_n = nullptr, *d_drop_p = nullptr;
+  uint64_t *d_old_pbase = nullptr, *d_new_pbase = nullptr, *npend = nullptr, *d_lvl_pbase = nullptr;
+  P *npool = nullptr, *d_lvl_pool = nullptr;
+  uint32_t* d_lvl_pend = nullptr;
+  bool ok = nbase && npost && ntf && d_lvl_off && d_lvl_doc && d_lvl_tf && d_bad;
+  if (ok && with_pos) {
+    d_old_pbase = (uint64_t*)dalloc(old_pbase.size() * 8);
+    d_new_pbase = (uint64_t*)dalloc(pbase.size() * 8);
+    npend = (uint64_t*)dalloc((size_t)tot * 8);
+    d_lvl_pbase = (uint64_t*)dalloc(((size_t)n_lists + 1) * 8);
+    npool = (P*)dalloc((size_t)pbase[n_lists] * sizeof(P));
+    d_lvl_pool = (P*)dalloc((size_t)n_positions * sizeof(P));
+    d_lvl_pend = (uint32_t*)dalloc((size_t)n_new * 4);
+    ok = d_old_pbase && d_new_pbase && npend && d_lvl_pbase && npool && d_lvl_pool && d_lvl_pend;
+  }
+  if (ok && replace && n_old) {
+    d_drop_n = (uint32_t*)dalloc((size_t)n_old * 4);
+    if (with_pos) d_drop_p = (uint32_t*)dalloc((size_t)n_old * 4);
+    ok = d_drop_n && (!with_pos || d_drop_p);
+  }
+  if (!ok) { drop_all(); return SS_ENOMEM; }
+  const uint32_t zero = 0;
+  ok = up(nbase, base.data(), base.size() * 8) && up(d_lvl_off, in.off, ((size_t)n_lists + 1) * 8) && up(d_lvl_doc, in.doc, (size_t)n_new * 4) &&
+       up(d_lvl_tf, in.tf, (size_t)n_new * F * 2) && up(d_bad, &zero, 4);
+  if (ok && with_pos)
+    ok = up(d_old_pbase, old_pbase.data(), old_pbase.size() * 8) && up(d_new_pbase, pbase.data(), pbase.size() * 8) &&
+         up(d_lvl_pbase, in.pbase, ((size_t)n_lists + 1) * 8) && up(d_lvl_pool, in.pool, (size_t)n_positions * sizeof(P)) &&
+         up(d_lvl_pend, in.pend, (size_t)n_new * 4);
+  if (ok && d_drop_n) ok = up(d_drop_n, drop_n.data(), (size_t)n_old * 4) && (!d_drop_p || up(d_drop_p, drop_p.data(), (size_t)n_old * 4));
+  if (!ok) { drop_all(); return SS_EDEVICE; }
+  uint16_t* old_tf = nullptr;
+  {
+    std::lock_guard<std::mutex> g(g_spl_mu);
+    auto it = g_spl.find(s);
+    if (it != g_spl.end()) old_tf = it->second.d_tf;
+  }
+  SpExtend<P> A;
+  A.old_base = s->d_sp_base; A.n_old = n_old; A.new_base = nbase; A.n_lists = n_lists;
+  A.old_post = s->d_sp_post; A.old_tf = old_tf; A.new_post = npost; A.new_tf = ntf;
+  A.lvl_off = d_lvl_off; A.lvl_doc = d_lvl_doc; A.lvl_tf = d_lvl_tf; A.F = F;
+  A.drop_n = d_drop_n; A.drop_p = d_drop_p;
+  A.old_pbase = d_old_pbase; A.new_pbase = d_new_pbase; A.old_pend = s->d_sp_pos_end; A.new_pend = with_pos ? npend : nullptr;
+  A.old_pool = (const P*)s->d_sp_pos; A.new_pool = npool; A.lvl_pend = d_lvl_pend; A.lvl_pbase = d_lvl_pbase; A.lvl_pool = d_lvl_pool;
+  A.d_lo = (uint32_t)in.d_lo; A.n_docs = s->bm_n_docs; A.bad = d_bad;
+  sp_extend_kernel<P><<<(n_lists + 3u) / 4u, 256, 0, s->stream>>>(A);
+  uint32_t bad = 0;
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess ||
+      hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) { drop_all(); return SS_EDEVICE; }
+  if (bad) { drop_all(); return SS_EINVAL; }  // a level posting not behind its list's last doc: the tier stays as it was
+  // every posting's code under the image's average length (and merged scale): the arrays are nobody's yet, a refusal drops them
+  const int rc = sp_recode_run(npost, ntf, tot, F, s, s->stream, true);
+  if (rc != SS_OK) { drop_all(); return rc; }
+  // the swap (the caller holds s->mu and found the device idle)
+  auto keep = [&](void* p) { owned.erase(std::find(owned.begin(), owned.end(), p)); };
+  keep(nbase); keep(npost); keep(ntf);
+  if (with_pos) { keep(npend); keep(npool); }
+  drop_all();  // the staging
+  if (s->d_sp_base) (void)hipFree(s->d_sp_base);
+  if (s->d_sp_post) (void)hipFree(s->d_sp_post);
+  s->d_sp_base = nbase; s->d_sp_post = npost;
+  if (with_pos) {
+    if (s->d_sp_pos_end) (void)hipFree(s->d_sp_pos_end);
+    if (s->d_sp_pos) (void)hipFree(s->d_sp_pos);
+    s->d_sp_pos_end = npend; s->d_sp_pos = npool; s->sp_pos_n = pbase[n_lists]; s->sp_pos_elem = (uint32_t)sizeof(P);
+  }
+  s->h_sp_base = std::move(base);
+  s->sp_n = n_lists;
+  {
+    std::lock_guard<std::mutex> g(g_spl_mu);
+    SparseLevels& E = g_spl[s];
+    if (E.d_tf) (void)hipFree(E.d_tf);
+    E.d_tf = ntf;
+    E.n_fields = F;
+    E.h_pbase = std::move(pbase);
+    E.last_level = level;
+    E.h_last_n.resize(n_lists);
+    for (uint32_t i = 0; i < n_lists; i++) E.h_last_n[i] = (uint32_t)(in.off[i + 1] - in.off[i]);
+    E.h_last_pos.clear();
+    if (with_pos) {
+      E.h_last_pos.resize(n_lists);
+      for (uint32_t i = 0; i < n_lists; i++) E.h_last_pos[i] = (uint32_t)(in.pbase[i + 1] - in.pbase[i]);
+    }
+  }
+  return SS_OK;
 }
 
 int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
                                  const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
   if (!s->d_post || !s->d_doclen || !s->d_comp) return SS_ESTATE;
-  if (s->bm_n_fields != 1 || s->bm_merged) return SS_ENOTSUP;  // several indexed fields: whole-image uploads
+  if (s->bm_n_fields != 1 || s->bm_merged) return SS_ENOTSUP;  // several indexed fields: ssi_bm25_commit_sparse_level_fields
   const bool fresh = s->sp_n == 0;
   if (!fresh && !ssi_bm25_sparse_levels_has(s)) return SS_ESTATE;  // a tier of whole lists (ss_bm25_append_sparse) keeps no tfs
   if (n_lists < s->sp_n || (uint64_t)n_lists > 0x7FFFFFFFull - s->bm_n_terms) return n_lists < s->sp_n ? SS_EINVAL : SS_ENOTSUP;
@@ -1412,24 +1616,12 @@ int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, 
   for (uint32_t i = 0; i < n_lists; i++)
     if (offs[i + 1] < offs[i]) return SS_EINVAL;
   const uint64_t n_new = offs[n_lists] - offs[0], o0 = offs[0];
-  const uint32_t n_old = s->sp_n;
-  const uint64_t old_n = s->h_sp_base.empty() ? 0 : s->h_sp_base.back();
   // the level: the one the dense image committed last; a level this tier has seen already is replaced (the re-commit of a level
   // that was incomplete, commit.rs:204-206 merge_incomplete_index_level_to_level0)
   if ((uint64_t)level + 1 != s->raw.size()) return SS_EINVAL;
   std::vector<uint32_t> drop_n, drop_p;
   std::vector<uint64_t> old_pbase;
-  {
-    std::lock_guard<std::mutex> g(g_spl_mu);
-    auto it = g_spl.find(s);
-    if (it != g_spl.end()) {
-      if ((int64_t)level < it->second.last_level) return SS_EINVAL;
-      if ((int64_t)level == it->second.last_level) { drop_n = it->second.h_last_n; drop_p = it->second.h_last_pos; }
-      old_pbase = it->second.h_pbase;
-    }
-  }
-  const bool replace = !drop_n.empty();
-  if (replace && (drop_n.size() != n_old || (with_pos && drop_p.size() != n_old))) return SS_ESTATE;
+  if (const int rc_state = sp_level_state(s, level, s->sp_n, with_pos, &drop_n, &drop_p, &old_pbase)) return rc_state;
   const uint64_t d_lo = (uint64_t)level << 16;
   if (s->h_doclen.size() != s->bm_n_docs) return SS_ESTATE;
   float comp[SS_COMP_N];  // (the image's, d_comp: the level's weights are checked here, before the tier changes; the older postings
@@ -1444,18 +1636,11 @@ int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, 
       }
   });
   if (fail.load()) return fail.load();
-  // the new starts of the lists (postings; positions), the level's own offsets
-  std::vector<uint64_t> base((size_t)n_lists + 1, 0), lvl_off((size_t)n_lists + 1), pbase, lvl_pbase;
-  uint64_t dropped_p = 0;
-  for (uint32_t i = 0; i < n_lists; i++) {
-    uint64_t had = i < n_old ? s->h_sp_base[i + 1] - s->h_sp_base[i] : 0ull;
-    if (replace && i < n_old) { if (drop_n[i] > had) return SS_ESTATE; had -= drop_n[i]; }
-    base[i + 1] = base[i] + had + (offs[i + 1] - offs[i]);
-  }
-  for (uint32_t i = 0; i <= n_lists; i++) lvl_off[i] = offs[i] - o0;
+  // the level's own offsets, its postings' position ends
+  std::vector<uint64_t> lvl_off((size_t)n_lists + 1), lvl_pbase;
   std::vector<uint32_t> lvl_pend;
+  for (uint32_t i = 0; i <= n_lists; i++) lvl_off[i] = offs[i] - o0;
   if (with_pos) {
-    if (old_pbase.size() != (size_t)n_old + 1) { if (n_old) return SS_ESTATE; old_pbase.assign(1, 0); }
     lvl_pend.resize(n_new ? n_new : 1);
     lvl_pbase.assign((size_t)n_lists + 1, 0);
     ss_parallel_for(n_lists, 4096, [&](size_t a, size_t b, unsigned) {
@@ -1472,116 +1657,44 @@ int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, 
     if (fail.load()) return fail.load();
     for (uint32_t i = 0; i < n_lists; i++) lvl_pbase[i + 1] += lvl_pbase[i];
     if (lvl_pbase[n_lists] != n_positions) return SS_EINVAL;
-    pbase.assign((size_t)n_lists + 1, 0);
-    for (uint32_t i = 0; i < n_lists; i++) {
-      uint64_t had = i < n_old ? old_pbase[i + 1] - old_pbase[i] : 0ull;
-      if (replace && i < n_old) { if (drop_p[i] > had) return SS_ESTATE; had -= drop_p[i]; dropped_p += drop_p[i]; }
-      pbase[i + 1] = pbase[i] + had + (lvl_pbase[i + 1] - lvl_pbase[i]);
-    }
-    if (pbase[n_lists] != s->sp_pos_n - dropped_p + n_positions) return SS_ESTATE;
   }
-  // device: the new arrays, the level's staging
-  std::vector<void*> owned;
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) return nullptr;
-    owned.push_back(p);
-    return p;
-  };
-  auto drop_all = [&]() { for (void* p : owned) (void)hipFree(p); owned.clear(); };
-  auto up = [&](void* d, const void* h, size_t bytes) { return bytes == 0 || hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-  const uint64_t tot = base[n_lists];
-  (void)old_n;
-  uint64_t* nbase = (uint64_t*)dalloc(base.size() * 8);
-  uint64_t* npost = (uint64_t*)dalloc((size_t)tot * 8);
-  uint16_t* ntf = (uint16_t*)dalloc((size_t)tot * 2);
-  uint64_t* d_lvl_off = (uint64_t*)dalloc(lvl_off.size() * 8);
-  uint32_t* d_lvl_doc = (uint32_t*)dalloc((size_t)n_new * 4);
-  uint16_t* d_lvl_tf = (uint16_t*)dalloc((size_t)n_new * 2);
-  uint32_t* d_bad = (uint32_t*)dalloc(4);
-  uint32_t *d_drop_n = nullptr, *d_drop_p = nullptr;
-  uint64_t *d_old_pbase = nullptr, *d_new_pbase = nullptr, *npend = nullptr, *d_lvl_pbase = nullptr;
-  uint16_t *npool = nullptr, *d_lvl_pool = nullptr;
-  uint32_t* d_lvl_pend = nullptr;
-  bool ok = nbase && npost && ntf && d_lvl_off && d_lvl_doc && d_lvl_tf && d_bad;
-  if (ok && with_pos) {
-    d_old_pbase = (uint64_t*)dalloc(old_pbase.size() * 8);
-    d_new_pbase = (uint64_t*)dalloc(pbase.size() * 8);
-    npend = (uint64_t*)dalloc((size_t)tot * 8);
-    d_lvl_pbase = (uint64_t*)dalloc(lvl_pbase.size() * 8);
-    npool = (uint16_t*)dalloc((size_t)pbase[n_lists] * 2);
-    d_lvl_pool = (uint16_t*)dalloc((size_t)n_positions * 2);
-    d_lvl_pend = (uint32_t*)dalloc((size_t)n_new * 4);
-    ok = d_old_pbase && d_new_pbase && npend && d_lvl_pbase && npool && d_lvl_pool && d_lvl_pend;
-  }
-  if (ok && replace && n_old) {
-    d_drop_n = (uint32_t*)dalloc((size_t)n_old * 4);
-    if (with_pos) d_drop_p = (uint32_t*)dalloc((size_t)n_old * 4);
-    ok = d_drop_n && (!with_pos || d_drop_p);
-  }
-  if (!ok) { drop_all(); return SS_ENOMEM; }
-  const uint32_t zero = 0;
-  ok = up(nbase, base.data(), base.size() * 8) && up(d_lvl_off, lvl_off.data(), lvl_off.size() * 8) && up(d_lvl_doc, docs + o0, (size_t)n_new * 4) &&
-       up(d_lvl_tf, tfs + o0, (size_t)n_new * 2) && up(d_bad, &zero, 4);
-  if (ok && with_pos)
-    ok = up(d_old_pbase, old_pbase.data(), old_pbase.size() * 8) && up(d_new_pbase, pbase.data(), pbase.size() * 8) &&
-         up(d_lvl_pbase, lvl_pbase.data(), lvl_pbase.size() * 8) && up(d_lvl_pool, positions, (size_t)n_positions * 2) &&
-         up(d_lvl_pend, lvl_pend.data(), (size_t)n_new * 4);
-  if (ok && d_drop_n) ok = up(d_drop_n, drop_n.data(), (size_t)n_old * 4) && (!d_drop_p || up(d_drop_p, drop_p.data(), (size_t)n_old * 4));
-  if (!ok) { drop_all(); return SS_EDEVICE; }
-  uint16_t* old_tf = nullptr;
-  {
-    std::lock_guard<std::mutex> g(g_spl_mu);
-    auto it = g_spl.find(s);
-    if (it != g_spl.end()) old_tf = it->second.d_tf;
-  }
-  SpExtend A;
-  A.old_base = s->d_sp_base; A.n_old = n_old; A.new_base = nbase; A.n_lists = n_lists;
-  A.old_post = s->d_sp_post; A.old_tf = old_tf; A.new_post = npost; A.new_tf = ntf;
-  A.lvl_off = d_lvl_off; A.lvl_doc = d_lvl_doc; A.lvl_tf = d_lvl_tf;
-  A.drop_n = d_drop_n; A.drop_p = d_drop_p;
-  A.old_pbase = d_old_pbase; A.new_pbase = d_new_pbase; A.old_pend = s->d_sp_pos_end; A.new_pend = with_pos ? npend : nullptr;
-  A.old_pool = (const uint16_t*)s->d_sp_pos; A.new_pool = npool; A.lvl_pend = d_lvl_pend; A.lvl_pbase = d_lvl_pbase; A.lvl_pool = d_lvl_pool;
-  A.n_docs = s->bm_n_docs; A.bad = d_bad;
-  sp_extend_kernel<<<(n_lists + 3u) / 4u, 256, 0, s->stream>>>(A);
-  uint32_t bad = 0;
-  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess ||
-      hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost) != hipSuccess) { drop_all(); return SS_EDEVICE; }
-  if (bad) { drop_all(); return SS_EINVAL; }  // a level posting not behind its list's last doc: the tier stays as it was
-  // the swap (the caller holds s->mu and found the device idle)
-  auto keep = [&](void* p) { owned.erase(std::find(owned.begin(), owned.end(), p)); };
-  keep(nbase); keep(npost); keep(ntf);
-  if (with_pos) { keep(npend); keep(npool); }
-  drop_all();  // the staging
-  if (s->d_sp_base) (void)hipFree(s->d_sp_base);
-  if (s->d_sp_post) (void)hipFree(s->d_sp_post);
-  s->d_sp_base = nbase; s->d_sp_post = npost;
-  if (with_pos) {
-    if (s->d_sp_pos_end) (void)hipFree(s->d_sp_pos_end);
-    if (s->d_sp_pos) (void)hipFree(s->d_sp_pos);
-    s->d_sp_pos_end = npend; s->d_sp_pos = npool; s->sp_pos_n = pbase[n_lists]; s->sp_pos_elem = (uint32_t)sizeof(uint16_t);
-  }
-  s->h_sp_base = std::move(base);
-  s->sp_n = n_lists;
-  {
-    std::lock_guard<std::mutex> g(g_spl_mu);
-    SparseLevels& E = g_spl[s];
-    if (E.d_tf) (void)hipFree(E.d_tf);
-    E.d_tf = ntf;
-    E.h_pbase = std::move(pbase);
-    E.last_level = level;
-    E.h_last_n.resize(n_lists);
-    for (uint32_t i = 0; i < n_lists; i++) E.h_last_n[i] = (uint32_t)(offs[i + 1] - offs[i]);
-    E.h_last_pos.clear();
-    if (with_pos) {
-      E.h_last_pos.resize(n_lists);
-      for (uint32_t i = 0; i < n_lists; i++) E.h_last_pos[i] = (uint32_t)(lvl_pbase[i + 1] - lvl_pbase[i]);
-    }
-  }
-  const int rc = ssi_bm25_sparse_levels_recode(s, s->stream);
-  if (rc != SS_OK) return rc;
-  SS_HIP(hipStreamSynchronize(s->stream));
-  return SS_OK;
+  SpLevelIn in;
+  in.F = 1;
+  in.off = lvl_off.data(); in.doc = n_new ? docs + o0 : docs; in.tf = n_new ? tfs + o0 : tfs;
+  in.with_pos = with_pos; in.pend = lvl_pend.data(); in.pbase = lvl_pbase.data(); in.pool = positions; in.n_positions = with_pos ? n_positions : 0;
+  in.d_lo = d_lo;
+  return sp_level_install<uint16_t>(s, level, n_lists, in, drop_n, drop_p, std::move(old_pbase));
+}
+
+// ... of an image with SEVERAL indexed fields whose levels came through ss_bm25_commit_level_fields: the entries (doc, field, tf) of every
+// rare term in `level`, one merged posting per (list, doc) with its tf row (mf_sparse_level.h), positions field-tagged.
+int ssi_bm25_commit_sparse_level_fields(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
+                                        const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
+  if (!s->d_post) return SS_ESTATE;
+  const ss_mf_levels* M = ssi_mf_levels(s, false);
+  if (!M || M->raw.empty()) return SS_ESTATE;  // an image that was not built by ss_bm25_commit_level_fields
+  const uint32_t F = M->raw[0].n_fields;
+  const bool fresh = s->sp_n == 0;
+  if (!fresh && ssi_bm25_sparse_levels_fields(s) != F) return SS_ESTATE;  // a tier of whole lists (ss_bm25_append_sparse_fields) keeps no tfs
+  if (!s->bm_merged || !s->d_doclen || !s->d_comp || bm_real_fields(s) != F) return SS_ENOTSUP;  // boosts too far apart for merged lists: no tier
+  if (n_lists < s->sp_n) return SS_EINVAL;
+  if ((uint64_t)n_lists > 0x7FFFFFFFull - s->bm_n_terms / s->bm_n_fields) return SS_ENOTSUP;
+  const bool with_pos = M->raw[0].d_tpos != nullptr;  // every level of the tier brings positions exactly when the image's levels carry them
+  if (with_pos != (positions != nullptr) || (!with_pos && n_positions)) return SS_EINVAL;
+  if (with_pos && !fresh && s->sp_pos_elem != sizeof(uint32_t)) return SS_ESTATE;
+  if ((uint64_t)level + 1 != M->raw.size()) return SS_EINVAL;  // the level the dense image committed last
+  std::vector<uint32_t> drop_n, drop_p;
+  std::vector<uint64_t> old_pbase;
+  if (const int rc_state = sp_level_state(s, level, s->sp_n, with_pos, &drop_n, &drop_p, &old_pbase)) return rc_state;
+  mf_sparse_level_host H;
+  if (const int rc_pass = mf_sparse_level_prepare(level, M->raw[level].n_docs, F, n_lists, offs, docs, fields, tfs, npos, positions, n_positions, &H))
+    return rc_pass;
+  SpLevelIn in;
+  in.F = F;
+  in.off = H.moff.data(); in.doc = H.mdoc.data(); in.tf = H.mtf.data();
+  in.with_pos = with_pos; in.pend = H.mpend.data(); in.pbase = H.lpos.data(); in.pool = H.pos.data(); in.n_positions = with_pos ? n_positions : 0;
+  in.d_lo = (uint64_t)level << 16;
+  return sp_level_install<uint32_t>(s, level, n_lists, in, drop_n, drop_p, std::move(old_pbase));
 }
 
 // ---------------------------------------------------------------- positions (phrase queries)

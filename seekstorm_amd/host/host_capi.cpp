@@ -275,6 +275,13 @@ int ssh_commit_level(ssh_index* ix, int shard, uint32_t level, uint32_t n_level_
                      uint64_t n_positions) {
   return ix->shards[shard]->commit_level(level, n_level_docs, level_doclen, n_terms, n_dense_terms, offs, docs, tfs, positions, n_positions);
 }
+// Shard::commit_level_fields: one commit of an image with several indexed fields and a tiered vocabulary
+int ssh_commit_level_fields(ssh_index* ix, int shard, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen,
+                            const float* boost, uint32_t n_terms, uint32_t n_dense_terms, const uint64_t* offs, const uint32_t* docs,
+                            const uint8_t* fields, const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
+  return ix->shards[shard]->commit_level_fields(level, n_level_docs, n_fields, level_doclen, boost, n_terms, n_dense_terms, offs, docs, fields, tfs,
+                                                positions, n_positions);
+}
 // Shard::facet_count of one query; out_counts [n_buckets + 1]
 int ssh_facet_count(ssh_index* ix, int shard, const uint32_t* terms, uint32_t n_terms, uint32_t query_type, uint32_t facet_offset,
                     uint32_t facet_type, uint32_t n_buckets, const uint64_t* bounds, uint32_t n_bounds, const ss_facet_point* base,

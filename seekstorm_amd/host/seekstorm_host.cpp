@@ -243,6 +243,28 @@ int Shard::commit_level(uint32_t level, uint32_t n_level_docs, const uint8_t* le
   return rc;
 }
 
+int Shard::commit_level_fields(uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost, uint32_t n_terms,
+                               uint32_t n_dense_terms, const uint64_t* term_offsets, const uint32_t* doc_ids, const uint8_t* field_ids, const uint16_t* tfs,
+                               const uint16_t* positions, uint64_t n_positions, const uint16_t* npos) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  if (!term_offsets || n_dense_terms == 0 || n_dense_terms > n_terms) return SS_EINVAL;
+  // the same split as commit_level: the entries (doc, field, tf) of the dense terms, then those of the rare ones
+  const uint64_t cut = term_offsets[n_dense_terms];
+  uint64_t p_cut = 0;
+  if (positions)
+    for (uint64_t j = term_offsets[0]; j < cut; j++) p_cut += npos ? npos[j] : tfs[j];
+  if (positions && p_cut > n_positions) return SS_EINVAL;
+  int rc = ss_bm25_commit_level_fields(h_, level, n_level_docs, n_fields, level_doclen, boost, n_dense_terms, term_offsets, doc_ids, field_ids, tfs, npos,
+                                       positions, positions ? p_cut : 0);
+  if (rc != SS_OK) return rc;
+  lexical_fields_ = n_fields;
+  n_docs_ = (uint64_t)level * 65536u + n_level_docs;
+  if (n_dense_terms < n_terms)
+    rc = ss_bm25_commit_sparse_level_fields(h_, level, n_terms - n_dense_terms, term_offsets + n_dense_terms, doc_ids, field_ids, tfs, npos,
+                                            positions ? positions + p_cut : nullptr, positions ? n_positions - p_cut : 0);
+  return rc;
+}
+
 int Shard::set_deleted(const uint64_t* doc_ids, uint64_t n) {
   if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
   const int rc = ss_set_deleted(h_, doc_ids, n);

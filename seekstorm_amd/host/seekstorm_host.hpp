@@ -174,6 +174,11 @@ class Shard {
   int commit_level(uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, uint32_t n_dense_terms,
                    const uint64_t* term_offsets, const uint32_t* doc_ids, const uint16_t* tfs, const uint16_t* positions = nullptr,
                    uint64_t n_positions = 0, const uint16_t* npos = nullptr);
+  // ... of an image with several indexed fields (ss_bm25_commit_level_fields + ss_bm25_commit_sparse_level_fields): entries (doc, field,
+  // tf) sorted by (doc, field) per term, level_doclen [n_fields][n_level_docs]; positions (optional): every entry's, tf of them or npos[i]
+  int commit_level_fields(uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost, uint32_t n_terms,
+                          uint32_t n_dense_terms, const uint64_t* term_offsets, const uint32_t* doc_ids, const uint8_t* field_ids, const uint16_t* tfs,
+                          const uint16_t* positions = nullptr, uint64_t n_positions = 0, const uint16_t* npos = nullptr);
   // VectorSimilarity of the image (index-wide in the reference): Dot / Cosine (default) or Euclidean; BEFORE the upload
   int set_vector_similarity(bool euclidean);
   int upload_vectors(uint64_t n_rows, uint32_t dim, const float* rows, const uint32_t* row_doc_ids);

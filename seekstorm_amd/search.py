@@ -563,6 +563,50 @@ class Shard:
             self.append_sparse_level(level, off[nd:] - off[nd], d[cut:], t[cut:], None if positions is None else positions[p_cut:],
                                      None if npos is None else npos[cut:])
 
+    def commit_sparse_level_fields(self, level, offs, docs, fields, tfs, positions=None, npos=None):
+        """the committed level's entries (doc, field, tf) of the RARE terms of an image with several indexed fields that grows by
+        commit_level_fields (ss_bm25_commit_sparse_level_fields, after the dense commit of the same level): list i continues sparse
+        list i, further lists are new terms; a level brought before is replaced.  positions: every entry's, exactly when the image's
+        levels carry them; npos: their number per entry where not tf"""
+        o = np.ascontiguousarray(offs, np.uint64)
+        d = np.ascontiguousarray(docs, np.uint32)
+        f = np.ascontiguousarray(fields, np.uint8)
+        t = np.ascontiguousarray(tfs, np.uint16)
+        ps = None if positions is None else np.ascontiguousarray(positions, np.uint16)
+        if ps is not None and len(ps) == 0:
+            ps = np.zeros(1, np.uint16)  # (a non-null pointer says "this level brings positions")
+            n_ps = 0
+        else:
+            n_ps = 0 if ps is None else len(ps)
+        npc = None if npos is None else np.ascontiguousarray(npos, np.uint16)
+        N.check(N.lib().ss_bm25_commit_sparse_level_fields(self._h, int(level), len(o) - 1, N.ptr(o, N.u64p), N.ptr(d, N.u32p), N.ptr(f, N.u8p),
+                                                           N.ptr(t, N.u16p), N.ptr(npc, N.u16p), N.ptr(ps, N.u16p), n_ps),
+                "ss_bm25_commit_sparse_level_fields")
+        self._df_cache.clear()
+
+    def commit_level_fields_tiered(self, level, level_doclen, boost, term_offsets, doc_ids, fields, tfs, n_dense_terms, positions=None, npos=None):
+        """one commit of an image with several indexed fields as the seam sees it: the level's entries of ALL known
+        terms in id order -- ids below n_dense_terms belong to the dense image (commit_level_fields), the others are the sparse tier's
+        lists (commit_sparse_level_fields; new rare terms simply extend the id range)"""
+        off = np.ascontiguousarray(term_offsets, np.uint64)
+        nt = len(off) - 1
+        nd = int(n_dense_terms)
+        if nd > nt:
+            raise ValueError("fewer terms than the dense image holds")
+        d = np.ascontiguousarray(doc_ids, np.uint32)
+        f = np.ascontiguousarray(fields, np.uint8)
+        t = np.ascontiguousarray(tfs, np.uint16)
+        cut = int(off[nd])
+        p_cut = None
+        if positions is not None:
+            cnt = t if npos is None else np.ascontiguousarray(npos, np.uint16)
+            p_cut = int(cnt[int(off[0]):cut].astype(np.int64).sum())
+        self.commit_level_fields(level, level_doclen, boost, off[:nd + 1], d[:cut], f[:cut], t[:cut],
+                                 None if positions is None else positions[:p_cut], None if npos is None else npos[:cut])
+        if nd < nt:
+            self.commit_sparse_level_fields(level, off[nd:] - off[nd], d[cut:], f[cut:], t[cut:], None if positions is None else positions[p_cut:],
+                                            None if npos is None else npos[cut:])
+
     def incremental_info(self):
         """(levels, bytes of the raw postings kept for rebuilds, ms of the last append, of which the device rebuild)"""
         nl, rb, a, b = C.c_uint32(), C.c_uint64(), C.c_double(), C.c_double()
