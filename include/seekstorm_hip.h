@@ -505,7 +505,8 @@ typedef struct {
  * intersection of the unique terms (get_bm25f_multiterm_singlefield) and counted only when the phrase matches.  Needs the
  * positions in the image; up to 6 unique terms and k <= 128 run over the probe index (every list with a probe row: on a rationed
  * vocabulary the rows built on demand go to a batch's phrase queries first), 7 .. SS_MAX_PHRASE unique terms or a larger k on the
- * generic kernel (csrc/bm25_gallop.hip; no probe rows needed).  One indexed field: ss_bm25_upload_positions.  Several indexed fields
+ * generic kernel (csrc/bm25_gallop.hip; no probe rows needed -- it also takes every phrase of an image without a probe index, a
+ * budget below two rows).  One indexed field: ss_bm25_upload_positions.  Several indexed fields
  * (ss_bm25_upload_fields_positions; add_result.rs:3248-3386): the phrase must stand inside ONE field, fields tried in ascending
  * order, only listed ones under SS_OP_FIELD_FILTER; the score sums all fields of the unique terms.  Host-pointer batches may mix
  * phrase queries with others (run as two sub-batches inside the library, answers back in the callers' order); a DEVICE-resident

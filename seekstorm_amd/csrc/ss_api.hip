@@ -2032,8 +2032,10 @@ static int bm25_shape_of(const ss_shard* s, const ss_bm25_query& Q, uint32_t kk,
     if (np > 6 || kk > 128) *shape = SH_GALLOP_PHRASE;
     // a rationed vocabulary: the phrase kernel of the probe index needs a row for EVERY list it reads and has no scan to fall back on -- a
     // phrase over a list without one takes the generic kernel, which needs none (round 5 built pool rows for it first and refused the
-    // batch whose phrases alone exceeded the pool); the pool stays with the queries that gain from it
-    if (!any_sparse && s->bm_probe_rows != 0 && s->bm_probe_rows < s->bm_n_terms)
+    // batch whose phrases alone exceeded the pool); the pool stays with the queries that gain from it.  No probe index at all (a budget
+    // below two rows, or none that fitted): every list is row-less, and the phrase is answered the same way instead of being refused
+    if (!any_sparse && s->bm_probe_rows == 0) *shape = SH_GALLOP_PHRASE;
+    else if (!any_sparse && s->bm_probe_rows < s->bm_n_terms)
       for (uint32_t t = 0; t < all; t++) {
         const uint32_t v = Q.term[t] * L + (L - 1u);
         if (s->h_probe_row[v] == BM_NO_PROBE_ROW && s->h_df[v] != 0) *shape = SH_GALLOP_PHRASE;
