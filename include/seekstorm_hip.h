@@ -174,6 +174,13 @@ int ss_bm25_upload_positions(ss_shard* s, uint64_t n_docs, const uint8_t* doclen
  * (index.rs:5110).  The call replaces the set (n = 0 clears it); it applies to lexical and vector searches alike: a
  * deleted doc is skipped before it counts or ranks (add_result.rs:3435, union.rs:975, vector.rs:1450-1452). */
 int ss_set_deleted(ss_shard* s, const uint64_t* doc_ids, uint64_t n);
+/* delete_document / delete_documents (index.rs:5099-5140): the docs are ADDED to the set, which is otherwise left as it is.  The ids go
+ * up, a scatter kernel ORs their bits into the bitmap and counts those that were clear before -- the set's size stays the number of
+ * distinct docs whatever the call repeats or the set already held --, and the bitmap grows when an id lies beyond its words: O(n), not
+ * O(set).  Afterwards every entry answers as after ss_set_deleted(old set + doc_ids).  n = 0: nothing happens.  Arguments as
+ * ss_set_deleted's: an id >= 0xFFFFFFFF is SS_EINVAL and changes nothing.  The call holds the shard lock with the shard's streams idle,
+ * as ss_set_deleted does: a search sees none or all of it. */
+int ss_add_deleted(ss_shard* s, const uint64_t* doc_ids, uint64_t n);
 
 /* Same image from the reference's own in-RAM block format (first step of SURVEY section 8 f-1): one ss_ref_block per
  * (term, 65 536-doc block) = BlockObjectIndex (index.rs:781-789) + the key-body byte array of the segment the posting
@@ -586,6 +593,40 @@ typedef struct ss_facet_filter {
 #define SS_FACET_HI_INCLUSIVE 1u
 #define SS_FACET_LO_EXCLUSIVE 2u
 int ss_facet_upload(ss_shard* s, uint64_t n_docs, uint32_t record_size, const uint8_t* records);
+/* The facet image committed LEVEL BY LEVEL, by the level rules of ss_bm25_append_level: records = the facet.bin records of docs
+ * [level * 65536, level * 65536 + n_level_docs); level = the number of complete levels held (an append) or the last level (its
+ * re-commit, commit.rs:204-206, which never shrinks it); only the last level may hold fewer than 65 536 docs.  The first call on a shard
+ * without facet records creates the image (level 0); an image that came from ss_facet_upload is continued the same way (70 000 docs =
+ * level 0 and a partial level 1) -- and ss_facet_upload in turn drops the reserved room and the rank tables below with the image it
+ * replaces.  O(level): the records are staged in a scratch buffer, checked against the rank tables, and copied behind or over the
+ * image's rows; when the room is used up the image (and every rank column) moves into one half as large again, ss_facet_reserve takes
+ * the room for n_docs_cap docs once (before the first level too).  The number of docs is bumped under the shard lock with the shard's
+ * streams idle.  More records than the lexical image has docs is legal: a host appends the facets FIRST and commits the lexical level
+ * second, and no query meets SS_ESTATE in between.
+ * SS_EINVAL, before anything is touched: a null argument, n_level_docs 0 or above 65 536, a record_size other than the image's, a level
+ * beyond the next one or older than the last, a new level while the last is incomplete, a shrinking re-commit, a record whose id of a
+ * registered string facet lies beyond its table (ss_facet_set_string_ranks comes first).  A refused or failed call leaves records,
+ * doc count, capacity and rank columns as they were -- but for SS_EDEVICE out of the final device-to-device copies of a RE-COMMIT, which
+ * write over the last level's rows in place: part of the new level may then stand under the old doc count.
+ * ss_facet_info: docs held, record size, docs there is room for, rank tables registered (any pointer may be NULL). */
+int ss_facet_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t record_size, const uint8_t* records);
+int ss_facet_reserve(ss_shard* s, uint64_t n_docs_cap);
+int ss_facet_info(ss_shard* s, uint64_t* n_docs, uint32_t* record_size, uint64_t* capacity_docs, uint32_t* n_rank_tables);
+/* STRING facets sort by their strings, which live in the host's facet.json.  ss_facet_set_string_ranks hands over what the order needs:
+ * rank[id] = the rank of value id `id`'s string in Rust's String order (byte-wise UTF-8; equal strings share a rank; a StringSet facet:
+ * the rank of its first string -- the comparisons of min_heap.rs:860-976), O(distinct values).  The device materialises one u32 column
+ * doc -> rank per registered (facet_offset, facet_type) with a gather kernel, and ss_bm25_search_sorted / ss_docs_search then accept
+ * that field as a sort field (deep pages included; string and numeric fields mix freely).  Setting a table again -- new strings moved
+ * the ranks -- re-derives the column; ss_facet_append_level extends it with the table in force, so: the table for the new id space
+ * first, then the level.  A table may name ids no doc holds yet.  n_ids = 0 (rank may be NULL): the table is forgotten.
+ * SS_EINVAL: a type other than SS_FACET_STRING16 / _STRING32, an offset beyond the record, a doc whose id is >= n_ids (the crate would
+ * panic on it) -- the table and column in force stay.  SS_ENOTSUP: more than SS_MAX_STRING_RANKS tables.  SS_ESTATE: no facet records.
+ * ss_facet_string_ranks: out_rank[i] = the rank of doc_ids[i] in that column (0xFFFFFFFF: a doc beyond the records) -- what a merge of
+ * several shards' sorted answers compares (result_ordering_root), given that every shard's table came from ONE order over the union of
+ * all shards' strings.  SS_ESTATE without a table for (facet_offset, facet_type). */
+#define SS_MAX_STRING_RANKS 8
+int ss_facet_set_string_ranks(ss_shard* s, uint32_t facet_offset, uint32_t facet_type, uint32_t n_ids, const uint32_t* rank);
+int ss_facet_string_ranks(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t facet_offset, uint32_t facet_type, uint32_t* out_rank);
 int ss_bm25_search_filtered(ss_shard* s, uint32_t n_queries, const ss_bm25_query* queries, uint32_t k, uint32_t result_type,
                             uint32_t n_filters, const ss_facet_filter* filters /* host */, uint32_t* out_doc, float* out_score,
                             uint32_t* out_count, uint64_t* out_total);
@@ -619,8 +660,8 @@ int ss_bm25_facet_count(ss_shard* s, const ss_bm25_query* query, uint32_t n_filt
  * the pivot is the worst match).  The top-k under the sort is then: the n_better docs of a search filtered to "better than
  * the pivot" (SS_FACET_LO_EXCLUSIVE / _HI_INCLUSIVE) ordered by their values (ss_facet_values), followed by the best
  * k - n_better docs of a search filtered to "equal to the pivot" -- by the next sort field the same way, by score when none
- * is left.  String facets sort by their strings: SS_ENOTSUP on the id column itself -- the host appends a u32 rank column
- * (rank of each id's string) to the records it uploads and sorts by that.
+ * is left.  String facets sort by their strings: SS_ENOTSUP here -- ss_bm25_search_sorted sorts by them once the host has set their
+ * rank table (ss_facet_set_string_ranks); a host may also append a u32 rank column to the records it uploads and sort by that.
  * ss_facet_values: the stored bits of a facet for a list of docs (host arrays).
  * Point facets: the *_point entry points take the base point; the value that is counted into ranges (Ranges::Point,
  * add_result.rs:605-618; bounds = f64 bits of the distances), selected (morton_ordering, min_heap.rs:510-528 /
@@ -633,7 +674,8 @@ int ss_facet_values(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t f
  * back to back on the device (the prefix never visits the host), leaving two doc sets -- the docs that are in the answer for sure
  * (strictly better than a pivot at some field) and the tie group of the last pivot --, which two ordinary searches under exclusion
  * bitmaps turn into scored lists and a compose kernel orders by (field 1, ..., field n, score desc, doc asc).  The host only
- * launches: one synchronisation per call.  n_sorts <= SS_MAX_SORT_FIELDS numeric or Point fields (n_sorts = 0: by score alone);
+ * launches: one synchronisation per call.  n_sorts <= SS_MAX_SORT_FIELDS numeric or Point fields (n_sorts = 0: by score alone), or
+ * String16 / String32 fields with a rank table (ss_facet_set_string_ranks; SS_ENOTSUP without one);
  * every list of every query needs a probe row (SS_ENOTSUP otherwise, as for ss_bm25_facet_kth); phrase queries are answered as
  * ss_bm25_facet_count answers them (a chunk of <= 64 queries that holds one runs its two searches query by query).
  * out_doc / out_score [n_queries][k], out_count [n_queries], out_total [n_queries] = all matches of the query.
@@ -642,7 +684,8 @@ int ss_facet_values(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t f
 #define SS_MAX_SORT_FIELDS 4
 typedef struct ss_result_sort {   /* search.rs ResultSort */
   uint32_t facet_offset;
-  uint32_t facet_type;            /* SS_FACET_U8 .. SS_FACET_F64, or SS_FACET_POINT: by simplified_distance to the base */
+  uint32_t facet_type;            /* SS_FACET_U8 .. SS_FACET_F64; SS_FACET_POINT: by simplified_distance to the base;
+                                     SS_FACET_STRING16 / _STRING32: by the strings' ranks (ss_facet_set_string_ranks) */
   uint32_t descending;            /* SortOrder */
   uint32_t reserved;
   double base_lat, base_lon;      /* Point facets */
@@ -692,7 +735,8 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* 
  * out_doc [k]: the docs of rank [skip, skip + k) in that order; *out_count = their number = min(k, matches - skip); the slots beyond
  * them are NOT written.  skip and k may be anything: by doc id alone (n_sorts = 0) a page of any depth is one pass over a bitmap of the
  * docs; under a sort the ranks [0, skip + k) are found in passes of SS_MAX_K as ss_bm25_search_sorted finds a deep page.
- * sorts: exactly ss_bm25_search_sorted's (numeric and Point fields, at most SS_MAX_SORT_FIELDS; -0.0 ties +0.0, NaN out of scope).
+ * sorts: exactly ss_bm25_search_sorted's (numeric and Point fields, string fields with a rank table, at most SS_MAX_SORT_FIELDS; -0.0
+ * ties +0.0, NaN out of scope).
  * The facet arguments and out_facet_counts [sum_f (n_buckets[f] + 1)]: ss_bm25_search_facets' for one query (n_facets = 0: none, the
  * pointers may be NULL).
  * result_type: SS_RT_COUNT -- no docs (out_doc may be NULL, *out_count = 0), *out_total and the facet counts exact;
@@ -700,7 +744,7 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* 
  * ss_bm25_search_facets leaves them for SS_RT_TOPK: the counters are counted all the same, *out_total is only promised to be
  * >= *out_count (the crate's Topk bumps neither, add_result.rs:226-230).
  * SS_ESTATE: no lexical image; filters, sorts or facets without facet records for every doc of it.  SS_EINVAL: a result type, facet
- * type or unit out of range, a string sort field, more than SS_MAX_SORT_FIELDS / SS_MAX_QUERY_FACETS / SS_MAX_FACET_FILTERS, an offset
+ * type or unit out of range, a string sort field without a rank table, more than SS_MAX_SORT_FIELDS / SS_MAX_QUERY_FACETS / SS_MAX_FACET_FILTERS, an offset
  * beyond the record, k = 0 with a result type that wants docs.  Never SS_ENOTSUP: no posting list is read, so probe rows, the sparse
  * tier, the number of indexed fields and the probe budget make no difference. */
 int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t result_type, uint32_t doc_ascending,

@@ -74,6 +74,7 @@ class ResultSortC(C.Structure):  # ss_result_sort
 
 
 SS_MAX_SORT_FIELDS = 4
+SS_MAX_STRING_RANKS = 8
 
 
 class VecLevelC(C.Structure):  # ss_vec_level
@@ -94,6 +95,7 @@ SYMBOLS = [
     ("ss_shard_destroy", C.c_int, [C.c_void_p]),
     ("ss_shard_sync", C.c_int, [C.c_void_p]),
     ("ss_set_deleted", C.c_int, [C.c_void_p, u64p, C.c_uint64]),
+    ("ss_add_deleted", C.c_int, [C.c_void_p, u64p, C.c_uint64]),
     ("ss_bm25_upload", C.c_int, [C.c_void_p, C.c_uint64, u8p, C.c_uint32, u64p, u32p, u16p]),
     ("ss_bm25_upload_positions", C.c_int, [C.c_void_p, C.c_uint64, u8p, C.c_uint32, u64p, u32p, u16p, u16p, C.c_uint64]),
     ("ss_bm25_fields_info", C.c_int, [C.c_void_p, u32p, u32p, u32p]),
@@ -155,6 +157,11 @@ SYMBOLS = [
     ("ss_vec_search_i8_dev", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("ss_facet_upload", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    ("ss_facet_append_level", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u8p]),
+    ("ss_facet_reserve", C.c_int, [C.c_void_p, C.c_uint64]),
+    ("ss_facet_info", C.c_int, [C.c_void_p, u64p, u32p, u64p, u32p]),
+    ("ss_facet_set_string_ranks", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p]),
+    ("ss_facet_string_ranks", C.c_int, [C.c_void_p, C.c_uint32, u32p, C.c_uint32, C.c_uint32, u32p]),
     ("ss_bm25_search_filtered", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, u32p,
                                           f32p, u32p, u64p]),
     ("ss_bm25_search_filtered_dev", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -2,6 +2,7 @@
 // selection of a bitmap's docs by doc id.  Internal.
 #pragma once
 #include "ss_common.h"
+#include "facet_commit.h"
 
 constexpr uint32_t BROWSE_SLICE = 256;  // 64-bit words of a bitmap per slice (= per workgroup): 16384 docs
 inline uint64_t browse_slices(uint64_t groups) { return (groups + BROWSE_SLICE - 1) / BROWSE_SLICE; }
@@ -19,5 +20,5 @@ int ssi_browse_select(ss_shard* s, const unsigned long long* d_bits, bool descen
 int ssi_browse_clear(ss_shard* s, unsigned long long* d_bits, const uint32_t* d_docs, uint32_t n, unsigned long long* d_count, hipStream_t st);
 // facet.hip: the compose step of a sorted browse (sort_compose_kernel's browse instances)
 int ssi_sort_compose_browse(ss_shard* s, const uint32_t* a_doc, const uint32_t* a_cnt, const uint32_t* c_doc, const uint32_t* c_cnt,
-                            const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k, bool doc_ascending,
-                            uint32_t* out_doc, uint32_t* out_count, unsigned long long* out_total, hipStream_t st);
+                            const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts, const ss_sort_sources& src, uint32_t k,
+                            bool doc_ascending, uint32_t* out_doc, uint32_t* out_count, unsigned long long* out_total, hipStream_t st);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "facet_point.h"
+#include "facet_commit.h"
 #include "bit_select.h"
 
 struct FacetFilters {
@@ -412,8 +413,25 @@ struct SortState { unsigned long long prefix, want, n_better, n_equal, count_e, 
 struct SortFieldsDev {
   uint32_t n;
   uint32_t offset[SS_MAX_SORT_FIELDS], type[SS_MAX_SORT_FIELDS], bytes[SS_MAX_SORT_FIELDS], desc[SS_MAX_SORT_FIELDS];
+  const uint8_t* base[SS_MAX_SORT_FIELDS];  // where the field's keys live: the facet records, or a string facet's rank column
+  uint32_t stride[SS_MAX_SORT_FIELDS];
   FacetPoint pt[SS_MAX_SORT_FIELDS];
 };
+// where every sort field's key is read (facet_commit.h ss_sort_sources)
+int ssi_sort_resolve(const ss_shard* s, uint32_t n_sorts, const ss_result_sort* sorts, ss_sort_sources* out) {
+  memset(out, 0, sizeof(*out));
+  if (n_sorts > SS_MAX_SORT_FIELDS) return SS_EINVAL;
+  for (uint32_t f = 0; f < n_sorts; f++) {
+    if (sorts[f].facet_type == SS_FACET_STRING16 || sorts[f].facet_type == SS_FACET_STRING32) {
+      const uint32_t* col = ssi_facet_rank_column(s, sorts[f].facet_offset, sorts[f].facet_type);
+      if (!col) return SS_ENOTSUP;  // no table: the strings live in the host's facet.json
+      out->base[f] = (const uint8_t*)col; out->stride[f] = 4u; out->offset[f] = 0u; out->type[f] = SS_FACET_U32;
+    } else {
+      out->base[f] = s->d_facets; out->stride[f] = s->facet_record_size; out->offset[f] = sorts[f].facet_offset; out->type[f] = sorts[f].facet_type;
+    }
+  }
+  return SS_OK;
+}
 
 // (every kernel below: blockIdx.y / blockIdx.x of the one-block kernels = the query of the batch; bit sets [nq][groups], states [nq],
 // histograms [nq][256])
@@ -533,8 +551,8 @@ template <int BROWSE>
 __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __restrict__ a_doc, const float* __restrict__ a_score,
                                                             const uint32_t* __restrict__ a_cnt, const uint32_t* __restrict__ c_doc,
                                                             const float* __restrict__ c_score, const uint32_t* __restrict__ c_cnt,
-                                                            const unsigned long long* __restrict__ total, const uint8_t* __restrict__ records,
-                                                            uint32_t record_size, unsigned long long n_facet_docs, SortFieldsDev F, uint32_t k,
+                                                            const unsigned long long* __restrict__ total, unsigned long long n_facet_docs,
+                                                            SortFieldsDev F, uint32_t k,
                                                             uint32_t* __restrict__ out_doc, float* __restrict__ out_score,
                                                             uint32_t* __restrict__ out_count, unsigned long long* __restrict__ out_total) {
   __shared__ unsigned long long key[SS_MAX_SORT_FIELDS][1024];
@@ -553,7 +571,7 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
     unsigned long long kk = 0ull;
     if (i < na && f < F.n && dc[i] < n_facet_docs) {
       uint32_t ty = F.type[f];
-      const unsigned long long v = facet_load(records + (size_t)dc[i] * record_size + F.offset[f], F.bytes[f], ty, F.pt[f]);
+      const unsigned long long v = facet_load(F.base[f] + (size_t)dc[i] * F.stride[f] + F.offset[f], F.bytes[f], ty, F.pt[f]);
       kk = facet_order_key(v, ty, 8u * F.bytes[f], F.desc[f] != 0u);
     }
     key[f][i] = kk;
@@ -588,14 +606,14 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
 // bit sets [nq][groups], d_total / d_state [nq], d_hist [nq][256].  d_ex_b = nullptr: no exclusion bitmaps (ss_docs_search reads B and E)
 int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned long long* d_B, unsigned long long* d_ex_b, unsigned long long* d_ex_e,
                     const unsigned long long* d_total, unsigned long long* d_hist, void* d_state, uint32_t n_sorts, const ss_result_sort* sorts,
-                    uint32_t k, hipStream_t st) {
+                    const ss_sort_sources& src, uint32_t k, hipStream_t st) {
   const unsigned long long n_docs = s->bm_n_docs, groups = (unsigned long long)s->bm_n_sub * (BM_SUB / 64);
   const dim3 grid((unsigned)((groups + 255) / 256), nq);
   SortState* state = (SortState*)d_state;
   SS_HIP(hipMemsetAsync(d_B, 0, (size_t)nq * groups * 8, st));
   sort_begin_kernel<<<nq, 64, 0, st>>>(state, d_total, (unsigned long long)k);
   for (uint32_t f = 0; f < n_sorts; f++) {
-    const uint32_t type = sorts[f].facet_type;
+    const uint32_t type = src.type[f];
     FacetPoint pt{0, 0, 0};
     if (type == SS_FACET_POINT) {
       const ss_facet_point base{sorts[f].base_lat, sorts[f].base_lon, SS_POINT_SORTKEY, 0};
@@ -604,11 +622,11 @@ int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned 
     const uint32_t key_bits = 8u * ssi_facet_width(type);
     sort_level_begin_kernel<<<nq, 256, 0, st>>>(state, d_hist);
     for (uint32_t b = 0; b < key_bits / 8u; b++) {
-      sort_radix_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, s->d_facets, s->facet_record_size, sorts[f].facet_offset, type, key_bits,
+      sort_radix_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, src.base[f], src.stride[f], src.offset[f], type, key_bits,
                                               sorts[f].descending ? 1u : 0u, state, b, d_hist, pt);
       sort_decide_kernel<<<nq, 256, 0, st>>>(state, d_hist);
     }
-    sort_classify_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, s->d_facets, s->facet_record_size, sorts[f].facet_offset, type, key_bits,
+    sort_classify_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, src.base[f], src.stride[f], src.offset[f], type, key_bits,
                                                sorts[f].descending ? 1u : 0u, state, pt);
     sort_level_end_kernel<<<nq, 64, 0, st>>>(state);
   }
@@ -616,12 +634,13 @@ int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned 
   SS_HIP(hipGetLastError());
   return SS_OK;
 }
-static int sort_fields_dev(uint32_t n_sorts, const ss_result_sort* sorts, SortFieldsDev* out) {
+static int sort_fields_dev(uint32_t n_sorts, const ss_result_sort* sorts, const ss_sort_sources& src, SortFieldsDev* out) {
   SortFieldsDev& F = *out;
   memset(&F, 0, sizeof(F));
   F.n = n_sorts;
   for (uint32_t f = 0; f < n_sorts; f++) {
-    F.offset[f] = sorts[f].facet_offset; F.type[f] = sorts[f].facet_type; F.bytes[f] = ssi_facet_width(sorts[f].facet_type); F.desc[f] = sorts[f].descending ? 1u : 0u;
+    F.base[f] = src.base[f]; F.stride[f] = src.stride[f];
+    F.offset[f] = src.offset[f]; F.type[f] = src.type[f]; F.bytes[f] = ssi_facet_width(src.type[f]); F.desc[f] = sorts[f].descending ? 1u : 0u;
     if (sorts[f].facet_type == SS_FACET_POINT) {
       const ss_facet_point base{sorts[f].base_lat, sorts[f].base_lon, SS_POINT_SORTKEY, 0};
       if (facet_point_of(&base, &F.pt[f]) != SS_OK) return SS_EINVAL;
@@ -631,33 +650,50 @@ static int sort_fields_dev(uint32_t n_sorts, const ss_result_sort* sorts, SortFi
 }
 // the browse order of ONE answer (ss_docs_search): list A by (sort keys, doc id), then the first k - |A| of list C; no scores
 int ssi_sort_compose_browse(ss_shard* s, const uint32_t* a_doc, const uint32_t* a_cnt, const uint32_t* c_doc, const uint32_t* c_cnt,
-                            const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k, bool doc_ascending,
-                            uint32_t* out_doc, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
+                            const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts, const ss_sort_sources& src, uint32_t k,
+                            bool doc_ascending, uint32_t* out_doc, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
   if (k == 0 || k > 1024u) return SS_EINVAL;  // (one tuple per thread)
   SortFieldsDev F;
-  if (sort_fields_dev(n_sorts, sorts, &F) != SS_OK) return SS_EINVAL;
+  if (sort_fields_dev(n_sorts, sorts, src, &F) != SS_OK) return SS_EINVAL;
   if (doc_ascending)
-    sort_compose_kernel<2><<<1, 1024, 0, st>>>(a_doc, nullptr, a_cnt, c_doc, nullptr, c_cnt, d_total, s->d_facets, s->facet_record_size,
-                                                (unsigned long long)s->facet_docs, F, k, out_doc, nullptr, out_count, out_total);
+    sort_compose_kernel<2><<<1, 1024, 0, st>>>(a_doc, nullptr, a_cnt, c_doc, nullptr, c_cnt, d_total, (unsigned long long)s->facet_docs, F, k,
+                                                out_doc, nullptr, out_count, out_total);
   else
-    sort_compose_kernel<1><<<1, 1024, 0, st>>>(a_doc, nullptr, a_cnt, c_doc, nullptr, c_cnt, d_total, s->d_facets, s->facet_record_size,
-                                                (unsigned long long)s->facet_docs, F, k, out_doc, nullptr, out_count, out_total);
+    sort_compose_kernel<1><<<1, 1024, 0, st>>>(a_doc, nullptr, a_cnt, c_doc, nullptr, c_cnt, d_total, (unsigned long long)s->facet_docs, F, k,
+                                                out_doc, nullptr, out_count, out_total);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }
 // lists [nq][k], counts / totals / outputs per query
 int ssi_sort_compose(ss_shard* s, uint32_t nq, const uint32_t* a_doc, const float* a_score, const uint32_t* a_cnt, const uint32_t* c_doc,
                      const float* c_score, const uint32_t* c_cnt, const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts,
-                     uint32_t k, uint32_t* out_doc, float* out_score, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
+                     const ss_sort_sources& src, uint32_t k, uint32_t* out_doc, float* out_score, uint32_t* out_count, unsigned long long* out_total,
+                     hipStream_t st) {
   SortFieldsDev F;
-  if (sort_fields_dev(n_sorts, sorts, &F) != SS_OK) return SS_EINVAL;
-  sort_compose_kernel<0><<<nq, 1024, 0, st>>>(a_doc, a_score, a_cnt, c_doc, c_score, c_cnt, d_total, s->d_facets, s->facet_record_size,
-                                           (unsigned long long)s->facet_docs, F, k, out_doc, out_score, out_count, out_total);
+  if (sort_fields_dev(n_sorts, sorts, src, &F) != SS_OK) return SS_EINVAL;
+  sort_compose_kernel<0><<<nq, 1024, 0, st>>>(a_doc, a_score, a_cnt, c_doc, c_score, c_cnt, d_total, (unsigned long long)s->facet_docs, F, k,
+                                           out_doc, out_score, out_count, out_total);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }
 
-// the signatures ss_common.h declares: no base point
+// the signatures ss_common.h declares: the sort's sources resolved here
+int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned long long* d_B, unsigned long long* d_ex_b, unsigned long long* d_ex_e,
+                    const unsigned long long* d_total, unsigned long long* d_hist, void* d_state, uint32_t n_sorts, const ss_result_sort* sorts,
+                    uint32_t k, hipStream_t st) {
+  ss_sort_sources src;
+  const int rc = ssi_sort_resolve(s, n_sorts, sorts, &src);
+  return rc != SS_OK ? rc : ssi_sort_select(s, nq, d_E, d_B, d_ex_b, d_ex_e, d_total, d_hist, d_state, n_sorts, sorts, src, k, st);
+}
+int ssi_sort_compose(ss_shard* s, uint32_t nq, const uint32_t* a_doc, const float* a_score, const uint32_t* a_cnt, const uint32_t* c_doc,
+                     const float* c_score, const uint32_t* c_cnt, const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts,
+                     uint32_t k, uint32_t* out_doc, float* out_score, uint32_t* out_count, unsigned long long* out_total, hipStream_t st) {
+  ss_sort_sources src;
+  const int rc = ssi_sort_resolve(s, n_sorts, sorts, &src);
+  return rc != SS_OK ? rc : ssi_sort_compose(s, nq, a_doc, a_score, a_cnt, c_doc, c_score, c_cnt, d_total, n_sorts, sorts, src, k, out_doc, out_score,
+                                             out_count, out_total, st);
+}
+// ... no base point
 int ssi_facet_kth(ss_shard* s, const unsigned long long* d_bits, uint64_t n_docs, uint64_t n_matches, uint32_t offset, uint32_t type,
                   bool descending, uint64_t k, unsigned long long* d_hist, uint64_t* value_bits, uint64_t* n_better, uint64_t* n_equal,
                   hipStream_t st) {

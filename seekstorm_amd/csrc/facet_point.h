@@ -4,7 +4,7 @@
 #include "ss_common.h"
 
 // bytes a facet of `type` (<= SS_FACET_POINT, checked by the caller) takes in the record; a Point is its 8-byte Morton code.  (The
-// sorts never read a string's: they refuse string facets first.)  The kernels keep their own device-side tables.
+// sorts never read a string's id: a string sort field resolves to its u32 rank column, facet_commit.h, or is refused.)  The kernels keep their own device-side tables.
 inline uint32_t ssi_facet_width(uint32_t type) {
   static const uint8_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
   return width[type];

@@ -26,6 +26,7 @@
 #include "bm25_match.h"
 #include "bm25_pack.h"
 #include "browse.h"
+#include "facet_commit.h"
 
 #define SS_TRY(x)          \
   do {                     \
@@ -354,6 +355,7 @@ int ss_shard_destroy(ss_shard* s) {
   free_vec(s);
   free_bm25(s);
   ssi_mf_levels_drop(s);
+  ssi_facet_side_drop(s);
   for (void* p_ : {(void*)s->d_vq, (void*)s->d_vdoc, (void*)s->d_vscore, (void*)s->d_vcount, (void*)s->d_vtotal}) if (p_) (void)hipFree(p_);
   void* ptrs[] = {s->d_qstage, s->d_out_doc, s->d_out_score, s->d_out_count, s->d_out_total, s->d_bq, s->d_deleted, s->d_facets, s->d_filter_bits, s->d_facet_ws, s->d_pool_stage, s->d_tier_ws, s->d_tier_hold, s->d_excl_bits, s->d_sort_ws, s->d_route_ws, s->d_peel_bits, s->d_gate_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -1052,10 +1054,255 @@ int ss_facet_upload(ss_shard* s, uint64_t n_docs, uint32_t record_size, const ui
   SS_HIP(hipStreamSynchronize(s->stream));
   if (s->d_facets) { (void)hipFree(s->d_facets); s->d_facets = nullptr; }
   s->facet_docs = 0; s->facet_record_size = 0;
+  ssi_facet_side_drop(s);  // the reserved room and the rank tables described the image that went
   SS_HIP(hipMalloc(&s->d_facets, (size_t)n_docs * record_size));
   SS_HIP(hipMemcpy(s->d_facets, records, (size_t)n_docs * record_size, hipMemcpyHostToDevice));
   s->facet_docs = n_docs;
   s->facet_record_size = record_size;
+  return SS_OK;
+}
+
+// ---- the facet image committed level by level (facet_commit.h): the records of one 65 536-doc level behind (an append) or over (the
+// re-commit of the last level) the image's rows, every registered rank column extended with them.  O(level); nothing of the shard is
+// read but -- when the room is used up -- one device-to-device copy into an image half as large again.
+extern "C++" {
+namespace {
+// the shard's streams and the callers' own (filtered searches on their streams read the records) idle; caller holds the lock
+int facet_quiesce(ss_shard* s) {
+  if (s->vstream) (void)hipStreamSynchronize(s->vstream);
+  SS_HIP(hipSetDevice(s->device));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  SS_HIP(hipDeviceSynchronize());
+  return SS_OK;
+}
+struct DevBuf {  // a scratch device block freed when the call returns
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t bytes) { SS_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); return SS_OK; }
+};
+template <typename T>
+void swap_in(T*& dst, DevBuf& b) {  // the block becomes the shard's, the shard's old one is the DevBuf's to free
+  T* old = dst;
+  dst = (T*)b.p;
+  b.p = old;
+}
+}  // namespace
+}  // extern "C++"
+
+int ss_facet_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t record_size, const uint8_t* records) {
+  if (!s || !records || n_level_docs == 0 || n_level_docs > 65536u || record_size == 0) return SS_EINVAL;
+  ShardLock g(s);
+  const bool have = s->d_facets != nullptr;
+  const uint64_t old_docs = have ? s->facet_docs : 0, base_doc = (uint64_t)level * 65536u, new_docs = base_doc + n_level_docs;
+  if (have) {
+    if (record_size != s->facet_record_size) return SS_EINVAL;
+    const uint64_t last = (old_docs - 1) / 65536u;  // the last level held (an image holds at least one doc)
+    const bool last_full = old_docs % 65536u == 0;
+    if (level < last || level > last + 1) return SS_EINVAL;         // older than the last level, beyond the next one
+    if (level == last + 1 && !last_full) return SS_EINVAL;          // only the last level may be partial
+    if (level == last && new_docs < old_docs) return SS_EINVAL;     // a re-committed level never shrinks
+  } else if (level != 0) {
+    return SS_EINVAL;
+  }
+  if (new_docs > 0xFFFFFFFEull) return SS_ENOTSUP;
+  SS_TRY(facet_quiesce(s));
+  ss_facet_side* S = ssi_facet_side(s, true);
+  if (!S) return SS_ENOMEM;
+  const uint32_t n_ranks = have ? S->n_ranks : 0u;
+  // staged aside and checked: the level's records, and for every registered string facet the level's slice of the rank column.  The
+  // 64-bit counter of ids beyond a table stands at the HEAD of the block (hipMalloc's alignment: the gather kernel adds to it
+  // atomically, which wants 8 bytes' alignment whatever the level's size), records and column slices behind it at multiples of 256
+  const size_t level_bytes = (size_t)n_level_docs * record_size, o_rec = 256, o_cols = o_rec + ((level_bytes + 255) & ~(size_t)255);
+  DevBuf stage;
+  SS_TRY(stage.alloc(o_cols + (size_t)n_ranks * n_level_docs * 4));
+  unsigned long long* d_bad = (unsigned long long*)stage.p;
+  uint8_t* d_stage = (uint8_t*)stage.p + o_rec;
+  uint32_t* d_cols = (uint32_t*)((uint8_t*)stage.p + o_cols);
+  SS_HIP(hipMemcpyAsync(d_stage, records, level_bytes, hipMemcpyHostToDevice, s->stream));
+  SS_HIP(hipMemsetAsync(d_bad, 0, 8, s->stream));
+  for (uint32_t r = 0; r < n_ranks; r++) {
+    const ss_facet_rank& R = S->ranks[r];
+    SS_TRY(ssi_facet_rank_gather(d_stage, record_size, R.offset, R.type, n_level_docs, R.d_rank, R.n_ids,
+                                 d_cols + (size_t)r * n_level_docs, d_bad, s->stream));
+  }
+  unsigned long long bad = 0;
+  SS_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s->stream));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  if (bad) return SS_EINVAL;  // an id beyond a registered table: the table for the new id space comes first
+  // room: the arrays as they are, or -- all allocated before anything is swapped -- their successors with the old rows copied over
+  const uint64_t cap = have ? std::max<uint64_t>(S->cap_docs, old_docs) : 0;
+  uint64_t new_cap = cap;
+  uint8_t* img = s->d_facets;
+  DevBuf grown[1 + SS_MAX_STRING_RANKS];
+  if (new_docs > cap) {
+    new_cap = have ? std::max<uint64_t>(new_docs, cap + cap / 2) : std::max<uint64_t>(new_docs, S->cap_docs);
+    SS_TRY(grown[0].alloc((size_t)new_cap * record_size));
+    img = (uint8_t*)grown[0].p;
+    if (have) SS_HIP(hipMemcpyAsync(img, s->d_facets, (size_t)old_docs * record_size, hipMemcpyDeviceToDevice, s->stream));
+    for (uint32_t r = 0; r < n_ranks; r++) {
+      SS_TRY(grown[1 + r].alloc((size_t)new_cap * 4));
+      SS_HIP(hipMemcpyAsync(grown[1 + r].p, S->ranks[r].d_col, (size_t)old_docs * 4, hipMemcpyDeviceToDevice, s->stream));
+    }
+  }
+  // Everything that can be refused or run out of memory lies behind; what follows are device-to-device copies.  Into room that was
+  // free, or into the successors, they touch nothing a reader sees before the doc count moves; the re-commit of the last level writes
+  // over that level's rows IN PLACE, so a device error from here on (SS_EDEVICE: the device is lost to the shard anyway) may leave
+  // part of the new level under the old doc count -- the one exception to "a failed call changes nothing" (seekstorm_hip.h).
+  SS_HIP(hipMemcpyAsync(img + (size_t)base_doc * record_size, d_stage, level_bytes, hipMemcpyDeviceToDevice, s->stream));
+  for (uint32_t r = 0; r < n_ranks; r++) {
+    uint32_t* col = new_docs > cap ? (uint32_t*)grown[1 + r].p : S->ranks[r].d_col;
+    SS_HIP(hipMemcpyAsync(col + base_doc, d_cols + (size_t)r * n_level_docs, (size_t)n_level_docs * 4, hipMemcpyDeviceToDevice, s->stream));
+  }
+  SS_HIP(hipStreamSynchronize(s->stream));
+  if (new_docs > cap) {  // the swap: the old arrays leave with the DevBufs
+    swap_in(s->d_facets, grown[0]);
+    for (uint32_t r = 0; r < n_ranks; r++) swap_in(S->ranks[r].d_col, grown[1 + r]);
+  }
+  S->cap_docs = new_cap;
+  s->facet_docs = new_docs;
+  s->facet_record_size = record_size;
+  return SS_OK;
+}
+
+int ss_facet_reserve(ss_shard* s, uint64_t n_docs_cap) {
+  if (!s) return SS_EINVAL;
+  if (n_docs_cap > 0xFFFFFFFEull) return SS_ENOTSUP;
+  ShardLock g(s);
+  ss_facet_side* S = ssi_facet_side(s, true);
+  if (!S) return SS_ENOMEM;
+  if (!s->d_facets) {  // no image yet: the first level takes the room
+    S->cap_docs = std::max(S->cap_docs, n_docs_cap);
+    return SS_OK;
+  }
+  const uint64_t cap = std::max<uint64_t>(S->cap_docs, s->facet_docs);
+  if (n_docs_cap <= cap) { S->cap_docs = cap; return SS_OK; }
+  SS_TRY(facet_quiesce(s));
+  DevBuf grown[1 + SS_MAX_STRING_RANKS];
+  SS_TRY(grown[0].alloc((size_t)n_docs_cap * s->facet_record_size));
+  SS_HIP(hipMemcpy(grown[0].p, s->d_facets, (size_t)s->facet_docs * s->facet_record_size, hipMemcpyDeviceToDevice));
+  for (uint32_t r = 0; r < S->n_ranks; r++) {
+    SS_TRY(grown[1 + r].alloc((size_t)n_docs_cap * 4));
+    SS_HIP(hipMemcpy(grown[1 + r].p, S->ranks[r].d_col, (size_t)s->facet_docs * 4, hipMemcpyDeviceToDevice));
+  }
+  swap_in(s->d_facets, grown[0]);
+  for (uint32_t r = 0; r < S->n_ranks; r++) swap_in(S->ranks[r].d_col, grown[1 + r]);
+  S->cap_docs = n_docs_cap;
+  return SS_OK;
+}
+
+int ss_facet_info(ss_shard* s, uint64_t* n_docs, uint32_t* record_size, uint64_t* capacity_docs, uint32_t* n_rank_tables) {
+  if (!s) return SS_EINVAL;
+  ShardLock g(s);
+  const ss_facet_side* S = ssi_facet_side(s, false);
+  const uint64_t docs = s->d_facets ? s->facet_docs : 0;
+  if (n_docs) *n_docs = docs;
+  if (record_size) *record_size = s->d_facets ? s->facet_record_size : 0u;
+  if (capacity_docs) *capacity_docs = std::max<uint64_t>(S ? S->cap_docs : 0, docs);
+  if (n_rank_tables) *n_rank_tables = S && s->d_facets ? S->n_ranks : 0u;
+  return SS_OK;
+}
+
+// String sorts: the host's table id -> rank (O(distinct values)), the device's column doc -> rank (one gather per table or commit)
+int ss_facet_set_string_ranks(ss_shard* s, uint32_t facet_offset, uint32_t facet_type, uint32_t n_ids, const uint32_t* rank) {
+  if (!s || (n_ids && !rank)) return SS_EINVAL;
+  if (facet_type != SS_FACET_STRING16 && facet_type != SS_FACET_STRING32) return SS_EINVAL;
+  ShardLock g(s);
+  if (!s->d_facets) return SS_ESTATE;
+  if ((uint64_t)facet_offset + ssi_facet_width(facet_type) > s->facet_record_size) return SS_EINVAL;
+  ss_facet_side* S = ssi_facet_side(s, true);
+  if (!S) return SS_ENOMEM;
+  uint32_t at = 0;
+  while (at < S->n_ranks && !(S->ranks[at].offset == facet_offset && S->ranks[at].type == facet_type)) at++;
+  if (n_ids == 0) {  // forget the table
+    if (at == S->n_ranks) return SS_OK;
+    SS_TRY(facet_quiesce(s));
+    (void)hipFree(S->ranks[at].d_rank);
+    (void)hipFree(S->ranks[at].d_col);
+    for (uint32_t i = at; i + 1 < S->n_ranks; i++) S->ranks[i] = S->ranks[i + 1];
+    S->ranks[--S->n_ranks] = ss_facet_rank{};
+    return SS_OK;
+  }
+  if (at == S->n_ranks && S->n_ranks == SS_MAX_STRING_RANKS) return SS_ENOTSUP;
+  SS_TRY(facet_quiesce(s));
+  const uint64_t cap = std::max<uint64_t>(S->cap_docs, s->facet_docs);
+  DevBuf tab, col, cnt;  // built aside: the table and column in force stay until the new ones are whole
+  SS_TRY(tab.alloc((size_t)n_ids * 4));
+  SS_TRY(col.alloc((size_t)cap * 4));
+  SS_TRY(cnt.alloc(8));
+  SS_HIP(hipMemcpyAsync(tab.p, rank, (size_t)n_ids * 4, hipMemcpyHostToDevice, s->stream));
+  SS_HIP(hipMemsetAsync(cnt.p, 0, 8, s->stream));
+  SS_TRY(ssi_facet_rank_gather(s->d_facets, s->facet_record_size, facet_offset, facet_type, s->facet_docs, (const uint32_t*)tab.p, n_ids,
+                               (uint32_t*)col.p, (unsigned long long*)cnt.p, s->stream));
+  unsigned long long bad = 0;
+  SS_HIP(hipMemcpyAsync(&bad, cnt.p, 8, hipMemcpyDeviceToHost, s->stream));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  if (bad) return SS_EINVAL;  // a doc holds an id the table does not name (the crate would panic on it)
+  ss_facet_rank& R = S->ranks[at];
+  swap_in(R.d_rank, tab);
+  swap_in(R.d_col, col);
+  R.offset = facet_offset; R.type = facet_type; R.n_ids = n_ids;
+  if (at == S->n_ranks) S->n_ranks++;
+  S->cap_docs = cap;
+  return SS_OK;
+}
+
+int ss_facet_string_ranks(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t facet_offset, uint32_t facet_type, uint32_t* out_rank) {
+  if (!s || (n && (!doc_ids || !out_rank))) return SS_EINVAL;
+  if (facet_type != SS_FACET_STRING16 && facet_type != SS_FACET_STRING32) return SS_EINVAL;
+  ShardLock g(s);
+  const uint32_t* d_col = s->d_facets ? ssi_facet_rank_column(s, facet_offset, facet_type) : nullptr;
+  if (!d_col) return SS_ESTATE;
+  if (n == 0) return SS_OK;
+  SS_HIP(hipSetDevice(s->device));
+  SS_TRY(ensure_qstage(s, (size_t)n * 8));
+  uint32_t *d_out = (uint32_t*)s->d_qstage, *d_docs = d_out + n;
+  SS_HIP(hipMemcpyAsync(d_docs, doc_ids, (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
+  SS_TRY(ssi_facet_rank_read(d_col, s->facet_docs, d_docs, n, d_out, s->stream));
+  SS_HIP(hipMemcpyAsync(out_rank, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  return SS_OK;
+}
+
+// delete_document / delete_documents (index.rs:5099-5140): docs ADDED to the tombstone set -- the ids go up, a scatter kernel ORs their
+// bits in and counts those that were clear, so n_deleted stays the number of distinct docs.  The bitmap grows when an id lies beyond
+// its words (then to cover every doc of the images, so that the deletes that follow find their words).
+int ss_add_deleted(ss_shard* s, const uint64_t* doc_ids, uint64_t n) {
+  if (!s || (n && !doc_ids)) return SS_EINVAL;
+  uint64_t mx = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (doc_ids[i] >= 0xFFFFFFFFull) return SS_EINVAL;
+    mx = std::max(mx, doc_ids[i]);
+  }
+  if (n == 0) return SS_OK;
+  std::vector<uint32_t> ids(doc_ids, doc_ids + n);
+  ShardLock g(s);
+  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call writes; none starts while mu is ours)
+  SS_HIP(hipSetDevice(s->device));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  const uint64_t old_words = s->d_deleted ? s->deleted_words : 0;
+  uint64_t words = old_words;
+  DevBuf stage, grown;
+  if ((mx >> 5) + 1 > old_words) {
+    const uint64_t docs = std::max<uint64_t>(std::max<uint64_t>(s->bm_n_docs, s->facet_docs), s->n_rows);
+    words = std::max<uint64_t>((mx >> 5) + 1, (docs + 31) / 32);
+    SS_TRY(grown.alloc((size_t)words * 4));
+    if (old_words) SS_HIP(hipMemcpyAsync(grown.p, s->d_deleted, (size_t)old_words * 4, hipMemcpyDeviceToDevice, s->stream));
+    SS_HIP(hipMemsetAsync((uint32_t*)grown.p + old_words, 0, (size_t)(words - old_words) * 4, s->stream));
+  }
+  SS_TRY(stage.alloc((size_t)n * 4 + 8));
+  unsigned long long* d_new = (unsigned long long*)stage.p;
+  SS_HIP(hipMemsetAsync(d_new, 0, 8, s->stream));
+  SS_HIP(hipMemcpyAsync(d_new + 1, ids.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
+  SS_TRY(ssi_deleted_scatter(grown.p ? (uint32_t*)grown.p : s->d_deleted, (const uint32_t*)(d_new + 1), n, d_new, s->stream));
+  unsigned long long fresh = 0;
+  SS_HIP(hipMemcpyAsync(&fresh, d_new, 8, hipMemcpyDeviceToHost, s->stream));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  // (Without growth the scatter wrote the live bitmap: had the read-back or the wait above failed, bits would stand that n_deleted
+  // does not count.  Harmless: a live bitmap means n_deleted != 0 -- ss_set_deleted frees it with the last doc --, which is all the
+  // kernels ask of the number, and a set bit only ever says "deleted", which the caller asked for.)
+  if (grown.p) swap_in(s->d_deleted, grown);  // (the old bitmap leaves with the DevBuf)
+  s->deleted_words = words;
+  s->n_deleted = (old_words ? s->n_deleted : 0) + fresh;
   return SS_OK;
 }
 
@@ -3457,7 +3704,8 @@ int ss_bm25_facet_kth_point(ss_shard* s, const ss_bm25_query* query, uint32_t n_
 // classification -> the exclusion bitmaps -> TWO batched searches, each query inside its own doc set (the pruned kernel's filtered
 // instances take one bitmap per query) -> compose into the queries' output rows.  One synchronisation per call.  A chunk the pruned
 // kernel does not serve (k > 128, more than 4 lists per query, the exhaustive strategy) runs its searches query by query instead.
-static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
+static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
+                                     const ss_sort_sources& src, uint32_t k,
                                      uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                                      uint64_t* out_total) {
   if (!s->d_post) return SS_ESTATE;
@@ -3495,7 +3743,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
     MatchBatchInfo b;
     SS_TRY(match_prepare(s, nb, qc, &mc, &b));
     SS_TRY(match_enqueue(s, nb, qc, mc, n_filters, filters, false, d_q, (ss_bm25_query*)(W + o_sub), (ss_bm25_query*)(W + o_ph), d_E, d_total));
-    SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, k, s->stream));
+    SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, src, k, s->stream));
     bool batched = !batched_off && !mc.tier.any_tiered && !mc.any_phrase();
     for (int part = 0; part < 2 && batched; part++) {  // both searches as ONE batch each: every query under its own exclusion bitmap
       ExclSwap sw(s, (uint32_t*)(part == 0 ? d_xb : d_xe), groups * 2);
@@ -3519,7 +3767,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
         }
     }
     SS_TRY(ssi_sort_compose(s, nb, (const uint32_t*)(W + o_ad), (const float*)(W + o_as), (const uint32_t*)(W + o_ac), (const uint32_t*)(W + o_cd),
-                            (const float*)(W + o_cs), (const uint32_t*)(W + o_cc), d_total, n_sorts, sorts, k, (uint32_t*)(W + o_od) + (size_t)c0 * k,
+                            (const float*)(W + o_cs), (const uint32_t*)(W + o_cc), d_total, n_sorts, sorts, src, k, (uint32_t*)(W + o_od) + (size_t)c0 * k,
                             (float*)(W + o_os) + (size_t)c0 * k, (uint32_t*)(W + o_oc) + c0, (unsigned long long*)(W + o_ot) + c0, s->stream));
   }
   SS_HIP(hipMemcpyAsync(out_doc, W + o_od, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s->stream));
@@ -3539,10 +3787,13 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   if (n_sorts > SS_MAX_SORT_FIELDS) return SS_ENOTSUP;
   for (uint32_t f = 0; f < n_sorts; f++) {
     if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
-    if (sorts[f].facet_type == SS_FACET_STRING16 || sorts[f].facet_type == SS_FACET_STRING32) return SS_ENOTSUP;  // by their strings: the host's rank column
   }
   ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
-  if (k <= SS_MAX_K) return bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+  // where every field's key is read, resolved once for the call.  A string field sorts by the rank column of
+  // ss_facet_set_string_ranks; without a table SS_ENOTSUP: the host's own rank column
+  ss_sort_sources src;
+  SS_TRY(ssi_sort_resolve(s, n_sorts, sorts, &src));
+  if (k <= SS_MAX_K) return bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
   // a DEEP page sorted by facets: the order is total (field 1, ..., field n, score desc, doc asc), so it is peeled like any other ("deep
   // pages" above) -- query by query, every pass the sorted search of SS_MAX_K results under (tombstones | the docs of the earlier passes);
   // a facet filter's bitmap is built on top of that inside the pass
@@ -3564,7 +3815,7 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
       const uint32_t kk = std::min<uint32_t>(SS_MAX_K, k - got);
       uint32_t c = 0;
       uint64_t t = 0;
-      SS_TRY(bm25_search_sorted_locked(s, 1, queries + i, n_sorts, sorts, kk, n_filters, filters, h_doc.data(), h_score.data(), &c, &t));
+      SS_TRY(bm25_search_sorted_locked(s, 1, queries + i, n_sorts, sorts, src, kk, n_filters, filters, h_doc.data(), h_score.data(), &c, &t));
       if (pass == 0) total = t;
       c = std::min(c, kk);
       memcpy(out_doc + (size_t)i * k + got, h_doc.data(), (size_t)c * sizeof(uint32_t));
@@ -3696,12 +3947,14 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t
   if (want_docs && (k == 0 || !out_doc)) return SS_EINVAL;
   if (n_sorts > SS_MAX_SORT_FIELDS || (n_sorts && !sorts) || n_filters > SS_MAX_FACET_FILTERS || (n_filters && !filters)) return SS_EINVAL;
   for (uint32_t f = 0; f < n_sorts; f++)
-    if (sorts[f].facet_type > SS_FACET_POINT || sorts[f].facet_type == SS_FACET_STRING16 || sorts[f].facet_type == SS_FACET_STRING32) return SS_EINVAL;
+    if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
   if (n_facets > SS_MAX_QUERY_FACETS || (n_facets && (!facet_offset || !facet_type || !n_buckets || !out_facet_counts))) return SS_EINVAL;
   size_t n_bounds = 0, stride = 0;
   SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
   if (n_bounds && !range_lower_bounds) return SS_EINVAL;
   ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
+  ss_sort_sources src;  // where every sort field's key is read, resolved once for the call
+  if (ssi_sort_resolve(s, n_sorts, sorts, &src) != SS_OK) return SS_EINVAL;  // a string sort field without a rank table (ss_facet_set_string_ranks)
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
   if ((n_sorts || n_filters || n_facets) && (!s->d_facets || s->facet_docs < s->bm_n_docs)) return SS_ESTATE;
@@ -3774,12 +4027,12 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t
     for (uint64_t got = 0; rc == SS_OK && got < n_rank;) {
       const uint32_t kk = (uint32_t)std::min<uint64_t>(SS_MAX_K, n_rank - got);
       if (!hip_ok(hipMemcpyAsync(d_E, d_M, groups * 8, hipMemcpyDeviceToDevice, s->stream))) break;
-      rc = ssi_sort_select(s, 1, d_E, d_B, nullptr, nullptr, d_head + 1, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, kk, s->stream);
+      rc = ssi_sort_select(s, 1, d_E, d_B, nullptr, nullptr, d_head + 1, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, src, kk, s->stream);
       // list A: all of B (fewer than kk docs); list C: the best kk of the last pivot's tie group by doc id, of which the compose takes kk - |A|
       if (rc == SS_OK) rc = ssi_browse_select(s, d_B, descending, 0, kk, d_scnt, d_sbeg, false, d_a, d_n + 1, s->stream);
       if (rc == SS_OK) rc = ssi_browse_select(s, d_E, descending, 0, kk, d_scnt, d_sbeg, false, d_c, d_n + 2, s->stream);
       if (rc == SS_OK)
-        rc = ssi_sort_compose_browse(s, d_a, d_n + 1, d_c, d_n + 2, d_head, n_sorts, sorts, kk, !descending, d_out + got, d_n + 3, d_head + 2, s->stream);
+        rc = ssi_sort_compose_browse(s, d_a, d_n + 1, d_c, d_n + 2, d_head, n_sorts, sorts, src, kk, !descending, d_out + got, d_n + 3, d_head + 2, s->stream);
       if (rc == SS_OK && got + kk < n_rank) rc = ssi_browse_clear(s, d_M, d_out + got, kk, d_head + 1, s->stream);  // (deep: every pass is full)
       got += kk;
     }

@@ -232,6 +232,56 @@ uint32_t ssh_string_rank_column(const uint8_t* records, uint64_t n_docs, uint32_
   std::memcpy(out, r.data(), r.size());
   return off;
 }
+// NUL-separated strings -> a vector (n_strings entries)
+static std::vector<std::string> split_strings(const char* strings, uint64_t strings_len, uint32_t n_strings) {
+  std::vector<std::string> v;
+  const char* p = strings;
+  const char* end = strings + strings_len;
+  for (uint32_t i = 0; i < n_strings && p <= end; i++) {
+    const char* q = (const char*)memchr(p, 0, (size_t)(end - p));
+    if (!q) q = end;
+    v.emplace_back(p, q);
+    p = q + 1;
+  }
+  return v;
+}
+// string_ranks: the table of ss_facet_set_string_ranks for a NUL-separated buffer of strings; out_rank [n_strings]
+void ssh_string_ranks(const char* strings, uint64_t strings_len, uint32_t n_strings, uint32_t* out_rank) {
+  const std::vector<uint32_t> r = string_ranks(split_strings(strings, strings_len, n_strings));
+  std::memcpy(out_rank, r.data(), r.size() * sizeof(uint32_t));
+}
+// the facet commit seam of one shard
+int ssh_append_facet_level(ssh_index* ix, int shard, uint32_t level, uint32_t n_level_docs, uint32_t record_size, const uint8_t* records) {
+  return ix->shards[shard]->append_facet_level(level, n_level_docs, record_size, records);
+}
+int ssh_reserve_facets(ssh_index* ix, int shard, uint64_t n_docs_cap) { return ix->shards[shard]->reserve_facets(n_docs_cap); }
+int ssh_facet_info(ssh_index* ix, int shard, uint64_t* n_docs, uint32_t* record_size, uint64_t* capacity_docs, uint32_t* n_rank_tables) {
+  return ix->shards[shard]->facet_info(n_docs, record_size, capacity_docs, n_rank_tables);
+}
+int ssh_set_string_facet_ranks(ssh_index* ix, int shard, uint32_t facet_offset, uint32_t facet_type, const char* strings, uint64_t strings_len,
+                               uint32_t n_strings) {
+  return ix->shards[shard]->set_string_facet_ranks(facet_offset, facet_type, split_strings(strings, strings_len, n_strings));
+}
+// Index::set_string_facet_ranks: the shards' strings back to back, n_strings [shards] of them each
+int ssh_index_set_string_facet_ranks(ssh_index* ix, uint32_t facet_offset, uint32_t facet_type, const char* strings, uint64_t strings_len,
+                                     const uint32_t* n_strings) {
+  uint32_t total = 0;
+  for (size_t i = 0; i < ix->shards.size(); i++) total += n_strings[i];
+  const std::vector<std::string> all = split_strings(strings, strings_len, total);
+  std::vector<std::vector<std::string>> per(ix->shards.size());
+  size_t at = 0;
+  for (size_t i = 0; i < ix->shards.size(); i++) {
+    for (uint32_t j = 0; j < n_strings[i] && at < all.size(); j++) per[i].push_back(all[at++]);
+  }
+  if (!ix->index) ix->index.reset(new Index(ix->shards));
+  return ix->index->set_string_facet_ranks(facet_offset, facet_type, per);
+}
+int ssh_string_facet_ranks(ssh_index* ix, int shard, const uint32_t* doc_ids, uint32_t n, uint32_t facet_offset, uint32_t facet_type, uint32_t* out_rank) {
+  std::vector<uint32_t> r;
+  const int rc = ix->shards[shard]->string_facet_ranks(std::vector<uint32_t>(doc_ids, doc_ids + n), facet_offset, facet_type, &r);
+  if (rc == SS_OK) std::memcpy(out_rank, r.data(), r.size() * sizeof(uint32_t));
+  return rc;
+}
 // Index::search, lexical mode, with the seam's NOT terms and field filter
 int ssh_search_lexical_ex(ssh_index* ix, const uint32_t* terms, uint32_t n_terms, uint32_t query_type, uint32_t offset, uint32_t length,
                           uint32_t result_type, const uint32_t* not_terms, uint32_t n_not, const uint16_t* field_filter, uint32_t n_ff,
@@ -270,6 +320,7 @@ int ssh_upload_lexical_fields_positions(ssh_index* ix, int shard, uint64_t n_doc
   return ix->shards[shard]->upload_lexical_fields(n_docs, n_fields, doclen, boost, n_terms, offs, docs, fields, tfs, positions, n_positions);
 }
 int ssh_set_deleted(ssh_index* ix, int shard, const uint64_t* doc_ids, uint64_t n) { return ix->shards[shard]->set_deleted(doc_ids, n); }
+int ssh_add_deleted(ssh_index* ix, int shard, const uint64_t* doc_ids, uint64_t n) { return ix->shards[shard]->add_deleted(doc_ids, n); }
 int ssh_commit_level(ssh_index* ix, int shard, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms,
                      uint32_t n_dense_terms, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, const uint16_t* positions,
                      uint64_t n_positions) {

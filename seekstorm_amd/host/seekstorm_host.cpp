@@ -272,6 +272,13 @@ int Shard::set_deleted(const uint64_t* doc_ids, uint64_t n) {
   return rc;
 }
 
+int Shard::add_deleted(const uint64_t* doc_ids, uint64_t n) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  const int rc = ss_add_deleted(h_, doc_ids, n);
+  if (rc == SS_OK) n_deleted_ += n;  // (read as "any": an upper bound of the set's size)
+  return rc;
+}
+
 int Shard::synth_lexical(uint64_t seed, uint64_t n_docs, uint32_t n_terms, const uint32_t* thresh32,
                          const uint8_t* len_table1024) {
   if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
@@ -344,6 +351,31 @@ int Shard::make_query(const std::vector<uint32_t>& terms, QueryType qt, ss_bm25_
 int Shard::upload_facets(uint64_t n_docs, uint32_t record_size, const uint8_t* records) {
   if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
   return ss_facet_upload(h_, n_docs, record_size, records);
+}
+
+int Shard::append_facet_level(uint32_t level, uint32_t n_level_docs, uint32_t record_size, const uint8_t* records) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  return ss_facet_append_level(h_, level, n_level_docs, record_size, records);
+}
+int Shard::reserve_facets(uint64_t n_docs_cap) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  return ss_facet_reserve(h_, n_docs_cap);
+}
+int Shard::facet_info(uint64_t* n_docs, uint32_t* record_size, uint64_t* capacity_docs, uint32_t* n_rank_tables) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  return ss_facet_info(h_, n_docs, record_size, capacity_docs, n_rank_tables);
+}
+int Shard::set_string_facet_ranks(uint32_t facet_offset, uint32_t facet_type, const std::vector<std::string>& strings,
+                                  const std::vector<std::string>* order) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  const std::vector<uint32_t> rank = string_ranks(strings, order);
+  return ss_facet_set_string_ranks(h_, facet_offset, facet_type, (uint32_t)rank.size(), rank.empty() ? nullptr : rank.data());
+}
+int Shard::string_facet_ranks(const std::vector<uint32_t>& doc_ids, uint32_t facet_offset, uint32_t facet_type, std::vector<uint32_t>* ranks) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  if (!ranks) return SS_EINVAL;
+  ranks->assign(doc_ids.size(), 0);
+  return ss_facet_string_ranks(h_, (uint32_t)doc_ids.size(), doc_ids.data(), facet_offset, facet_type, ranks->data());
 }
 
 // all_terms_frequent (intersection.rs:198-209), evaluated where the reference evaluates it -- on the host, per query:
@@ -602,6 +634,20 @@ std::vector<uint8_t> string_facet_rank_column(const uint8_t* records, uint64_t n
   return out;
 }
 
+std::vector<uint32_t> string_ranks(const std::vector<std::string>& strings, const std::vector<std::string>* order) {
+  std::vector<std::string> own;
+  if (!order) {
+    own = strings;
+    std::sort(own.begin(), own.end());  // std::string compares bytes as unsigned chars: Rust's String order
+    own.erase(std::unique(own.begin(), own.end()), own.end());
+    order = &own;
+  }
+  std::vector<uint32_t> rank(strings.size());
+  for (size_t i = 0; i < strings.size(); i++)
+    rank[i] = (uint32_t)(std::lower_bound(order->begin(), order->end(), strings[i]) - order->begin());
+  return rank;
+}
+
 ss_facet_filter point_facet_filter(uint32_t facet_offset, const double base[2], double lo, double hi, uint32_t unit, uint32_t flags) {
   ss_facet_filter f;
   std::memset(&f, 0, sizeof(f));
@@ -731,12 +777,18 @@ int Shard::sort_keys(const std::vector<uint32_t>& doc_ids, const ResultSort& sf,
   if (sf.facet_type == SS_FACET_POINT) {
     const ss_facet_point base{sf.base[0], sf.base[1], SS_POINT_SORTKEY, 0};
     rc = ss_facet_point_distances(h_, (uint32_t)doc_ids.size(), doc_ids.data(), sf.facet_offset, &base, keys->data());
+  } else if (sf.facet_type == SS_FACET_STRING16 || sf.facet_type == SS_FACET_STRING32) {  // the ranks of the strings: a u32 key
+    std::vector<uint32_t> ranks;
+    rc = string_facet_ranks(doc_ids, sf.facet_offset, sf.facet_type, &ranks);
+    for (size_t i = 0; i < ranks.size(); i++) (*keys)[i] = ranks[i];
   } else {
     if (sf.facet_type > SS_FACET_F64) return SS_ENOTSUP;
     rc = ss_facet_values(h_, (uint32_t)doc_ids.size(), doc_ids.data(), sf.facet_offset, sf.facet_type, keys->data());
   }
   if (rc != SS_OK) return rc;
-  const uint32_t kt = sf.facet_type == SS_FACET_POINT ? (uint32_t)SS_FACET_F64 : sf.facet_type;
+  const uint32_t kt = sf.facet_type == SS_FACET_POINT ? (uint32_t)SS_FACET_F64
+                      : sf.facet_type > SS_FACET_F64  ? (uint32_t)SS_FACET_U32
+                                                      : sf.facet_type;
   for (uint64_t& x : *keys) x = order_key(x, kt, sf.descending);
   return SS_OK;
 }
@@ -877,6 +929,19 @@ ResultObject Shard::search_vector_shard(const float* query_vector, size_t length
                                         const AnnMode& ann_mode, const std::vector<uint16_t>& field_filter) {
   if (!query_vector) return ResultObject();
   return std::move(search_vector_batch(query_vector, 1, length, similarity_threshold, ann_mode, field_filter)[0]);
+}
+
+int Index::set_string_facet_ranks(uint32_t facet_offset, uint32_t facet_type, const std::vector<std::vector<std::string>>& strings_per_shard) {
+  if (strings_per_shard.size() != shards_.size()) return SS_EINVAL;
+  std::vector<std::string> order;
+  for (const std::vector<std::string>& v : strings_per_shard) order.insert(order.end(), v.begin(), v.end());
+  std::sort(order.begin(), order.end());
+  order.erase(std::unique(order.begin(), order.end()), order.end());
+  for (size_t i = 0; i < shards_.size(); i++) {
+    const int rc = shards_[i]->set_string_facet_ranks(facet_offset, facet_type, strings_per_shard[i], &order);
+    if (rc != SS_OK) return rc;
+  }
+  return SS_OK;
 }
 
 ResultObject Index::search_lexical_sorted(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset, size_t length,

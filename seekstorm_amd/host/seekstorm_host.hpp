@@ -108,6 +108,10 @@ struct ResultSort {
 // *rank_offset = the column's offset.
 std::vector<uint8_t> string_facet_rank_column(const uint8_t* records, uint64_t n_docs, uint32_t record_size, uint32_t facet_offset,
                                               uint32_t facet_type, const std::vector<std::string>& strings, uint32_t* rank_offset);
+// The same order WITHOUT a host-built column: rank[id] of strings[id] (equal strings share a rank) -- the table of
+// Shard::set_string_facet_ranks.  order: the sorted distinct strings to rank in (nullptr: those of `strings`; an index of several
+// shards passes the union of all shards' strings, so that the ranks compare across shards -- Index::set_string_facet_ranks).
+std::vector<uint32_t> string_ranks(const std::vector<std::string>& strings, const std::vector<std::string>* order = nullptr);
 // FacetFilter::Point (search.rs:852-859) as an ss_facet_filter: the distance to base inside [lo, hi), unit SS_POINT_KM / _MILES
 ss_facet_filter point_facet_filter(uint32_t facet_offset, const double base[2], double lo, double hi, uint32_t unit, uint32_t flags = 0);
 
@@ -199,6 +203,8 @@ class Shard {
   bool euclidean() const { return euclidean_; }
   // delete_hashset (index.rs:1594): replaces the tombstone set; delete_document (index.rs:5110) re-sends it
   int set_deleted(const uint64_t* doc_ids, uint64_t n);
+  // delete_document / delete_documents (index.rs:5099-5140): the docs are ADDED to the set on the device (ss_add_deleted), O(n)
+  int add_deleted(const uint64_t* doc_ids, uint64_t n);
   int synth_lexical(uint64_t seed, uint64_t n_docs, uint32_t n_terms, const uint32_t* thresh32, const uint8_t* len_table1024);
   int synth_vectors(uint64_t seed, uint64_t n_rows, uint32_t dim);
 
@@ -255,6 +261,17 @@ class Shard {
   // sets SS_OP_ALL_TERMS_FREQUENT on *q when the reference's condition holds for this shard and top_k (intersection.rs:198-209)
   bool mark_all_terms_frequent(ss_bm25_query* q, size_t top_k) const;
   int upload_facets(uint64_t n_docs, uint32_t record_size, const uint8_t* records);  // facet.bin records
+  // the facet.bin records of ONE committed level -- docs [level * 65536, level * 65536 + n_level_docs) -- behind the image or over its
+  // last level (ss_facet_append_level, O(level)).  In a commit the facets go first, the lexical level second.
+  int append_facet_level(uint32_t level, uint32_t n_level_docs, uint32_t record_size, const uint8_t* records);
+  int reserve_facets(uint64_t n_docs_cap);  // room for that many records, taken once
+  int facet_info(uint64_t* n_docs, uint32_t* record_size, uint64_t* capacity_docs, uint32_t* n_rank_tables);
+  // Result sort by a String16 / String32 facet: strings[id] = the facet value of id (facet.json).  The host ranks the distinct values
+  // (string_ranks), the device keeps a doc -> rank column and extends it at every append_facet_level; a ResultSort of the facet's own
+  // (offset, type) then sorts by it.  New strings: the table for the new id space first, then the level.  Empty strings: forget it.
+  int set_string_facet_ranks(uint32_t facet_offset, uint32_t facet_type, const std::vector<std::string>& strings,
+                             const std::vector<std::string>* order = nullptr);
+  int string_facet_ranks(const std::vector<uint32_t>& doc_ids, uint32_t facet_offset, uint32_t facet_type, std::vector<uint32_t>* ranks);
   std::vector<ResultObject> search_vector_batch(const float* query_vectors, size_t n_queries, size_t k,
                                                 const float* similarity_threshold, const AnnMode& ann_mode = AnnMode(),
                                                 const std::vector<uint16_t>& field_filter = {});
@@ -296,6 +313,9 @@ class Index {
   std::vector<ResultObject> search_lexical_batch(const std::vector<std::vector<uint32_t>>& query_terms, QueryType query_type_default,
                                                  size_t k, ResultType result_type);
   Shard& shard(size_t i) { return *shards_[i]; }
+  // Result sort by a string facet across shards: strings_per_shard[i][id] = the facet value of id in shard i.  ONE rank order over the
+  // union of all shards' strings, every shard's table set from it: the ranks the shards sort by are the ranks the merge compares.
+  int set_string_facet_ranks(uint32_t facet_offset, uint32_t facet_type, const std::vector<std::vector<std::string>>& strings_per_shard);
   // search() for SearchMode::Lexical with result_sort: every shard returns its best offset + length under the sort
   // (Shard::search_lexical_shard with result_sort), the lists are merged under the same order across shards -- the facet
   // values of the two docs, each read from its own shard, then the score (result_ordering_root, min_heap.rs:56-300;

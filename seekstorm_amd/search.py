@@ -666,6 +666,13 @@ class Shard:
         N.check(N.lib().ss_set_deleted(self._h, N.ptr(ids, N.u64p) if len(ids) else None, len(ids)), "ss_set_deleted")
         self._n_deleted = len(ids)
 
+    def add_deleted(self, doc_ids):
+        """delete_document / delete_documents (index.rs:5099-5140): the docs are ADDED to the tombstone set -- O(len(doc_ids)), the set
+        in force is not sent again; duplicates and docs already deleted count once (ss_add_deleted)"""
+        ids = np.ascontiguousarray(doc_ids, np.uint64)
+        N.check(N.lib().ss_add_deleted(self._h, N.ptr(ids, N.u64p) if len(ids) else None, len(ids)), "ss_add_deleted")
+        self._n_deleted = getattr(self, "_n_deleted", 0) + len(ids)  # (read as "any": an upper bound of the set's size)
+
     def synth_partition(self, shard_id, n_shards):
         """the following synth_* calls build shard `shard_id` of `n_shards` of one generator stream (doc g -> shard g % S)"""
         N.check(N.lib().ss_synth_set_partition(self._h, int(shard_id), int(n_shards)), "ss_synth_set_partition")
@@ -868,6 +875,55 @@ class Shard:
             r = np.ascontiguousarray(records, np.uint8)
         N.check(N.lib().ss_facet_upload(self._h, r.shape[0], r.shape[1], r.ctypes.data), "ss_facet_upload")
 
+    def append_facet_level(self, level, records, record_size=None):
+        """the facet.bin records of ONE committed level -- docs [level * 65536, level * 65536 + len(records)) -- behind the image (level =
+        the number of complete levels) or over its last level (a re-commit, which never shrinks it): ss_facet_append_level, O(level).
+        Registered string rank columns (set_string_facet_ranks) are extended on the device.  In a commit the facets go FIRST, the lexical
+        level second: no query meets the image with fewer facet records than docs."""
+        if isinstance(records, (bytes, bytearray, memoryview)):
+            r = np.frombuffer(bytes(records), np.uint8).reshape(-1, int(record_size))
+        else:
+            r = np.ascontiguousarray(records, np.uint8)
+        N.check(N.lib().ss_facet_append_level(self._h, int(level), r.shape[0], r.shape[1], N.ptr(r, N.u8p)), "ss_facet_append_level")
+
+    def reserve_facets(self, n_docs_cap):
+        """room for n_docs_cap facet records (and rank columns), taken once: appends inside it copy nothing but the level"""
+        N.check(N.lib().ss_facet_reserve(self._h, int(n_docs_cap)), "ss_facet_reserve")
+
+    def facet_info(self):
+        """(docs with facet records, record size, docs there is room for, string rank tables registered)"""
+        n, rs, cap, nt = C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint32()
+        N.check(N.lib().ss_facet_info(self._h, C.byref(n), C.byref(rs), C.byref(cap), C.byref(nt)), "ss_facet_info")
+        return n.value, rs.value, cap.value, nt.value
+
+    @staticmethod
+    def string_ranks(strings, order=None):
+        """rank[id] of strings[id] in Rust's String order (byte-wise UTF-8), equal strings sharing a rank: the table of
+        ss_facet_set_string_ranks.  order: the sorted distinct UTF-8 byte strings to rank in (default: those of `strings`; several
+        shards pass the union of all their strings, so that ranks compare across shards -- Index.set_string_facet_ranks)."""
+        keys = [str(x).encode("utf-8") for x in strings]
+        if order is None:
+            order = sorted(set(keys))
+        rank_of = {kb: i for i, kb in enumerate(order)}
+        return np.array([rank_of[kb] for kb in keys], np.uint32)
+
+    def set_string_facet_ranks(self, facet_offset, facet_type, strings, order=None):
+        """Result sort by a String16 / String32 facet WITHOUT a host-built column: strings[id] = the facet value of id (facet.json; a
+        StringSet facet: its first string).  The host ranks the distinct values (string_ranks), the device keeps a doc -> rank column
+        and extends it at every append_facet_level; result_sort then takes (offset, "string16" | "string32", descending).  New strings:
+        set the table for the new id space first, then append the level.  strings = None or empty: the table is forgotten."""
+        rank = self.string_ranks(strings, order) if strings is not None and len(strings) else np.zeros(0, np.uint32)
+        N.check(N.lib().ss_facet_set_string_ranks(self._h, int(facet_offset), N.FACET_TYPES[facet_type], len(rank),
+                                                  N.ptr(rank, N.u32p) if len(rank) else None), "ss_facet_set_string_ranks")
+
+    def string_facet_ranks(self, doc_ids, facet_offset, facet_type):
+        """the ranks of the docs' strings under the table in force (what a merge across shards compares): ss_facet_string_ranks"""
+        d = np.ascontiguousarray(doc_ids, np.uint32)
+        out = np.zeros(len(d), np.uint32)
+        N.check(N.lib().ss_facet_string_ranks(self._h, len(d), N.ptr(d, N.u32p), int(facet_offset), N.FACET_TYPES[facet_type],
+                                              N.ptr(out, N.u32p)), "ss_facet_string_ranks")
+        return out
+
     @staticmethod
     def facet_filters(filters):
         """[(offset, type, lo, hi)] for numeric facets -- passes iff lo <= value < hi, Rust's Range --,
@@ -1005,7 +1061,8 @@ class Shard:
 
     @staticmethod
     def _result_sorts(result_sort):
-        """result_sort = [(facet offset, type, descending[, base])] -> (n, ss_result_sort array)"""
+        """result_sort = [(facet offset, type, descending[, base])] -> (n, ss_result_sort array); type "string16" / "string32": by the
+        strings' ranks, once set_string_facet_ranks has registered the facet"""
         n = len(result_sort)
         arr = (N.ResultSortC * max(n, 1))()
         for i, sf in enumerate(result_sort):
@@ -1606,6 +1663,16 @@ def rrf_merge_device(lex_doc, lex_count, vec_doc, vec_count, offset, length, str
     return od, os_, src, cnt
 
 
+def _sort_key_values(sh, doc_ids, sf):
+    """(stored bits, type) of sort field sf for docs of shard sh, as Shard._facet_order_key takes them: a Point field's distances, a
+    string field's ranks (Shard.set_string_facet_ranks), else the facet's values"""
+    if sf[1] == "point":
+        return sh.facet_point_distances(doc_ids, sf[0], sf[3], "sortkey").view(np.uint64), "f64"
+    if sf[1] in ("string16", "string32"):
+        return sh.string_facet_ranks(doc_ids, sf[0], sf[1]), "u32"
+    return sh.facet_values(doc_ids, sf[0], sf[1]), sf[1]
+
+
 class Index:
     """In-process multi-shard index: doc g lives in shard g % S with local id g // S (index.rs:5284)."""
 
@@ -1615,6 +1682,16 @@ class Index:
     @property
     def shard_number(self):
         return len(self.shards)
+
+    def set_string_facet_ranks(self, facet_offset, facet_type, strings_per_shard):
+        """Result sort by a string facet across shards: strings_per_shard[i][id] = the facet value of id in shard i (each shard has its
+        own ids).  ONE rank order over the union of all shards' strings, every shard's table set from it -- so the ranks the shards sort
+        by are the ranks the merge compares (result_ordering_root)."""
+        if len(strings_per_shard) != self.shard_number:
+            raise ValueError("one string list per shard")
+        order = sorted({str(x).encode("utf-8") for strings in strings_per_shard for x in strings})
+        for sh, strings in zip(self.shards, strings_per_shard):
+            sh.set_string_facet_ranks(facet_offset, facet_type, strings, order)
 
     def search(self, query_terms: Optional[Sequence[int]] = None, query_vector=None,
                query_type_default=QueryType.Union, search_mode=SearchMode.Lexical, offset=0, length=10,
@@ -1650,10 +1727,7 @@ class Index:
                 ro.result_count_total += tot
                 keys = []
                 for sf in result_sort:
-                    if sf[1] == "point":
-                        vals, ty = sh.facet_point_distances(d, sf[0], sf[3], "sortkey").view(np.uint64), "f64"
-                    else:
-                        vals, ty = sh.facet_values(d, sf[0], sf[1]), sf[1]
+                    vals, ty = _sort_key_values(sh, d, sf)
                     keys.append([Shard._facet_order_key(x, ty, sf[2]) for x in vals])
                 for i in range(len(d)):
                     rows.append((tuple(-kk[i] for kk in keys), -float(sc[i]), int(d[i]) * S + sh.shard_id))
@@ -1730,10 +1804,7 @@ class Index:
                 shard_maps.append(finish_facets(query_facets, per, S))
             keys = []
             for sf in fsorts:
-                if sf[1] == "point":
-                    vals, ty = sh.facet_point_distances(d, sf[0], sf[3], "sortkey").view(np.uint64), "f64"
-                else:
-                    vals, ty = sh.facet_values(d, sf[0], sf[1]), sf[1]
+                vals, ty = _sort_key_values(sh, d, sf)
                 keys.append([Shard._facet_order_key(x, ty, sf[2]) for x in vals])
             for i in range(len(d)):
                 g = int(d[i]) * S + sh.shard_id
