@@ -17,6 +17,8 @@
  *                    <- facet_filter / query_facets of search_lexical_shard (add_result.rs:341-640)
  *   ss_bm25_search_facets
  *                    <- the same search returning ResultObject.facets beside its hits (add_result.rs:487-643, search.rs:3598-3760)
+ *   ss_bm25_search_sorted_facets
+ *                    <- the same search under a result_sort, facets and sorted hits from one match set (min_heap.rs:574-1050)
  *   ss_docs_search   <- the empty query: the query_list_len == 0 arm of search_lexical_shard -> search_iterator_shard
  *                       (search.rs:3374-3386, iterator.rs:316-358)
  *   ss_index_bin_*, ss_ref_decode_block*, ss_vec_upload_vector_bin*
@@ -726,6 +728,31 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* 
                           uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
                           const uint64_t* range_lower_bounds, const ss_facet_point* bases,
                           uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
+
+/* A SORTED search with its query_facets, as ONE call for a batch (the crate's search_lexical_shard with result_sort AND query_facets: a
+ * shop page's terms, facet filter, sidebar counts and sort by price in one request).  out_doc / out_score / out_count / out_total:
+ * exactly what ss_bm25_search_sorted writes for the same queries, sorts, k and filters, bit for bit; out_facet_counts: exactly what
+ * ss_bm25_search_facets writes for the same queries, filters and facets.  Every chunk of <= 64 queries builds its match sets ONCE; one
+ * kernel launch then counts every facet of every query and, on the same visit of each matched doc's record, the first radix byte of
+ * the first sort field's select, which ss_bm25_search_sorted spends a pass of its own on (SS_SORT_FUSED=0 in the environment, read
+ * once: the count and the whole select apart, same answers).  One synchronisation per call for k <= SS_MAX_K.
+ * result_type: SS_RT_TOPKCOUNT -- as above; SS_RT_TOPK -- the same docs, and *out_total and the facet counts as for SS_RT_TOPKCOUNT:
+ * the totals and counters are counted all the same (the crate's Topk bumps neither, add_result.rs:226-230; ss_docs_search does
+ * likewise); SS_RT_COUNT -- no docs and no select (out_doc / out_score may be NULL, k is not read): the call IS
+ * ss_bm25_search_facets(SS_RT_COUNT) once the sort fields have passed their checks.
+ * n_sorts = 0: ss_bm25_search_facets.  n_facets = 0 (and docs wanted): ss_bm25_search_sorted.  k > SS_MAX_K: the facets are counted once
+ * by ss_bm25_search_facets' batched count, then the page is peeled as ss_bm25_search_sorted peels a deep page.
+ * The refusals are the two entries', checked before anything is staged: SS_EINVAL -- a result type beyond SS_RT_TOPKCOUNT, NULL
+ * arguments, n_queries = 0, k = 0 with docs wanted, a sort or facet type beyond SS_FACET_POINT, more than SS_MAX_QUERY_FACETS facets, a
+ * Point facet without bases, bounds missing, n_buckets 0 or above 2^24; SS_ENOTSUP -- n_sorts > SS_MAX_SORT_FIELDS, a string sort field
+ * without a rank table; SS_ESTATE -- no lexical image, facet records for fewer docs than it holds, an offset beyond the record;
+ * SS_ENOTSUP for the whole call, outputs unspecified -- a chunk whose match sets the other two entries refuse as well (INTEGRATION.md
+ * section 4). */
+int ss_bm25_search_sorted_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
+                                 uint32_t k, uint32_t result_type, uint32_t n_filters, const ss_facet_filter* filters,
+                                 uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
+                                 const uint64_t* range_lower_bounds, const ss_facet_point* bases,
+                                 uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
 
 /* The EMPTY query of a shard (the crate's search(.., enable_empty_query, ..) with no query string: search_iterator_shard,
  * iterator.rs:316-358, reached from the query_list_len == 0 arm of search_lexical_shard, search.rs:3374-3386): every doc of the

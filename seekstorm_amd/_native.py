@@ -209,6 +209,8 @@ SYMBOLS = [
     ("ss_facet_point_distances", C.c_int, [C.c_void_p, C.c_uint32, u32p, C.c_uint32, C.c_void_p, u64p]),
     ("ss_bm25_search_facets", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                         C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
+    ("ss_bm25_search_sorted_facets", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
     ("ss_docs_search", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, u32p, u64p, u64p]),
     ("ss_bm25_search_sharded", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -439,9 +439,10 @@ __global__ void sort_begin_kernel(SortState* st, const unsigned long long* total
   st += blockIdx.x;
   if (threadIdx.x == 0) { st->count_e = total[blockIdx.x]; st->k_left = k; st->better_total = 0ull; }
 }
-__global__ void sort_level_begin_kernel(SortState* st, unsigned long long* hist) {
+// (keep_hist: the histogram already holds the level's byte 0 -- facet_sort_first_kernel counted it)
+__global__ void sort_level_begin_kernel(SortState* st, unsigned long long* hist, uint32_t keep_hist) {
   st += blockIdx.x;
-  hist[(size_t)blockIdx.x * 256u + (threadIdx.x & 255u)] = 0ull;
+  if (!keep_hist) hist[(size_t)blockIdx.x * 256u + (threadIdx.x & 255u)] = 0ull;
   if (threadIdx.x == 0) { st->want = st->k_left < st->count_e ? st->k_left : st->count_e; st->prefix = 0ull; st->n_better = 0ull; st->n_equal = 0ull; }
 }
 // One byte of the select: the histogram of byte `byte_index` over the docs of E that share the prefix decided so far -- and, on the way,
@@ -606,7 +607,7 @@ __global__ void __launch_bounds__(1024) sort_compose_kernel(const uint32_t* __re
 // bit sets [nq][groups], d_total / d_state [nq], d_hist [nq][256].  d_ex_b = nullptr: no exclusion bitmaps (ss_docs_search reads B and E)
 int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned long long* d_B, unsigned long long* d_ex_b, unsigned long long* d_ex_e,
                     const unsigned long long* d_total, unsigned long long* d_hist, void* d_state, uint32_t n_sorts, const ss_result_sort* sorts,
-                    const ss_sort_sources& src, uint32_t k, hipStream_t st) {
+                    const ss_sort_sources& src, uint32_t k, hipStream_t st, bool byte0_counted) {
   const unsigned long long n_docs = s->bm_n_docs, groups = (unsigned long long)s->bm_n_sub * (BM_SUB / 64);
   const dim3 grid((unsigned)((groups + 255) / 256), nq);
   SortState* state = (SortState*)d_state;
@@ -620,10 +621,12 @@ int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned 
       if (facet_point_of(&base, &pt) != SS_OK) return SS_EINVAL;
     }
     const uint32_t key_bits = 8u * ssi_facet_width(type);
-    sort_level_begin_kernel<<<nq, 256, 0, st>>>(state, d_hist);
+    const bool counted = byte0_counted && f == 0;  // pass 0 only counts (it never modifies E): the histogram is all it leaves
+    sort_level_begin_kernel<<<nq, 256, 0, st>>>(state, d_hist, counted ? 1u : 0u);
     for (uint32_t b = 0; b < key_bits / 8u; b++) {
-      sort_radix_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, src.base[f], src.stride[f], src.offset[f], type, key_bits,
-                                              sorts[f].descending ? 1u : 0u, state, b, d_hist, pt);
+      if (!(counted && b == 0))
+        sort_radix_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, src.base[f], src.stride[f], src.offset[f], type, key_bits,
+                                                sorts[f].descending ? 1u : 0u, state, b, d_hist, pt);
       sort_decide_kernel<<<nq, 256, 0, st>>>(state, d_hist);
     }
     sort_classify_kernel<<<grid, 256, 0, st>>>(d_E, d_B, n_docs, groups, src.base[f], src.stride[f], src.offset[f], type, key_bits,
@@ -749,10 +752,23 @@ __device__ __forceinline__ uint32_t facet_bucket(const uint8_t* p, uint32_t stor
   }
   return lo ? lo - 1 : n_buckets;  // below the first bound (or NaN): "other"
 }
-__global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned long long* __restrict__ bits, unsigned long long groups,
-                                                                 unsigned long long n_docs, const uint8_t* __restrict__ records,
-                                                                 uint32_t record_size, uint32_t wpt, const unsigned long long* __restrict__ bounds,
-                                                                 unsigned long long* __restrict__ counts, FacetMulti F) {
+// The sort field whose first radix byte facet_sort_first_kernel counts beside the facets (ss_sort_sources' entry 0 of the call)
+struct FacetSortKey {
+  const uint8_t* base;  // the facet records, or a string facet's rank column
+  uint32_t stride, offset, type, key_bits, descending;
+  FacetPoint pt;
+};
+// The body both kernels share.  SORT: every matched doc's key of sort field 0 is loaded too (facet_load + facet_order_key, as
+// sort_radix_kernel does) and its TOP byte counted into a 256-counter LDS histogram of its own (1 KiB beside the 18 KiB above: eight
+// workgroups per CU still fit), flushed into hist [nq][256] -- what sort_radix_kernel's pass 0 of field 0 would count, without its
+// second visit of every match (ssi_sort_select, byte0_counted).
+template <bool SORT>
+__device__ __forceinline__ void facet_multi_body(const unsigned long long* __restrict__ bits, unsigned long long groups,
+                                                 unsigned long long n_docs, const uint8_t* __restrict__ records,
+                                                 uint32_t record_size, uint32_t wpt, const unsigned long long* __restrict__ bounds,
+                                                 unsigned long long* __restrict__ counts, const FacetMulti& F, const FacetSortKey& K,
+                                                 unsigned long long* __restrict__ hist) {
+  __shared__ uint32_t s_radix[SORT ? 256 : 1];
   __shared__ unsigned long long s_word[FM_THREADS * FM_MAX_WPT];
   __shared__ uint32_t s_pre[FM_THREADS * FM_MAX_WPT + 1];
   __shared__ uint32_t s_wave[FM_THREADS / 64];
@@ -791,6 +807,7 @@ __global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned 
     if (j < wpt) { s_pre[tid * wpt + j] = e; e += (uint32_t)__popcll(mw[j]); }
   if (tid == 0) s_pre[W] = T;
   for (uint32_t i = tid; i < F.lds_used; i += FM_THREADS) s_cnt[i] = 0u;
+  if (SORT) s_radix[tid & 255u] = 0u;
   const uint32_t nb_lds = F.n_bounds < FM_LDS_BOUNDS ? F.n_bounds : FM_LDS_BOUNDS;
   for (uint32_t i = tid; i < nb_lds; i += FM_THREADS) s_bounds[i] = bounds[i];
   __syncthreads();
@@ -802,6 +819,15 @@ __global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned 
     }
     const unsigned long long d = (w0 + lo) * 64ull + facet_select64(s_word[lo], i - s_pre[lo]);  // < n_docs: the words were masked
     const uint8_t* rec = records + d * record_size;
+    if (SORT) {
+      uint32_t ty = K.type;
+      const unsigned long long v = facet_load(K.base + d * K.stride + K.offset, K.key_bits / 8u, ty, K.pt);
+      const uint32_t top = (uint32_t)(facet_order_key(v, ty, K.key_bits, K.descending != 0u) >> (K.key_bits - 8u)) & 255u;
+      const unsigned long long active = __ballot(1);  // keys of one wave mostly share their top byte: then one add for all of them
+      const uint32_t first = (uint32_t)__shfl((int)top, __builtin_ctzll(active));
+      if (__ballot(top == first) == active) { if ((int)lane == __builtin_ctzll(active)) atomicAdd(&s_radix[first], (uint32_t)__popcll(active)); }
+      else atomicAdd(&s_radix[top], 1u);
+    }
     for (uint32_t f = 0; f < F.n; f++) {
       const FacetMultiDesc& D = F.f[f];
       const unsigned long long* bnd = D.bounds_begin + D.n_buckets <= nb_lds ? s_bounds + D.bounds_begin : bounds + D.bounds_begin;
@@ -834,15 +860,31 @@ __global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned 
       if (v) atomicAdd(&counts[D.cnt_begin + i], (unsigned long long)v);
     }
   }
+  if (SORT && tid < 256u && s_radix[tid]) atomicAdd(&hist[(size_t)blockIdx.y * 256u + tid], (unsigned long long)s_radix[tid]);
+}
+__global__ void __launch_bounds__(FM_THREADS) facet_multi_kernel(const unsigned long long* __restrict__ bits, unsigned long long groups,
+                                                                 unsigned long long n_docs, const uint8_t* __restrict__ records,
+                                                                 uint32_t record_size, uint32_t wpt, const unsigned long long* __restrict__ bounds,
+                                                                 unsigned long long* __restrict__ counts, FacetMulti F) {
+  facet_multi_body<false>(bits, groups, n_docs, records, record_size, wpt, bounds, counts, F, FacetSortKey{}, nullptr);
+}
+// facet_multi_kernel + the histogram of the top byte of sort field 0's keys: the first pass of a sorted search that counts facets too
+// (ss_bm25_search_sorted_facets).  hist [nq][256], zeroed by the caller.
+__global__ void __launch_bounds__(FM_THREADS) facet_sort_first_kernel(const unsigned long long* __restrict__ bits, unsigned long long groups,
+                                                                      unsigned long long n_docs, const uint8_t* __restrict__ records,
+                                                                      uint32_t record_size, uint32_t wpt,
+                                                                      const unsigned long long* __restrict__ bounds,
+                                                                      unsigned long long* __restrict__ counts, FacetMulti F, FacetSortKey K,
+                                                                      unsigned long long* __restrict__ hist) {
+  facet_multi_body<true>(bits, groups, n_docs, records, record_size, wpt, bounds, counts, F, K, hist);
 }
 
 // d_bits [nq][groups] match sets, d_bounds: the range facets' lower bounds back to back in facet order, d_counts [nq][sum_f (n_buckets[f] + 1)]
 // (zeroed by the caller).  The arguments were validated by the caller (types, bases, offsets inside the record).
-int ssi_facet_count_multi(ss_shard* s, uint32_t nq, const unsigned long long* d_bits, uint32_t n_facets, const uint32_t* offset, const uint32_t* type,
-                          const uint32_t* n_buckets, const ss_facet_point* bases, const uint64_t* d_bounds, unsigned long long* d_counts,
-                          hipStream_t st) {
+static int facet_multi_desc(uint32_t nq, uint32_t n_facets, const uint32_t* offset, const uint32_t* type, const uint32_t* n_buckets,
+                            const ss_facet_point* bases, FacetMulti* out) {
   if (nq == 0 || nq > 65535u || n_facets == 0 || n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
-  FacetMulti F;
+  FacetMulti& F = *out;
   memset(&F, 0, sizeof(F));
   F.n = n_facets;
   for (uint32_t f = 0; f < n_facets; f++) {
@@ -858,12 +900,44 @@ int ssi_facet_count_multi(ss_shard* s, uint32_t nq, const unsigned long long* d_
     D.lds_begin = FM_NO_LDS;
     if (n_buckets[f] + 1u <= FM_LDS_COUNTERS - F.lds_used) { D.lds_begin = F.lds_used; F.lds_used += n_buckets[f] + 1u; }
   }
+  return SS_OK;
+}
+// two words per thread unless that leaves the chip short of workgroups
+static uint32_t facet_multi_wpt(unsigned long long groups, uint32_t nq) {
+  return ((groups + 2 * FM_THREADS - 1) / (2 * FM_THREADS)) * nq >= 2048u ? 2u : 1u;
+}
+int ssi_facet_count_multi(ss_shard* s, uint32_t nq, const unsigned long long* d_bits, uint32_t n_facets, const uint32_t* offset, const uint32_t* type,
+                          const uint32_t* n_buckets, const ss_facet_point* bases, const uint64_t* d_bounds, unsigned long long* d_counts,
+                          hipStream_t st) {
+  FacetMulti F;
+  if (const int rc = facet_multi_desc(nq, n_facets, offset, type, n_buckets, bases, &F)) return rc;
   const unsigned long long groups = (unsigned long long)s->bm_n_sub * (BM_SUB / 64);
-  // two words per thread unless that leaves the chip short of workgroups
-  const uint32_t wpt = ((groups + 2 * FM_THREADS - 1) / (2 * FM_THREADS)) * nq >= 2048u ? 2u : 1u;
+  const uint32_t wpt = facet_multi_wpt(groups, nq);
   const dim3 grid((unsigned)((groups + (unsigned long long)FM_THREADS * wpt - 1) / ((unsigned long long)FM_THREADS * wpt)), nq);
   facet_multi_kernel<<<grid, FM_THREADS, 0, st>>>(d_bits, groups, (unsigned long long)s->bm_n_docs, s->d_facets, s->facet_record_size, wpt,
                                                   (const unsigned long long*)d_bounds, d_counts, F);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+// ssi_facet_count_multi's counters AND, in the same launch, the histogram of the top byte of sort field 0's keys over every query's
+// match set into d_hist [nq][256] (cleared here): what pass 0 of ssi_sort_select's first field counts -- hand it byte0_counted = true.
+int ssi_facet_sort_first(ss_shard* s, uint32_t nq, const unsigned long long* d_bits, uint32_t n_facets, const uint32_t* offset, const uint32_t* type,
+                         const uint32_t* n_buckets, const ss_facet_point* bases, const uint64_t* d_bounds, unsigned long long* d_counts,
+                         const ss_result_sort* sorts, const ss_sort_sources& src, unsigned long long* d_hist, hipStream_t st) {
+  FacetMulti F;
+  if (const int rc = facet_multi_desc(nq, n_facets, offset, type, n_buckets, bases, &F)) return rc;
+  FacetSortKey K{src.base[0], src.stride[0], src.offset[0], src.type[0], 8u * ssi_facet_width(src.type[0]), sorts[0].descending ? 1u : 0u,
+                 FacetPoint{0, 0, 0}};
+  if (K.type == SS_FACET_POINT) {
+    const ss_facet_point base{sorts[0].base_lat, sorts[0].base_lon, SS_POINT_SORTKEY, 0};
+    if (facet_point_of(&base, &K.pt) != SS_OK) return SS_EINVAL;
+  }
+  const unsigned long long groups = (unsigned long long)s->bm_n_sub * (BM_SUB / 64);
+  const uint32_t wpt = facet_multi_wpt(groups, nq);
+  const dim3 grid((unsigned)((groups + (unsigned long long)FM_THREADS * wpt - 1) / ((unsigned long long)FM_THREADS * wpt)), nq);
+  SS_HIP(hipMemsetAsync(d_hist, 0, (size_t)nq * 256 * 8, st));
+  facet_sort_first_kernel<<<grid, FM_THREADS, 0, st>>>(d_bits, groups, (unsigned long long)s->bm_n_docs, s->d_facets, s->facet_record_size, wpt,
+                                                       (const unsigned long long*)d_bounds, d_counts, F, K, d_hist);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }

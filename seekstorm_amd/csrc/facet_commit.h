@@ -35,7 +35,12 @@ struct ss_sort_sources {
 int ssi_sort_resolve(const ss_shard* s, uint32_t n_sorts, const ss_result_sort* sorts, ss_sort_sources* out);  // SS_ENOTSUP: a string field without a table
 int ssi_sort_select(ss_shard* s, uint32_t nq, unsigned long long* d_E, unsigned long long* d_B, unsigned long long* d_ex_b, unsigned long long* d_ex_e,
                     const unsigned long long* d_total, unsigned long long* d_hist, void* d_state, uint32_t n_sorts, const ss_result_sort* sorts,
-                    const ss_sort_sources& src, uint32_t k, hipStream_t st);
+                    const ss_sort_sources& src, uint32_t k, hipStream_t st, bool byte0_counted = false);
+// the facet counters of a batch (ssi_facet_count_multi's arguments and counters) and byte 0 of sort field 0's radix select in ONE launch:
+// d_hist [nq][256] then holds what ssi_sort_select's first pass would count -- call it with byte0_counted = true
+int ssi_facet_sort_first(ss_shard* s, uint32_t nq, const unsigned long long* d_bits, uint32_t n_facets, const uint32_t* offset, const uint32_t* type,
+                         const uint32_t* n_buckets, const ss_facet_point* bases, const uint64_t* d_bounds, unsigned long long* d_counts,
+                         const ss_result_sort* sorts, const ss_sort_sources& src, unsigned long long* d_hist, hipStream_t st);
 int ssi_sort_compose(ss_shard* s, uint32_t nq, const uint32_t* a_doc, const float* a_score, const uint32_t* a_cnt, const uint32_t* c_doc,
                      const float* c_score, const uint32_t* c_cnt, const unsigned long long* d_total, uint32_t n_sorts, const ss_result_sort* sorts,
                      const ss_sort_sources& src, uint32_t k, uint32_t* out_doc, float* out_score, uint32_t* out_count, unsigned long long* out_total,

@@ -3704,15 +3704,33 @@ int ss_bm25_facet_kth_point(ss_shard* s, const ss_bm25_query* query, uint32_t n_
 // classification -> the exclusion bitmaps -> TWO batched searches, each query inside its own doc set (the pruned kernel's filtered
 // instances take one bitmap per query) -> compose into the queries' output rows.  One synchronisation per call.  A chunk the pruned
 // kernel does not serve (k > 128, more than 4 lists per query, the exhaustive strategy) runs its searches query by query instead.
+// With `qf` (ss_bm25_search_sorted_facets) the chunk's match sets serve the batch's query_facets too: ONE launch counts every facet of
+// every query and, on the same visit of each matched doc, byte 0 of the first sort field's radix select (facet.hip
+// facet_sort_first_kernel), so the select starts at its second pass.  SS_SORT_FUSED=0 (read once): the two steps apart --
+// ssi_facet_count_multi, then the whole select -- for measurements; the answers are the same.
+struct SortedFacets {  // the validated facet arguments of ss_bm25_search_sorted_facets (check_query_facets)
+  uint32_t n_facets;
+  const uint32_t *facet_offset, *facet_type, *n_buckets;
+  const uint64_t* range_lower_bounds;
+  const ss_facet_point* bases;
+  size_t n_bounds, stride;
+  uint64_t* out_counts;  // [nq][stride]
+};
+static bool sort_fused() {
+  static const int on = [] { const char* e = getenv("SS_SORT_FUSED"); return e ? atoi(e) : 1; }();
+  return on != 0;
+}
 static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
                                      const ss_sort_sources& src, uint32_t k,
                                      uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
-                                     uint64_t* out_total) {
+                                     uint64_t* out_total, const SortedFacets* qf = nullptr) {
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
   if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
   for (uint32_t f = 0; f < n_sorts; f++)
     if (sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_ESTATE;
+  for (uint32_t f = 0; qf && f < qf->n_facets; f++)
+    if ((uint64_t)qf->facet_offset[f] + ssi_facet_width(qf->facet_type[f]) > s->facet_record_size) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
   const uint32_t CH = std::min<uint32_t>(nq, 64u);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -3722,9 +3740,17 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                o_ac = o_as + al((size_t)CH * k * 4), o_cd = o_ac + al((size_t)CH * 4), o_cs = o_cd + al((size_t)CH * k * 4),
                o_cc = o_cs + al((size_t)CH * k * 4), o_at = o_cc + al((size_t)CH * 4), o_od = o_at + al((size_t)CH * 8),
                o_os = o_od + al((size_t)nq * k * 4), o_oc = o_os + al((size_t)nq * k * 4), o_ot = o_oc + al((size_t)nq * 4),
-               o_sub = o_ot + al((size_t)nq * 8), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)), need = o_ph + al((size_t)CH * sizeof(ss_bm25_query));
+               o_sub = o_ot + al((size_t)nq * 8), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
+               o_bounds = o_ph + al((size_t)CH * sizeof(ss_bm25_query)), o_cnt = o_bounds + al(qf ? qf->n_bounds * 8 : 0),
+               need = o_cnt + al(qf ? (size_t)nq * qf->stride * 8 : 0);  // (the facets' bounds and counters [nq][stride] behind the sort's own)
   SS_TRY(reserve(s, &s->d_sort_ws, &s->sort_ws_cap, need));
   char* W = (char*)s->d_sort_ws;
+  uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
+  unsigned long long* d_counts = (unsigned long long*)(W + o_cnt);
+  if (qf) {
+    SS_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * qf->stride * 8, s->stream));
+    if (qf->n_bounds) SS_HIP(hipMemcpyAsync(d_bounds, qf->range_lower_bounds, qf->n_bounds * 8, hipMemcpyHostToDevice, s->stream));
+  }
   ss_bm25_query* d_q = (ss_bm25_query*)(W + o_q);
   unsigned long long* d_total = (unsigned long long*)(W + o_tot);
   unsigned long long *d_E = (unsigned long long*)(W + o_E), *d_B = (unsigned long long*)(W + o_B), *d_xb = (unsigned long long*)(W + o_xb),
@@ -3743,7 +3769,15 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
     MatchBatchInfo b;
     SS_TRY(match_prepare(s, nb, qc, &mc, &b));
     SS_TRY(match_enqueue(s, nb, qc, mc, n_filters, filters, false, d_q, (ss_bm25_query*)(W + o_sub), (ss_bm25_query*)(W + o_ph), d_E, d_total));
-    SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, src, k, s->stream));
+    const bool fused = qf && sort_fused();
+    if (fused)
+      SS_TRY(ssi_facet_sort_first(s, nb, d_E, qf->n_facets, qf->facet_offset, qf->facet_type, qf->n_buckets, qf->bases, d_bounds,
+                                  d_counts + (size_t)c0 * qf->stride, sorts, src, (unsigned long long*)(W + o_hist), s->stream));
+    else if (qf)
+      SS_TRY(ssi_facet_count_multi(s, nb, d_E, qf->n_facets, qf->facet_offset, qf->facet_type, qf->n_buckets, qf->bases, d_bounds,
+                                   d_counts + (size_t)c0 * qf->stride, s->stream));
+    SS_TRY(ssi_sort_select(s, nb, d_E, d_B, d_xb, d_xe, d_total, (unsigned long long*)(W + o_hist), W + o_state, n_sorts, sorts, src, k, s->stream,
+                           fused));
     bool batched = !batched_off && !mc.tier.any_tiered && !mc.any_phrase();
     for (int part = 0; part < 2 && batched; part++) {  // both searches as ONE batch each: every query under its own exclusion bitmap
       ExclSwap sw(s, (uint32_t*)(part == 0 ? d_xb : d_xe), groups * 2);
@@ -3774,9 +3808,14 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
   SS_HIP(hipMemcpyAsync(out_score, W + o_os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipMemcpyAsync(out_count, W + o_oc, (size_t)nq * 4, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipMemcpyAsync(out_total, W + o_ot, (size_t)nq * 8, hipMemcpyDeviceToHost, s->stream));
+  if (qf) SS_HIP(hipMemcpyAsync(qf->out_counts, d_counts, (size_t)nq * qf->stride * 8, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipStreamSynchronize(s->stream));
   return SS_OK;
 }
+
+static int bm25_search_sorted_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
+                                          const ss_sort_sources& src, uint32_t k, uint32_t n_filters, const ss_facet_filter* filters,
+                                          uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total);
 
 int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
                           uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
@@ -3794,6 +3833,11 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   ss_sort_sources src;
   SS_TRY(ssi_sort_resolve(s, n_sorts, sorts, &src));
   if (k <= SS_MAX_K) return bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+  return bm25_search_sorted_deep_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+}
+static int bm25_search_sorted_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
+                                          const ss_sort_sources& src, uint32_t k, uint32_t n_filters, const ss_facet_filter* filters,
+                                          uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
   // a DEEP page sorted by facets: the order is total (field 1, ..., field n, score desc, doc asc), so it is peeled like any other ("deep
   // pages" above) -- query by query, every pass the sorted search of SS_MAX_K results under (tombstones | the docs of the earlier passes);
   // a facet filter's bitmap is built on top of that inside the pass
@@ -3930,6 +3974,67 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
   if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) rc = SS_EDEVICE;
   if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (also on an error: the plans and the caller's arrays are being read)
   return rc;
+}
+
+// A SORTED search with its query_facets: ss_bm25_search_sorted's hits and ss_bm25_search_facets' counters from ONE match-set build per
+// chunk (bm25_search_sorted_locked with `qf`).  Without sort fields, without facets, or for SS_RT_COUNT one of the two entries answers
+// alone; a deep page counts the facets once (bm25_facets_enqueue) and then peels the page as ss_bm25_search_sorted does.
+int ss_bm25_search_sorted_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
+                                 uint32_t rt, uint32_t n_filters, const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset,
+                                 const uint32_t* facet_type, const uint32_t* n_buckets, const uint64_t* range_lower_bounds,
+                                 const ss_facet_point* bases, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
+                                 uint64_t* out_facet_counts) {
+  if (rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
+  if (n_sorts == 0)
+    return ss_bm25_search_facets(s, nq, queries, k, rt, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases,
+                                 out_doc, out_score, out_count, out_total, out_facet_counts);
+  // the sorted entry's argument checks ...
+  if (!s || !queries || nq == 0 || !out_count || !out_total || !sorts) return SS_EINVAL;
+  if (rt != SS_RT_COUNT && (k == 0 || !out_doc || !out_score)) return SS_EINVAL;
+  if (n_sorts > SS_MAX_SORT_FIELDS) return SS_ENOTSUP;
+  for (uint32_t f = 0; f < n_sorts; f++)
+    if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
+  if (rt != SS_RT_COUNT && n_facets == 0)
+    return ss_bm25_search_sorted(s, nq, queries, n_sorts, sorts, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+  // ... and the facet entry's
+  size_t n_bounds = 0, stride = 0;
+  if (n_facets) {
+    if (!out_facet_counts || !facet_offset || !facet_type || !n_buckets || n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
+    SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
+    if (n_bounds && !range_lower_bounds) return SS_EINVAL;
+  }
+  ss_sort_sources src;
+  {
+    ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
+    SS_TRY(ssi_sort_resolve(s, n_sorts, sorts, &src));  // SS_ENOTSUP: a string field without a rank table
+    if (rt != SS_RT_COUNT) {
+      SortedFacets qf{n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, n_bounds, stride, out_facet_counts};
+      if (k <= SS_MAX_K)
+        return bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total, &qf);
+      // a deep page: the counters once, through ss_bm25_search_facets' batched count, then ss_bm25_search_sorted's passes
+      if (!s->d_post) return SS_ESTATE;
+      SS_HIP(hipSetDevice(s->device));
+      if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
+      for (uint32_t f = 0; f < n_sorts; f++)
+        if (sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_ESTATE;
+      for (uint32_t f = 0; f < n_facets; f++)
+        if ((uint64_t)facet_offset[f] + ssi_facet_width(facet_type[f]) > s->facet_record_size) return SS_ESTATE;
+      std::vector<MatchChunk> plans;
+      unsigned long long* d_counts = nullptr;
+      int rc = n_filters ? ssi_facet_build(s, n_filters, filters, s->stream) : SS_OK;
+      if (rc == SS_OK)
+        rc = bm25_facets_enqueue(s, nq, queries, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, n_bounds,
+                                 stride, plans, &d_counts);
+      if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+        rc = SS_EDEVICE;
+      if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (the plans and the caller's array are being read)
+      if (rc != SS_OK) return rc;
+      return bm25_search_sorted_deep_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+    }
+  }
+  // SS_RT_COUNT: no docs, so no select -- the sort fields were checked above and play no further part
+  return ss_bm25_search_facets(s, nq, queries, k, rt, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases,
+                               out_doc, out_score, out_count, out_total, out_facet_counts);
 }
 
 // The empty query of a shard (browse.hip; search_iterator_shard, iterator.rs:316-358).  Everything runs on s->stream: the match set of

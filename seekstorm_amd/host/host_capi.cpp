@@ -603,4 +603,27 @@ int ssh_index_search_empty(ssh_index* ix, uint32_t offset, uint32_t length, uint
   return write_out(ro, cap, out_doc, out_score, nullptr, nullptr, nullptr, out_meta);
 }
 
+// Index::search_lexical_sorted with query_facets: sorts as ssh_index_search_sorted takes them, spec / results / facets as
+// ssh_index_search_facets takes and writes them
+int ssh_index_search_sorted_facets(ssh_index* ix, const uint32_t* terms, uint32_t n_terms, uint32_t query_type, uint32_t offset, uint32_t length,
+                                   uint32_t result_type, uint32_t n_filters, const ss_facet_filter* filters, const ssh_result_sort* sorts,
+                                   uint32_t n_sorts, const char* spec, uint32_t cap, uint64_t* out_doc, float* out_score, uint64_t* out_meta,
+                                   char* out_facets, uint32_t facets_cap, int* facets_len) {
+  std::vector<QueryFacet> qf;
+  if (!parse_facets(spec, &qf)) return SS_EINVAL;
+  std::vector<ResultSort> rs(n_sorts);
+  for (uint32_t i = 0; i < n_sorts; i++) {
+    rs[i].facet_offset = sorts[i].facet_offset;
+    rs[i].facet_type = sorts[i].facet_type;
+    rs[i].descending = sorts[i].descending != 0;
+    rs[i].base[0] = sorts[i].base[0];
+    rs[i].base[1] = sorts[i].base[1];
+  }
+  if (!ix->index) ix->index.reset(new Index(ix->shards));
+  ResultObject ro = ix->index->search_lexical_sorted(std::vector<uint32_t>(terms, terms + n_terms), (QueryType)query_type, offset, length, rs,
+                                                     std::vector<ss_facet_filter>(filters, filters + n_filters), {}, qf, (ResultType)result_type);
+  *facets_len = write_facets(ro.facets, out_facets, facets_cap);
+  return write_out(ro, cap, out_doc, out_score, nullptr, nullptr, nullptr, out_meta);
+}
+
 }  // extern "C"

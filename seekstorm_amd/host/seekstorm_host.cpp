@@ -894,20 +894,77 @@ int Shard::sorted_topk(const ss_bm25_query& q, const ResultSort* sorts, size_t n
   return SS_OK;
 }
 
+ResultObject Shard::search_lexical_sorted_facets(const ss_bm25_query& query, const std::vector<ResultSort>& result_sort, size_t k,
+                                                 ResultType result_type, const std::vector<QueryFacet>& query_facets,
+                                                 const std::vector<ss_facet_filter>& facet_filter, size_t shard_number) {
+  ResultObject ro;
+  const size_t n_sorts = result_sort.size(), nf = query_facets.size();
+  if (n_sorts == 0 || n_sorts > SS_MAX_SORT_FIELDS) { ro.last_error = SS_EINVAL; return ro; }
+  std::vector<ss_result_sort> rs(n_sorts);
+  for (size_t f = 0; f < n_sorts; f++) {
+    if (result_sort[f].field != ResultSort::Field::Facet) { ro.last_error = SS_EINVAL; return ro; }
+    rs[f].facet_offset = result_sort[f].facet_offset; rs[f].facet_type = result_sort[f].facet_type;
+    rs[f].descending = result_sort[f].descending ? 1u : 0u; rs[f].reserved = 0;
+    rs[f].base_lat = result_sort[f].base[0]; rs[f].base_lon = result_sort[f].base[1];
+  }
+  std::vector<uint32_t> f_off(nf), f_type(nf), f_nb(nf);
+  std::vector<uint64_t> bounds;
+  std::vector<ss_facet_point> bases(nf);
+  size_t stride = 0;
+  for (size_t f = 0; f < nf; f++) {
+    const QueryFacet& qf = query_facets[f];
+    f_off[f] = qf.facet_offset; f_type[f] = qf.facet_type; f_nb[f] = qf.n_buckets(); bases[f] = qf.base;
+    if (qf.is_range())
+      for (const auto& r : qf.ranges) bounds.push_back(r.second);
+    stride += (size_t)f_nb[f] + 1;
+  }
+  const bool want_docs = result_type != ResultType::Count && k != 0;
+  const size_t kk = std::max<size_t>(k, 1);
+  std::vector<uint32_t> doc(kk);
+  std::vector<float> score(kk);
+  std::vector<uint64_t> counts(std::max<size_t>(stride, 1), 0);
+  uint32_t cnt = 0;
+  uint64_t tot = 0;
+  const int rc = h_ ? ss_bm25_search_sorted_facets(h_, 1, &query, (uint32_t)n_sorts, rs.data(), (uint32_t)k,
+                                                   (uint32_t)(want_docs ? result_type : ResultType::Count), (uint32_t)facet_filter.size(),
+                                                   facet_filter.empty() ? nullptr : facet_filter.data(), (uint32_t)nf, f_off.data(), f_type.data(),
+                                                   f_nb.data(), bounds.empty() ? nullptr : bounds.data(), bases.data(), doc.data(), score.data(),
+                                                   &cnt, &tot, counts.data())
+                    : (create_rc_ ? create_rc_ : SS_ESTATE);
+  if (rc != SS_OK) { ro.last_error = rc; return ro; }  // degrade to empty (search.rs:2461-2463)
+  if (nf) ro.facets = finish_facets(query_facets, counts.data(), shard_number);
+  const size_t n = want_docs ? std::min<size_t>(cnt, k) : 0;
+  ro.results.resize(n);
+  for (size_t i = 0; i < n; i++) {
+    Result& r = ro.results[i];
+    r.doc_id = doc[i];
+    r.score = r.lexical_score = score[i];
+    r.shard_id = shard_id_;
+    r.level_id = (uint32_t)(r.doc_id >> 16);  // 65 536-doc levels (index.rs:115)
+    r.source = ResultSource::Lexical;
+  }
+  ro.result_count = n;
+  ro.result_count_total = tot;
+  return ro;
+}
+
 ResultObject Shard::search_lexical_shard(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset,
                                          size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
                                          const std::vector<uint32_t>& not_terms, const std::vector<uint16_t>& field_filter,
                                          const std::vector<ResultSort>& result_sort, const std::vector<QueryFacet>& query_facets,
                                          size_t shard_number) {
   ResultObject ro;
-  if (!query_facets.empty() && !result_sort.empty()) { ro.last_error = SS_EINVAL; return ro; }  // query_facets belong to searches by score
+  // query_facets under a result_sort: one call for both (more sort fields than it takes: the composition has no facets to offer)
+  if (!query_facets.empty() && result_sort.size() > SS_MAX_SORT_FIELDS) { ro.last_error = SS_EINVAL; return ro; }
   // a union of several terms under a field filter goes down like any other query: per-term gating inside the scan kernels (<= 7
   // terms, round 3) or the reference's own sub-queries composed BEHIND the ABI (8 .. 10 terms, a sparse-tier term; round 6).
   {
     ss_bm25_query q;
     const int rc = make_query(query_terms, query_type_default, &q, not_terms, lexical_fields_ > 1 ? field_filter : std::vector<uint16_t>());
     if (rc != SS_OK) { ro.last_error = rc; return ro; }
-    if (!result_sort.empty() && result_type != ResultType::Count) {
+    if (!result_sort.empty() && !query_facets.empty()) {
+      ro = search_lexical_sorted_facets(q, result_sort, offset + length, result_type, query_facets, facet_filter, shard_number);
+    } else if (!result_sort.empty() && result_type != ResultType::Count) {
       uint64_t total = 0;
       bool have_total = false;
       const int rs = sorted_topk(q, result_sort.data(), result_sort.size(), offset + length, facet_filter, &ro.results, &total, &have_total);
@@ -946,18 +1003,22 @@ int Index::set_string_facet_ranks(uint32_t facet_offset, uint32_t facet_type, co
 
 ResultObject Index::search_lexical_sorted(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset, size_t length,
                                           const std::vector<ResultSort>& result_sort, const std::vector<ss_facet_filter>& facet_filter,
-                                          const std::vector<uint32_t>& not_terms) {
+                                          const std::vector<uint32_t>& not_terms, const std::vector<QueryFacet>& query_facets,
+                                          ResultType result_type) {
   ResultObject ro;
   const size_t S = shards_.size();
   if (S == 0 || result_sort.empty()) { ro.last_error = SS_EINVAL; return ro; }
   struct Row { std::vector<uint64_t> keys; Result r; };
   std::vector<Row> rows;
+  std::vector<Facets> maps;
+  const bool faceted = !query_facets.empty();
   for (size_t i = 0; i < S; i++) {
     Shard& sh = *shards_[i];
-    ResultObject part = sh.search_lexical_shard(query_terms, query_type_default, 0, offset + length, ResultType::TopkCount, facet_filter,
-                                                not_terms, {}, result_sort);
+    ResultObject part = sh.search_lexical_shard(query_terms, query_type_default, 0, offset + length, faceted ? result_type : ResultType::TopkCount,
+                                                facet_filter, not_terms, {}, result_sort, query_facets, S);
     if (part.last_error != SS_OK) { ro.last_error = part.last_error; continue; }  // a failing shard degrades to empty
     ro.result_count_total += part.result_count_total;
+    if (faceted) maps.push_back(std::move(part.facets));
     std::vector<uint32_t> docs(part.results.size());
     for (size_t j = 0; j < docs.size(); j++) docs[j] = (uint32_t)part.results[j].doc_id;
     std::vector<std::vector<uint64_t>> keys(result_sort.size());
@@ -979,6 +1040,7 @@ ResultObject Index::search_lexical_sorted(const std::vector<uint32_t>& query_ter
     return a.r.doc_id < b.r.doc_id;
   });
   for (size_t j = offset; j < rows.size() && j < offset + length; j++) ro.results.push_back(rows[j].r);
+  if (faceted) ro.facets = merge_facets(query_facets, maps, result_type);
   ro.result_count = ro.results.size();
   return ro;
 }

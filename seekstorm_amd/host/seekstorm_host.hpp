@@ -238,6 +238,11 @@ class Shard {
   std::vector<ResultObject> search_facets(const std::vector<ss_bm25_query>& queries, size_t k, ResultType result_type,
                                           const std::vector<QueryFacet>& query_facets, const std::vector<ss_facet_filter>& facet_filter = {},
                                           size_t shard_number = 1, std::vector<uint64_t>* counts = nullptr, bool mark_frequent = true);
+  // ONE query under result_sort WITH its query_facets (ss_bm25_search_sorted_facets): the hits of search_lexical_shard(.., result_sort)
+  // at (0, k) and the facets of search_facets, from one match set.  1 .. SS_MAX_SORT_FIELDS sort fields; ResultType::Count: no docs.
+  ResultObject search_lexical_sorted_facets(const ss_bm25_query& query, const std::vector<ResultSort>& result_sort, size_t k,
+                                            ResultType result_type, const std::vector<QueryFacet>& query_facets,
+                                            const std::vector<ss_facet_filter>& facet_filter = {}, size_t shard_number = 1);
   // query_facets of one query (facet_count, add_result.rs:484-640): counts [n_buckets + 1], the last slot = outside the buckets.
   // String facets: n_buckets ids (bounds empty); numeric facets: the ranges' ascending lower bounds as the value's bits;
   // Point facets (facet_type SS_FACET_POINT): base + the lower bounds of the distance ranges as f64 bits.
@@ -320,9 +325,12 @@ class Index {
   // (Shard::search_lexical_shard with result_sort), the lists are merged under the same order across shards -- the facet
   // values of the two docs, each read from its own shard, then the score (result_ordering_root, min_heap.rs:56-300;
   // search.rs:2088) --, then offset / length.  Global ids, totals summed.  Any query type, QueryType::Phrase included.
+  // query_facets: counted by every shard in the same call as its sorted hits (Shard::search_lexical_sorted_facets), the shards' maps
+  // merged into ResultObject::facets (merge_facets; result_type as for search(): Topk no facets, Count no docs).
   ResultObject search_lexical_sorted(const std::vector<uint32_t>& query_terms, QueryType query_type_default, size_t offset, size_t length,
                                      const std::vector<ResultSort>& result_sort, const std::vector<ss_facet_filter>& facet_filter = {},
-                                     const std::vector<uint32_t>& not_terms = {});
+                                     const std::vector<uint32_t>& not_terms = {}, const std::vector<QueryFacet>& query_facets = {},
+                                     ResultType result_type = ResultType::TopkCount);
 
   // <IndexArc as Search>::search for this path.  query_terms: resolved term ids (empty = no lexical part);
   // query_vector: dim floats or nullptr; Cosine with external inference -> normalised here when normalize_query.

@@ -1364,6 +1364,38 @@ class Shard:
             at += int(n) + 1
         return doc, score, cnt, tot, per
 
+    def search_lexical_sorted_facets(self, queries, result_sort, k, query_facets, result_type=ResultType.TopkCount, facet_filter=None):
+        """search_lexical_sorted_batch with the batch's query_facets in the same call (ss_bm25_search_sorted_facets): every chunk's match
+        sets are built once, and one launch counts the facets and the first radix byte of the sort.  -> (doc, score, count, total,
+        counts_per_facet): the first four are search_lexical_sorted_batch's, counts_per_facet search_lexical_facets'.
+        ResultType.Topk: the same docs, totals and counters; ResultType.Count: no docs (k is not read), totals and counters."""
+        n, arr = self._result_sorts(list(result_sort or []))
+        q = np.ascontiguousarray(queries)
+        query_facets = list(query_facets or [])
+        nq, nf_ = len(q), len(query_facets)
+        kk = max(int(k), 1)
+        doc = np.full((nq, kk), N.SS_NO_DOC, np.uint32)
+        score = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.uint32)
+        tot = np.zeros(nq, np.uint64)
+        off = ty = nb = allb = bases = out = None
+        stride = 0
+        if nf_:
+            off, ty, nb, allb, bases, stride = self._query_facet_args(query_facets)
+            out = np.zeros((nq, stride), np.uint64)
+        farr, nf = self.facet_filters(facet_filter) if facet_filter else (None, 0)
+        N.check(N.lib().ss_bm25_search_sorted_facets(self._h, nq, q.ctypes.data_as(C.c_void_p), n, C.cast(arr, C.c_void_p) if n else None, int(k),
+                                                     int(result_type), nf, None if farr is None else C.cast(farr, C.c_void_p), nf_,
+                                                     N.ptr(off, N.u32p), N.ptr(ty, N.u32p), N.ptr(nb, N.u32p), N.ptr(allb, N.u64p),
+                                                     None if bases is None else C.cast(bases, C.c_void_p), N.ptr(doc, N.u32p),
+                                                     N.ptr(score, N.f32p), N.ptr(cnt, N.u32p), N.ptr(tot, N.u64p), N.ptr(out, N.u64p)),
+                "ss_bm25_search_sorted_facets")
+        per, at = [], 0
+        for b in (nb if nf_ else []):
+            per.append(out[:, at:at + int(b) + 1])
+            at += int(b) + 1
+        return doc, score, cnt, tot, per
+
     def search_vector_batch(self, query_vectors, k, similarity_threshold=None, ann_mode=None, with_clusters=False,
                             field_filter=None, with_observed=False):
         """with_observed: -> (..., observed_cluster_count, observed_vector_count) per query (vector.rs:421, 1394, 1510)"""
@@ -1704,7 +1736,8 @@ class Index:
         the sort, the lists are merged under the same order across shards -- the facet values of the two docs, each read from its
         own shard, then the score (result_ordering_root, min_heap.rs:56-300; search.rs:2088).
         query_facets (SearchMode.Lexical / Hybrid; see finish_facets): counted on the lexical side of every shard in the same call as
-        its hits, the shards' maps merged into ResultObject.facets (merge_facets).  Both work with query_type_default = Phrase: the
+        its hits, the shards' maps merged into ResultObject.facets (merge_facets).  With a result_sort too (SearchMode.Lexical): every
+        shard answers both from one match set (Shard.search_lexical_sorted_facets).  Both work with query_type_default = Phrase: the
         shards count and sort a phrase's matches on the device.
         enable_empty_query (the crate's argument, default False: nothing changes): SearchMode.Lexical with no query terms lists the
         docs instead of raising or returning nothing -- see _search_empty; in result_sort the `_id` / `_score` fields are spelt
@@ -1714,16 +1747,27 @@ class Index:
         ro = ResultObject()
         if enable_empty_query and not query_terms and search_mode == SearchMode.Lexical and query_vector is None:
             return self._search_empty(offset, length, result_type, facet_filter, result_sort, query_facets)
-        if query_facets and (result_sort or search_mode not in (SearchMode.Lexical, SearchMode.Hybrid) or not query_terms):
-            raise ValueError("query_facets apply to lexical and hybrid searches by score")
+        if query_facets and (search_mode not in (SearchMode.Lexical, SearchMode.Hybrid) or not query_terms):
+            raise ValueError("query_facets apply to lexical and hybrid searches")
+        if query_facets and result_sort and (search_mode != SearchMode.Lexical or not self.shards):
+            # (without a shard there is no facet schema to resolve the sort field against)
+            raise ValueError("query_facets under a result_sort apply to lexical searches of an index with shards")
         if result_sort:
             if search_mode != SearchMode.Lexical or not query_terms:
                 raise ValueError("result_sort applies to lexical searches")
-            rows = []
+            rows, shard_maps = [], []
             for sh in self.shards:
                 q = sh.make_queries([list(query_terms)], query_type_default, [list(not_terms)],
                                     field_filter=field_filter if sh.lexical_field_count > 1 else None)
-                d, sc, tot = sh.search_lexical_sorted(q, list(result_sort), offset + length, facet_filter)
+                if query_facets:  # the shard's sorted hits and its counters from one match set (ss_bm25_search_sorted_facets)
+                    want_docs = int(result_type) != int(ResultType.Count) and offset + length > 0
+                    dd, ss, cc, tt, per = sh.search_lexical_sorted_facets(q[:1], list(result_sort), offset + length, query_facets,
+                                                                          result_type if want_docs else ResultType.Count, facet_filter)
+                    n = min(int(cc[0]), dd.shape[1]) if want_docs else 0
+                    d, sc, tot = dd[0][:n].copy(), ss[0][:n].copy(), int(tt[0])
+                    shard_maps.append(finish_facets(query_facets, [c[0] for c in per], S))
+                else:
+                    d, sc, tot = sh.search_lexical_sorted(q, list(result_sort), offset + length, facet_filter)
                 ro.result_count_total += tot
                 keys = []
                 for sf in result_sort:
@@ -1734,6 +1778,8 @@ class Index:
             rows.sort()
             if result_type != ResultType.Count:
                 ro.results = [Result(g, -ns, ResultSource.Lexical) for _, ns, g in rows[offset:offset + length]]
+            if query_facets:
+                ro.facets = merge_facets(query_facets, shard_maps, result_type)
             ro.result_count = len(ro.results)
             return ro
         want_lex = search_mode in (SearchMode.Lexical, SearchMode.Hybrid) and query_terms
