@@ -1,7 +1,6 @@
 // C ABI of the MI355X-native SeekStorm query hot path (see include/seekstorm_hip.h for the contract and the
 // reference seams each entry point replaces).  Host-side plumbing only; the kernels live in vec_scan.hip / bm25.hip.
-#include <linux/futex.h>
-#include <sys/syscall.h>
+// The coalescer of concurrent callers stands in api_coalesce.hip, the deep pages in api_deep.hip; api_internal.h is what the three share.
 #include <sched.h>
 #include <time.h>
 #include <unistd.h>
@@ -27,49 +26,9 @@
 #include "bm25_pack.h"
 #include "browse.h"
 #include "facet_commit.h"
-
-#define SS_TRY(x)          \
-  do {                     \
-    int _rc = (x);         \
-    if (_rc) return _rc;   \
-  } while (0)
+#include "api_internal.h"
 
 namespace {
-// The shard's exclusion bitmap (d_deleted / deleted_words / n_deleted: its tombstones, as a rule) replaced by another one for the life
-// of the object; n_deleted = 1 says "some doc may be excluded": the kernels take their filtered instantiations.  per_query() /
-// vec_stride(): the bitmap is one of `words` words PER QUERY of the lexical / vector batch in flight; both flags are restored with the
-// bitmap and otherwise left as they stand (0 outside such a batch: no guard nests inside one).  The caller holds the shard lock.
-struct ExclSwap {
-  ss_shard* s;
-  uint32_t* del; uint64_t dw, nd; uint32_t pq, stride;
-  ExclSwap(ss_shard* s_, uint32_t* bits, uint64_t words)
-      : s(s_), del(s_->d_deleted), dw(s_->deleted_words), nd(s_->n_deleted), pq(s_->del_per_query), stride(s_->vec_del_stride) {
-    s->d_deleted = bits; s->deleted_words = words; s->n_deleted = 1;
-  }
-  ExclSwap(const ExclSwap&) = delete;
-  ~ExclSwap() { s->d_deleted = del; s->deleted_words = dw; s->n_deleted = nd; s->del_per_query = pq; s->vec_del_stride = stride; }
-  void per_query() { s->del_per_query = 1; }
-  void vec_stride(uint32_t words) { s->vec_del_stride = words; }
-};
-
-// Grow-only device workspace: *ptr holds at least `need` units (bytes behind a void*, elements else); a hipMalloc / hipFree pair per
-// call would synchronise the device.  Growing waits for s->stream first -- work still queued may read the old block --, frees it and
-// allocates `alloc` units (where a caller keeps slack against the next growth).  hipFree waits for the device anyway, so the explicit
-// wait costs the call sites that had none nothing, and the steady state (need <= *cap) does not touch the device at all.  On
-// failure *ptr = nullptr and *cap = 0.
-template <typename T>
-int reserve(ss_shard* s, T** ptr, size_t* cap, size_t need, size_t alloc = 0) {
-  if (need <= *cap) return SS_OK;
-  alloc = std::max(alloc, need);
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr;
-  *cap = 0;
-  SS_HIP(hipMalloc((void**)ptr, alloc * sizeof(std::conditional_t<std::is_void<T>::value, char, T>)));
-  *cap = alloc;
-  return SS_OK;
-}
-
 // runs `search` with the shard's tombstone bitmap replaced by the filter's exclusion bitmap (built on `st` first; `prebuilt`: the caller
 // has built THESE filters' bitmap on `st` already and nothing has written d_filter_bits since -- ss_bm25_search_facets builds it once)
 template <typename F>
@@ -113,17 +72,6 @@ int level_rules(uint32_t level, uint32_t n_level_docs, const Levels& levels) {
   return SS_OK;
 }
 }  // namespace
-
-// SS_CO_TRACE: where a coalesced lexical batch spends its time (sums in us; printed when the shard is destroyed)
-struct CoTrace { std::atomic<uint64_t> n{0}, stage{0}, enqueue{0}, wait{0}, scatter{0}, linger{0}, wake{0}, members{0}; };
-static CoTrace g_co_trace;
-// ... and of the VECTOR coalescer, batch by batch (SS_CO_TRACE: what a pass waited for and whom it left behind)
-struct CoVecBatch { uint32_t members, left_queued, linger_us, batch_us; uint64_t t_formed_us; };
-static std::vector<CoVecBatch> g_co_vec_trace;
-static std::vector<uint32_t> g_co_vec_wake_us, g_co_vec_run_us;  // per vector batch: the leader's wake loop, and the batch itself (stage .. answers scattered)
-static std::mutex g_co_vec_trace_mu;
-static const bool g_co_trace_on = getenv("SS_CO_TRACE") != nullptr;
-static inline uint64_t co_now_us() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 extern "C" {
 
@@ -193,20 +141,6 @@ int ss_shard_create(int device, ss_shard** out) {
   *out = s;
   return SS_OK;
 }
-
-// The shard mutex, as everybody but the coalescer's lane path takes it: with the lane streams drained (ss_common.h lstream) -- whoever
-// holds it may write the lexical image or enqueue writers on s->stream, and no lane kernel is in flight to meet them.
-struct ShardLock {
-  std::unique_lock<std::mutex> g;
-  explicit ShardLock(ss_shard* s) : g(s->mu) {
-    s->main_dirty = true;  // (whatever this section enqueues on s->stream: the next lane launch waits for it)
-    if (s->lanes_inflight) {
-      for (hipStream_t st : s->lstream)
-        if (st) (void)hipStreamSynchronize(st);
-      s->lanes_inflight = false;
-    }
-  }
-};
 
 // RAII: a search on a stream other than the shard's own runs on that stream's set of scan buffers (swapped into the shard's
 // fields while the launches are enqueued -- under s->mu -- and back afterwards; buffers are allocated lazily by the scan code)
@@ -307,46 +241,7 @@ static void free_bm25(ss_shard* s, bool keep_tier = false) {
 
 int ss_shard_destroy(ss_shard* s) {
   if (!s) return SS_EINVAL;
-  if (g_co_trace_on && g_co_trace.n.load()) {
-    const double n = (double)g_co_trace.n.load() * 1000.0;  // ns -> us per batch
-    fprintf(stderr, "[co] %llu lexical batches: stage %.1f us, search call %.1f us (enqueue %.1f + device wait %.1f), scatter %.1f us, waking %.1f members %.1f us per batch\n",
-            (unsigned long long)g_co_trace.n.load(), g_co_trace.stage.load() / n, g_co_trace.wait.load() / n, g_co_trace.enqueue.load() / n,
-            g_co_trace.linger.load() / n, g_co_trace.scatter.load() / n, g_co_trace.members.load() / (double)g_co_trace.n.load(), g_co_trace.wake.load() / n);
-  }
-  if (g_co_trace_on && !g_co_vec_trace.empty()) {
-    std::lock_guard<std::mutex> gt(g_co_vec_trace_mu);
-    std::vector<uint32_t> m, l, q;
-    std::vector<uint64_t> gap;
-    for (size_t i = 0; i < g_co_vec_trace.size(); i++) {
-      m.push_back(g_co_vec_trace[i].members); l.push_back(g_co_vec_trace[i].linger_us); q.push_back(g_co_vec_trace[i].left_queued);
-      if (i) gap.push_back(g_co_vec_trace[i].t_formed_us - g_co_vec_trace[i - 1].t_formed_us);
-    }
-    auto pc = [](std::vector<uint32_t> v, double p) { std::sort(v.begin(), v.end()); return v[(size_t)(p * (v.size() - 1))]; };
-    auto pc64 = [](std::vector<uint64_t> v, double p) { if (v.empty()) return (uint64_t)0; std::sort(v.begin(), v.end()); return v[(size_t)(p * (v.size() - 1))]; };
-    fprintf(stderr, "[co-vec] %zu batches: members p1 %u p10 %u p50 %u; linger us p50 %u p90 %u p99 %u; left queued p50 %u p90 %u p99 %u; formed-to-formed us p50 %llu p90 %llu p99 %llu\n",
-            m.size(), pc(m, 0.01), pc(m, 0.10), pc(m, 0.50), pc(l, 0.50), pc(l, 0.90), pc(l, 0.99), pc(q, 0.50), pc(q, 0.90), pc(q, 0.99),
-            (unsigned long long)pc64(gap, 0.50), (unsigned long long)pc64(gap, 0.90), (unsigned long long)pc64(gap, 0.99));
-    if (!g_co_vec_wake_us.empty())
-      fprintf(stderr, "[co-vec] wake loop us p50 %u p90 %u p99 %u max %u; batch (formed .. scattered) us p50 %u p99 %u max %u\n", pc(g_co_vec_wake_us, 0.5), pc(g_co_vec_wake_us, 0.9),
-              pc(g_co_vec_wake_us, 0.99), pc(g_co_vec_wake_us, 1.0), pc(g_co_vec_run_us, 0.5), pc(g_co_vec_run_us, 0.99), pc(g_co_vec_run_us, 1.0));
-    // the batches that make a tail: fewer members than usual, a long pass, or a long gap to the batch before -- with their neighbours
-    if (g_co_vec_run_us.size() == g_co_vec_trace.size() && g_co_vec_wake_us.size() == g_co_vec_trace.size() && gap.size() > 8) {
-      const uint32_t m50 = pc(m, 0.5), r50 = pc(g_co_vec_run_us, 0.5);
-      const uint64_t g50 = pc64(gap, 0.5);
-      int shown = 0;
-      for (size_t i = 1; i < g_co_vec_trace.size() && shown < 24; i++) {
-        const uint64_t g = g_co_vec_trace[i].t_formed_us - g_co_vec_trace[i - 1].t_formed_us;
-        if (g_co_vec_trace[i].members * 4u >= m50 * 3u && g_co_vec_run_us[i] * 4u <= r50 * 5u && g * 10u <= g50 * 13u) continue;
-        shown++;
-        for (size_t j = i - 1; j <= std::min(i + 1, g_co_vec_trace.size() - 1); j++)
-          fprintf(stderr, "[co-vec]   %s batch %zu: members %u, left queued %u, linger %u us, formed-to-scattered %u us, wake loop %u us, since the batch before %llu us\n",
-                  j == i ? "*" : " ", j, g_co_vec_trace[j].members, g_co_vec_trace[j].left_queued, g_co_vec_trace[j].linger_us, g_co_vec_run_us[j], g_co_vec_wake_us[j],
-                  (unsigned long long)(j ? g_co_vec_trace[j].t_formed_us - g_co_vec_trace[j - 1].t_formed_us : 0));
-      }
-    }
-    g_co_vec_wake_us.clear(); g_co_vec_run_us.clear();
-    g_co_vec_trace.clear();
-  }
+  ssi_co_trace_report();
   (void)hipSetDevice(s->device);
   (void)hipStreamSynchronize(s->stream);
   if (s->vstream) (void)hipStreamSynchronize(s->vstream);
@@ -413,11 +308,6 @@ static int ensure_out(ss_shard* s, size_t nq, size_t k) {
   SS_HIP(hipMalloc(&s->d_out_total, nq * sizeof(uint64_t)));
   s->out_cap = need; s->q_cap = nq;
   return SS_OK;
-}
-
-// device staging of host-pointer queries
-static int ensure_qstage(ss_shard* s, size_t bytes) {
-  return reserve(s, &s->d_qstage, &s->qstage_cap, bytes);
 }
 
 // ------------------------------------------------------------------ BM25
@@ -671,21 +561,6 @@ int ss_bm25_synth(ss_shard* s, uint64_t seed, uint64_t n_docs, uint32_t n_terms,
 // image, not a host pass over the shard.  The new image is built beside the old one; searches keep running on the old image until the
 // swap, which waits for the searches in flight and releases the old arrays.
 static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, const uint64_t* offs,
-                             const uint32_t* docs, const uint16_t* tfs, bool with_pos, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions);
-int ss_bm25_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, const uint64_t* offs,
-                         const uint32_t* docs, const uint16_t* tfs) {
-  return ss_guard([&] { return append_level_impl(s, level, n_level_docs, level_doclen, n_terms, offs, docs, tfs, false, nullptr, nullptr, 0); }, SS_ENOMEM, SS_EDEVICE);
-}
-// ... with the postings' POSITIONS (phrase queries on an image that grows by commits): positions = every posting's, in CSR order, tf of
-// them each -- or npos[i] where that is not the tf (npos may be NULL): the component terms of an n-gram key, whose own positions stand
-// behind its first component's postings.  Every level of an image brings positions, or none does.
-int ss_bm25_append_level_positions(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms,
-                                   const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions,
-                                   uint64_t n_positions) {
-  if (n_positions && !positions) return SS_EINVAL;
-  return ss_guard([&] { return append_level_impl(s, level, n_level_docs, level_doclen, n_terms, offs, docs, tfs, true, npos, positions, n_positions); }, SS_ENOMEM, SS_EDEVICE);
-}
-static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, const uint64_t* offs,
                              const uint32_t* docs, const uint16_t* tfs, bool with_pos, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
   if (!s || !level_doclen || !offs || n_terms == 0 || n_level_docs == 0 || n_level_docs > 65536u) return SS_EINVAL;
   if (offs[n_terms] && (!docs || !tfs)) return SS_EINVAL;
@@ -807,6 +682,20 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   // the dense image is swapped in either way; a sparse tier that could not follow the new average length would score its terms with
   // the old one: the caller hears about it, and commits again or rebuilds
   return rc_recode;
+}
+
+int ss_bm25_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, const uint64_t* offs,
+                         const uint32_t* docs, const uint16_t* tfs) {
+  return ss_guard([&] { return append_level_impl(s, level, n_level_docs, level_doclen, n_terms, offs, docs, tfs, false, nullptr, nullptr, 0); }, SS_ENOMEM, SS_EDEVICE);
+}
+// ... with the postings' POSITIONS (phrase queries on an image that grows by commits): positions = every posting's, in CSR order, tf of
+// them each -- or npos[i] where that is not the tf (npos may be NULL): the component terms of an n-gram key, whose own positions stand
+// behind its first component's postings.  Every level of an image brings positions, or none does.
+int ss_bm25_append_level_positions(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms,
+                                   const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions,
+                                   uint64_t n_positions) {
+  if (n_positions && !positions) return SS_EINVAL;
+  return ss_guard([&] { return append_level_impl(s, level, n_level_docs, level_doclen, n_terms, offs, docs, tfs, true, npos, positions, n_positions); }, SS_ENOMEM, SS_EDEVICE);
 }
 
 // INCREMENTAL COMMIT of an image with SEVERAL indexed fields (round 6; VERDICT r5 missing 6; commit.rs:142-148 -> the "(re)build device image"
@@ -1443,7 +1332,7 @@ int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, ui
   return SS_OK;
 }
 
-// What the pass over a batch that is about to be uploaded collects besides its verdict (bm25_search_host_queries): the batch in the packed
+// What the pass over a batch that is about to be uploaded collects besides its verdict (ssi_bm25_search_host_queries): the batch in the packed
 // form (bm25_pack.h; given up when a phrase query turns up -- those need phrase_seq / phrase_len), and the postings its scored terms
 // name in all (the pruned kernel's partition rule, ss_common.h bm_batch_postings).
 struct bm_batch_sink {
@@ -1832,15 +1721,249 @@ static int bm25_search_split_batch(ss_shard* s, uint32_t nq, const ss_bm25_query
   return SS_OK;
 }
 
-static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
-                                    const ss_facet_filter* filters, bool filter_prebuilt = false);
+// A UNION that excludes a SPARSE term, or an intersection of dense terms that does (add_result.rs:3440-3497 applies NOT lists to every
+// query type): the dense kernels probe NOT lists through directory rows a sparse list does not have.  Such a query -- rare: a rare word after a minus sign -- is answered on
+// its own with the docs of its sparse NOT lists added to the exclusion bitmap the kernels already honour (tombstones, or a facet
+// filter's bitmap): top-k and exact counts then follow from the paths that serve a shard with deleted docs.  The other queries of
+// the batch run together as always; the single answers are put back into their rows.
+static int bm25_search_tiered_excl(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& special) {
+  const uint32_t kw = std::max<uint32_t>(kk, 1), n_sp = (uint32_t)special.size(), n_dense = s->bm_n_terms / s->bm_n_fields;
+  const size_t words = ((size_t)s->bm_n_docs + 31) / 32;
+  SS_TRY(ensure_out(s, nq, kw));
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t h_doc = 0, h_sc = h_doc + al((size_t)n_sp * kw * 4), h_cnt = h_sc + al((size_t)n_sp * kw * 4), h_tot = h_cnt + al((size_t)n_sp * 4),
+               h_need = h_tot + al((size_t)n_sp * 8);
+  SS_TRY(reserve(s, &s->d_tier_hold, &s->tier_hold_cap, h_need, h_need * 2));
+  SS_TRY(reserve(s, &s->d_excl_bits, &s->excl_words_cap, words));
+  char* H = (char*)s->d_tier_hold;
+  std::vector<ss_bm25_query> rest(q, q + nq);
+  for (uint32_t j = 0; j < n_sp; j++) {
+    const ss_bm25_query& Q = q[special[j]];
+    const uint32_t np = Q.n_terms, n_not = bm_q_nnot(Q.op);
+    ss_bm25_query R = Q;  // the query without its sparse NOT terms
+    uint32_t lists[SS_MAX_QUERY_TERMS], n_lists = 0, kept = 0;
+    for (uint32_t t = 0; t < n_not; t++) {
+      const uint32_t term = Q.term[np + t];
+      if (term >= n_dense) lists[n_lists++] = term - n_dense;
+      else R.term[np + kept++] = term;
+    }
+    for (uint32_t t = np + kept; t < (uint32_t)SS_MAX_QUERY_TERMS; t++) R.term[t] = 0;
+    R.op = (Q.op & ~0xFF00u) | SS_OP_NOT_TERMS(kept);
+    rest[special[j]] = R;  // keeps the row's place in the batch below; its answer is overwritten
+    const bool had = s->n_deleted != 0;
+    SS_TRY(ssi_bm25_sparse_excl_bits(s, had ? s->d_deleted : nullptr, had ? (uint32_t)s->deleted_words : 0u, lists, n_lists, s->d_excl_bits, (uint32_t)words, s->stream));
+    {
+      ExclSwap sw(s, s->d_excl_bits, words);
+      SS_TRY(ssi_bm25_search_host_queries(s, 1, &R, kk, rt, 0, nullptr));
+    }
+    if (nq == 1) return SS_OK;  // the answer stands in row 0 already
+    if (kk) {
+      SS_HIP(hipMemcpyAsync(H + h_doc + (size_t)j * kw * 4, s->d_out_doc, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
+      SS_HIP(hipMemcpyAsync(H + h_sc + (size_t)j * kw * 4, s->d_out_score, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
+    }
+    SS_HIP(hipMemcpyAsync(H + h_cnt + (size_t)j * 4, s->d_out_count, 4, hipMemcpyDeviceToDevice, s->stream));
+    SS_HIP(hipMemcpyAsync(H + h_tot + (size_t)j * 8, s->d_out_total, 8, hipMemcpyDeviceToDevice, s->stream));
+  }
+  SS_TRY(ssi_bm25_search_host_queries(s, nq, rest.data(), kk, rt, 0, nullptr));
+  for (uint32_t j = 0; j < n_sp; j++) {
+    const size_t i = special[j];
+    if (kk) {
+      SS_HIP(hipMemcpyAsync(s->d_out_doc + i * kw, H + h_doc + (size_t)j * kw * 4, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
+      SS_HIP(hipMemcpyAsync(s->d_out_score + i * kw, H + h_sc + (size_t)j * kw * 4, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
+    }
+    SS_HIP(hipMemcpyAsync(s->d_out_count + i, H + h_cnt + (size_t)j * 4, 4, hipMemcpyDeviceToDevice, s->stream));
+    SS_HIP(hipMemcpyAsync(s->d_out_total + i, H + h_tot + (size_t)j * 8, 8, hipMemcpyDeviceToDevice, s->stream));
+  }
+  return SS_OK;
+}
+
+// A UNION of several terms under a field filter that the gated scan does not take: one that names a term of the sparse tier (the dense
+// tier gates every term's unlisted (term, field) lists inside the scan, BM_AND_GATED; the sparse tier keeps one merged list per term),
+// or one of 8 .. 10 terms (the match byte holds 7 term bits).  The
+// query is answered the way the reference itself answers it (union.rs:1168-1305, 1330-1425: union_docid_3 queues the intersection
+// of all terms and every subset down to pairs, union_docid_2 runs a pair as its intersection plus the two single terms; the filter
+// applies to the terms of the sub-query that finds the doc, add_result.rs:3124-3136; a doc found again keeps its better score,
+// min_heap.rs:1193-1260): the 2^n - 1 filtered intersections as ONE batch through both tiers, merged per doc by the maximum -- a doc
+// of the union's top-k is in the top-k of the sub-query that gives it its score.  Totals as the reference reports them: two terms
+// |pass(X) u pass(Y)| (union_docid_2's count), more the UNFILTERED union (union_scan counts a doc before the filter sees it,
+// union.rs:552-553).  Rare (a rare word in a multi-word query under a field filter, or 8+ words under one); <= 10 terms -- the range
+// of union_docid_3 (search.rs:3497-3520) -- i.e. <= 1023 sub-queries in one batch (the sub-queries the specialised kernels do not take
+// run on bm25_gallop.hip); the merge is the host's.
+// A UNION of MORE than 10 terms under a field filter.  The reference leaves union_docid_3's range here (search.rs:3497-3520) and runs
+// union_blockid -> union_scan_32 (union.rs:598-805), whose candidates meet the filter inside add_result_multiterm_multifield
+// (add_result.rs:3124-3136) -- ANOTHER rule than the sub-queries' above: the loop over the doc's PRESENT terms returns at the first one
+// that stands in no listed field, so a doc is an answer iff EVERY term it holds passes the filter, and then scores with all of them (all
+// fields of each, as ever); union_scan has counted it before the filter saw it (union.rs:760-761), so result_count_total is the
+// UNFILTERED union's.  With  R = U_t { docs of t that hold t in unlisted fields only }  that is: the plain union of the merged lists under
+// the exclusion bitmap  tombstones | R.  R comes from the probe index's bit records: the match sets M_t (term t, no filter) and P_t (term
+// t under the filter) of the 2 n single-term queries in ONE ssi_bm25_match_bits call, R |= M_t & ~P_t.  Then the ordinary many-list
+// union runs under that bitmap (every kernel family honours it), its count under the tombstones alone.  Dense terms with probe rows.
+__global__ void gate_rule_bits_kernel(const unsigned long long* __restrict__ sets /*[2 n][groups]: M_0, P_0, M_1, P_1, ...*/, uint32_t n, size_t groups,
+                                      const uint32_t* __restrict__ base, uint32_t base_words, uint32_t* __restrict__ out, uint32_t words) {
+  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 2 < words; g += (size_t)gridDim.x * blockDim.x) {
+    unsigned long long r = 0ull;
+    if (g < groups)
+      for (uint32_t t = 0; t < n; t++) r |= sets[(size_t)(2 * t) * groups + g] & ~sets[(size_t)(2 * t + 1) * groups + g];
+    const size_t w0 = g * 2, w1 = g * 2 + 1;
+    out[w0] = (uint32_t)r | ((base && w0 < base_words) ? base[w0] : 0u);
+    if (w1 < words) out[w1] = (uint32_t)(r >> 32) | ((base && w1 < base_words) ? base[w1] : 0u);
+  }
+}
+static int bm25_search_gated_scan_rule(ss_shard* s, const ss_bm25_query& Q, uint32_t kk, uint32_t rt, uint32_t* a_doc, float* a_score, uint32_t* a_cnt,
+                                       unsigned long long* a_tot) {
+  const uint32_t n = Q.n_terms, nn = bm_q_nnot(Q.op), n_dense = s->bm_n_terms / s->bm_n_fields, kw = std::max<uint32_t>(kk, 1);
+  if (!s->bm_merged || !s->d_probe || 2 * n > 64) return SS_ENOTSUP;
+  SS_HIP(hipSetDevice(s->device));
+  // dense terms: M_t and P_t from the bit records; sparse-tier terms: their postings carry their fields (marked below)
+  std::vector<ss_bm25_query> subs;
+  uint32_t sp_lists[SS_MAX_QUERY_TERMS], n_sp = 0;
+  for (uint32_t t = 0; t < n; t++) {
+    if (Q.term[t] >= n_dense) { sp_lists[n_sp++] = Q.term[t] - n_dense; continue; }
+    for (int f = 0; f < 2; f++) {
+      ss_bm25_query S;
+      memset(&S, 0, sizeof(S));
+      S.n_terms = 1; S.term[0] = Q.term[t]; S.idf[0] = Q.idf[t];
+      S.op = SS_OP_INTERSECTION | (f ? SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op)) : 0u);
+      subs.push_back(S);
+    }
+  }
+  const uint32_t nd2 = (uint32_t)subs.size();  // 2 x the dense terms
+  if (nd2) {
+    bool has_and, has_or, all_probed, any_frequent, phrase = false, any_filter = false, uniform = false, gated = false;
+    uint32_t nt_max, np_max, nn_max = 0;
+    SS_TRY(ssi_bm25_ensure_probe_rows(s, nd2, subs.data(), s->stream));
+    SS_TRY(check_queries(s, nd2, subs.data(), &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
+    if (!all_probed) return SS_ENOTSUP;  // (a rationed vocabulary: the match sets are read from the bit records)
+  }
+  const size_t groups = (size_t)s->bm_n_sub * (BM_SUB / 64), words = ((size_t)s->bm_n_docs + 31) / 32;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_q = 0, o_tot = o_q + al(64 * sizeof(ss_bm25_query)), o_sets = o_tot + al(64 * 8), need = o_sets + al(2 * (size_t)n * groups * 8);
+  SS_TRY(reserve(s, &s->d_gate_ws, &s->gate_ws_cap, need));
+  SS_TRY(reserve(s, &s->d_excl_bits, &s->excl_words_cap, words));
+  char* W = (char*)s->d_gate_ws;
+  if (nd2) {
+    SS_HIP(hipMemcpy(W + o_q, subs.data(), subs.size() * sizeof(ss_bm25_query), hipMemcpyHostToDevice));  // (synchronous: `subs` is a local)
+    SS_TRY(ssi_bm25_match_bits(s, (const ss_bm25_query*)(W + o_q), (unsigned long long*)(W + o_sets), (unsigned long long*)(W + o_tot), s->stream, nd2));
+  }
+  const bool had = s->n_deleted != 0;
+  gate_rule_bits_kernel<<<(uint32_t)std::min<size_t>(2048, (words / 2 + 256) / 256), 256, 0, s->stream>>>(
+      (const unsigned long long*)(W + o_sets), nd2 / 2, groups, had ? s->d_deleted : nullptr, had ? (uint32_t)s->deleted_words : 0u, s->d_excl_bits, (uint32_t)words);
+  SS_HIP(hipGetLastError());
+  SS_TRY(ssi_bm25_sparse_mark_unlisted(s, sp_lists, n_sp, bm_q_field_filter(Q.op), s->d_excl_bits, (uint32_t)words, s->stream));
+  ss_bm25_query U = Q;  // the plain union: the filter is in the bitmap now
+  U.op = SS_OP_UNION | SS_OP_NOT_TERMS(nn);
+  *a_cnt = 0; *a_tot = 0;
+  if (kk && rt != SS_RT_COUNT) {
+    {
+      ExclSwap sw(s, s->d_excl_bits, words);
+      SS_TRY(ssi_bm25_search_host_queries(s, 1, &U, kk, SS_RT_TOPK, 0, nullptr));
+    }
+    SS_HIP(hipStreamSynchronize(s->stream));
+    SS_HIP(hipMemcpy(a_doc, s->d_out_doc, (size_t)kw * 4, hipMemcpyDeviceToHost));
+    SS_HIP(hipMemcpy(a_score, s->d_out_score, (size_t)kw * 4, hipMemcpyDeviceToHost));
+    SS_HIP(hipMemcpy(a_cnt, s->d_out_count, 4, hipMemcpyDeviceToHost));
+    *a_tot = *a_cnt;
+  }
+  if (rt != SS_RT_TOPK) {
+    SS_TRY(ssi_bm25_search_host_queries(s, 1, &U, 0, SS_RT_COUNT, 0, nullptr));
+    SS_HIP(hipStreamSynchronize(s->stream));
+    SS_HIP(hipMemcpy(a_tot, s->d_out_total, 8, hipMemcpyDeviceToHost));
+  }
+  return SS_OK;
+}
+
+static int bm25_search_compose(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& composed) {
+  const uint32_t kw = std::max<uint32_t>(kk, 1), n_co = (uint32_t)composed.size();
+  std::vector<uint32_t> a_doc((size_t)n_co * kw, SS_NO_DOC), a_cnt(n_co, 0);
+  std::vector<float> a_score((size_t)n_co * kw, 0.f);
+  std::vector<unsigned long long> a_tot(n_co, 0);
+  std::vector<ss_bm25_query> rest(q, q + nq);
+  const uint32_t rt_sub = rt == SS_RT_TOPK ? SS_RT_TOPK : (rt == SS_RT_COUNT ? SS_RT_COUNT : SS_RT_TOPKCOUNT);
+  for (uint32_t j = 0; j < n_co; j++) {
+    const ss_bm25_query& Q = q[composed[j]];
+    const uint32_t n = Q.n_terms, nn = bm_q_nnot(Q.op);
+    const uint32_t op_sub = SS_OP_INTERSECTION | SS_OP_NOT_TERMS(nn) | SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op));
+    if (n > 10) {  // the reference's other rule (union_scan + the per-doc filter): above
+      SS_TRY(bm25_search_gated_scan_rule(s, Q, kk, rt, a_doc.data() + (size_t)j * kw, a_score.data() + (size_t)j * kw, &a_cnt[j], &a_tot[j]));
+      rest[composed[j]] = Q;  // keeps the row's place in the batch below; its answer is overwritten
+      rest[composed[j]].n_terms = 1;
+      for (uint32_t t = 1; t < (uint32_t)SS_MAX_QUERY_TERMS; t++) { rest[composed[j]].term[t] = 0; rest[composed[j]].idf[t] = 0.f; }
+      rest[composed[j]].op = SS_OP_INTERSECTION | SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op));
+      continue;
+    }
+    std::vector<ss_bm25_query> subs;
+    for (uint32_t m = 1; m < (1u << n); m++) {
+      ss_bm25_query S;
+      memset(&S, 0, sizeof(S));
+      for (uint32_t t = 0; t < n; t++)
+        if ((m >> t) & 1u) { S.term[S.n_terms] = Q.term[t]; S.idf[S.n_terms] = Q.idf[t]; S.n_terms++; }
+      if (S.n_terms + nn > (uint32_t)SS_MAX_QUERY_TERMS) return SS_EINVAL;
+      for (uint32_t t = 0; t < nn; t++) S.term[S.n_terms + t] = Q.term[n + t];
+      S.op = op_sub;
+      subs.push_back(S);
+    }
+    rest[composed[j]] = subs[0];  // keeps the row's place in the batch below; its answer is overwritten
+    rest[composed[j]].op = SS_OP_INTERSECTION | SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op));
+    const uint32_t ns = (uint32_t)subs.size();
+    std::vector<unsigned long long> tot(ns, 0);
+    std::vector<std::pair<float, uint32_t>> ranked;
+    const bool need_subs = rt != SS_RT_COUNT || n == 2;
+    if (need_subs) {
+      SS_TRY(ssi_bm25_search_host_queries(s, ns, subs.data(), kk, rt_sub, 0, nullptr));
+      std::vector<uint32_t> doc((size_t)ns * kw), cnt(ns);
+      std::vector<float> score((size_t)ns * kw);
+      SS_HIP(hipStreamSynchronize(s->stream));
+      if (kk && rt != SS_RT_COUNT) {
+        SS_HIP(hipMemcpy(doc.data(), s->d_out_doc, (size_t)ns * kw * 4, hipMemcpyDeviceToHost));
+        SS_HIP(hipMemcpy(score.data(), s->d_out_score, (size_t)ns * kw * 4, hipMemcpyDeviceToHost));
+        SS_HIP(hipMemcpy(cnt.data(), s->d_out_count, (size_t)ns * 4, hipMemcpyDeviceToHost));
+        std::unordered_map<uint32_t, float> best;
+        for (uint32_t i = 0; i < ns; i++)
+          for (uint32_t r = 0; r < std::min(cnt[i], kk); r++) {
+            auto it = best.find(doc[(size_t)i * kw + r]);
+            if (it == best.end()) best.emplace(doc[(size_t)i * kw + r], score[(size_t)i * kw + r]);
+            else if (score[(size_t)i * kw + r] > it->second) it->second = score[(size_t)i * kw + r];
+          }
+        ranked.reserve(best.size());
+        for (const auto& e : best) ranked.emplace_back(e.second, e.first);
+        std::sort(ranked.begin(), ranked.end(), [](const std::pair<float, uint32_t>& a, const std::pair<float, uint32_t>& b) {
+          return a.first != b.first ? a.first > b.first : a.second < b.second;
+        });
+        if (ranked.size() > kk) ranked.resize(kk);
+      }
+      if (rt != SS_RT_TOPK) SS_HIP(hipMemcpy(tot.data(), s->d_out_total, (size_t)ns * 8, hipMemcpyDeviceToHost));
+    }
+    for (size_t r = 0; r < ranked.size(); r++) { a_doc[(size_t)j * kw + r] = ranked[r].second; a_score[(size_t)j * kw + r] = ranked[r].first; }
+    a_cnt[j] = (uint32_t)ranked.size();
+    if (rt == SS_RT_TOPK) a_tot[j] = ranked.size();
+    else if (n == 2) a_tot[j] = tot[0] + tot[1] - tot[2];  // subsets in mask order: {X}, {Y}, {X, Y}
+    else {
+      ss_bm25_query U = Q;
+      U.op = SS_OP_UNION | SS_OP_NOT_TERMS(nn);
+      SS_TRY(ssi_bm25_search_host_queries(s, 1, &U, 0, SS_RT_COUNT, 0, nullptr));
+      SS_HIP(hipStreamSynchronize(s->stream));
+      SS_HIP(hipMemcpy(&a_tot[j], s->d_out_total, 8, hipMemcpyDeviceToHost));
+    }
+  }
+  if (n_co < nq) SS_TRY(ssi_bm25_search_host_queries(s, nq, rest.data(), kk, rt, 0, nullptr));
+  else SS_TRY(ensure_out(s, nq, kw));
+  SS_HIP(hipStreamSynchronize(s->stream));
+  for (uint32_t j = 0; j < n_co; j++) {
+    const size_t i = composed[j];
+    if (kk && rt != SS_RT_COUNT) {
+      SS_HIP(hipMemcpy(s->d_out_doc + i * kw, a_doc.data() + (size_t)j * kw, (size_t)kw * 4, hipMemcpyHostToDevice));
+      SS_HIP(hipMemcpy(s->d_out_score + i * kw, a_score.data() + (size_t)j * kw, (size_t)kw * 4, hipMemcpyHostToDevice));
+    }
+    SS_HIP(hipMemcpy(s->d_out_count + i, &a_cnt[j], 4, hipMemcpyHostToDevice));
+    SS_HIP(hipMemcpy(s->d_out_total + i, &a_tot[j], 8, hipMemcpyHostToDevice));
+  }
+  return SS_OK;
+}
 
 // A batch in which some query names a term of the SPARSE tier (bm25_sparse.hip).  Those queries are answered in two parts -- their
 // dense terms through the ordinary path (together with the batch's all-dense queries: one sub-batch), their sparse lists by the
 // sparse kernel, which scores every doc of a sparse list in full -- and put together per query by bm25_tier_merge_kernel; the
 // answers land in s->d_out_* in the callers' order, like any other batch's.  Caller holds s->mu.
-static int bm25_search_tiered_excl(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& special);
-static int bm25_search_compose(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& composed);  // (defined below)
 static int bm25_search_tiered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt) {
   const uint32_t n_dense = s->bm_n_terms / s->bm_n_fields;  // public terms of the dense image
   if (s->bm_n_fields != 1 && !s->bm_merged) return SS_ENOTSUP;  // (several indexed fields: the sparse tier holds merged weights)
@@ -1951,7 +2074,7 @@ static int bm25_search_tiered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, 
       s->d_ext_seed = (const float*)(W + o_seed);
       s->ext_seed_n = nd;
     }
-    const int rc_sub = bm25_search_host_queries(s, nd, sub.data(), kk, rt, 0, nullptr);  // -> s->d_out_* rows [0, nd)
+    const int rc_sub = ssi_bm25_search_host_queries(s, nd, sub.data(), kk, rt, 0, nullptr);  // -> s->d_out_* rows [0, nd)
     s->d_ext_seed = nullptr; s->ext_seed_n = 0;
     if (rc_sub != SS_OK) return rc_sub;
   }
@@ -1965,245 +2088,6 @@ static int bm25_search_tiered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, 
   }
   SS_HIP(hipMemcpyAsync(s->d_out_count, W + o_cnt, (size_t)nq * 4, hipMemcpyDeviceToDevice, s->stream));
   SS_HIP(hipMemcpyAsync(s->d_out_total, W + o_tot, (size_t)nq * 8, hipMemcpyDeviceToDevice, s->stream));
-  return SS_OK;
-}
-
-// A UNION that excludes a SPARSE term, or an intersection of dense terms that does (add_result.rs:3440-3497 applies NOT lists to every
-// query type): the dense kernels probe NOT lists through directory rows a sparse list does not have.  Such a query -- rare: a rare word after a minus sign -- is answered on
-// its own with the docs of its sparse NOT lists added to the exclusion bitmap the kernels already honour (tombstones, or a facet
-// filter's bitmap): top-k and exact counts then follow from the paths that serve a shard with deleted docs.  The other queries of
-// the batch run together as always; the single answers are put back into their rows.
-static int bm25_search_tiered_excl(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& special) {
-  const uint32_t kw = std::max<uint32_t>(kk, 1), n_sp = (uint32_t)special.size(), n_dense = s->bm_n_terms / s->bm_n_fields;
-  const size_t words = ((size_t)s->bm_n_docs + 31) / 32;
-  SS_TRY(ensure_out(s, nq, kw));
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t h_doc = 0, h_sc = h_doc + al((size_t)n_sp * kw * 4), h_cnt = h_sc + al((size_t)n_sp * kw * 4), h_tot = h_cnt + al((size_t)n_sp * 4),
-               h_need = h_tot + al((size_t)n_sp * 8);
-  SS_TRY(reserve(s, &s->d_tier_hold, &s->tier_hold_cap, h_need, h_need * 2));
-  SS_TRY(reserve(s, &s->d_excl_bits, &s->excl_words_cap, words));
-  char* H = (char*)s->d_tier_hold;
-  std::vector<ss_bm25_query> rest(q, q + nq);
-  for (uint32_t j = 0; j < n_sp; j++) {
-    const ss_bm25_query& Q = q[special[j]];
-    const uint32_t np = Q.n_terms, n_not = bm_q_nnot(Q.op);
-    ss_bm25_query R = Q;  // the query without its sparse NOT terms
-    uint32_t lists[SS_MAX_QUERY_TERMS], n_lists = 0, kept = 0;
-    for (uint32_t t = 0; t < n_not; t++) {
-      const uint32_t term = Q.term[np + t];
-      if (term >= n_dense) lists[n_lists++] = term - n_dense;
-      else R.term[np + kept++] = term;
-    }
-    for (uint32_t t = np + kept; t < (uint32_t)SS_MAX_QUERY_TERMS; t++) R.term[t] = 0;
-    R.op = (Q.op & ~0xFF00u) | SS_OP_NOT_TERMS(kept);
-    rest[special[j]] = R;  // keeps the row's place in the batch below; its answer is overwritten
-    const bool had = s->n_deleted != 0;
-    SS_TRY(ssi_bm25_sparse_excl_bits(s, had ? s->d_deleted : nullptr, had ? (uint32_t)s->deleted_words : 0u, lists, n_lists, s->d_excl_bits, (uint32_t)words, s->stream));
-    {
-      ExclSwap sw(s, s->d_excl_bits, words);
-      SS_TRY(bm25_search_host_queries(s, 1, &R, kk, rt, 0, nullptr));
-    }
-    if (nq == 1) return SS_OK;  // the answer stands in row 0 already
-    if (kk) {
-      SS_HIP(hipMemcpyAsync(H + h_doc + (size_t)j * kw * 4, s->d_out_doc, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
-      SS_HIP(hipMemcpyAsync(H + h_sc + (size_t)j * kw * 4, s->d_out_score, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
-    }
-    SS_HIP(hipMemcpyAsync(H + h_cnt + (size_t)j * 4, s->d_out_count, 4, hipMemcpyDeviceToDevice, s->stream));
-    SS_HIP(hipMemcpyAsync(H + h_tot + (size_t)j * 8, s->d_out_total, 8, hipMemcpyDeviceToDevice, s->stream));
-  }
-  SS_TRY(bm25_search_host_queries(s, nq, rest.data(), kk, rt, 0, nullptr));
-  for (uint32_t j = 0; j < n_sp; j++) {
-    const size_t i = special[j];
-    if (kk) {
-      SS_HIP(hipMemcpyAsync(s->d_out_doc + i * kw, H + h_doc + (size_t)j * kw * 4, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
-      SS_HIP(hipMemcpyAsync(s->d_out_score + i * kw, H + h_sc + (size_t)j * kw * 4, (size_t)kw * 4, hipMemcpyDeviceToDevice, s->stream));
-    }
-    SS_HIP(hipMemcpyAsync(s->d_out_count + i, H + h_cnt + (size_t)j * 4, 4, hipMemcpyDeviceToDevice, s->stream));
-    SS_HIP(hipMemcpyAsync(s->d_out_total + i, H + h_tot + (size_t)j * 8, 8, hipMemcpyDeviceToDevice, s->stream));
-  }
-  return SS_OK;
-}
-
-// A UNION of several terms under a field filter that the gated scan does not take: one that names a term of the sparse tier (the dense
-// tier gates every term's unlisted (term, field) lists inside the scan, BM_AND_GATED; the sparse tier keeps one merged list per term),
-// or one of 8 .. 10 terms (the match byte holds 7 term bits).  The
-// query is answered the way the reference itself answers it (union.rs:1168-1305, 1330-1425: union_docid_3 queues the intersection
-// of all terms and every subset down to pairs, union_docid_2 runs a pair as its intersection plus the two single terms; the filter
-// applies to the terms of the sub-query that finds the doc, add_result.rs:3124-3136; a doc found again keeps its better score,
-// min_heap.rs:1193-1260): the 2^n - 1 filtered intersections as ONE batch through both tiers, merged per doc by the maximum -- a doc
-// of the union's top-k is in the top-k of the sub-query that gives it its score.  Totals as the reference reports them: two terms
-// |pass(X) u pass(Y)| (union_docid_2's count), more the UNFILTERED union (union_scan counts a doc before the filter sees it,
-// union.rs:552-553).  Rare (a rare word in a multi-word query under a field filter, or 8+ words under one); <= 10 terms -- the range
-// of union_docid_3 (search.rs:3497-3520) -- i.e. <= 1023 sub-queries in one batch (the sub-queries the specialised kernels do not take
-// run on bm25_gallop.hip); the merge is the host's.
-// A UNION of MORE than 10 terms under a field filter.  The reference leaves union_docid_3's range here (search.rs:3497-3520) and runs
-// union_blockid -> union_scan_32 (union.rs:598-805), whose candidates meet the filter inside add_result_multiterm_multifield
-// (add_result.rs:3124-3136) -- ANOTHER rule than the sub-queries' above: the loop over the doc's PRESENT terms returns at the first one
-// that stands in no listed field, so a doc is an answer iff EVERY term it holds passes the filter, and then scores with all of them (all
-// fields of each, as ever); union_scan has counted it before the filter saw it (union.rs:760-761), so result_count_total is the
-// UNFILTERED union's.  With  R = U_t { docs of t that hold t in unlisted fields only }  that is: the plain union of the merged lists under
-// the exclusion bitmap  tombstones | R.  R comes from the probe index's bit records: the match sets M_t (term t, no filter) and P_t (term
-// t under the filter) of the 2 n single-term queries in ONE ssi_bm25_match_bits call, R |= M_t & ~P_t.  Then the ordinary many-list
-// union runs under that bitmap (every kernel family honours it), its count under the tombstones alone.  Dense terms with probe rows.
-__global__ void gate_rule_bits_kernel(const unsigned long long* __restrict__ sets /*[2 n][groups]: M_0, P_0, M_1, P_1, ...*/, uint32_t n, size_t groups,
-                                      const uint32_t* __restrict__ base, uint32_t base_words, uint32_t* __restrict__ out, uint32_t words) {
-  for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g * 2 < words; g += (size_t)gridDim.x * blockDim.x) {
-    unsigned long long r = 0ull;
-    if (g < groups)
-      for (uint32_t t = 0; t < n; t++) r |= sets[(size_t)(2 * t) * groups + g] & ~sets[(size_t)(2 * t + 1) * groups + g];
-    const size_t w0 = g * 2, w1 = g * 2 + 1;
-    out[w0] = (uint32_t)r | ((base && w0 < base_words) ? base[w0] : 0u);
-    if (w1 < words) out[w1] = (uint32_t)(r >> 32) | ((base && w1 < base_words) ? base[w1] : 0u);
-  }
-}
-static int bm25_search_gated_scan_rule(ss_shard* s, const ss_bm25_query& Q, uint32_t kk, uint32_t rt, uint32_t* a_doc, float* a_score, uint32_t* a_cnt,
-                                       unsigned long long* a_tot) {
-  const uint32_t n = Q.n_terms, nn = bm_q_nnot(Q.op), n_dense = s->bm_n_terms / s->bm_n_fields, kw = std::max<uint32_t>(kk, 1);
-  if (!s->bm_merged || !s->d_probe || 2 * n > 64) return SS_ENOTSUP;
-  SS_HIP(hipSetDevice(s->device));
-  // dense terms: M_t and P_t from the bit records; sparse-tier terms: their postings carry their fields (marked below)
-  std::vector<ss_bm25_query> subs;
-  uint32_t sp_lists[SS_MAX_QUERY_TERMS], n_sp = 0;
-  for (uint32_t t = 0; t < n; t++) {
-    if (Q.term[t] >= n_dense) { sp_lists[n_sp++] = Q.term[t] - n_dense; continue; }
-    for (int f = 0; f < 2; f++) {
-      ss_bm25_query S;
-      memset(&S, 0, sizeof(S));
-      S.n_terms = 1; S.term[0] = Q.term[t]; S.idf[0] = Q.idf[t];
-      S.op = SS_OP_INTERSECTION | (f ? SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op)) : 0u);
-      subs.push_back(S);
-    }
-  }
-  const uint32_t nd2 = (uint32_t)subs.size();  // 2 x the dense terms
-  if (nd2) {
-    bool has_and, has_or, all_probed, any_frequent, phrase = false, any_filter = false, uniform = false, gated = false;
-    uint32_t nt_max, np_max, nn_max = 0;
-    SS_TRY(ssi_bm25_ensure_probe_rows(s, nd2, subs.data(), s->stream));
-    SS_TRY(check_queries(s, nd2, subs.data(), &has_and, &has_or, &nt_max, &np_max, &all_probed, &any_frequent, &phrase, &any_filter, &uniform, &gated, &nn_max));
-    if (!all_probed) return SS_ENOTSUP;  // (a rationed vocabulary: the match sets are read from the bit records)
-  }
-  const size_t groups = (size_t)s->bm_n_sub * (BM_SUB / 64), words = ((size_t)s->bm_n_docs + 31) / 32;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_q = 0, o_tot = o_q + al(64 * sizeof(ss_bm25_query)), o_sets = o_tot + al(64 * 8), need = o_sets + al(2 * (size_t)n * groups * 8);
-  SS_TRY(reserve(s, &s->d_gate_ws, &s->gate_ws_cap, need));
-  SS_TRY(reserve(s, &s->d_excl_bits, &s->excl_words_cap, words));
-  char* W = (char*)s->d_gate_ws;
-  if (nd2) {
-    SS_HIP(hipMemcpy(W + o_q, subs.data(), subs.size() * sizeof(ss_bm25_query), hipMemcpyHostToDevice));  // (synchronous: `subs` is a local)
-    SS_TRY(ssi_bm25_match_bits(s, (const ss_bm25_query*)(W + o_q), (unsigned long long*)(W + o_sets), (unsigned long long*)(W + o_tot), s->stream, nd2));
-  }
-  const bool had = s->n_deleted != 0;
-  gate_rule_bits_kernel<<<(uint32_t)std::min<size_t>(2048, (words / 2 + 256) / 256), 256, 0, s->stream>>>(
-      (const unsigned long long*)(W + o_sets), nd2 / 2, groups, had ? s->d_deleted : nullptr, had ? (uint32_t)s->deleted_words : 0u, s->d_excl_bits, (uint32_t)words);
-  SS_HIP(hipGetLastError());
-  SS_TRY(ssi_bm25_sparse_mark_unlisted(s, sp_lists, n_sp, bm_q_field_filter(Q.op), s->d_excl_bits, (uint32_t)words, s->stream));
-  ss_bm25_query U = Q;  // the plain union: the filter is in the bitmap now
-  U.op = SS_OP_UNION | SS_OP_NOT_TERMS(nn);
-  *a_cnt = 0; *a_tot = 0;
-  if (kk && rt != SS_RT_COUNT) {
-    {
-      ExclSwap sw(s, s->d_excl_bits, words);
-      SS_TRY(bm25_search_host_queries(s, 1, &U, kk, SS_RT_TOPK, 0, nullptr));
-    }
-    SS_HIP(hipStreamSynchronize(s->stream));
-    SS_HIP(hipMemcpy(a_doc, s->d_out_doc, (size_t)kw * 4, hipMemcpyDeviceToHost));
-    SS_HIP(hipMemcpy(a_score, s->d_out_score, (size_t)kw * 4, hipMemcpyDeviceToHost));
-    SS_HIP(hipMemcpy(a_cnt, s->d_out_count, 4, hipMemcpyDeviceToHost));
-    *a_tot = *a_cnt;
-  }
-  if (rt != SS_RT_TOPK) {
-    SS_TRY(bm25_search_host_queries(s, 1, &U, 0, SS_RT_COUNT, 0, nullptr));
-    SS_HIP(hipStreamSynchronize(s->stream));
-    SS_HIP(hipMemcpy(a_tot, s->d_out_total, 8, hipMemcpyDeviceToHost));
-  }
-  return SS_OK;
-}
-
-static int bm25_search_compose(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& composed) {
-  const uint32_t kw = std::max<uint32_t>(kk, 1), n_co = (uint32_t)composed.size();
-  std::vector<uint32_t> a_doc((size_t)n_co * kw, SS_NO_DOC), a_cnt(n_co, 0);
-  std::vector<float> a_score((size_t)n_co * kw, 0.f);
-  std::vector<unsigned long long> a_tot(n_co, 0);
-  std::vector<ss_bm25_query> rest(q, q + nq);
-  const uint32_t rt_sub = rt == SS_RT_TOPK ? SS_RT_TOPK : (rt == SS_RT_COUNT ? SS_RT_COUNT : SS_RT_TOPKCOUNT);
-  for (uint32_t j = 0; j < n_co; j++) {
-    const ss_bm25_query& Q = q[composed[j]];
-    const uint32_t n = Q.n_terms, nn = bm_q_nnot(Q.op);
-    const uint32_t op_sub = SS_OP_INTERSECTION | SS_OP_NOT_TERMS(nn) | SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op));
-    if (n > 10) {  // the reference's other rule (union_scan + the per-doc filter): above
-      SS_TRY(bm25_search_gated_scan_rule(s, Q, kk, rt, a_doc.data() + (size_t)j * kw, a_score.data() + (size_t)j * kw, &a_cnt[j], &a_tot[j]));
-      rest[composed[j]] = Q;  // keeps the row's place in the batch below; its answer is overwritten
-      rest[composed[j]].n_terms = 1;
-      for (uint32_t t = 1; t < (uint32_t)SS_MAX_QUERY_TERMS; t++) { rest[composed[j]].term[t] = 0; rest[composed[j]].idf[t] = 0.f; }
-      rest[composed[j]].op = SS_OP_INTERSECTION | SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op));
-      continue;
-    }
-    std::vector<ss_bm25_query> subs;
-    for (uint32_t m = 1; m < (1u << n); m++) {
-      ss_bm25_query S;
-      memset(&S, 0, sizeof(S));
-      for (uint32_t t = 0; t < n; t++)
-        if ((m >> t) & 1u) { S.term[S.n_terms] = Q.term[t]; S.idf[S.n_terms] = Q.idf[t]; S.n_terms++; }
-      if (S.n_terms + nn > (uint32_t)SS_MAX_QUERY_TERMS) return SS_EINVAL;
-      for (uint32_t t = 0; t < nn; t++) S.term[S.n_terms + t] = Q.term[n + t];
-      S.op = op_sub;
-      subs.push_back(S);
-    }
-    rest[composed[j]] = subs[0];  // keeps the row's place in the batch below; its answer is overwritten
-    rest[composed[j]].op = SS_OP_INTERSECTION | SS_OP_FIELD_FILTER(bm_q_field_filter(Q.op));
-    const uint32_t ns = (uint32_t)subs.size();
-    std::vector<unsigned long long> tot(ns, 0);
-    std::vector<std::pair<float, uint32_t>> ranked;
-    const bool need_subs = rt != SS_RT_COUNT || n == 2;
-    if (need_subs) {
-      SS_TRY(bm25_search_host_queries(s, ns, subs.data(), kk, rt_sub, 0, nullptr));
-      std::vector<uint32_t> doc((size_t)ns * kw), cnt(ns);
-      std::vector<float> score((size_t)ns * kw);
-      SS_HIP(hipStreamSynchronize(s->stream));
-      if (kk && rt != SS_RT_COUNT) {
-        SS_HIP(hipMemcpy(doc.data(), s->d_out_doc, (size_t)ns * kw * 4, hipMemcpyDeviceToHost));
-        SS_HIP(hipMemcpy(score.data(), s->d_out_score, (size_t)ns * kw * 4, hipMemcpyDeviceToHost));
-        SS_HIP(hipMemcpy(cnt.data(), s->d_out_count, (size_t)ns * 4, hipMemcpyDeviceToHost));
-        std::unordered_map<uint32_t, float> best;
-        for (uint32_t i = 0; i < ns; i++)
-          for (uint32_t r = 0; r < std::min(cnt[i], kk); r++) {
-            auto it = best.find(doc[(size_t)i * kw + r]);
-            if (it == best.end()) best.emplace(doc[(size_t)i * kw + r], score[(size_t)i * kw + r]);
-            else if (score[(size_t)i * kw + r] > it->second) it->second = score[(size_t)i * kw + r];
-          }
-        ranked.reserve(best.size());
-        for (const auto& e : best) ranked.emplace_back(e.second, e.first);
-        std::sort(ranked.begin(), ranked.end(), [](const std::pair<float, uint32_t>& a, const std::pair<float, uint32_t>& b) {
-          return a.first != b.first ? a.first > b.first : a.second < b.second;
-        });
-        if (ranked.size() > kk) ranked.resize(kk);
-      }
-      if (rt != SS_RT_TOPK) SS_HIP(hipMemcpy(tot.data(), s->d_out_total, (size_t)ns * 8, hipMemcpyDeviceToHost));
-    }
-    for (size_t r = 0; r < ranked.size(); r++) { a_doc[(size_t)j * kw + r] = ranked[r].second; a_score[(size_t)j * kw + r] = ranked[r].first; }
-    a_cnt[j] = (uint32_t)ranked.size();
-    if (rt == SS_RT_TOPK) a_tot[j] = ranked.size();
-    else if (n == 2) a_tot[j] = tot[0] + tot[1] - tot[2];  // subsets in mask order: {X}, {Y}, {X, Y}
-    else {
-      ss_bm25_query U = Q;
-      U.op = SS_OP_UNION | SS_OP_NOT_TERMS(nn);
-      SS_TRY(bm25_search_host_queries(s, 1, &U, 0, SS_RT_COUNT, 0, nullptr));
-      SS_HIP(hipStreamSynchronize(s->stream));
-      SS_HIP(hipMemcpy(&a_tot[j], s->d_out_total, 8, hipMemcpyDeviceToHost));
-    }
-  }
-  if (n_co < nq) SS_TRY(bm25_search_host_queries(s, nq, rest.data(), kk, rt, 0, nullptr));
-  else SS_TRY(ensure_out(s, nq, kw));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  for (uint32_t j = 0; j < n_co; j++) {
-    const size_t i = composed[j];
-    if (kk && rt != SS_RT_COUNT) {
-      SS_HIP(hipMemcpy(s->d_out_doc + i * kw, a_doc.data() + (size_t)j * kw, (size_t)kw * 4, hipMemcpyHostToDevice));
-      SS_HIP(hipMemcpy(s->d_out_score + i * kw, a_score.data() + (size_t)j * kw, (size_t)kw * 4, hipMemcpyHostToDevice));
-    }
-    SS_HIP(hipMemcpy(s->d_out_count + i, &a_cnt[j], 4, hipMemcpyHostToDevice));
-    SS_HIP(hipMemcpy(s->d_out_total + i, &a_tot[j], 8, hipMemcpyHostToDevice));
-  }
   return SS_OK;
 }
 
@@ -2302,10 +2186,6 @@ static int bm25_shape_of(const ss_shard* s, const ss_bm25_query& Q, uint32_t kk,
   return SS_OK;
 }
 
-static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
-                                    const ss_facet_filter* filters, bool filter_prebuilt);
-static int bm25_search_compose(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, const std::vector<uint32_t>& composed);
-
 // *handled = false: every query is NATIVE (`*use` = the batch to run: q itself, or `norm` -- the copy with the dropped bits)
 static int bm25_route_shapes(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, std::vector<ss_bm25_query>& norm,
                              const ss_bm25_query** use, bool* handled) {
@@ -2327,7 +2207,7 @@ static int bm25_route_shapes(ss_shard* s, uint32_t nq, const ss_bm25_query* q, u
   if (n_class[SH_NATIVE] == nq) return SS_OK;
   *handled = true;
   const ss_bm25_query* Q = *use;
-  if (n_class[SH_COMPOSE]) {  // (the rest of the batch comes back here through bm25_search_host_queries)
+  if (n_class[SH_COMPOSE]) {  // (the rest of the batch comes back here through ssi_bm25_search_host_queries)
     std::vector<uint32_t> composed;
     for (uint32_t i = 0; i < nq; i++)
       if (shape[i] == SH_COMPOSE) composed.push_back(i);
@@ -2355,7 +2235,7 @@ static int bm25_route_shapes(ss_shard* s, uint32_t nq, const ss_bm25_query* q, u
     const uint32_t n = (uint32_t)sub.size();
     SS_HIP(hipMemcpy(W + o_perm + (size_t)at * 4, perm.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     if (c == SH_NATIVE) {
-      SS_TRY(bm25_search_host_queries(s, n, sub.data(), kk, rt, 0, nullptr));
+      SS_TRY(ssi_bm25_search_host_queries(s, n, sub.data(), kk, rt, 0, nullptr));
     } else {
       SS_HIP(hipMemcpy(W + o_q + (size_t)at * sizeof(ss_bm25_query), sub.data(), (size_t)n * sizeof(ss_bm25_query), hipMemcpyHostToDevice));
       SS_TRY(ssi_bm25_gallop_search(s, n, (const ss_bm25_query*)(W + o_q) + at, c == SH_GALLOP_PHRASE, longest, kk, rt, s->d_out_doc, s->d_out_score,
@@ -2379,10 +2259,10 @@ static int bm25_route_shapes(ss_shard* s, uint32_t nq, const ss_bm25_query* q, u
 }
 
 // the search of ss_bm25_search_filtered / _sharded up to the device lists (s->d_out_*, on s->stream); caller holds s->mu
-static int bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
+extern "C++" int ssi_bm25_search_host_queries(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t kk, uint32_t rt, uint32_t n_filters,
                                     const ss_facet_filter* filters, bool filter_prebuilt) {
   // (a facet filter: its exclusion bitmap stands in for the tombstones of everything below -- every kernel family reads the same one)
-  if (n_filters) return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return bm25_search_host_queries(s, nq, q, kk, rt, 0, nullptr); }, filter_prebuilt);
+  if (n_filters) return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_search_host_queries(s, nq, q, kk, rt, 0, nullptr); }, filter_prebuilt);
   std::vector<ss_bm25_query> norm;
   {
     bool handled = false;
@@ -2681,7 +2561,6 @@ __global__ void __launch_bounds__(256) bm25_answers_home_kernel(const uint32_t* 
     }
   }
 }
-static int bm25_small_wait(ss_shard* s, uint32_t slot, uint32_t seq, bool mu_held);
 // rows [0, nq) of s->d_out_* -> the caller's arrays.  Called under s->mu, behind the search on s->stream.
 static int bm25_answers_home(ss_shard* s, uint32_t nq, uint32_t kk, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
   const size_t cells = (size_t)nq * kk, dwords = 2 * cells + 3 * (size_t)nq;
@@ -2734,7 +2613,7 @@ static int bm25_search_direct_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
                                      bool filter_prebuilt = false) {
   if (!s->d_post) return SS_ESTATE;
   const uint32_t kk = rt == SS_RT_COUNT ? 0 : k, kw = std::max<uint32_t>(kk, 1u);
-  // by shape, like a coalesced batch (bm25_search_direct_lane): the queries that fit the one-launch path take it, the staged pipeline
+  // by shape, like a coalesced batch (ssi_bm25_search_direct_lane): the queries that fit the one-launch path take it, the staged pipeline
   // runs the rest -- one all-dense phrase among a caller's 96 queries used to send all of them down the staged tiered pipeline
   static thread_local std::vector<ss_bm25_query> qs;
   static thread_local std::vector<uint32_t> row_of;
@@ -2772,7 +2651,7 @@ static int bm25_search_direct_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
       memcpy(out_total, s->h_small + SM_H_TOTAL, (size_t)nq * sizeof(uint64_t));
       return SS_OK;
     }
-    SS_TRY(bm25_search_host_queries(s, nq, q, kk, rt, n_filters, filters, filter_prebuilt));
+    SS_TRY(ssi_bm25_search_host_queries(s, nq, q, kk, rt, n_filters, filters, filter_prebuilt));
     return bm25_answers_home(s, nq, kk, out_doc, out_score, out_count, out_total);
   }
   // split: the staged part behind the launch on the same stream, its answers into rows [r0, nq) of a host copy in run order
@@ -2782,7 +2661,7 @@ static int bm25_search_direct_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
   t_doc.resize((size_t)nq * kw); t_score.resize((size_t)nq * kw); t_cnt.resize(nq); t_tot.resize(nq);
   int rc = SS_OK;
   if (nr) {
-    rc = bm25_search_host_queries(s, nr, qq + r0, kk, rt, 0, nullptr);
+    rc = ssi_bm25_search_host_queries(s, nr, qq + r0, kk, rt, 0, nullptr);
     if (rc == SS_OK) {
       SS_HIP(hipStreamSynchronize(s->stream));  // (the launch ahead of it on the stream is done as well)
       SS_HIP(hipMemcpy(t_doc.data() + (size_t)r0 * kw, s->d_out_doc, (size_t)nr * kk * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -2811,7 +2690,7 @@ static int bm25_search_direct_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
   }
   return SS_OK;
 }
-static int bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
+extern "C++" int ssi_bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
                               const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
   ShardLock g(s);
   return bm25_search_direct_locked(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
@@ -2824,9 +2703,10 @@ static int bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, 
 // five terms, ...) must not send sixty-three others down the staged pipeline.  The batch is therefore split by shape: the queries that
 // fit take the one launch (answers in rows 0 .. of the lane's pinned buffers), the rest the staged pipeline (rows behind them); row_of[i]
 // = where query i's answer stands.
-static int bm25_search_direct_lane(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,
+extern "C++" int ssi_bm25_search_direct_lane(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,
                                    uint32_t* out_count, uint64_t* out_total, hipEvent_t ev, uint32_t lane_slot, std::vector<uint32_t>& row_of) {
-  const uint64_t t_in = g_co_trace_on ? co_now_us() : 0;
+  const bool trace = ssi_co_trace_on();
+  const uint64_t t_in = trace ? co_now_us() : 0;
   bool small = false, staged = false;
   uint32_t small_seq = 0;
   row_of.resize(nq);
@@ -2858,7 +2738,7 @@ static int bm25_search_direct_lane(ss_shard* s, uint32_t nq, const ss_bm25_query
     const uint32_t r0 = small ? n_fit : 0u, nr = nq - r0;  // what the staged pipeline runs: the rest, or (no launch) everything
     if (nr) {
       staged = true;
-      SS_TRY(bm25_search_host_queries(s, nr, q + r0, kk, rt, 0, nullptr));
+      SS_TRY(ssi_bm25_search_host_queries(s, nr, q + r0, kk, rt, 0, nullptr));
       if (kk) {
         SS_HIP(hipMemcpyAsync(out_doc + (size_t)r0 * kw, s->d_out_doc, (size_t)nr * kk * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         SS_HIP(hipMemcpyAsync(out_score + (size_t)r0 * kw, s->d_out_score, (size_t)nr * kk * sizeof(float), hipMemcpyDeviceToHost, s->stream));
@@ -2868,515 +2748,28 @@ static int bm25_search_direct_lane(ss_shard* s, uint32_t nq, const ss_bm25_query
       SS_HIP(hipEventRecord(ev, s->stream));
     }
   }
-  const uint64_t te = g_co_trace_on ? co_now_us() : 0;
+  const uint64_t te = trace ? co_now_us() : 0;
   int rc = SS_OK;
   if (small) rc = bm25_small_wait(s, lane_slot, small_seq, false);
   if (staged && hipEventSynchronize(ev) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (both waited for whatever the first says: the buffers are the lane's)
-  if (g_co_trace_on) { g_co_trace.enqueue += te - t_in; g_co_trace.linger += co_now_us() - te; }
+  if (trace) ssi_co_trace_lane(te - t_in, co_now_us() - te);
   return rc;
 }
 
-// ------------------------------------------------------------------ coalescing of concurrent callers (group commit)
-static int vec_search_host(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
-                           float thr, const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count,
-                           uint64_t* out_total, uint32_t* out_clusters, const float* query_norm = nullptr);
-static int vec_search_host_lists(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
-                                 float thr, const ss_ann_mode* mode, uint32_t* h_count, uint32_t** d_ncl_out,
-                                 const float* query_norm = nullptr, bool want_clusters = false, size_t out_slot = 0);
-static int vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
-                                uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total);
-namespace {
-inline void co_futex_wait(std::atomic<uint32_t>* a, uint32_t expect) { (void)syscall(SYS_futex, (uint32_t*)a, FUTEX_WAIT_PRIVATE, expect, nullptr, nullptr, 0); }
-inline void co_futex_wake(std::atomic<uint32_t>* a) { (void)syscall(SYS_futex, (uint32_t*)a, FUTEX_WAKE_PRIVATE, 1, nullptr, nullptr, 0); }
-// set a request's state (1 = done, 3 = lead) and wake its thread if it went to sleep
-inline void co_signal(ss_co_req* r, uint32_t st) {
-  const uint32_t old = r->state.exchange(st, std::memory_order_acq_rel);
-  if (old & 4u) co_futex_wake(&r->state);
-}
-// wait until the state leaves "pending": a SHORT spin, then the futex.  (Spinning for about a batch's duration -- a sleeping
-// follower costs its leader a system call, ~1.5 us each -- was measured and is wrong for a library: 64 spinning callers ran the
-// process into its CPU quota, 185 K -> 47 K q/s with a p99 of 73 ms, the CFS throttling period; gpurun_out/conc_linger2.log)
-inline void co_cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#elif defined(__aarch64__)
-  asm volatile("yield");
-#endif
-}
-inline uint32_t co_wait(ss_co_req* r, uint32_t spin_us) {
-  const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(spin_us);
-  for (;;) {
-    for (int i = 0; i < 64; i++) {
-      const uint32_t v = r->state.load(std::memory_order_acquire);
-      if (v != 0u) return v;
-      co_cpu_relax();
-    }
-    if (std::chrono::steady_clock::now() >= until) break;
-  }
-  for (;;) {
-    uint32_t v = 0u;
-    if (r->state.compare_exchange_strong(v, 4u, std::memory_order_acq_rel)) v = 4u;
-    if (v != 4u) return v;  // done / lead arrived before (or instead of) the sleep
-    co_futex_wait(&r->state, 4u);
-    v = r->state.load(std::memory_order_acquire);
-    if (v != 4u) return v;
-  }
-}
-// requests that can share a batch.  k may differ: the batch runs at the largest k and every member keeps its own prefix -- the
-// result order is total (score descending, then doc id ascending), so the top-k' of a query is the head of its top-k.
-// Only requests of one k CLASS merge (<= 64, <= 128, <= 256, more -- the kernels' top-k register budgets): a caller with a large k
-// must not push the others off the pruned / 16-bit kernels, which serve k <= 128 / k <= 64.
-inline uint32_t co_k_class(uint32_t k) { return k <= 64u ? 0u : k <= 128u ? 1u : k <= 256u ? 2u : 3u; }
-inline bool co_compatible(const ss_co_req* a, const ss_co_req* b) {
-  return (a->k == 0) == (b->k == 0) && co_k_class(a->k) == co_k_class(b->k) && a->rt == b->rt && a->elem == b->elem && a->thr == b->thr &&
-         (a->qscale != nullptr) == (b->qscale != nullptr);
-}
-
-int co_run_lexical_one(ss_shard* s, ss_co_req* r) {
-  return bm25_search_direct(s, r->nq, (const ss_bm25_query*)r->q, r->k, r->rt, 0, nullptr, r->out_doc, r->out_score, r->out_count, r->out_total);
-}
-int co_run_vector_one(ss_shard* s, ss_co_req* r) {
-  return vec_search_host(s, r->nq, r->q, r->elem, r->qscale, r->k, r->thr, nullptr, r->out_doc, r->out_score, r->out_count, r->out_total, nullptr);
-}
-
-// one merged batch: the members' queries back to back, one search, every member's rows copied to its own buffers
-int co_run_batch(ss_shard* s, ss_coalescer& co, bool lexical, const std::vector<ss_co_req*>& batch, uint32_t lane_ix) {
-  ss_co_req* f = batch[0];
-  ss_coalescer::Lane& ln = co.lane[lane_ix];
-  uint32_t total = 0, kk = 0;
-  for (ss_co_req* r : batch) { total += r->nq; kk = std::max(kk, r->k); }
-  const uint32_t kw = std::max<uint32_t>(kk, 1u);
-  const size_t qbytes = lexical ? sizeof(ss_bm25_query) : (size_t)s->dim * f->elem;
-  auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-  const size_t o_q = 0, o_qs = o_q + al((size_t)total * qbytes), o_doc = o_qs + al((size_t)total * 4), o_sc = o_doc + al((size_t)total * kw * 4),
-               o_cnt = o_sc + al((size_t)total * kw * 4), o_tot = o_cnt + al((size_t)total * 4), need = o_tot + al((size_t)total * 8);
-  SS_HIP(hipSetDevice(s->device));
-  if (need > ln.h_pin_cap) {
-    if (ln.h_pin) (void)hipHostFree(ln.h_pin);
-    ln.h_pin = nullptr; ln.h_pin_cap = 0;
-    const size_t cap = std::max<size_t>(need * 2, 1u << 20);
-    SS_HIP(hipHostMalloc((void**)&ln.h_pin, cap, hipHostMallocDefault));
-    ln.h_pin_cap = cap;
-  }
-  if (!ln.ev) SS_HIP(hipEventCreateWithFlags(&ln.ev, hipEventDisableTiming));
-  char* h_q = ln.h_pin + o_q;
-  float* h_qs = (float*)(ln.h_pin + o_qs);
-  uint32_t* h_doc = (uint32_t*)(ln.h_pin + o_doc);
-  float* h_sc = (float*)(ln.h_pin + o_sc);
-  uint32_t* h_cnt = (uint32_t*)(ln.h_pin + o_cnt);
-  uint64_t* h_tot = (uint64_t*)(ln.h_pin + o_tot);
-  const uint64_t tr0 = g_co_trace_on ? co_now_us() : 0;
-  uint32_t at = 0;
-  for (ss_co_req* r : batch) {
-    memcpy(h_q + (size_t)at * qbytes, r->q, (size_t)r->nq * qbytes);
-    if (f->qscale) memcpy(h_qs + at, r->qscale, (size_t)r->nq * sizeof(float));
-    at += r->nq;
-  }
-  const uint64_t tr1 = g_co_trace_on ? co_now_us() : 0;
-  int rc;
-  static thread_local std::vector<uint32_t> row_of;  // lexical: the row of the lane's buffers that holds query i's answer (bm25_search_direct_lane)
-  if (lexical)
-    rc = bm25_search_direct_lane(s, total, (const ss_bm25_query*)h_q, kk, f->rt, h_doc, h_sc, h_cnt, h_tot, ln.ev, 1u + lane_ix, row_of);
-  else
-    rc = vec_search_host_lane(s, total, h_q, f->elem, f->qscale ? h_qs : nullptr, kk, f->thr, h_doc, h_sc, h_cnt, h_tot);
-  if (rc != SS_OK) return rc;
-  const uint64_t tr2 = g_co_trace_on ? co_now_us() : 0;
-  at = 0;
-  for (ss_co_req* r : batch) {
-    for (uint32_t i = 0; i < r->nq; i++) {
-      const size_t row = lexical ? row_of[at + i] : at + i;
-      if (r->k) {
-        memcpy(r->out_doc + (size_t)i * r->k, h_doc + row * kk, (size_t)r->k * sizeof(uint32_t));
-        memcpy(r->out_score + (size_t)i * r->k, h_sc + row * kk, (size_t)r->k * sizeof(float));
-      }
-      r->out_count[i] = std::min(h_cnt[row], r->k);
-      r->out_total[i] = h_tot[row];
-    }
-    r->rc = SS_OK;
-    at += r->nq;
-  }
-  if (g_co_trace_on && lexical) {
-    g_co_trace.n++; g_co_trace.stage += tr1 - tr0; g_co_trace.wait += tr2 - tr1; g_co_trace.scatter += co_now_us() - tr2;
-  }
-  return SS_OK;
-}
-
-int co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_co_req* me) {
-  bool lead;
-  {
-    std::lock_guard<std::mutex> g(co.mu);
-    // a free lane: this thread leads a batch on it at once (nobody in flight: alone, straight away -- a lone caller pays nothing);
-    // invariant: a non-empty queue always has a leader at work, or a successor already told to lead
-    lead = co.leaders < ((co.n_lanes == 2u && (co.lanes_forced || co.callers_est >= co.lanes_from)) ? 2u : 1u);
-    if (lead) {
-      co.leaders++;
-      me->lane = co.lane[0].busy ? 1u : 0u;
-      co.lane[me->lane].busy = true;
-    }
-    co.queue.push_back(me);
-    co.queued_nq.fetch_add(me->nq, std::memory_order_relaxed);
-  }
-  std::vector<ss_co_req*> batch;
-  for (;;) {
-    if (!lead) {
-      // No spin before the sleep (round 6).  Rounds 3-5 spun 30 us first -- a request that arrives in the last 30 us of the batch in flight
-      // saves a futex round trip -- and at T = 64 / 256 callers that was 12.7 / 16 cores busy (290 K .. 350 K calls a second x 30 us), the
-      // whole CPU quota of the box at T = 256, throttled in 19 of 20 CFS periods.  Without it: T = 64 283 -> 297 K q/s on 4.2 cores,
-      // T = 256 345 -> 393 K on 6.7 (p99 1.5 - 2.5 ms -> 0.85), T = 8 unchanged (profiles/r6_spin.log).
-#ifndef CO_SPIN_US
-#define CO_SPIN_US 0u
-#endif
-      const uint32_t v = co_wait(me, CO_SPIN_US);
-      if (v == 1u) return me->rc;
-      me->state.store(0u, std::memory_order_release);  // v == 3: this thread leads the next batch (its request is the queue's front)
-      lead = true;
-    }
-    // Linger.  With T callers in a loop and one batch in flight, half of them ride in the batch and half wait: batches of T / 2
-    // (vectors, T = 64: two 32-query passes of 7.5 ms where one 64-query pass takes 9 ms).  The callers a finished batch has just
-    // released are back within microseconds, so the next leader waits for them -- until as many requests are queued as callers
-    // seem to be around, at most an eighth of the last batch's duration (<= 1 ms), and only if that batch had company at all: a
-    // lone caller is never delayed.  max_wait_us > 0 (ss_shard_set_coalescing) waits that long unconditionally.
-    const uint64_t trace_t_lead_ns = g_co_trace_on && !lexical ? co_now_us() : 0;
-    {
-      uint32_t want, wait_us;
-      {
-        std::lock_guard<std::mutex> g(co.mu);
-        // (several lanes: the callers around are shared between the batches in flight)
-        want = co.max_wait_us ? co.max_batch : std::min(co.callers_est / std::max(co.leaders, 1u), co.max_batch);
-        // (round 5, with the spin still there: an eighth of the last batch's duration, <= 1 ms -- measured at 8 / 4 / 2 / 1 on the C2 image,
-        // T = 64: 247 / 245 / 233 / 254 K q/s at batches of 39 / 48 / 62 / 64; profiles/r5_linger.log)
-        // VECTOR passes: a quarter, <= 3 ms.  A pass costs the same 9 ms for 44 queries as for 64, so whoever misses it pays a whole pass
-        // more -- and a hybrid caller comes back through its lexical half first, which at k = 100 takes 0.5 - 1.5 ms for 64 callers
-        // (profiles/r6_co_vec_trace.log: with the 1 ms cap 6 % of the hybrid searches missed their pass, p99 = 2.3 x p50).
-        // LEXICAL, round 6 (the followers' spin gone, CPU to spare): up to the WHOLE of the last batch's duration, at most 150 us -- a
-        // one-launch batch of top-10 queries takes ~100 us, so the callers it released are all back (one futex wake each, ~1.2 us apiece)
-        // and every batch is full: T = 32 195 -> 245 K q/s, T = 64 303 -> 320 - 346 K (p99 280 -> 240 - 255 us), T = 8 p99 160 -> 94 us
-        // (profiles/r6_linger_div.log).  The cap keeps a hybrid caller's lexical half (k = 100: 0.4 - 0.8 ms a batch) from lingering its
-        // callers past their vector pass (uncapped: hybrid T = 64 p99 21 ms in one of two runs, r6_linger_div_hybrid.log).
-        const uint32_t div = lexical ? 1u : 4u, cap = lexical ? 150u : 3000u;
-        wait_us = co.max_wait_us ? co.max_wait_us : (co.callers_est > 1 ? std::min<uint32_t>(cap, co.last_batch_us / div) : 0u);
-      }
-      if (wait_us) {
-        const auto t_in = std::chrono::steady_clock::now(), until = t_in + std::chrono::microseconds(wait_us);
-        const auto hard_until = t_in + std::chrono::microseconds(std::max<uint32_t>(wait_us, std::min<uint32_t>(co.last_batch_us, 10000u)));
-        // VECTOR passes also leave when the batch is NEARLY full and the arrivals have gone quiet: of 64 callers released together, 63 are
-        // back within ~150 us; now and then one is not (the scheduler's doing) -- waiting out the cap for it costs the 63 a quarter of a
-        // pass each (their p99: 12 - 14 ms against a p50 of 9.4, profiles/r6_tail_repeat.log), where going without it costs ONE caller a
-        // second pass.  (A hybrid caller's lexical halves come back in two or three clumps half a millisecond apart: between clumps the
-        // batch is half empty, and the rule does not fire.)
-#ifndef CO_VEC_QUIET_US
-#define CO_VEC_QUIET_US 700
-#endif
-        const uint32_t nearly = want - std::max(1u, want / 16u);
-        uint32_t have_prev = 0;
-        auto t_change = t_in;
-        for (;;) {
-          uint32_t have = 0;
-          have = co.queued_nq.load(std::memory_order_relaxed);
-          if (have >= want) break;
-          const auto now = std::chrono::steady_clock::now();
-          // members of the batch before that its leader has NOT EVEN WOKEN yet are certain to come: the wake loop is 64 system calls one
-          // after the other, ~100 us as a rule -- and 6 ms now and then, when the leader loses its CPU in the middle (SS_CO_TRACE:
-          // "wake loop us p50 103 p99 572 max 6318").  The three callers it had reached used to lead the next pass without the sixty it
-          // had not (members p1 3): those paid a second pass, 19 ms.  Waited for beyond the cap, up to a pass's duration.
-          const bool pending = co.waking.load(std::memory_order_relaxed) != 0u;
-          if (now >= until && (!pending || now >= hard_until)) break;
-          if (have != have_prev) { have_prev = have; t_change = now; }
-          if (!lexical && !pending && want >= 16u && have >= nearly && now - t_change >= std::chrono::microseconds(CO_VEC_QUIET_US)) break;  // (longer than a lexical linger + batch: a hybrid caller's last clump)
-          for (int i = 0; i < 32; i++) __builtin_ia32_pause();
-        }
-      }
-    }
-    const auto batch_t0 = std::chrono::steady_clock::now();
-    const uint64_t trace_linger_ns = g_co_trace_on && !lexical ? co_now_us() : 0;
-    batch.clear();
-    {
-      std::lock_guard<std::mutex> g(co.mu);
-      uint32_t total = 0;
-      // the leader's own request (told to lead as the queue's front, or just arrived -- then another lane's leader may have taken
-      // requests ahead of it, never its own); with it every queued request that can share its batch
-      ss_co_req* f = me;
-      for (auto it = co.queue.begin(); it != co.queue.end(); ++it)
-        if (*it == me) { co.queue.erase(it); co.queued_nq.fetch_sub(me->nq, std::memory_order_relaxed); break; }
-      batch.push_back(me);  // first, whatever else fits
-      total = me->nq;
-      for (auto it = co.queue.begin(); it != co.queue.end();) {
-        if ((*it)->lane == 0xFFFFFFFFu &&  // (a request that leads a lane itself is not a member of anybody's batch)
-            co_compatible(f, *it) && total + (*it)->nq <= co.max_batch) {
-          total += (*it)->nq;
-          batch.push_back(*it);
-          co.queued_nq.fetch_sub((*it)->nq, std::memory_order_relaxed);
-          it = co.queue.erase(it);
-        } else {
-          ++it;
-        }
-      }
-      co.batches++;
-      co.queries += total;
-      if (g_co_trace_on && !lexical) {
-        uint32_t left = 0;
-        for (ss_co_req* r : co.queue) left += r->nq;
-        std::lock_guard<std::mutex> gt(g_co_vec_trace_mu);
-        g_co_vec_trace.push_back(CoVecBatch{total, left, (uint32_t)((trace_linger_ns - trace_t_lead_ns) / 1000), 0u, trace_linger_ns / 1000});
-      }
-    }
-    // (a lone VECTOR request takes the batch form too: the lane's pinned staging and the scan's own stream -- its pass must not hold the
-    // shard mutex either)
-    if (batch.size() == 1 && lexical) {
-      batch[0]->rc = co_run_lexical_one(s, batch[0]);
-    } else if (co_run_batch(s, co, lexical, batch, me->lane) != SS_OK) {
-      // somebody's request is at fault (or the device is): every member is re-run alone and gets its own verdict
-      for (ss_co_req* r : batch) r->rc = lexical ? co_run_lexical_one(s, r) : co_run_vector_one(s, r);
-    }
-    ss_co_req* succ = nullptr;
-    {
-      std::lock_guard<std::mutex> g(co.mu);
-      uint32_t members = 0, queued = 0;
-      for (ss_co_req* r : batch) members += r->nq;
-      for (ss_co_req* r : co.queue) queued += r->nq;
-      // Callers around = the most seen at the end of any of the last FOUR batches, and never less than 15/16 of the estimate before.  Callers
-      // seen at THIS moment miss those on their way back (a hybrid caller is in its lexical half just now), and one straggler's batch of ONE
-      // used to zero the estimate: the next leader then did not linger at all, took the three callers that happened to be there, and sixty
-      // paid a second pass (profiles/r6_quiet_ab.log: "members p1 3").  A lone caller is not delayed: after four batches of one the
-      // estimate is zero.
-      const uint32_t seen = members + queued, floor_ = co.callers_est - std::max(1u, co.callers_est / 16u);
-      co.seen_ring[co.seen_at++ & 3u] = seen;
-      const uint32_t recent = std::max(std::max(co.seen_ring[0], co.seen_ring[1]), std::max(co.seen_ring[2], co.seen_ring[3]));
-      co.callers_est = recent > 1u ? std::max(recent, co.callers_est > 1u ? floor_ : 0u) : 0u;
-      co.last_batch_us = (uint32_t)std::min<long long>(1000000, std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - batch_t0).count());
-      // hand the lane to the queue's front unless another lane's leader already told it to lead
-      for (ss_co_req* r : co.queue)
-        if (r->lane == 0xFFFFFFFFu) { succ = r; break; }
-      if (succ) succ->lane = me->lane;
-      else { co.leaders--; co.lane[me->lane].busy = false; }
-    }
-    const uint64_t tw0 = g_co_trace_on ? co_now_us() : 0;
-    if (succ) co_signal(succ, 3u);  // first: the next batch forms while this one's members are being woken
-    // (one futex wake per sleeping member, 1.26 us each.  Waking them faster was built twice and is wrong on a CPU quota: one shared futex
-    // with FUTEX_WAKE(all), round 5, and a tree -- the leader wakes every 8th member, who wakes its group --, round 6: the leader's part falls
-    // 47 -> 4.4 us per batch, all members run, spin and re-submit at once, and the process is throttled: T = 256 344 K -> 75 K q/s with
-    // p99 = 78 ms, the CFS period; T = 64 283 K -> 220 K.  The serial wake is the pacing.  profiles/r6_tree_wake_rejected.log)
-    // (re-measured in round 6 WITHOUT the followers' spin, which had been what ran the process into its quota: the tree still loses --
-    // T = 64 299 -> 277 K q/s, T = 256 394 -> 100-140 K with 18 - 30 s of SYSTEM time per 2 s: members woken together re-submit together
-    // and fight over the queue's mutex.  The serial wake paces that too.  profiles/r6_spin_tree.log)
-    bool mine = false;
-    co.waking.fetch_add((uint32_t)batch.size(), std::memory_order_relaxed);
-    for (ss_co_req* r : batch) {
-      if (r == me) mine = true;
-      else co_signal(r, 1u);
-      co.waking.fetch_sub(1u, std::memory_order_relaxed);
-    }
-    if (g_co_trace_on && lexical && batch.size() > 1) { g_co_trace.wake += co_now_us() - tw0; g_co_trace.members += batch.size() - 1; }
-    if (g_co_trace_on && !lexical) {
-      std::lock_guard<std::mutex> gt(g_co_vec_trace_mu);
-      g_co_vec_wake_us.push_back((uint32_t)((co_now_us() - tw0) / 1000));
-      g_co_vec_run_us.push_back((uint32_t)((tw0 - trace_linger_ns) / 1000));
-    }
-    if (mine) return me->rc;
-    lead = false;  // (cannot happen while the leader's request is the front of its own batch; kept for safety)
-  }
-}
-}  // namespace
-
-int ss_shard_set_coalescing(ss_shard* s, uint32_t max_lexical_batch, uint32_t max_vector_batch, uint32_t max_wait_us) {
-  if (!s || max_vector_batch > SS_VEC_BATCH) return SS_EINVAL;
-  { std::lock_guard<std::mutex> g(s->co_lex.mu); s->co_lex.max_batch = max_lexical_batch; s->co_lex.max_wait_us = max_wait_us; }
-  { std::lock_guard<std::mutex> g(s->co_vec.mu); s->co_vec.max_batch = max_vector_batch; s->co_vec.max_wait_us = max_wait_us; }
-  return SS_OK;
-}
-int ss_bm25_path_stats(ss_shard* s, uint64_t* one_launch_batches) {
-  if (!s || !one_launch_batches) return SS_EINVAL;
-  ShardLock g(s);
-  *one_launch_batches = s->small_launches;
-  return SS_OK;
-}
-int ss_bm25_shape_stats(ss_shard* s, uint64_t* generic_batches) {
-  if (!s || !generic_batches) return SS_EINVAL;
-  ShardLock g(s);
-  *generic_batches = s->gallop_batches;
-  return SS_OK;
-}
-int ss_shard_coalescing_stats(ss_shard* s, uint64_t* lexical_batches, uint64_t* lexical_queries, uint64_t* vector_batches, uint64_t* vector_queries) {
-  if (!s) return SS_EINVAL;
-  { std::lock_guard<std::mutex> g(s->co_lex.mu); if (lexical_batches) *lexical_batches = s->co_lex.batches; if (lexical_queries) *lexical_queries = s->co_lex.queries; }
-  { std::lock_guard<std::mutex> g(s->co_vec.mu); if (vector_batches) *vector_batches = s->co_vec.batches; if (vector_queries) *vector_queries = s->co_vec.queries; }
-  return SS_OK;
-}
-
-// ------------------------------------------------------------------ deep pages: offset + length beyond SS_MAX_K results
-// The crate's top_k = offset + length is unbounded (search.rs:1658-1659); the kernels' top-k structures hold SS_MAX_K.  A deeper page is
-// answered in PASSES of SS_MAX_K results: the result order is total (score descending, then doc id ascending), so the docs ranked
-// (p * SS_MAX_K, (p + 1) * SS_MAX_K] of a query are its top SS_MAX_K once the docs of the earlier passes are excluded -- and every kernel
-// family already searches under an exclusion bitmap, the tombstones' (or a facet filter's, which stands in for it).  Pass p runs the
-// ordinary search under  (what excluded docs before) | (the docs passes 0 .. p - 1 returned);  the totals are pass 0's (the first pass
-// counts exactly what a k = SS_MAX_K call counts).  Every shape the library answers at k <= SS_MAX_K is answered at any k this way, on
-// every image (both tiers, several indexed fields, phrases, composed unions); the cost is linear in k / SS_MAX_K, a page that deep is rare.
-__global__ void peel_init_kernel(uint32_t* __restrict__ bits, uint32_t words, uint32_t rows, const uint32_t* __restrict__ base, uint32_t base_words) {
-  const size_t n = (size_t)words * rows;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const uint32_t w = (uint32_t)(i % words);
-    bits[i] = (base && w < base_words) ? base[w] : 0u;
-  }
-}
-// row r = blockIdx.y: the first min(counts[r], k) docs of docs[r * k ..] into bitmap r
-__global__ void peel_mark_kernel(const uint32_t* __restrict__ docs, const uint32_t* __restrict__ counts, uint32_t k, uint32_t* __restrict__ bits,
-                                 uint32_t words) {
-  const uint32_t r = blockIdx.y;
-  const uint32_t n = counts[r] < k ? counts[r] : k;
-  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const uint32_t doc = docs[(size_t)r * k + i];
-    if (doc != SS_NO_DOC && (doc >> 5) < words) atomicOr(&bits[(size_t)r * words + (doc >> 5)], 1u << (doc & 31u));
-  }
-}
-__global__ void peel_max_kernel(const uint32_t* __restrict__ v, unsigned long long n, uint32_t* __restrict__ out) {
-  uint32_t m = 0;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) m = v[i] > m ? v[i] : m;
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t y = __shfl_down(m, o); m = y > m ? y : m; }
-  if ((threadIdx.x & 63u) == 0) atomicMax(out, m);
-}
-
-// lexical: query by query (each pass is a single-query search of the ordinary paths).  Caller holds the shard lock; a facet filter's
-// bitmap already stands in s->d_deleted (with_facet_filter).
-static int bm25_search_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,
-                                   uint32_t* out_count, uint64_t* out_total) {
-  const uint32_t base_words = s->n_deleted ? (uint32_t)s->deleted_words : 0u;
-  const uint32_t words = std::max<uint32_t>((uint32_t)(((uint64_t)s->bm_n_docs + 31) / 32), base_words);
-  SS_HIP(hipSetDevice(s->device));
-  SS_TRY(reserve(s, &s->d_peel_bits, &s->peel_words_cap, words));
-  const uint32_t* base = s->n_deleted ? s->d_deleted : nullptr;
-  std::vector<uint32_t> h_doc(SS_MAX_K);
-  std::vector<float> h_score(SS_MAX_K);
-  for (uint32_t i = 0; i < nq; i++) {
-    uint32_t* od = out_doc + (size_t)i * k;
-    float* os = out_score + (size_t)i * k;
-    uint32_t got = 0;
-    uint64_t total = 0;
-    peel_init_kernel<<<std::min<uint32_t>(1024u, (words + 255u) / 256u), 256, 0, s->stream>>>(s->d_peel_bits, words, 1, base, base_words);
-    SS_HIP(hipGetLastError());
-    {
-      ExclSwap sw(s, s->d_peel_bits, words);
-      for (uint32_t pass = 0; got < k; pass++) {
-        const uint32_t kk = std::min<uint32_t>(SS_MAX_K, k - got);
-        SS_TRY(bm25_search_host_queries(s, 1, q + i, kk, pass == 0 ? rt : (uint32_t)SS_RT_TOPK, 0, nullptr));
-        uint32_t c = 0;
-        SS_HIP(hipMemcpyAsync(&c, s->d_out_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        if (pass == 0) SS_HIP(hipMemcpyAsync(&total, s->d_out_total, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-        SS_HIP(hipMemcpyAsync(h_doc.data(), s->d_out_doc, (size_t)kk * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        SS_HIP(hipMemcpyAsync(h_score.data(), s->d_out_score, (size_t)kk * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-        SS_HIP(hipStreamSynchronize(s->stream));
-        c = std::min(c, kk);
-        memcpy(od + got, h_doc.data(), (size_t)c * sizeof(uint32_t));
-        memcpy(os + got, h_score.data(), (size_t)c * sizeof(float));
-        got += c;
-        if (c < kk || got >= k) break;  // the list ran dry, or the page is full
-        peel_mark_kernel<<<dim3(4, 1), 256, 0, s->stream>>>(s->d_out_doc, s->d_out_count, kk, s->d_peel_bits, words);
-        SS_HIP(hipGetLastError());
-      }
-    }
-    for (uint32_t r = got; r < k; r++) { od[r] = SS_NO_DOC; os[r] = 0.f; }
-    out_count[i] = got;
-    out_total[i] = total;
-  }
-  return SS_OK;
-}
 static int bm25_search_deep(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters, const ss_facet_filter* filters,
                             uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
   ShardLock g(s);
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
-  return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); });
+  return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); });
 }
 
-// vectors: groups of <= SS_VEC_BATCH queries, one exclusion bitmap PER QUERY of the group (vec_refine_kernel's del_stride); a pass is one
-// scan of the group at k = SS_MAX_K.  The exclusion is by DOC (a doc of several records is returned once, by its best record).
-static int vec_search_deep_locked(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
-                                  const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
-                                  uint32_t* out_clusters, const float* query_norm);
 static int vec_search_host_deep(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
                                 const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
                                 uint32_t* out_clusters, const float* query_norm) {
   if (nq == 0) return SS_OK;
   ShardLock g(s);
-  return vec_search_deep_locked(s, nq, queries, elem, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total, out_clusters, query_norm);
-}
-static int vec_search_deep_locked(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
-                                  const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
-                                  uint32_t* out_clusters, const float* query_norm) {
-  if (s->vstream) SS_HIP(hipStreamSynchronize(s->vstream));
-  SS_HIP(hipSetDevice(s->device));
-  // the largest doc id a row can stand for
-  uint64_t doc_bound = s->n_rows;
-  if (s->d_row_doc) {
-    SS_TRY(ensure_qstage(s, 256));
-    SS_HIP(hipMemsetAsync(s->d_qstage, 0, sizeof(uint32_t), s->stream));
-    peel_max_kernel<<<1024, 256, 0, s->stream>>>(s->d_row_doc, (unsigned long long)s->n_rows, (uint32_t*)s->d_qstage);
-    uint32_t mx = 0;
-    SS_HIP(hipMemcpyAsync(&mx, s->d_qstage, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-    SS_HIP(hipStreamSynchronize(s->stream));
-    doc_bound = (uint64_t)mx + 1;
-  }
-  const uint32_t base_words = s->n_deleted ? (uint32_t)s->deleted_words : 0u;
-  const uint32_t words = std::max<uint32_t>((uint32_t)((doc_bound + 31) / 32), base_words);
-  const uint32_t G = (uint32_t)std::min<size_t>(nq, SS_VEC_BATCH);
-  SS_TRY(reserve(s, &s->d_peel_bits, &s->peel_words_cap, (size_t)words * G));
-  const uint32_t* base = s->n_deleted ? s->d_deleted : nullptr;
-  const uint32_t ocw = (mode && (mode->flags & SS_ANN_REPORT_OBSERVED)) ? 3u : 1u;
-  std::vector<uint32_t> h_doc((size_t)G * SS_MAX_K), h_count(G), got(G);
-  std::vector<float> h_score((size_t)G * SS_MAX_K);
-  std::vector<uint8_t> dry(G);
-  for (uint32_t g0 = 0; g0 < nq; g0 += G) {
-    const uint32_t nb = std::min<uint32_t>(G, nq - g0);
-    peel_init_kernel<<<std::min<uint32_t>(4096u, (uint32_t)(((size_t)words * nb + 255u) / 256u)), 256, 0, s->stream>>>(s->d_peel_bits, words, nb, base, base_words);
-    SS_HIP(hipGetLastError());
-    std::fill(got.begin(), got.end(), 0u);
-    std::fill(dry.begin(), dry.end(), (uint8_t)0);
-    ExclSwap sw(s, s->d_peel_bits, words);
-    sw.vec_stride(words);
-    for (uint32_t pass = 0;; pass++) {
-      uint32_t* d_ncl = nullptr;
-      SS_TRY(vec_search_host_lists(s, nb, (const char*)queries + (size_t)g0 * s->dim * elem, elem, query_scale ? query_scale + g0 : nullptr, SS_MAX_K, thr, mode,
-                                   h_count.data(), &d_ncl, query_norm ? query_norm + g0 : nullptr, out_clusters != nullptr && pass == 0));
-      SS_HIP(hipMemcpy(h_doc.data(), s->d_out_doc, (size_t)nb * SS_MAX_K * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      SS_HIP(hipMemcpy(h_score.data(), s->d_out_score, (size_t)nb * SS_MAX_K * sizeof(float), hipMemcpyDeviceToHost));
-      if (pass == 0) {
-        SS_HIP(hipMemcpy(out_total + g0, s->d_out_total, (size_t)nb * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (d_ncl && out_clusters) SS_HIP(hipMemcpy(out_clusters + (size_t)g0 * ocw, d_ncl, (size_t)nb * ocw * sizeof(uint32_t), hipMemcpyDeviceToHost));
-      }
-      bool more = false;
-      for (uint32_t i = 0; i < nb; i++) {
-        if (dry[i] || got[i] >= k) continue;
-        const uint32_t c = std::min<uint32_t>(std::min<uint32_t>(h_count[i], SS_MAX_K), k - got[i]);
-        memcpy(out_doc + (size_t)(g0 + i) * k + got[i], h_doc.data() + (size_t)i * SS_MAX_K, (size_t)c * sizeof(uint32_t));
-        memcpy(out_score + (size_t)(g0 + i) * k + got[i], h_score.data() + (size_t)i * SS_MAX_K, (size_t)c * sizeof(float));
-        got[i] += c;
-        if (h_count[i] < SS_MAX_K) dry[i] = 1;
-        more |= !dry[i] && got[i] < k;
-      }
-      if (!more) break;
-      peel_mark_kernel<<<dim3(4, nb), 256, 0, s->stream>>>(s->d_out_doc, s->d_out_count, SS_MAX_K, s->d_peel_bits, words);
-      SS_HIP(hipGetLastError());
-    }
-    for (uint32_t i = 0; i < nb; i++) {
-      for (uint32_t r = got[i]; r < k; r++) { out_doc[(size_t)(g0 + i) * k + r] = SS_NO_DOC; out_score[(size_t)(g0 + i) * k + r] = 0.f; }
-      out_count[g0 + i] = got[i];
-      // f32 Euclidean: a pass is the exact top SS_MAX_K of what is left up to the reference's own rounding (the cut keeps a margin, see
-      // vec_euclid_margin_kernel), ordered by the rescored values: the seams stand in order but for records tied within that rounding,
-      // which one stable sort of the assembled page puts right
-      if (s->vec_similarity == SS_SIM_EUCLIDEAN && elem == sizeof(float) && got[i] > SS_MAX_K) {
-        uint32_t* dd = out_doc + (size_t)(g0 + i) * k;
-        float* ss = out_score + (size_t)(g0 + i) * k;
-        std::vector<uint32_t> order(got[i]);
-        for (uint32_t r = 0; r < got[i]; r++) order[r] = r;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ss[a] > ss[b]; });
-        std::vector<uint32_t> d2(got[i]);
-        std::vector<float> s2(got[i]);
-        for (uint32_t r = 0; r < got[i]; r++) { d2[r] = dd[order[r]]; s2[r] = ss[order[r]]; }
-        memcpy(dd, d2.data(), (size_t)got[i] * 4);
-        memcpy(ss, s2.data(), (size_t)got[i] * 4);
-      }
-    }
-  }
-  return SS_OK;
+  return ssi_vec_search_deep_locked(s, nq, queries, elem, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total, out_clusters, query_norm);
 }
 
 int ss_bm25_search_filtered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
@@ -3393,9 +2786,9 @@ int ss_bm25_search_filtered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, ui
     ss_co_req r;
     r.q = q; r.nq = nq; r.k = rt == SS_RT_COUNT ? 0u : k; r.rt = rt;
     r.out_doc = out_doc; r.out_score = out_score; r.out_count = out_count; r.out_total = out_total;
-    return co_submit(s, s->co_lex, true, &r);
+    return ssi_co_submit(s, s->co_lex, true, &r);
   }
-  return bm25_search_direct(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
+  return ssi_bm25_search_direct(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
 }
 
 // One shard's part of <IndexArc as Search>::search over shards on different GPUs (search.rs:1637-1743 + 1875-2119): search
@@ -3416,18 +2809,18 @@ int ss_bm25_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const ss_bm25_q
   // still enters the exchange, empty-handed, and every rank returns an error (ssi_comm_exchange) instead of blocking in it.
   ShardLock g(s);
   int rc = dev != s->device ? SS_EINVAL : !s->d_post ? SS_ESTATE : SS_OK;
-  if (rc == SS_OK && kk > SS_MAX_K) {  // a deep page: this shard's (0, k) list in passes ("deep pages" above), then the exchange as ever
+  if (rc == SS_OK && kk > SS_MAX_K) {  // a deep page: this shard's (0, k) list in passes (api_deep.hip), then the exchange as ever
     std::vector<uint32_t> h_doc((size_t)nq * kk), h_cnt(nq);
     std::vector<float> h_score((size_t)nq * kk);
     std::vector<uint64_t> h_tot(nq);
-    rc = bm25_search_deep_locked(s, nq, q, kk, rt, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data());
+    rc = ssi_bm25_search_deep_locked(s, nq, q, kk, rt, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data());
     if (rc == SS_OK) rc = ensure_out(s, nq, kk);
     if (rc == SS_OK && (hipMemcpy(s->d_out_doc, h_doc.data(), h_doc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemcpy(s->d_out_score, h_score.data(), h_score.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemcpy(s->d_out_count, h_cnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemcpy(s->d_out_total, h_tot.data(), (size_t)nq * 8, hipMemcpyHostToDevice) != hipSuccess))
       rc = SS_EDEVICE;
-  } else if (rc == SS_OK) rc = bm25_search_host_queries(s, nq, q, kk, rt, 0, nullptr);
+  } else if (rc == SS_OK) rc = ssi_bm25_search_host_queries(s, nq, q, kk, rt, 0, nullptr);
   const ss_dev_list L{s->d_out_doc, s->d_out_score, s->d_out_count, kk};
   return ssi_comm_exchange(c, nq, kk ? 1 : 0, &L, s->d_out_total, nullptr, rc, false, 0, 0, out_doc, out_score, nullptr, out_count, out_total,
                            s->stream);
@@ -3450,14 +2843,14 @@ int ss_vec_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const float* que
     std::vector<uint32_t> h_doc((size_t)nq * k);
     std::vector<float> h_score((size_t)nq * k);
     std::vector<uint64_t> h_tot(nq);
-    rc = vec_search_deep_locked(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_doc.data(), h_score.data(), h_count.data(), h_tot.data(), nullptr, nullptr);
+    rc = ssi_vec_search_deep_locked(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_doc.data(), h_score.data(), h_count.data(), h_tot.data(), nullptr, nullptr);
     if (rc == SS_OK) rc = ensure_out(s, nq, k);
     if (rc == SS_OK && (hipMemcpy(s->d_out_doc, h_doc.data(), h_doc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemcpy(s->d_out_score, h_score.data(), h_score.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemcpy(s->d_out_count, h_count.data(), (size_t)nq * 4, hipMemcpyHostToDevice) != hipSuccess ||
                         hipMemcpy(s->d_out_total, h_tot.data(), (size_t)nq * 8, hipMemcpyHostToDevice) != hipSuccess))
       rc = SS_EDEVICE;
-  } else if (rc == SS_OK) rc = vec_search_host_lists(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_count.data(), nullptr);
+  } else if (rc == SS_OK) rc = ssi_vec_search_host_lists(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_count.data(), nullptr);
   const ss_dev_list L{s->d_out_doc, s->d_out_score, s->d_out_count, k};
   return ssi_comm_exchange(c, nq, 1, &L, s->d_out_total, nullptr, rc, false, 0, 0, out_doc, out_score, nullptr, out_count, out_total, s->stream);
 }
@@ -3487,13 +2880,13 @@ int ss_hybrid_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const ss_bm25
   // outputs of the two searches side by side: the vector lists behind the lexical ones (reserved before either runs)
   if (rc == SS_OK && hipSetDevice(s->device) != hipSuccess) rc = SS_EDEVICE;
   std::vector<uint32_t> h_count(nq);
-  if (rc == SS_OK && k > SS_MAX_K) {  // both shard tasks as deep pages ("deep pages" above), then placed as the exchange expects them
+  if (rc == SS_OK && k > SS_MAX_K) {  // both shard tasks as deep pages (api_deep.hip), then placed as the exchange expects them
     std::vector<uint32_t> h_doc(2 * (size_t)nq * k), h_cnt(2 * (size_t)nq);
     std::vector<float> h_score(2 * (size_t)nq * k);
     std::vector<uint64_t> h_tot(2 * (size_t)nq);
-    rc = bm25_search_deep_locked(s, nq, q, k, rt, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data());
+    rc = ssi_bm25_search_deep_locked(s, nq, q, k, rt, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data());
     if (rc == SS_OK)
-      rc = vec_search_deep_locked(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_doc.data() + (size_t)nq * k, h_score.data() + (size_t)nq * k,
+      rc = ssi_vec_search_deep_locked(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_doc.data() + (size_t)nq * k, h_score.data() + (size_t)nq * k,
                                   h_cnt.data() + nq, h_tot.data() + nq, nullptr, nullptr);
     if (rc == SS_OK) rc = ensure_out(s, 2 * (size_t)nq, k);
     if (rc == SS_OK && (hipMemcpy(s->d_out_doc, h_doc.data(), h_doc.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -3503,8 +2896,8 @@ int ss_hybrid_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const ss_bm25
       rc = SS_EDEVICE;
   } else {
     if (rc == SS_OK) rc = ensure_out(s, 2 * (size_t)nq, k);
-    if (rc == SS_OK) rc = bm25_search_host_queries(s, nq, q, k, rt, 0, nullptr);
-    if (rc == SS_OK) rc = vec_search_host_lists(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_count.data(), nullptr, nullptr, false, nq);
+    if (rc == SS_OK) rc = ssi_bm25_search_host_queries(s, nq, q, k, rt, 0, nullptr);
+    if (rc == SS_OK) rc = ssi_vec_search_host_lists(s, nq, queries, sizeof(float), nullptr, k, thr, nullptr, h_count.data(), nullptr, nullptr, false, nq);
   }
   const ss_dev_list L[2] = {{s->d_out_doc, s->d_out_score, s->d_out_count, k},
                             {s->d_out_doc + (size_t)nq * k, s->d_out_score + (size_t)nq * k, s->d_out_count + nq, k}};
@@ -3699,6 +3092,43 @@ int ss_bm25_facet_kth_point(ss_shard* s, const ss_bm25_query* query, uint32_t n_
   return facet_kth_impl(s, query, n_filters, filters, facet_offset, SS_FACET_POINT, base, descending, k, out_value, out_n_better, out_n_equal, out_total);
 }
 
+// The query_facets of a call (ss_bm25_search_facets, ss_bm25_search_sorted_facets, ss_docs_search): the caller's arrays as
+// query_facets_check passed them; n_bounds = the lower bounds of the range facets, back to back; stride = the counters of one query.
+struct QueryFacets {
+  uint32_t n_facets = 0;
+  const uint32_t *facet_offset = nullptr, *facet_type = nullptr, *n_buckets = nullptr;
+  const uint64_t* range_lower_bounds = nullptr;
+  const ss_facet_point* bases = nullptr;
+  size_t n_bounds = 0, stride = 0;
+  uint64_t* out_counts = nullptr;  // [queries][stride]
+};
+// every argument check of the query-facet arrays (SS_EINVAL): nulls, the number of facets, every type, bucket count and Point base
+static int query_facets_check(uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
+                              const uint64_t* range_lower_bounds, const ss_facet_point* bases, uint64_t* out_counts, QueryFacets* qf) {
+  if (n_facets > SS_MAX_QUERY_FACETS || (n_facets && (!facet_offset || !facet_type || !n_buckets || !out_counts))) return SS_EINVAL;
+  *qf = QueryFacets{n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, 0, 0, out_counts};
+  for (uint32_t f = 0; f < n_facets; f++) {
+    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
+    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
+    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) qf->n_bounds += n_buckets[f];
+    qf->stride += (size_t)n_buckets[f] + 1;
+  }
+  return qf->n_bounds && !range_lower_bounds ? SS_EINVAL : SS_OK;
+}
+// what an entry asks of the facet records, under the shard lock; the return code is the entry's (ss_docs_search answers SS_EINVAL for
+// a field outside the record, the other entries SS_ESTATE)
+static bool facet_records_cover(const ss_shard* s) { return s->d_facets && s->facet_docs >= s->bm_n_docs; }  // a record for every doc
+static bool facets_fit_records(const ss_shard* s, const QueryFacets& qf) {
+  for (uint32_t f = 0; f < qf.n_facets; f++)
+    if ((uint64_t)qf.facet_offset[f] + ssi_facet_width(qf.facet_type[f]) > s->facet_record_size) return false;
+  return true;
+}
+static bool sorts_fit_records(const ss_shard* s, uint32_t n_sorts, const ss_result_sort* sorts) {
+  for (uint32_t f = 0; f < n_sorts; f++)
+    if ((uint64_t)sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return false;
+  return true;
+}
+
 // Result sort for a batch (facet.hip: "Result sort for a BATCH, pivots on the device").  The batch runs in chunks of <= 64 queries,
 // every step a grid over the chunk: match sets (one expansion + one bit-record pass) -> per sort field the radix select and the
 // classification -> the exclusion bitmaps -> TWO batched searches, each query inside its own doc set (the pruned kernel's filtered
@@ -3708,29 +3138,17 @@ int ss_bm25_facet_kth_point(ss_shard* s, const ss_bm25_query* query, uint32_t n_
 // every query and, on the same visit of each matched doc, byte 0 of the first sort field's radix select (facet.hip
 // facet_sort_first_kernel), so the select starts at its second pass.  SS_SORT_FUSED=0 (read once): the two steps apart --
 // ssi_facet_count_multi, then the whole select -- for measurements; the answers are the same.
-struct SortedFacets {  // the validated facet arguments of ss_bm25_search_sorted_facets (check_query_facets)
-  uint32_t n_facets;
-  const uint32_t *facet_offset, *facet_type, *n_buckets;
-  const uint64_t* range_lower_bounds;
-  const ss_facet_point* bases;
-  size_t n_bounds, stride;
-  uint64_t* out_counts;  // [nq][stride]
-};
 static bool sort_fused() {
   static const int on = [] { const char* e = getenv("SS_SORT_FUSED"); return e ? atoi(e) : 1; }();
   return on != 0;
 }
-static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
+extern "C++" int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
                                      const ss_sort_sources& src, uint32_t k,
                                      uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
-                                     uint64_t* out_total, const SortedFacets* qf = nullptr) {
+                                     uint64_t* out_total, const QueryFacets* qf) {
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
-  if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
-  for (uint32_t f = 0; f < n_sorts; f++)
-    if (sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_ESTATE;
-  for (uint32_t f = 0; qf && f < qf->n_facets; f++)
-    if ((uint64_t)qf->facet_offset[f] + ssi_facet_width(qf->facet_type[f]) > s->facet_record_size) return SS_ESTATE;
+  if (!facet_records_cover(s) || !sorts_fit_records(s, n_sorts, sorts) || (qf && !facets_fit_records(s, *qf))) return SS_ESTATE;
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
   const uint32_t CH = std::min<uint32_t>(nq, 64u);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -3762,7 +3180,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = queries + c0;
     // a chunk that names a sparse-tier term: its match sets from both tiers (bm25_match.h), its two searches query by query below
-    // (bm25_search_host_queries routes each to bm25_search_tiered under the swapped exclusion bitmap); select and compose stay batched
+    // (ssi_bm25_search_host_queries routes each to bm25_search_tiered under the swapped exclusion bitmap); select and compose stay batched
     // a chunk that holds a phrase: match sets of the intersection forms, refined (bm25_phrase_bits.hip); its two searches query by
     // query as well -- the ordinary search answers a phrase under the swapped bitmap and routes it to its own kernel family
     MatchChunk& mc = plans[c0 / CH];
@@ -3793,7 +3211,7 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
         for (int part = 0; part < 2; part++) {
           {
             ExclSwap sw(s, (uint32_t*)((part == 0 ? d_xb : d_xe) + (size_t)i * groups), groups * 2);
-            SS_TRY(bm25_search_host_queries(s, 1, qc + i, k, SS_RT_TOPK, 0, nullptr));
+            SS_TRY(ssi_bm25_search_host_queries(s, 1, qc + i, k, SS_RT_TOPK, 0, nullptr));
           }
           SS_HIP(hipMemcpyAsync(W + (part == 0 ? o_ad : o_cd) + (size_t)i * k * 4, s->d_out_doc, (size_t)k * 4, hipMemcpyDeviceToDevice, s->stream));
           SS_HIP(hipMemcpyAsync(W + (part == 0 ? o_as : o_cs) + (size_t)i * k * 4, s->d_out_score, (size_t)k * 4, hipMemcpyDeviceToDevice, s->stream));
@@ -3813,10 +3231,6 @@ static int bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_que
   return SS_OK;
 }
 
-static int bm25_search_sorted_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
-                                          const ss_sort_sources& src, uint32_t k, uint32_t n_filters, const ss_facet_filter* filters,
-                                          uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total);
-
 int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
                           uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                           uint64_t* out_total) {
@@ -3832,96 +3246,36 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   // ss_facet_set_string_ranks; without a table SS_ENOTSUP: the host's own rank column
   ss_sort_sources src;
   SS_TRY(ssi_sort_resolve(s, n_sorts, sorts, &src));
-  if (k <= SS_MAX_K) return bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
-  return bm25_search_sorted_deep_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+  if (k <= SS_MAX_K) return ssi_bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+  return ssi_bm25_search_sorted_deep_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
 }
-static int bm25_search_sorted_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
-                                          const ss_sort_sources& src, uint32_t k, uint32_t n_filters, const ss_facet_filter* filters,
-                                          uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
-  // a DEEP page sorted by facets: the order is total (field 1, ..., field n, score desc, doc asc), so it is peeled like any other ("deep
-  // pages" above) -- query by query, every pass the sorted search of SS_MAX_K results under (tombstones | the docs of the earlier passes);
-  // a facet filter's bitmap is built on top of that inside the pass
-  if (!s->d_post) return SS_ESTATE;
-  SS_HIP(hipSetDevice(s->device));
-  const uint32_t base_words = s->n_deleted ? (uint32_t)s->deleted_words : 0u;
-  const uint32_t words = std::max<uint32_t>((uint32_t)(((uint64_t)s->bm_n_docs + 31) / 32), base_words);
-  SS_TRY(reserve(s, &s->d_peel_bits, &s->peel_words_cap, words));
-  const uint32_t* base = s->n_deleted ? s->d_deleted : nullptr;
-  std::vector<uint32_t> h_doc(SS_MAX_K);
-  std::vector<float> h_score(SS_MAX_K);
-  for (uint32_t i = 0; i < nq; i++) {
-    uint32_t got = 0;
-    uint64_t total = 0;
-    peel_init_kernel<<<std::min<uint32_t>(1024u, (words + 255u) / 256u), 256, 0, s->stream>>>(s->d_peel_bits, words, 1, base, base_words);
-    SS_HIP(hipGetLastError());
-    ExclSwap sw(s, s->d_peel_bits, words);
-    for (uint32_t pass = 0; got < k; pass++) {
-      const uint32_t kk = std::min<uint32_t>(SS_MAX_K, k - got);
-      uint32_t c = 0;
-      uint64_t t = 0;
-      SS_TRY(bm25_search_sorted_locked(s, 1, queries + i, n_sorts, sorts, src, kk, n_filters, filters, h_doc.data(), h_score.data(), &c, &t));
-      if (pass == 0) total = t;
-      c = std::min(c, kk);
-      memcpy(out_doc + (size_t)i * k + got, h_doc.data(), (size_t)c * sizeof(uint32_t));
-      memcpy(out_score + (size_t)i * k + got, h_score.data(), (size_t)c * sizeof(float));
-      got += c;
-      if (c < kk || got >= k) break;
-      SS_TRY(ensure_qstage(s, (size_t)SS_MAX_K * 4 + 16));  // the pass's docs back to the device for the mark
-      SS_HIP(hipMemcpyAsync(s->d_qstage, h_doc.data(), (size_t)c * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-      SS_HIP(hipMemcpyAsync((char*)s->d_qstage + (size_t)SS_MAX_K * 4, &c, sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-      peel_mark_kernel<<<dim3(4, 1), 256, 0, s->stream>>>((const uint32_t*)s->d_qstage, (const uint32_t*)((char*)s->d_qstage + (size_t)SS_MAX_K * 4), kk, s->d_peel_bits, words);
-      SS_HIP(hipGetLastError());
-      SS_HIP(hipStreamSynchronize(s->stream));  // (h_doc and c are read by the copies)
-    }
-    for (uint32_t r = got; r < k; r++) { out_doc[(size_t)i * k + r] = SS_NO_DOC; out_score[(size_t)i * k + r] = 0.f; }
-    out_count[i] = got;
-    out_total[i] = total;
-  }
-  return SS_OK;
-}
-
-// The query-facet arrays of ss_bm25_search_facets / ss_docs_search (their null checks are the callers'): every type, bucket count and
-// Point base -> *n_bounds = the lower bounds of the range facets, back to back; *stride = the counters of one query
-static int check_query_facets(uint32_t n_facets, const uint32_t* facet_type, const uint32_t* n_buckets, const ss_facet_point* bases, size_t* n_bounds,
-                              size_t* stride) {
-  for (uint32_t f = 0; f < n_facets; f++) {
-    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24)) return SS_EINVAL;
-    if (facet_type[f] == SS_FACET_POINT && (!bases || bases[f].unit > SS_POINT_MILES)) return SS_EINVAL;
-    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) *n_bounds += n_buckets[f];
-    *stride += (size_t)n_buckets[f] + 1;
-  }
-  return SS_OK;
-}
-
 // A search WITH its query_facets (search.rs:3598-3760 finishes what add_result.rs:487-643 counted beside the hits): the facet counts
 // of the whole batch are enqueued first -- per chunk of <= 64 queries one match-set build (both tiers) and ONE launch that counts every
 // facet of every query (facet.hip: "Facet counts of a BATCH") -- and the search itself runs behind them on the same stream, through
-// ss_bm25_search_filtered's direct path (bm25_search_direct_locked / bm25_search_deep_locked: that entry's answers, bit for bit; where
+// ss_bm25_search_filtered's direct path (bm25_search_direct_locked / ssi_bm25_search_deep_locked: that entry's answers, bit for bit; where
 // the lexical coalescer is on, that entry hands an unfiltered request to it -- this one never does, the answers are the same).  The
 // facet filter's bitmap is built once for all of it (`prebuilt`).  Waits: the search waits for its own answers (a deep page once per
 // pass), and by then the counters are done; their copy home into the caller's pageable array and the wait that ends it are the call's
 // second, short one -- the search paths own their waits, and the counters are not theirs to carry.  A workspace that has to grow waits
 // for the stream before it is freed, the first time only.
 static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t n_filters, const ss_facet_filter* filters,
-                               uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
-                               const uint64_t* range_lower_bounds, const ss_facet_point* bases, size_t n_bounds, size_t stride,
-                               std::vector<MatchChunk>& plans, unsigned long long** d_counts_out) {
+                               const QueryFacets& qf, std::vector<MatchChunk>& plans, unsigned long long** d_counts_out) {
   const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
   const bool prebuilt = n_filters != 0;  // (the entry built the bitmap)
   const uint32_t CH = std::min<uint32_t>(nq, 64u);  // (tier_prepare plans batches of <= 64, ssi_bm25_match_bits takes as many)
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t o_q = 0, o_sub = o_q + al((size_t)CH * sizeof(ss_bm25_query)), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
                o_tot = o_ph + al((size_t)CH * sizeof(ss_bm25_query)),
-               o_bits = o_tot + al((size_t)CH * 8), o_bounds = o_bits + al((size_t)CH * groups * 8), o_cnt = o_bounds + al(n_bounds * 8),
-               need = o_cnt + al((size_t)nq * stride * 8);
+               o_bits = o_tot + al((size_t)CH * 8), o_bounds = o_bits + al((size_t)CH * groups * 8), o_cnt = o_bounds + al(qf.n_bounds * 8),
+               need = o_cnt + al((size_t)nq * qf.stride * 8);
   SS_TRY(reserve(s, &s->d_facet_ws, &s->facet_ws_cap, need));
   char* W = (char*)s->d_facet_ws;
   ss_bm25_query *d_q = (ss_bm25_query*)(W + o_q), *d_sub = (ss_bm25_query*)(W + o_sub), *d_ph = (ss_bm25_query*)(W + o_ph);
   unsigned long long *d_total = (unsigned long long*)(W + o_tot), *d_bits = (unsigned long long*)(W + o_bits), *d_counts = (unsigned long long*)(W + o_cnt);
   uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
   *d_counts_out = d_counts;
-  SS_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * stride * 8, s->stream));
-  if (n_bounds) SS_HIP(hipMemcpyAsync(d_bounds, range_lower_bounds, n_bounds * 8, hipMemcpyHostToDevice, s->stream));
+  SS_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * qf.stride * 8, s->stream));
+  if (qf.n_bounds) SS_HIP(hipMemcpyAsync(d_bounds, qf.range_lower_bounds, qf.n_bounds * 8, hipMemcpyHostToDevice, s->stream));
   plans.resize((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
   for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
@@ -3930,7 +3284,8 @@ static int bm25_facets_enqueue(ss_shard* s, uint32_t nq, const ss_bm25_query* q,
     SS_TRY(match_prepare(s, nb, qc, &mc));
     SS_HIP(hipMemsetAsync(d_total, 0, (size_t)((char*)(d_bits + (size_t)nb * groups) - (char*)d_total), s->stream));
     SS_TRY(match_enqueue(s, nb, qc, mc, n_filters, filters, prebuilt, d_q, d_sub, d_ph, d_bits, d_total));
-    SS_TRY(ssi_facet_count_multi(s, nb, d_bits, n_facets, facet_offset, facet_type, n_buckets, bases, d_bounds, d_counts + (size_t)c0 * stride, s->stream));
+    SS_TRY(ssi_facet_count_multi(s, nb, d_bits, qf.n_facets, qf.facet_offset, qf.facet_type, qf.n_buckets, qf.bases, d_bounds,
+                                 d_counts + (size_t)c0 * qf.stride, s->stream));
   }
   return SS_OK;
 }
@@ -3940,38 +3295,32 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
                           const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases, uint32_t* out_doc,
                           float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts) {
   if (n_facets == 0) return ss_bm25_search_filtered(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
-  if (!s || !q || !out_count || !out_total || !out_facet_counts || !facet_offset || !facet_type || !n_buckets) return SS_EINVAL;
+  if (!s || !q || !out_count || !out_total) return SS_EINVAL;
+  QueryFacets qf;
+  SS_TRY(query_facets_check(n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, out_facet_counts, &qf));
   if (rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
   if (rt != SS_RT_COUNT && (k == 0 || !out_doc || !out_score)) return SS_EINVAL;
-  if (n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
-  size_t n_bounds = 0, stride = 0;
-  SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
-  if (n_bounds && !range_lower_bounds) return SS_EINVAL;
   if (!s->d_post) return SS_ESTATE;
   if (nq == 0) return SS_OK;
   ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
-  if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
-  for (uint32_t f = 0; f < n_facets; f++)
-    if ((uint64_t)facet_offset[f] + ssi_facet_width(facet_type[f]) > s->facet_record_size) return SS_ESTATE;
+  if (!facet_records_cover(s) || !facets_fit_records(s, qf)) return SS_ESTATE;
   std::vector<MatchChunk> plans;
   unsigned long long* d_counts = nullptr;
   int rc = SS_OK;
   if (n_filters) {  // one exclusion bitmap for the match sets and the search
     rc = ssi_facet_build(s, n_filters, filters, s->stream);
   }
-  if (rc == SS_OK)
-    rc = bm25_facets_enqueue(s, nq, q, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, n_bounds, stride,
-                             plans, &d_counts);
+  if (rc == SS_OK) rc = bm25_facets_enqueue(s, nq, q, n_filters, filters, qf, plans, &d_counts);
   if (rc == SS_OK) {
     // (the crate's offset + length is unbounded: a page deeper than SS_MAX_K results is answered in passes, as ss_bm25_search_filtered does)
     if (rt != SS_RT_COUNT && k > SS_MAX_K)
-      rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); }, true);
+      rc = with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); }, true);
     else
       rc = bm25_search_direct_locked(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total, true);
   }
-  if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) rc = SS_EDEVICE;
+  if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * qf.stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess) rc = SS_EDEVICE;
   if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (also on an error: the plans and the caller's arrays are being read)
   return rc;
 }
@@ -3997,39 +3346,28 @@ int ss_bm25_search_sorted_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* 
   if (rt != SS_RT_COUNT && n_facets == 0)
     return ss_bm25_search_sorted(s, nq, queries, n_sorts, sorts, k, n_filters, filters, out_doc, out_score, out_count, out_total);
   // ... and the facet entry's
-  size_t n_bounds = 0, stride = 0;
-  if (n_facets) {
-    if (!out_facet_counts || !facet_offset || !facet_type || !n_buckets || n_facets > SS_MAX_QUERY_FACETS) return SS_EINVAL;
-    SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
-    if (n_bounds && !range_lower_bounds) return SS_EINVAL;
-  }
+  QueryFacets qf;
+  SS_TRY(query_facets_check(n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, out_facet_counts, &qf));
   ss_sort_sources src;
   {
     ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
     SS_TRY(ssi_sort_resolve(s, n_sorts, sorts, &src));  // SS_ENOTSUP: a string field without a rank table
     if (rt != SS_RT_COUNT) {
-      SortedFacets qf{n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, n_bounds, stride, out_facet_counts};
       if (k <= SS_MAX_K)
-        return bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total, &qf);
+        return ssi_bm25_search_sorted_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total, &qf);
       // a deep page: the counters once, through ss_bm25_search_facets' batched count, then ss_bm25_search_sorted's passes
       if (!s->d_post) return SS_ESTATE;
       SS_HIP(hipSetDevice(s->device));
-      if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
-      for (uint32_t f = 0; f < n_sorts; f++)
-        if (sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_ESTATE;
-      for (uint32_t f = 0; f < n_facets; f++)
-        if ((uint64_t)facet_offset[f] + ssi_facet_width(facet_type[f]) > s->facet_record_size) return SS_ESTATE;
+      if (!facet_records_cover(s) || !sorts_fit_records(s, n_sorts, sorts) || !facets_fit_records(s, qf)) return SS_ESTATE;
       std::vector<MatchChunk> plans;
       unsigned long long* d_counts = nullptr;
       int rc = n_filters ? ssi_facet_build(s, n_filters, filters, s->stream) : SS_OK;
-      if (rc == SS_OK)
-        rc = bm25_facets_enqueue(s, nq, queries, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, n_bounds,
-                                 stride, plans, &d_counts);
-      if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
+      if (rc == SS_OK) rc = bm25_facets_enqueue(s, nq, queries, n_filters, filters, qf, plans, &d_counts);
+      if (rc == SS_OK && hipMemcpyAsync(out_facet_counts, d_counts, (size_t)nq * qf.stride * 8, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
         rc = SS_EDEVICE;
       if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (the plans and the caller's array are being read)
       if (rc != SS_OK) return rc;
-      return bm25_search_sorted_deep_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
+      return ssi_bm25_search_sorted_deep_locked(s, nq, queries, n_sorts, sorts, src, k, n_filters, filters, out_doc, out_score, out_count, out_total);
     }
   }
   // SS_RT_COUNT: no docs, so no select -- the sort fields were checked above and play no further part
@@ -4053,20 +3391,16 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t rt, uint32_t
   if (n_sorts > SS_MAX_SORT_FIELDS || (n_sorts && !sorts) || n_filters > SS_MAX_FACET_FILTERS || (n_filters && !filters)) return SS_EINVAL;
   for (uint32_t f = 0; f < n_sorts; f++)
     if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
-  if (n_facets > SS_MAX_QUERY_FACETS || (n_facets && (!facet_offset || !facet_type || !n_buckets || !out_facet_counts))) return SS_EINVAL;
-  size_t n_bounds = 0, stride = 0;
-  SS_TRY(check_query_facets(n_facets, facet_type, n_buckets, bases, &n_bounds, &stride));
-  if (n_bounds && !range_lower_bounds) return SS_EINVAL;
+  QueryFacets qf;
+  SS_TRY(query_facets_check(n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, out_facet_counts, &qf));
+  const size_t n_bounds = qf.n_bounds, stride = qf.stride;
   ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
   ss_sort_sources src;  // where every sort field's key is read, resolved once for the call
   if (ssi_sort_resolve(s, n_sorts, sorts, &src) != SS_OK) return SS_EINVAL;  // a string sort field without a rank table (ss_facet_set_string_ranks)
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
-  if ((n_sorts || n_filters || n_facets) && (!s->d_facets || s->facet_docs < s->bm_n_docs)) return SS_ESTATE;
-  for (uint32_t f = 0; f < n_sorts; f++)
-    if ((uint64_t)sorts[f].facet_offset + ssi_facet_width(sorts[f].facet_type) > s->facet_record_size) return SS_EINVAL;
-  for (uint32_t f = 0; f < n_facets; f++)
-    if ((uint64_t)facet_offset[f] + ssi_facet_width(facet_type[f]) > s->facet_record_size) return SS_EINVAL;
+  if ((n_sorts || n_filters || n_facets) && !facet_records_cover(s)) return SS_ESTATE;
+  if (!sorts_fit_records(s, n_sorts, sorts) || !facets_fit_records(s, qf)) return SS_EINVAL;
   for (uint32_t f = 0; f < n_filters; f++)
     if (filters[f].type > SS_FACET_POINT || (uint64_t)filters[f].offset + ssi_facet_width(filters[f].type) > s->facet_record_size) return SS_EINVAL;
 
@@ -4209,7 +3543,7 @@ int ss_bm25_search_filtered_dev(ss_shard* s, uint32_t nq, const ss_bm25_query* d
   SS_HIP(hipSetDevice(s->device));
   hipStream_t st = stream ? (hipStream_t)stream : s->stream;
   if (rt != SS_RT_COUNT && k > SS_MAX_K) {
-    // a DEEP page ("deep pages" above): the passes are steered from the host, so the queries make one trip there (like the tiered batches
+    // a DEEP page (api_deep.hip): the passes are steered from the host, so the queries make one trip there (like the tiered batches
     // below) and the call is synchronous; the page is left in the caller's device arrays, ordered on `st`
     std::vector<ss_bm25_query> hq(nq);
     SS_HIP(hipMemcpyAsync(hq.data(), d_q, (size_t)nq * sizeof(ss_bm25_query), hipMemcpyDeviceToHost, st));
@@ -4218,7 +3552,7 @@ int ss_bm25_search_filtered_dev(ss_shard* s, uint32_t nq, const ss_bm25_query* d
     std::vector<float> h_score((size_t)nq * k);
     std::vector<uint64_t> h_tot(nq);
     SS_TRY(with_facet_filter(s, n_filters, filters, s->stream, [&]() {
-      return bm25_search_deep_locked(s, nq, hq.data(), k, rt, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data());
+      return ssi_bm25_search_deep_locked(s, nq, hq.data(), k, rt, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data());
     }));
     SS_HIP(hipMemcpyAsync(d_out_doc, h_doc.data(), h_doc.size() * 4, hipMemcpyHostToDevice, st));
     SS_HIP(hipMemcpyAsync(d_out_score, h_score.data(), h_score.size() * 4, hipMemcpyHostToDevice, st));
@@ -4234,7 +3568,7 @@ int ss_bm25_search_filtered_dev(ss_shard* s, uint32_t nq, const ss_bm25_query* d
     std::vector<ss_bm25_query> hq(nq);
     SS_HIP(hipMemcpyAsync(hq.data(), d_q, (size_t)nq * sizeof(ss_bm25_query), hipMemcpyDeviceToHost, st));
     SS_HIP(hipStreamSynchronize(st));
-    SS_TRY(bm25_search_host_queries(s, nq, hq.data(), kk, rt, n_filters, filters));
+    SS_TRY(ssi_bm25_search_host_queries(s, nq, hq.data(), kk, rt, n_filters, filters));
     if (kk) {
       SS_HIP(hipMemcpyAsync(d_out_doc, s->d_out_doc, (size_t)nq * kw * 4, hipMemcpyDeviceToDevice, s->stream));
       SS_HIP(hipMemcpyAsync(d_out_score, s->d_out_score, (size_t)nq * kw * 4, hipMemcpyDeviceToDevice, s->stream));
@@ -4312,12 +3646,24 @@ int ss_vec_upload(ss_shard* s, uint64_t n_rows, uint32_t dim, const float* rows,
   return vec_finish(s);
 }
 
+// the i8 image's rows ("i8 (quantised) vectors" below)
+static int vec8_alloc(ss_shard* s, uint64_t n_rows, uint32_t dim) {
+  free_vec(s);
+  s->n_rows = n_rows;
+  s->dim = dim;
+  s->dim_pad8 = (dim + 127u) / 128u * 128u;
+  if (s->dim_pad8 > 2560u) { free_vec(s); return SS_ENOTSUP; }  // the 64 queries stay in LDS: 64 x dim_pad8 <= 160 KB
+  s->n_rows_pad = (n_rows + VS_TR - 1) / VS_TR * VS_TR;
+  const size_t bytes = (size_t)s->n_rows_pad * s->dim_pad8;
+  SS_HIP(hipMalloc(&s->d_X8, bytes));
+  if (s->dim_pad8 != dim || s->n_rows_pad != n_rows) SS_HIP(hipMemsetAsync(s->d_X8, 0, bytes, s->stream));  // padding is interleaved
+  return SS_OK;
+}
+
 // vector.bin (writer vector.rs:1066-1094, reader 1279-1298): per level u32 cluster_count, cluster_count x u32 child_count,
 // then the records cluster after cluster, each a packed 24-byte VectorHeader (u16 doc_id first, vector.rs:62-73) + dim x f32.
 // Shard-local doc id of a record = (level << 16) | doc_id (vector.rs:1448).  The payloads go to HBM straight from the
 // file bytes with a strided copy per level; the cluster structure is kept for the ANN modes (vec_ann.hip).
-static int vec8_alloc(ss_shard* s, uint64_t n_rows, uint32_t dim);
-
 // i8 = Precision::I8 records (dim x i8 after the header); use_scale keeps VectorHeader.scale (f32 at byte 10) per record
 // for dot_i8_quantized (ScalarQuantizationI8 with Dot / Euclidean; Cosine scores are the raw integer dot, vector.rs:1331-1333)
 static int vec_bin_upload(ss_shard* s, const uint8_t* bytes, uint64_t len, uint32_t dim, bool i8, bool use_scale) {
@@ -4452,7 +3798,7 @@ int ss_vec_read_rows(ss_shard* s, uint64_t r0, uint64_t n, float* out) {
 
 // the search up to the device lists (s->d_out_* on s->stream, counts checked on the host: an overflowed batch is re-run in
 // safe mode); caller holds s->mu.  h_count: nq words of host scratch.
-static int vec_search_host_lists(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
+extern "C++" int ssi_vec_search_host_lists(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
                                  float thr, const ss_ann_mode* mode, uint32_t* h_count, uint32_t** d_ncl_out,
                                  const float* query_norm, bool want_clusters, size_t out_slot) {
   SS_HIP(hipSetDevice(s->device));
@@ -4492,7 +3838,7 @@ static int vec_search_host_lists(ss_shard* s, uint32_t nq, const void* queries, 
 // staging (ss_common.h vmu / vstream).  The shard mutex is held while the pass is enqueued -- the scan buffers of the stream are bound
 // into the shard's fields for that long (VecWsBind) -- and NOT while it runs: 9 ms at 10 M x 768, during which lexical searches of the
 // shard (a hybrid caller's first half) used to wait for the mutex, then for the stream.
-static int vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
+extern "C++" int ssi_vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
                                 uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
   if (nq == 0) return SS_OK;
   std::lock_guard<std::mutex> gv(s->vmu);
@@ -4546,13 +3892,13 @@ static int vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, s
 
 // host-pointer searches: queries (f32 or i8 rows) and scales are staged in the shard's grow-only buffer, out_clusters
 // (observed_cluster_count, ANN modes) rides behind them
-static int vec_search_host(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
+extern "C++" int ssi_vec_search_host(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
                            float thr, const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                            uint64_t* out_total, uint32_t* out_clusters, const float* query_norm) {
   if (nq == 0) return SS_OK;
   ShardLock g(s);
   uint32_t* d_ncl = nullptr;
-  int rc = vec_search_host_lists(s, nq, queries, elem, query_scale, k, thr, mode, out_count, &d_ncl, query_norm, out_clusters != nullptr);
+  int rc = ssi_vec_search_host_lists(s, nq, queries, elem, query_scale, k, thr, mode, out_count, &d_ncl, query_norm, out_clusters != nullptr);
   if (rc == SS_OK) {
     if (hipMemcpy(out_doc, s->d_out_doc, (size_t)nq * k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(out_score, s->d_out_score, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
@@ -4583,15 +3929,15 @@ int ss_vec_search_ann(ss_shard* s, uint32_t nq, const float* queries, uint32_t k
   if (!s->d_X) return SS_ESTATE;
   SS_TRY(ann_mode_ok(s, mode));
   mode = ann_effective(mode);
-  if (k > SS_MAX_K)  // (a page deeper than SS_MAX_K results: passes under per-query exclusion bitmaps, "deep pages" above)
+  if (k > SS_MAX_K)  // (a page deeper than SS_MAX_K results: passes under per-query exclusion bitmaps, api_deep.hip)
     return vec_search_host_deep(s, nq, queries, sizeof(float), nullptr, k, thr, mode, out_doc, out_score, out_count, out_total, mode ? out_clusters : nullptr, nullptr);
   if (!mode && nq != 0 && nq <= SS_COALESCE_MAX_REQUEST && s->co_vec.max_batch) {  // AnnMode::All from concurrent callers: one pass serves them
     ss_co_req r;
     r.q = queries; r.nq = nq; r.k = k; r.elem = (uint32_t)sizeof(float); r.thr = thr;
     r.out_doc = out_doc; r.out_score = out_score; r.out_count = out_count; r.out_total = out_total;
-    return co_submit(s, s->co_vec, false, &r);
+    return ssi_co_submit(s, s->co_vec, false, &r);
   }
-  return vec_search_host(s, nq, queries, sizeof(float), nullptr, k, thr, mode, out_doc, out_score, out_count, out_total,
+  return ssi_vec_search_host(s, nq, queries, sizeof(float), nullptr, k, thr, mode, out_doc, out_score, out_count, out_total,
                          mode ? out_clusters : nullptr);
 }
 int ss_vec_search(ss_shard* s, uint32_t nq, const float* queries, uint32_t k, float thr, uint32_t* out_doc,
@@ -4615,7 +3961,7 @@ static int vec_search_deep_dev_locked(ss_shard* s, uint32_t nq, const void* d_qu
   std::vector<uint32_t> h_doc((size_t)nq * k), h_cnt(nq), h_ncl(d_out_clusters ? (size_t)nq * ocw : 0);
   std::vector<float> h_score((size_t)nq * k);
   std::vector<uint64_t> h_tot(nq);
-  SS_TRY(vec_search_deep_locked(s, nq, hq.data(), elem, d_qscale ? hs.data() : nullptr, k, thr, mode, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data(),
+  SS_TRY(ssi_vec_search_deep_locked(s, nq, hq.data(), elem, d_qscale ? hs.data() : nullptr, k, thr, mode, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data(),
                                 d_out_clusters ? h_ncl.data() : nullptr, d_qnorm ? hn.data() : nullptr));
   SS_HIP(hipMemcpyAsync(d_out_doc, h_doc.data(), h_doc.size() * 4, hipMemcpyHostToDevice, st));
   SS_HIP(hipMemcpyAsync(d_out_score, h_score.data(), h_score.size() * 4, hipMemcpyHostToDevice, st));
@@ -4704,19 +4050,6 @@ int ss_vec_cluster_info(ss_shard* s, uint32_t* n_levels, uint32_t* n_clusters) {
 // i8 image: rows as the reference stores them for Precision::I8 (quantize_f32_to_i8, vector_similarity.rs:1226-1232, or a
 // per-record scale = VectorHeader.scale with ScalarQuantizationI8).  Score = dot_i8 as f32 (vector_similarity.rs:1011-1016)
 // or, with scales, dot_i8_quantized = dot as f32 * query_scale * embedding_scale (1754-1758).
-static int vec8_alloc(ss_shard* s, uint64_t n_rows, uint32_t dim) {
-  free_vec(s);
-  s->n_rows = n_rows;
-  s->dim = dim;
-  s->dim_pad8 = (dim + 127u) / 128u * 128u;
-  if (s->dim_pad8 > 2560u) { free_vec(s); return SS_ENOTSUP; }  // the 64 queries stay in LDS: 64 x dim_pad8 <= 160 KB
-  s->n_rows_pad = (n_rows + VS_TR - 1) / VS_TR * VS_TR;
-  const size_t bytes = (size_t)s->n_rows_pad * s->dim_pad8;
-  SS_HIP(hipMalloc(&s->d_X8, bytes));
-  if (s->dim_pad8 != dim || s->n_rows_pad != n_rows) SS_HIP(hipMemsetAsync(s->d_X8, 0, bytes, s->stream));  // padding is interleaved
-  return SS_OK;
-}
-
 int ss_vec_upload_i8(ss_shard* s, uint64_t n_rows, uint32_t dim, const int8_t* rows, const float* row_scale,
                      const uint32_t* row_doc_ids) {
   if (!s || !rows || n_rows == 0 || dim == 0) return SS_EINVAL;
@@ -4942,9 +4275,9 @@ int ss_vec_search_i8_euclid(ss_shard* s, uint32_t nq, const int8_t* queries, con
     ss_co_req r;
     r.q = queries; r.qscale = query_scale; r.nq = nq; r.k = k; r.elem = 1; r.thr = thr;
     r.out_doc = out_doc; r.out_score = out_score; r.out_count = out_count; r.out_total = out_total;
-    return co_submit(s, s->co_vec, false, &r);
+    return ssi_co_submit(s, s->co_vec, false, &r);
   }
-  return vec_search_host(s, nq, queries, 1, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total,
+  return ssi_vec_search_host(s, nq, queries, 1, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total,
                          mode ? out_clusters : nullptr, query_norm);
 }
 int ss_vec_search_i8_ann(ss_shard* s, uint32_t nq, const int8_t* queries, const float* query_scale, uint32_t k, float thr,

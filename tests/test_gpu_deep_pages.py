@@ -1,7 +1,7 @@
 """DEEP PAGES: offset + length beyond SS_MAX_K = 1024 results (search.rs:1658-1659 -- the crate's top_k is unbounded).
 
 The kernels' top-k structures hold SS_MAX_K; a deeper page is answered behind the ABI in passes of SS_MAX_K results, every pass the
-ordinary search under (what excluded docs before) | (the docs the earlier passes returned) -- csrc/ss_api.hip "deep pages".  Every
+ordinary search under (what excluded docs before) | (the docs the earlier passes returned) -- csrc/api_deep.hip.  Every
 shape the library answers at k <= SS_MAX_K must therefore come back at any k with the oracle's answer: both tiers, NOT terms,
 tombstones, a facet filter, several indexed fields (a union under a field filter composed from sub-queries), phrases; f32 and i8
 vectors with several records per doc, tombstones and a threshold -- and a list that runs dry before the page is full.

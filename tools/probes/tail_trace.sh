@@ -1,5 +1,5 @@
 #!/bin/bash
-# which batches make the vector / hybrid tail at T = 64: SS_CO_TRACE's per-batch outliers (ss_api.hip ss_shard_destroy) beside the call histogram
+# which batches make the vector / hybrid tail at T = 64: SS_CO_TRACE's per-batch outliers (api_coalesce.hip ssi_co_trace_report) beside the call histogram
 cd "${GRAFT_REPO_ROOT:-.}"
 for r in $(seq 1 ${1:-3}); do
   for leg in vector:64 hybrid:64; do
