@@ -109,6 +109,19 @@ int ss_shard_create(int device, ss_shard** out);
 int ss_shard_set_coalescing(ss_shard* s, uint32_t max_lexical_batch, uint32_t max_vector_batch, uint32_t max_wait_us);
 int ss_shard_coalescing_stats(ss_shard* s, uint64_t* lexical_batches, uint64_t* lexical_queries, uint64_t* vector_batches,
                               uint64_t* vector_queries);
+/* The same for FACETED callers, a kind of its own: ss_bm25_search_filtered with filters, ss_bm25_search_facets, ss_bm25_search_sorted and
+ * ss_bm25_search_sorted_facets of at most 16 queries, k <= SS_MAX_K, without an SS_FACET_IDS_EXTERN filter.  The seam is the same one
+ * (search.rs:2543-2727 resolves one request's facet filters, add_result.rs:341-646 applies them and counts its query_facets): a shop
+ * page -- terms, a facet filter, sidebar counts, a sort -- is one such call per user, and concurrent users of one page template differ
+ * in their FILTERS only.  Requests whose sorts, query_facets, k and result type are equal byte for byte share a batch of at most 64
+ * queries, run as ONE ss_bm25_search_each -- every query under its own request's filters -- and every caller gets its own rows and
+ * counters, bit for bit what its call returns alone.  One lane; a lone caller runs its entry's direct path at once; a batch that fails
+ * is re-run member by member, each its own verdict.  max_batch: queries per batch, 0 = off, at most 64 (SS_EINVAL beyond); the default
+ * is 64 -- at 10 M docs 64 concurrent callers of a sorted page with three facets get 8.1 - 8.2 K pages/s instead of 0.9 - 1.2 K, and one
+ * caller's median p50 lies inside the spread of the same probe on the build before (about 2 % wide; profiles/faceted_callers_time.json);
+ * max_wait_us as above.  The lexical and vector kinds, their settings and their counters are untouched by these two calls. */
+int ss_shard_set_coalescing_faceted(ss_shard* s, uint32_t max_batch, uint32_t max_wait_us);
+int ss_shard_coalescing_stats_faceted(ss_shard* s, uint64_t* batches, uint64_t* queries);
 /* Small host-pointer lexical batches -- the reference's call shape is ONE query per call (search.rs:1637-1743: one task per shard and
  * query) -- take a one-launch path (csrc/bm25_small.hip: <= 64 queries of <= 4 scored and <= 4 NOT terms each, k <= 128, one list per
  * term -- one indexed field, or several with merged lists and no field filter --, every list with a probe row, no facet filter): same answers bit for bit, a third of the latency.  ss_bm25_path_stats: how
@@ -753,6 +766,28 @@ int ss_bm25_search_sorted_facets(ss_shard* s, uint32_t n_queries, const ss_bm25_
                                  uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets,
                                  const uint64_t* range_lower_bounds, const ss_facet_point* bases,
                                  uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
+/* A batch whose queries each carry their OWN facet filters (the crate resolves ONE request's filters, search.rs:2543-2727, and applies
+ * them per candidate, add_result.rs:341-646; concurrent requests of one page template share sorts and query_facets and differ in their
+ * filters -- the batch entries above take one filter set for the whole call).  Query i runs under
+ * filters[filter_begin[i] .. filter_begin[i + 1]) (filter_begin [n_queries + 1], ascending; an empty set: the tombstones alone) and gets
+ * EXACTLY what ss_bm25_search_sorted_facets(s, 1, &queries[i], ..., its filters, ...) returns -- docs, scores, counts, totals and
+ * counters, bit for bit; so without sorts ss_bm25_search_facets' answer, without facets ss_bm25_search_sorted's / _filtered's.  Sorts,
+ * query_facets, k and result_type are the call's; n_sorts = 0, n_facets = 0 and SS_RT_COUNT are allowed as on those entries.
+ * Per chunk of <= 64 queries ONE pass over the facet records writes an exclusion row per distinct (byte-equal) filter set, the match
+ * sets are built under the tombstones and every query's row is taken off its own; facets, the sort's select, its two searches (one
+ * exclusion bitmap per query) and the compose run over the chunk as in ss_bm25_search_sorted_facets; without sorts SS_RT_TOPKCOUNT runs
+ * ONE batched search with a bitmap per query and takes the totals from the match sets, SS_RT_COUNT runs no search.  One synchronisation
+ * per call on that route.  Run alone through the single-filter entry instead: a query with an SS_FACET_IDS_EXTERN filter; every query of
+ * a call with k > SS_MAX_K; without sorts every SEARCH of an SS_RT_TOPK call (*out_total of SS_RT_TOPK is the answering kernel's) and of
+ * a chunk the batched search does not serve (a phrase, a sparse-tier term, a field filter, k > 128, the exhaustive strategy).
+ * Refusals are those entries': SS_EINVAL -- their argument checks, filter_begin NULL or not ascending, more than SS_MAX_FACET_FILTERS
+ * in a set, a filter ss_bm25_search_filtered refuses; SS_ESTATE -- no image, facet records missing where filters, sorts or facets need
+ * them; SS_ENOTSUP -- as ss_bm25_search_sorted_facets for the whole call (one query it refuses fails the call; retry query by query). */
+int ss_bm25_search_each(ss_shard* s, uint32_t n_queries, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
+                        uint32_t result_type, const uint32_t* filter_begin, const ss_facet_filter* filters, uint32_t n_facets,
+                        const uint32_t* facet_offset, const uint32_t* facet_type, const uint32_t* n_buckets, const uint64_t* range_lower_bounds,
+                        const ss_facet_point* bases, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
+                        uint64_t* out_facet_counts);
 
 /* The EMPTY query of a shard (the crate's search(.., enable_empty_query, ..) with no query string: search_iterator_shard,
  * iterator.rs:316-358, reached from the query_list_len == 0 arm of search_lexical_shard, search.rs:3374-3386): every doc of the

@@ -211,6 +211,8 @@ SYMBOLS = [
                                         C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
     ("ss_bm25_search_sorted_facets", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_void_p, C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
+    ("ss_bm25_search_each", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_void_p, C.c_uint32,
+                                      u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
     ("ss_docs_search", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, u32p, u64p, u64p]),
     ("ss_bm25_search_sharded", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
@@ -235,6 +237,8 @@ SYMBOLS = [
     ("ss_bm25_sparse_info", C.c_int, [C.c_void_p, u32p, u64p, u64p]),
     ("ss_shard_set_coalescing", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("ss_shard_coalescing_stats", C.c_int, [C.c_void_p, u64p, u64p, u64p, u64p]),
+    ("ss_shard_set_coalescing_faceted", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("ss_shard_coalescing_stats_faceted", C.c_int, [C.c_void_p, u64p, u64p]),
     ("ss_bm25_path_stats", C.c_int, [C.c_void_p, u64p]),
     ("ss_bm25_shape_stats", C.c_int, [C.c_void_p, u64p]),
     ("ss_profile_enable", C.c_int, [C.c_void_p, C.c_int]),

@@ -119,6 +119,85 @@ int co_run_vector_one(ss_shard* s, ss_co_req* r) {
   return ssi_vec_search_host(s, r->nq, r->q, r->elem, r->qscale, r->k, r->thr, nullptr, r->out_doc, r->out_score, r->out_count, r->out_total, nullptr);
 }
 
+// ---- the FACETED kind (ss_shard_abi::co_fac, api_internal.h): requests of ss_bm25_search_filtered with filters, _facets, _sorted and _sorted_facets.  Two share a
+// batch when their specs in ss_bm25_search_each's terms are equal byte for byte -- sorts, facets, bounds, bases of the Point facets, k
+// (equal, not a class: the select's pivot is the k-th value) and result type; their FILTERS may differ, that is the point of the batch.
+inline bool co_fac_compatible(const ss_co_fac_req* a, const ss_co_fac_req* b) {
+  if (a->k != b->k || a->rt != b->rt || a->n_sorts != b->n_sorts || a->n_facets != b->n_facets || a->n_bounds != b->n_bounds) return false;
+  if (a->n_sorts && memcmp(a->sorts, b->sorts, (size_t)a->n_sorts * sizeof(ss_result_sort)) != 0) return false;
+  if (a->n_facets) {
+    const size_t n = (size_t)a->n_facets * 4;
+    if (memcmp(a->facet_offset, b->facet_offset, n) != 0 || memcmp(a->facet_type, b->facet_type, n) != 0 || memcmp(a->n_buckets, b->n_buckets, n) != 0) return false;
+    if (a->n_bounds && memcmp(a->range_lower_bounds, b->range_lower_bounds, a->n_bounds * 8) != 0) return false;
+    for (uint32_t f = 0; f < a->n_facets; f++)
+      if (a->facet_type[f] == SS_FACET_POINT && memcmp(&a->bases[f], &b->bases[f], sizeof(ss_facet_point)) != 0) return false;
+  }
+  return true;
+}
+// this thread is the coalescer running ONE request through its caller's own entry: that entry must not hand it back
+thread_local int t_co_fac_direct = 0;
+int co_run_fac_one(ss_shard* s, ss_co_req* r_) {
+  ss_co_fac_req* r = static_cast<ss_co_fac_req*>(r_);
+  struct Guard { Guard() { t_co_fac_direct++; } ~Guard() { t_co_fac_direct--; } } guard;
+  const ss_bm25_query* q = (const ss_bm25_query*)r->q;
+  switch (r->kind) {
+    case SS_CO_FILTERED:
+      return ss_bm25_search_filtered(s, r->nq, q, r->k_own, r->rt_own, r->n_filters, r->filters, r->out_doc, r->out_score, r->out_count, r->out_total);
+    case SS_CO_FACETS:
+      return ss_bm25_search_facets(s, r->nq, q, r->k_own, r->rt_own, r->n_filters, r->filters, r->n_facets, r->facet_offset, r->facet_type, r->n_buckets,
+                                   r->range_lower_bounds, r->bases, r->out_doc, r->out_score, r->out_count, r->out_total, r->out_facet_counts);
+    case SS_CO_SORTED:
+      return ss_bm25_search_sorted(s, r->nq, q, r->n_sorts, r->sorts, r->k_own, r->n_filters, r->filters, r->out_doc, r->out_score, r->out_count, r->out_total);
+    case SS_CO_SORTED_FACETS:
+      return ss_bm25_search_sorted_facets(s, r->nq, q, r->n_sorts, r->sorts, r->k_own, r->rt_own, r->n_filters, r->filters, r->n_facets, r->facet_offset,
+                                          r->facet_type, r->n_buckets, r->range_lower_bounds, r->bases, r->out_doc, r->out_score, r->out_count, r->out_total,
+                                          r->out_facet_counts);
+    default: return SS_EINVAL;
+  }
+}
+// one merged batch of <= 64 queries: the members' queries and filters back to back, ONE ss_bm25_search_each -- every query of a member
+// under that member's filters --, every member's rows and counters copied to its own arrays
+int co_run_fac_batch(ss_shard* s, const std::vector<ss_co_req*>& batch) {
+  struct Guard { Guard() { t_co_fac_direct++; } ~Guard() { t_co_fac_direct--; } } guard;  // (nothing in here comes back as a request of its own)
+  const ss_co_fac_req* f = static_cast<const ss_co_fac_req*>(batch[0]);
+  uint32_t total = 0, total_f = 0;
+  for (const ss_co_req* r : batch) { total += r->nq; total_f += r->nq * static_cast<const ss_co_fac_req*>(r)->n_filters; }
+  const uint32_t k = f->k;
+  std::vector<ss_bm25_query> q(total);
+  std::vector<uint32_t> fb(total + 1, 0u), doc((size_t)total * k), cnt(total);
+  std::vector<ss_facet_filter> ff;
+  ff.reserve(total_f);
+  std::vector<float> score((size_t)total * k);
+  std::vector<uint64_t> tot(total), fc((size_t)total * f->stride);
+  uint32_t at = 0;
+  for (const ss_co_req* r_ : batch) {
+    const ss_co_fac_req* r = static_cast<const ss_co_fac_req*>(r_);
+    memcpy(q.data() + at, r->q, (size_t)r->nq * sizeof(ss_bm25_query));
+    for (uint32_t i = 0; i < r->nq; i++) {  // (every query of a request runs under the request's filters)
+      ff.insert(ff.end(), r->filters, r->filters + r->n_filters);
+      fb[at + i + 1] = (uint32_t)ff.size();
+    }
+    at += r->nq;
+  }
+  const int rc = ss_bm25_search_each(s, total, q.data(), f->n_sorts, f->sorts, k, f->rt, fb.data(), ff.data(), f->n_facets, f->facet_offset, f->facet_type,
+                                     f->n_buckets, f->range_lower_bounds, f->bases, doc.data(), score.data(), cnt.data(), tot.data(), fc.data());
+  if (rc != SS_OK) return rc;
+  at = 0;
+  for (ss_co_req* r_ : batch) {
+    ss_co_fac_req* r = static_cast<ss_co_fac_req*>(r_);
+    if (k) {
+      memcpy(r->out_doc, doc.data() + (size_t)at * k, (size_t)r->nq * k * sizeof(uint32_t));
+      memcpy(r->out_score, score.data() + (size_t)at * k, (size_t)r->nq * k * sizeof(float));
+    }
+    memcpy(r->out_count, cnt.data() + at, (size_t)r->nq * sizeof(uint32_t));
+    memcpy(r->out_total, tot.data() + at, (size_t)r->nq * sizeof(uint64_t));
+    if (f->stride) memcpy(r->out_facet_counts, fc.data() + (size_t)at * f->stride, (size_t)r->nq * f->stride * sizeof(uint64_t));
+    r->rc = SS_OK;
+    at += r->nq;
+  }
+  return SS_OK;
+}
+
 // one merged batch: the members' queries back to back, one search, every member's rows copied to its own buffers
 int co_run_batch(ss_shard* s, ss_coalescer& co, bool lexical, const std::vector<ss_co_req*>& batch, uint32_t lane_ix) {
   ss_co_req* f = batch[0];
@@ -182,7 +261,9 @@ int co_run_batch(ss_shard* s, ss_coalescer& co, bool lexical, const std::vector<
 }
 }  // namespace
 
-extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_co_req* me) {
+// faceted: `co` is the shard's faceted coalescer and every request in its queue an ss_co_fac_req (lexical in every other respect: the
+// linger's rule, a lone caller straight through its own path)
+static int co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_co_req* me, bool faceted) {
   bool lead;
   {
     std::lock_guard<std::mutex> g(co.mu);
@@ -219,7 +300,7 @@ extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_c
     // lone caller is never delayed.  max_wait_us > 0 (ss_shard_set_coalescing) waits that long unconditionally.
     const uint64_t trace_t_lead_ns = g_co_trace_on && !lexical ? co_now_us() : 0;
     {
-      uint32_t want, wait_us;
+      uint32_t want, wait_us, hard_us;
       {
         std::lock_guard<std::mutex> g(co.mu);
         // (several lanes: the callers around are shared between the batches in flight)
@@ -236,10 +317,11 @@ extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_c
         // callers past their vector pass (uncapped: hybrid T = 64 p99 21 ms in one of two runs, r6_linger_div_hybrid.log).
         const uint32_t div = lexical ? 1u : 4u, cap = lexical ? 150u : 3000u;
         wait_us = co.max_wait_us ? co.max_wait_us : (co.callers_est > 1 ? std::min<uint32_t>(cap, co.last_batch_us / div) : 0u);
+        hard_us = std::max<uint32_t>(wait_us, std::min<uint32_t>(co.last_batch_us, 10000u));  // (last_batch_us is written under co.mu: read here)
       }
       if (wait_us) {
         const auto t_in = std::chrono::steady_clock::now(), until = t_in + std::chrono::microseconds(wait_us);
-        const auto hard_until = t_in + std::chrono::microseconds(std::max<uint32_t>(wait_us, std::min<uint32_t>(co.last_batch_us, 10000u)));
+        const auto hard_until = t_in + std::chrono::microseconds(hard_us);
         // VECTOR passes also leave when the batch is NEARLY full and the arrivals have gone quiet: of 64 callers released together, 63 are
         // back within ~150 us; now and then one is not (the scheduler's doing) -- waiting out the cap for it costs the 63 a quarter of a
         // pass each (their p99: 12 - 14 ms against a p50 of 9.4, profiles/r6_tail_repeat.log), where going without it costs ONE caller a
@@ -283,7 +365,8 @@ extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_c
       total = me->nq;
       for (auto it = co.queue.begin(); it != co.queue.end();) {
         if ((*it)->lane == 0xFFFFFFFFu &&  // (a request that leads a lane itself is not a member of anybody's batch)
-            co_compatible(f, *it) && total + (*it)->nq <= co.max_batch) {
+            (faceted ? co_fac_compatible(static_cast<const ss_co_fac_req*>(f), static_cast<const ss_co_fac_req*>(*it)) : co_compatible(f, *it)) &&
+            total + (*it)->nq <= co.max_batch) {
           total += (*it)->nq;
           batch.push_back(*it);
           co.queued_nq.fetch_sub((*it)->nq, std::memory_order_relaxed);
@@ -304,10 +387,10 @@ extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_c
     // (a lone VECTOR request takes the batch form too: the lane's pinned staging and the scan's own stream -- its pass must not hold the
     // shard mutex either)
     if (batch.size() == 1 && lexical) {
-      batch[0]->rc = co_run_lexical_one(s, batch[0]);
-    } else if (co_run_batch(s, co, lexical, batch, me->lane) != SS_OK) {
+      batch[0]->rc = faceted ? co_run_fac_one(s, batch[0]) : co_run_lexical_one(s, batch[0]);
+    } else if ((faceted ? co_run_fac_batch(s, batch) : co_run_batch(s, co, lexical, batch, me->lane)) != SS_OK) {
       // somebody's request is at fault (or the device is): every member is re-run alone and gets its own verdict
-      for (ss_co_req* r : batch) r->rc = lexical ? co_run_lexical_one(s, r) : co_run_vector_one(s, r);
+      for (ss_co_req* r : batch) r->rc = faceted ? co_run_fac_one(s, r) : lexical ? co_run_lexical_one(s, r) : co_run_vector_one(s, r);
     }
     ss_co_req* succ = nullptr;
     {
@@ -347,7 +430,7 @@ extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_c
       else co_signal(r, 1u);
       co.waking.fetch_sub(1u, std::memory_order_relaxed);
     }
-    if (g_co_trace_on && lexical && batch.size() > 1) { g_co_trace.wake += co_now_us() - tw0; g_co_trace.members += batch.size() - 1; }
+    if (g_co_trace_on && lexical && !faceted && batch.size() > 1) { g_co_trace.wake += co_now_us() - tw0; g_co_trace.members += batch.size() - 1; }
     if (g_co_trace_on && !lexical) {
       std::lock_guard<std::mutex> gt(g_co_vec_trace_mu);
       g_co_vec_wake_us.push_back((uint32_t)((co_now_us() - tw0) / 1000));
@@ -358,6 +441,58 @@ extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_c
   }
 }
 
+extern "C++" int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_co_req* me) { return co_submit(s, co, lexical, me, false); }
+
+extern "C++" int ssi_co_fac_try(ss_shard* s, uint32_t kind, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k,
+                                uint32_t rt, uint32_t n_filters, const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset,
+                                const uint32_t* facet_type, const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases,
+                                uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts, bool* submitted) {
+  *submitted = false;
+  if (!s || t_co_fac_direct || nq == 0 || nq > SS_CO_FACETED_MAX_REQUEST) return SS_OK;
+  ss_coalescer* co = &ssi_co_fac(s);
+  if (!co->max_batch) return SS_OK;
+  // only what a batch can carry as it stands; everything else is its own entry's to answer or refuse
+  if (!queries || !out_count || !out_total || rt > SS_RT_TOPKCOUNT || n_sorts > SS_MAX_SORT_FIELDS || (n_sorts && !sorts) || n_filters > SS_MAX_FACET_FILTERS ||
+      (n_filters && !filters) || n_facets > SS_MAX_QUERY_FACETS)
+    return SS_OK;
+  if (rt != SS_RT_COUNT && (k == 0 || k > SS_MAX_K || !out_doc || !out_score)) return SS_OK;
+  if (n_facets && (!facet_offset || !facet_type || !n_buckets || !out_facet_counts)) return SS_OK;
+  for (uint32_t j = 0; j < n_filters; j++)
+    if (filters[j].n_values == SS_FACET_IDS_EXTERN && (filters[j].type == SS_FACET_STRING16 || filters[j].type == SS_FACET_STRING32)) return SS_OK;
+  ss_co_fac_req r;
+  r.kind = kind; r.k_own = k; r.rt_own = rt;
+  r.q = queries; r.nq = nq; r.k = rt == SS_RT_COUNT ? 0u : k; r.rt = rt;
+  r.n_sorts = n_sorts; r.sorts = sorts;
+  r.n_filters = n_filters; r.filters = filters;
+  r.n_facets = n_facets; r.facet_offset = facet_offset; r.facet_type = facet_type; r.n_buckets = n_buckets; r.range_lower_bounds = range_lower_bounds; r.bases = bases;
+  for (uint32_t f = 0; f < n_facets; f++) {
+    if (facet_type[f] > SS_FACET_POINT || n_buckets[f] == 0 || n_buckets[f] > (1u << 24) || (facet_type[f] == SS_FACET_POINT && !bases)) return SS_OK;
+    if (facet_type[f] != SS_FACET_STRING16 && facet_type[f] != SS_FACET_STRING32) r.n_bounds += n_buckets[f];
+    r.stride += (size_t)n_buckets[f] + 1;
+  }
+  if (r.n_bounds && !range_lower_bounds) return SS_OK;
+  if (rt == SS_RT_COUNT && n_sorts) return SS_OK;  // (no select, but its sort fields are still checked: by its own entry)
+  r.out_doc = out_doc; r.out_score = out_score; r.out_count = out_count; r.out_total = out_total; r.out_facet_counts = out_facet_counts;
+  *submitted = true;
+  return co_submit(s, *co, true, &r, true);
+}
+
+int ss_shard_set_coalescing_faceted(ss_shard* s, uint32_t max_batch, uint32_t max_wait_us) {
+  if (!s || max_batch > 64u) return SS_EINVAL;
+  ss_coalescer* co = &ssi_co_fac(s);
+  std::lock_guard<std::mutex> g(co->mu);
+  co->max_batch = max_batch;
+  co->max_wait_us = max_wait_us;
+  return SS_OK;
+}
+int ss_shard_coalescing_stats_faceted(ss_shard* s, uint64_t* batches, uint64_t* queries) {
+  if (!s) return SS_EINVAL;
+  ss_coalescer* co = &ssi_co_fac(s);
+  std::lock_guard<std::mutex> g(co->mu);
+  if (batches) *batches = co->batches;
+  if (queries) *queries = co->queries;
+  return SS_OK;
+}
 int ss_shard_set_coalescing(ss_shard* s, uint32_t max_lexical_batch, uint32_t max_vector_batch, uint32_t max_wait_us) {
   if (!s || max_vector_batch > SS_VEC_BATCH) return SS_EINVAL;
   { std::lock_guard<std::mutex> g(s->co_lex.mu); s->co_lex.max_batch = max_lexical_batch; s->co_lex.max_wait_us = max_wait_us; }

@@ -82,9 +82,13 @@ int ssi_bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uin
 int ssi_bm25_search_direct_lane(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,
                                 uint32_t* out_count, uint64_t* out_total, hipEvent_t ev, uint32_t lane_slot, std::vector<uint32_t>& row_of);
 struct QueryFacets;  // (the query_facets of a sorted search: ss_api.hip)
+// a batch whose queries each carry their OWN facet filters (ss_bm25_search_each): query i's are filters[filter_begin[i] .. filter_begin[i + 1]),
+// checked by ssi_filter_rows (filter_rows.h) and free of SS_FACET_IDS_EXTERN sets
+struct EachSets { const uint32_t* filter_begin; const ss_facet_filter* filters; };
 int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
                                   const ss_sort_sources& src, uint32_t k, uint32_t n_filters, const ss_facet_filter* filters,
-                                  uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, const QueryFacets* qf = nullptr);
+                                  uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, const QueryFacets* qf = nullptr,
+                                  const EachSets* each = nullptr);
 int ssi_vec_search_host(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
                         float thr, const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                         uint64_t* out_total, uint32_t* out_clusters, const float* query_norm = nullptr);
@@ -106,6 +110,40 @@ int ssi_bm25_search_sorted_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_q
 
 // ---- api_coalesce.hip
 int ssi_co_submit(ss_shard* s, ss_coalescer& co, bool lexical, ss_co_req* me);
+// A FACETED request (ss_bm25_search_filtered with filters, _facets, _sorted, _sorted_facets).  kind = the caller's entry (SS_CO_*), to run
+// it alone; k_own / rt_own as the caller gave them.  Everything else is the request in ss_bm25_search_each's terms -- the base's k = 0 for
+// SS_RT_COUNT, rt = SS_RT_TOPKCOUNT for ss_bm25_search_sorted, no sorts / no facets where the entry has none -- which is what a batch runs
+// and what makes two requests compatible.  The pointers are the caller's; n_bounds / stride as QueryFacets counts them.
+struct ss_co_fac_req : ss_co_req {
+  uint32_t kind = 0, k_own = 0, rt_own = 0, n_sorts = 0, n_filters = 0, n_facets = 0;
+  const ss_result_sort* sorts = nullptr;
+  const ss_facet_filter* filters = nullptr;
+  const uint32_t *facet_offset = nullptr, *facet_type = nullptr, *n_buckets = nullptr;
+  const uint64_t* range_lower_bounds = nullptr;
+  const ss_facet_point* bases = nullptr;
+  size_t n_bounds = 0, stride = 0;
+  uint64_t* out_facet_counts = nullptr;
+};
+enum { SS_CO_PLAIN = 0, SS_CO_FILTERED, SS_CO_FACETS, SS_CO_SORTED, SS_CO_SORTED_FACETS };
+// What ss_shard_create allocates: the shard and, behind it, the state only the ABI layer knows -- the FACETED kind's coalescer, co_fac,
+// next to co_lex and co_vec (one lane, batches of <= 64 through ss_bm25_search_each).  It stands here and not in ss_shard because
+// ss_common.h is one of the kernel sources whose hash ties profiles/pmc_traffic.json to the tree (bench.py kernel_source_hash): host-only
+// state must not move that hash.  Every ss_shard* that crosses the ABI came from ss_shard_create and is one of these; the scratch
+// images the builders make with `new ss_shard` never reach an entry point.
+// (the default batch: profiles/faceted_callers_time.json has the figures it follows)
+#define SS_CO_FACETED_DEFAULT 64u
+struct ss_shard_abi : ss_shard {
+  ss_coalescer co_fac;
+};
+static inline ss_coalescer& ssi_co_fac(ss_shard* s) { return static_cast<ss_shard_abi*>(s)->co_fac; }
+// the faceted kind.  *submitted = the call went through the coalescer and the return value is its answer; false -- the kind
+// is off, the call is not one it takes (more than SS_CO_FACETED_MAX_REQUEST queries, a deep page, an SS_FACET_IDS_EXTERN filter, arguments the entry
+// itself must judge) or this thread IS the coalescer running a request alone: the entry goes on as it always has
+#define SS_CO_FACETED_MAX_REQUEST 16u
+int ssi_co_fac_try(ss_shard* s, uint32_t kind, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k, uint32_t rt,
+                   uint32_t n_filters, const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset, const uint32_t* facet_type,
+                   const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases, uint32_t* out_doc, float* out_score,
+                   uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts, bool* submitted);
 // SS_CO_TRACE: where a coalesced batch spends its time.  _lane: a lexical lane batch's enqueue and device-wait times (ns);
 // _report: what was collected, to stderr (ss_shard_destroy)
 bool ssi_co_trace_on();

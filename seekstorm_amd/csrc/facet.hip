@@ -45,26 +45,7 @@ __host__ __device__ inline uint32_t morton_compact(unsigned long long x) {  // t
   x = (x ^ (x >> 16)) & 0x00000000FFFFFFFFull;
   return (uint32_t)x;
 }
-__host__ inline unsigned long long morton_spread(uint32_t v) {
-  unsigned long long x = v;
-  x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-  x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-  x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
-__host__ inline uint32_t morton_coord(double degrees) {  // (v * 1e7) as i32 as u32: Rust's cast truncates, saturates, NaN -> 0
-  const double v = degrees * 10000000.0;
-  int32_t i;
-  if (v != v) i = 0;
-  else if (v >= 2147483647.0) i = INT32_MAX;
-  else if (v <= -2147483648.0) i = INT32_MIN;
-  else i = (int32_t)v;
-  return (uint32_t)i;
-}
-__host__ inline unsigned long long morton_encode(double lat, double lon) { return (morton_spread(morton_coord(lon)) << 1) | morton_spread(morton_coord(lat)); }
-static constexpr double kDeg2Rad = 0.017453292519943295, kEarthKm = 6371.0087714, kEarthMi = 3958.761315801475;
+// (the host's half -- morton_encode, the constants -- stands in filter_rows.h: ssi_filter_prepare computes a filter's Morton corners)
 
 __device__ double facet_point_distance(const FacetPoint& b, unsigned long long code) {
 #pragma clang fp contract(off)
@@ -168,13 +149,10 @@ int ssi_facet_build(ss_shard* s, uint32_t n_filters, const ss_facet_filter* filt
   uint64_t set_words = 0, set_begin[SS_MAX_FACET_FILTERS] = {0}, set_bits[SS_MAX_FACET_FILTERS] = {0};
   for (uint32_t i = 0; i < n_filters; i++) {
     const ss_facet_filter& f = filters[i];
-    if (f.type > SS_FACET_POINT || f.offset + ssi_facet_width(f.type) > s->facet_record_size) return SS_EINVAL;
-    const bool strings = f.type == SS_FACET_STRING16 || f.type == SS_FACET_STRING32;
-    if (strings && f.n_values > 8 && f.n_values != SS_FACET_IDS_EXTERN) return SS_EINVAL;
-    F.f[i] = f;
-    if (strings && f.n_values == SS_FACET_IDS_EXTERN) {  // lo = host array of hi ids -> a bitmap over [0, largest id]
+    const int rcf = ssi_filter_prepare(f, s->facet_record_size, &F.f[i]);  // (filter_rows.h: the checks, a Point filter's Morton corners)
+    if (rcf != SS_OK) return rcf;
+    if (ssi_filter_is_extern(f)) {  // lo = host array of hi ids -> a bitmap over [0, largest id]
       const uint32_t* ids = (const uint32_t*)(uintptr_t)f.lo;
-      if (f.hi && !ids) return SS_EINVAL;
       uint64_t bits = 0;
       for (uint64_t j = 0; j < f.hi; j++) bits = std::max<uint64_t>(bits, (uint64_t)ids[j] + 1);
       if (f.type == SS_FACET_STRING16) bits = std::min<uint64_t>(bits, 65536);  // ids beyond the facet's width match nothing
@@ -182,22 +160,6 @@ int ssi_facet_build(ss_shard* s, uint32_t n_filters, const ss_facet_filter* filt
       set_begin[i] = set_words;
       set_bits[i] = bits;
       set_words += (bits + 31) / 32;
-    }
-    if (f.type == SS_FACET_POINT) {
-      if (f.n_values > SS_POINT_MILES) return SS_EINVAL;
-      if (f.n_values != SS_POINT_SORTKEY) {
-        // point_distance_to_morton_range(base, distance_range.end, unit), search.rs:2712-2722 / geo_search.rs:128-144: the
-        // codes of the two corners of the box around the base -- a range of the Z-ORDER, as the reference compares it
-        double lat, lon, end;
-        unsigned long long w0 = (unsigned long long)f.values[0] | ((unsigned long long)f.values[1] << 32),
-                           w1 = (unsigned long long)f.values[2] | ((unsigned long long)f.values[3] << 32);
-        memcpy(&lat, &w0, 8); memcpy(&lon, &w1, 8); memcpy(&end, &f.hi, 8);
-        const double radius = f.n_values == SS_POINT_KM ? kEarthKm : kEarthMi;
-        const double lat_delta = end / (kDeg2Rad * radius), lon_delta = end / (kDeg2Rad * radius * cos(kDeg2Rad * lat));
-        const unsigned long long m0 = morton_encode(lat - lat_delta, lon - lon_delta), m1 = morton_encode(lat + lat_delta, lon + lon_delta);
-        F.f[i].values[4] = (uint32_t)m0; F.f[i].values[5] = (uint32_t)(m0 >> 32);
-        F.f[i].values[6] = (uint32_t)m1; F.f[i].values[7] = (uint32_t)(m1 >> 32);
-      }
     }
   }
   const uint64_t words = (s->facet_docs + 31) / 32;
@@ -226,6 +188,100 @@ int ssi_facet_build(ss_shard* s, uint32_t n_filters, const ss_facet_filter* filt
   facet_filter_kernel<<<(unsigned)((s->facet_docs + 255) / 256), 256, 0, st>>>(
       s->d_facets, s->facet_record_size, (unsigned long long)s->facet_docs, F, s->n_deleted ? s->d_deleted : nullptr,
       (uint32_t)s->deleted_words, s->d_filter_bits);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+// ---- Exclusion ROWS: a batch whose queries each carry their own filter set (ss_bm25_search_each; filter_rows.h groups byte-equal sets
+// into rows).  ONE pass over the records writes all n_rows <= 64 rows: a block of 256 threads stages the sets -- [row_begin: n_rows + 1
+// u32, padded to 16 bytes][the filters, 64 bytes each]; 64 sets of 8 filters are 32 KB, beyond any kernarg -- and its 256 records in LDS
+// (one coalesced read of 256 * record_size bytes, whatever n_rows is; records of more than 64 bytes are read in place instead), then
+// every thread tests its doc against row after row with facet_pass as it stands, one ballot per row, and the lanes 0 and 32 of a wave
+// write the row's word | the tombstones' word.  The grid covers the whole row -- row_words * 32 docs, the lexical image's sub-blocks --
+// and a doc at or beyond n_docs is excluded, so every word of every row is written: no clearing, no atomics.
+constexpr uint32_t FR_THREADS = 256, FR_RECORD_LDS = 16384;
+static inline uint32_t filter_rows_head(uint32_t n_rows) { return ((n_rows + 1u) * 4u + 15u) & ~15u; }
+__global__ __launch_bounds__(FR_THREADS) void facet_filter_rows_kernel(const uint8_t* __restrict__ records, uint32_t record_size, unsigned long long n_docs,
+                                                                       const uint32_t* __restrict__ sets, uint32_t n_rows, uint32_t n_filters, uint32_t stage_records,
+                                                                       const uint32_t* __restrict__ del, uint32_t del_words, uint32_t* __restrict__ out,
+                                                                       uint32_t row_words) {
+  extern __shared__ __align__(16) uint8_t fr_lds[];
+  const uint32_t tid = threadIdx.x, head = ((n_rows + 1u) * 4u + 15u) & ~15u, set_words = (head + n_filters * (uint32_t)sizeof(ss_facet_filter)) / 4u;
+  const uint32_t* s_begin = (const uint32_t*)fr_lds;
+  const ss_facet_filter* s_f = (const ss_facet_filter*)(fr_lds + head);
+  uint8_t* s_rec = fr_lds + (size_t)set_words * 4u;
+  for (uint32_t i = tid; i < set_words; i += FR_THREADS) ((uint32_t*)fr_lds)[i] = sets[i];
+  const unsigned long long d0 = (unsigned long long)blockIdx.x * FR_THREADS, d = d0 + tid;
+  const uint8_t* rec = records + d * record_size;  // (dereferenced for d < n_docs only)
+  if (stage_records && d0 < n_docs) {
+    const uint32_t bytes = (uint32_t)min((unsigned long long)FR_THREADS, n_docs - d0) * record_size, words = bytes / 4u;
+    const uint8_t* src = records + d0 * record_size;  // (d0 is a multiple of 256: word-aligned whatever the record size)
+    for (uint32_t i = tid; i < words; i += FR_THREADS) ((uint32_t*)s_rec)[i] = ((const uint32_t*)src)[i];
+    for (uint32_t i = words * 4u + tid; i < bytes; i += FR_THREADS) s_rec[i] = src[i];
+    rec = s_rec + tid * record_size;
+  }
+  __syncthreads();
+  const bool live = d < n_docs;
+  const uint32_t lane = tid & 63u;
+  const unsigned long long w = d >> 5;
+  const bool writer = (lane & 31u) == 0u && w < row_words;
+  const uint32_t tomb = (writer && del && w < del_words) ? del[w] : 0u;
+  for (uint32_t r = 0; r < n_rows; r++) {
+    bool excluded = !live;
+    if (live)
+      for (uint32_t j = s_begin[r]; j < s_begin[r + 1] && !excluded; j++) excluded = !facet_pass(rec, s_f[j]);
+    const unsigned long long b = __ballot(excluded);
+    if (writer) out[(size_t)r * row_words + w] = (uint32_t)(b >> (lane & 32u)) | tomb;
+  }
+}
+
+size_t ssi_filter_rows_bytes(const ss_filter_rows& rows) { return filter_rows_head(rows.n_rows) + rows.prepared.size() * sizeof(ss_facet_filter); }
+
+int ssi_facet_build_rows(ss_shard* s, const ss_filter_rows& rows, void* d_sets, std::vector<uint8_t>* h_stage, uint32_t* d_rows, uint32_t row_words,
+                         hipStream_t st) {
+  if (!s->d_facets || s->facet_docs < s->bm_n_docs) return SS_ESTATE;
+  if (rows.n_rows == 0) return SS_OK;
+  if (rows.n_rows > 64 || rows.row_begin.size() != rows.n_rows + 1u || (uint64_t)row_words * 32u < s->bm_n_docs) return SS_EINVAL;
+  const uint32_t head = filter_rows_head(rows.n_rows), n_filters = (uint32_t)rows.prepared.size();
+  h_stage->assign(ssi_filter_rows_bytes(rows), 0);
+  memcpy(h_stage->data(), rows.row_begin.data(), rows.row_begin.size() * 4);
+  if (n_filters) memcpy(h_stage->data() + head, rows.prepared.data(), (size_t)n_filters * sizeof(ss_facet_filter));
+  SS_HIP(hipMemcpyAsync(d_sets, h_stage->data(), h_stage->size(), hipMemcpyHostToDevice, st));
+  const uint32_t stage_records = (uint64_t)FR_THREADS * s->facet_record_size <= FR_RECORD_LDS ? 1u : 0u;
+  const size_t lds = h_stage->size() + (stage_records ? (size_t)FR_THREADS * s->facet_record_size : 0);
+  const unsigned grid = (unsigned)(((uint64_t)row_words * 32u + FR_THREADS - 1) / FR_THREADS);
+  facet_filter_rows_kernel<<<grid, FR_THREADS, lds, st>>>(s->d_facets, s->facet_record_size, (unsigned long long)s->bm_n_docs, (const uint32_t*)d_sets,
+                                                          rows.n_rows, n_filters, stage_records, s->n_deleted ? s->d_deleted : nullptr,
+                                                          (uint32_t)s->deleted_words, d_rows, row_words);
+  SS_HIP(hipGetLastError());
+  return SS_OK;
+}
+
+// E[i] &= ~X[row_of[i]]: match sets built under the tombstones alone meet their queries' filters here; d_total[i] = what is left.
+// Xq (may be null): query i's row copied out as ITS exclusion bitmap, the one-per-query layout a batched search reads.
+__global__ __launch_bounds__(256) void match_exclude_rows_kernel(unsigned long long* __restrict__ E, const unsigned long long* __restrict__ X,
+                                                                 const uint32_t* __restrict__ row_of, unsigned long long groups,
+                                                                 unsigned long long* __restrict__ total, unsigned long long* __restrict__ Xq) {
+  const uint32_t i = blockIdx.y;
+  const unsigned long long* x = X + (size_t)row_of[i] * groups;
+  unsigned long long* e = E + (size_t)i * groups;
+  uint32_t n = 0;
+  for (unsigned long long g = (unsigned long long)blockIdx.x * 256u + threadIdx.x; g < groups; g += (unsigned long long)gridDim.x * 256u) {
+    const unsigned long long xg = x[g], v = e[g] & ~xg;
+    e[g] = v;
+    if (Xq) Xq[(size_t)i * groups + g] = xg;
+    n += (uint32_t)__popcll(v);
+  }
+  for (int off = 32; off; off >>= 1) n += __shfl_down(n, off);
+  if ((threadIdx.x & 63u) == 0u && n) atomicAdd(&total[i], (unsigned long long)n);
+}
+int ssi_match_exclude_rows(ss_shard* s, uint32_t nq, unsigned long long* d_E, const unsigned long long* d_X, const uint32_t* d_row_of, uint64_t groups,
+                           unsigned long long* d_total, unsigned long long* d_Xq, hipStream_t st) {
+  (void)s;
+  if (nq == 0 || nq > 64) return SS_EINVAL;
+  SS_HIP(hipMemsetAsync(d_total, 0, (size_t)nq * 8, st));
+  const unsigned gx = (unsigned)std::min<uint64_t>((groups + 1023) / 1024, 64u);  // (a block walks >= 4 words per thread)
+  match_exclude_rows_kernel<<<dim3(std::max(gx, 1u), nq), 256, 0, st>>>(d_E, d_X, d_row_of, groups, d_total, d_Xq);
   SS_HIP(hipGetLastError());
   return SS_OK;
 }

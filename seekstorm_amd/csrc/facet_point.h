@@ -2,13 +2,19 @@
 // (facet.hip; nullptr = the facet's stored bits, as the declarations in ss_common.h behave).
 #pragma once
 #include "ss_common.h"
+#include "filter_rows.h"  // ssi_facet_width and the host's checks of a filter
 
-// bytes a facet of `type` (<= SS_FACET_POINT, checked by the caller) takes in the record; a Point is its 8-byte Morton code.  (The
-// sorts never read a string's id: a string sort field resolves to its u32 rank column, facet_commit.h, or is refused.)  The kernels keep their own device-side tables.
-inline uint32_t ssi_facet_width(uint32_t type) {
-  static const uint8_t width[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 4, 8};
-  return width[type];
-}
+// exclusion ROWS for a batch whose queries each carry their own filter set (filter_rows.h groups the sets; facet.hip).  d_rows
+// [rows.n_rows][row_words] u32: bit set = doc excluded (a failed filter of the row's set, a tombstone, a doc at or beyond the lexical
+// image's); row_words = 2 * n_sub * (BM_SUB / 64), the layout ExclSwap::per_query() consumers read.  d_sets: room for
+// ssi_filter_rows_bytes(rows) bytes, the sets as the kernel reads them -- staged from h_stage, which lives until the stream has passed.
+size_t ssi_filter_rows_bytes(const ss_filter_rows& rows);
+int ssi_facet_build_rows(ss_shard* s, const ss_filter_rows& rows, void* d_sets, std::vector<uint8_t>* h_stage, uint32_t* d_rows, uint32_t row_words,
+                         hipStream_t st);
+// E[i] &= ~X[row_of[i]] over nq match sets of `groups` u64 words, d_total[i] = the docs left (d_row_of: row per query, on the device);
+// d_Xq (may be null) [nq][groups]: every query's row copied out, the one-bitmap-per-query layout of ExclSwap::per_query()
+int ssi_match_exclude_rows(ss_shard* s, uint32_t nq, unsigned long long* d_E, const unsigned long long* d_X, const uint32_t* d_row_of, uint64_t groups,
+                           unsigned long long* d_total, unsigned long long* d_Xq, hipStream_t st);
 
 int ssi_facet_kth(ss_shard* s, const unsigned long long* d_bits, uint64_t n_docs, uint64_t n_matches, uint32_t offset, uint32_t type,
                   bool descending, uint64_t k, unsigned long long* d_hist, uint64_t* value_bits, uint64_t* n_better, uint64_t* n_equal,

@@ -105,11 +105,12 @@ int ss_shard_create(int device, ss_shard** out) {
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return SS_EDEVICE;  // fail loudly: no CPU fallback exists
   if (device < 0 || device >= n) return SS_EINVAL;
   SS_HIP(hipSetDevice(device));
-  ss_shard* s = new (std::nothrow) ss_shard();
+  ss_shard_abi* s = new (std::nothrow) ss_shard_abi();  // (api_internal.h: the shard and the ABI layer's own state behind it)
   if (!s) return SS_ENOMEM;
   s->device = device;
   s->co_lex.max_batch = 1024;
   s->co_vec.max_batch = SS_VEC_BATCH;
+  s->co_fac.max_batch = SS_CO_FACETED_DEFAULT;
   // Lexical batches in flight: ONE, and a second lane while ~96 or more callers seem to be around (adaptive; SS_COALESCE_LANES=1 / 2 force
   // one / two, =autoN moves the threshold).  History: two unconditional lanes halve the batches, and the device's fixed cost per batch is
   // what bounds small ones (round 4: T = 8 54 K -> 25 K q/s; profiles/r4k_lanes.log); opening the lane from ~32 callers on gained 7 % at
@@ -280,7 +281,7 @@ int ss_shard_destroy(ss_shard* s) {
   (void)hipStreamDestroy(s->stream);
   if (s->vev) (void)hipEventDestroy(s->vev);
   if (s->vstream) (void)hipStreamDestroy(s->vstream);
-  delete s;
+  delete static_cast<ss_shard_abi*>(s);
   return SS_OK;
 }
 
@@ -2782,6 +2783,12 @@ int ss_bm25_search_filtered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, ui
   if (nq == 0) return SS_OK;
   // (the crate's offset + length is unbounded, search.rs:1658-1659: a page deeper than SS_MAX_K results is answered in passes)
   if (rt != SS_RT_COUNT && k > SS_MAX_K) return bm25_search_deep(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
+  if (n_filters) {  // concurrent filtered callers share batches, each query under its own filters (api_coalesce.hip)
+    bool submitted = false;
+    const int rc = ssi_co_fac_try(s, SS_CO_FILTERED, nq, q, 0, nullptr, k, rt, n_filters, filters, 0, nullptr, nullptr, nullptr, nullptr, nullptr, out_doc, out_score,
+                                  out_count, out_total, nullptr, &submitted);
+    if (submitted) return rc;
+  }
   if (n_filters == 0 && nq <= SS_COALESCE_MAX_REQUEST && s->co_lex.max_batch) {
     ss_co_req r;
     r.q = q; r.nq = nq; r.k = rt == SS_RT_COUNT ? 0u : k; r.rt = rt;
@@ -3129,6 +3136,23 @@ static bool sorts_fit_records(const ss_shard* s, uint32_t n_sorts, const ss_resu
   return true;
 }
 
+// The exclusion rows of ONE chunk (<= 64 queries) of a batch with a filter set per query: the sets grouped (filter_rows.h), staged and
+// evaluated in one pass over the records (facet.hip facet_filter_rows_kernel), the row of every query uploaded.  The EachChunk is read by
+// asynchronous copies: it lives until the call's synchronisation.
+struct EachChunk {
+  ss_filter_rows rows;
+  std::vector<uint8_t> stage;
+};
+static size_t each_sets_bytes(uint32_t ch) { return (((size_t)ch + 1) * 4 + 15) / 16 * 16 + (size_t)ch * SS_MAX_FACET_FILTERS * sizeof(ss_facet_filter); }
+static int each_chunk_rows(ss_shard* s, uint32_t nb, const uint32_t* filter_begin, const ss_facet_filter* filters, EachChunk* ec, void* d_sets,
+                           uint32_t* d_rows, uint32_t* d_row_of, uint64_t groups) {
+  SS_TRY(ssi_filter_rows(nb, filter_begin, filters, s->facet_record_size, &ec->rows));
+  if (ec->rows.n_slow) return SS_EINVAL;  // (the entry runs those queries alone)
+  SS_TRY(ssi_facet_build_rows(s, ec->rows, d_sets, &ec->stage, d_rows, (uint32_t)(groups * 2), s->stream));
+  SS_HIP(hipMemcpyAsync(d_row_of, ec->rows.row_of.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s->stream));
+  return SS_OK;
+}
+
 // Result sort for a batch (facet.hip: "Result sort for a BATCH, pivots on the device").  The batch runs in chunks of <= 64 queries,
 // every step a grid over the chunk: match sets (one expansion + one bit-record pass) -> per sort field the radix select and the
 // classification -> the exclusion bitmaps -> TWO batched searches, each query inside its own doc set (the pruned kernel's filtered
@@ -3145,7 +3169,7 @@ static bool sort_fused() {
 extern "C++" int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
                                      const ss_sort_sources& src, uint32_t k,
                                      uint32_t n_filters, const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
-                                     uint64_t* out_total, const QueryFacets* qf) {
+                                     uint64_t* out_total, const QueryFacets* qf, const EachSets* each) {
   if (!s->d_post) return SS_ESTATE;
   SS_HIP(hipSetDevice(s->device));
   if (!facet_records_cover(s) || !sorts_fit_records(s, n_sorts, sorts) || (qf && !facets_fit_records(s, *qf))) return SS_ESTATE;
@@ -3160,7 +3184,9 @@ extern "C++" int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const s
                o_os = o_od + al((size_t)nq * k * 4), o_oc = o_os + al((size_t)nq * k * 4), o_ot = o_oc + al((size_t)nq * 4),
                o_sub = o_ot + al((size_t)nq * 8), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
                o_bounds = o_ph + al((size_t)CH * sizeof(ss_bm25_query)), o_cnt = o_bounds + al(qf ? qf->n_bounds * 8 : 0),
-               need = o_cnt + al(qf ? (size_t)nq * qf->stride * 8 : 0);  // (the facets' bounds and counters [nq][stride] behind the sort's own)
+               o_X = o_cnt + al(qf ? (size_t)nq * qf->stride * 8 : 0),  // (the facets' bounds and counters [nq][stride] behind the sort's own)
+               o_sets = o_X + al(each ? (size_t)CH * groups * 8 : 0), o_rowof = o_sets + al(each ? each_sets_bytes(CH) : 0),
+               need = o_rowof + al(each ? (size_t)CH * 4 : 0);  // (`each`: the chunk's exclusion rows, its filter sets and the row of every query)
   SS_TRY(reserve(s, &s->d_sort_ws, &s->sort_ws_cap, need));
   char* W = (char*)s->d_sort_ws;
   uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
@@ -3176,6 +3202,10 @@ extern "C++" int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const s
   SS_TRY(ensure_out(s, 1, k));
   constexpr int batched_off = 0;
   std::vector<MatchChunk> plans((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
+  std::vector<EachChunk> each_plans(each ? plans.size() : 0);  // (likewise)
+  // (`each`: a later chunk's refusal returns while the copies of the chunks before it may still read these vectors -- the stream is
+  // waited for on every way out, before they go)
+  struct SyncOnExit { ss_shard* s; bool on; ~SyncOnExit() { if (on) (void)hipStreamSynchronize(s->stream); } } sync_on_exit{s, each != nullptr};
   for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
     const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
     const ss_bm25_query* qc = queries + c0;
@@ -3186,6 +3216,12 @@ extern "C++" int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const s
     MatchChunk& mc = plans[c0 / CH];
     MatchBatchInfo b;
     SS_TRY(match_prepare(s, nb, qc, &mc, &b));
+    if (each) {  // every query under its own filters: the match sets under the tombstones alone, then each query's exclusion row applied
+      EachChunk& ec = each_plans[c0 / CH];
+      SS_TRY(each_chunk_rows(s, nb, each->filter_begin + c0, each->filters, &ec, W + o_sets, (uint32_t*)(W + o_X), (uint32_t*)(W + o_rowof), groups));
+      SS_TRY(match_enqueue(s, nb, qc, mc, 0, nullptr, false, d_q, (ss_bm25_query*)(W + o_sub), (ss_bm25_query*)(W + o_ph), d_E, d_total));
+      SS_TRY(ssi_match_exclude_rows(s, nb, d_E, (const unsigned long long*)(W + o_X), (const uint32_t*)(W + o_rowof), groups, d_total, nullptr, s->stream));
+    } else
     SS_TRY(match_enqueue(s, nb, qc, mc, n_filters, filters, false, d_q, (ss_bm25_query*)(W + o_sub), (ss_bm25_query*)(W + o_ph), d_E, d_total));
     const bool fused = qf && sort_fused();
     if (fused)
@@ -3228,6 +3264,7 @@ extern "C++" int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const s
   SS_HIP(hipMemcpyAsync(out_total, W + o_ot, (size_t)nq * 8, hipMemcpyDeviceToHost, s->stream));
   if (qf) SS_HIP(hipMemcpyAsync(qf->out_counts, d_counts, (size_t)nq * qf->stride * 8, hipMemcpyDeviceToHost, s->stream));
   SS_HIP(hipStreamSynchronize(s->stream));
+  sync_on_exit.on = false;
   return SS_OK;
 }
 
@@ -3237,6 +3274,12 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
   if (!s || !queries || nq == 0 || !out_doc || !out_score || !out_count || !out_total || k == 0) return SS_EINVAL;
   if (n_sorts == 0) return ss_bm25_search_filtered(s, nq, queries, k, SS_RT_TOPKCOUNT, n_filters, filters, out_doc, out_score, out_count, out_total);
   if (!sorts) return SS_EINVAL;
+  {
+    bool submitted = false;
+    const int rc = ssi_co_fac_try(s, SS_CO_SORTED, nq, queries, n_sorts, sorts, k, SS_RT_TOPKCOUNT, n_filters, filters, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  out_doc, out_score, out_count, out_total, nullptr, &submitted);
+    if (submitted) return rc;
+  }
   if (n_sorts > SS_MAX_SORT_FIELDS) return SS_ENOTSUP;
   for (uint32_t f = 0; f < n_sorts; f++) {
     if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
@@ -3253,7 +3296,9 @@ int ss_bm25_search_sorted(ss_shard* s, uint32_t nq, const ss_bm25_query* queries
 // of the whole batch are enqueued first -- per chunk of <= 64 queries one match-set build (both tiers) and ONE launch that counts every
 // facet of every query (facet.hip: "Facet counts of a BATCH") -- and the search itself runs behind them on the same stream, through
 // ss_bm25_search_filtered's direct path (bm25_search_direct_locked / ssi_bm25_search_deep_locked: that entry's answers, bit for bit; where
-// the lexical coalescer is on, that entry hands an unfiltered request to it -- this one never does, the answers are the same).  The
+// the lexical coalescer is on, that entry hands an unfiltered request to it -- the search in here never goes that way, the answers are
+// the same; the CALL as a whole, like every faceted, filtered or sorted call of <= 16 queries, may share a batch with concurrent callers
+// through the faceted coalescer, ss_shard_set_coalescing_faceted).  The
 // facet filter's bitmap is built once for all of it (`prebuilt`).  Waits: the search waits for its own answers (a deep page once per
 // pass), and by then the counters are done; their copy home into the caller's pageable array and the wait that ends it are the call's
 // second, short one -- the search paths own their waits, and the counters are not theirs to carry.  A workspace that has to grow waits
@@ -3296,6 +3341,12 @@ int ss_bm25_search_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint
                           float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts) {
   if (n_facets == 0) return ss_bm25_search_filtered(s, nq, q, k, rt, n_filters, filters, out_doc, out_score, out_count, out_total);
   if (!s || !q || !out_count || !out_total) return SS_EINVAL;
+  {
+    bool submitted = false;
+    const int rc = ssi_co_fac_try(s, SS_CO_FACETS, nq, q, 0, nullptr, k, rt, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases,
+                                  out_doc, out_score, out_count, out_total, out_facet_counts, &submitted);
+    if (submitted) return rc;
+  }
   QueryFacets qf;
   SS_TRY(query_facets_check(n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, out_facet_counts, &qf));
   if (rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
@@ -3339,6 +3390,12 @@ int ss_bm25_search_sorted_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* 
                                  out_doc, out_score, out_count, out_total, out_facet_counts);
   // the sorted entry's argument checks ...
   if (!s || !queries || nq == 0 || !out_count || !out_total || !sorts) return SS_EINVAL;
+  {
+    bool submitted = false;
+    const int rc = ssi_co_fac_try(s, SS_CO_SORTED_FACETS, nq, queries, n_sorts, sorts, k, rt, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets,
+                                  range_lower_bounds, bases, out_doc, out_score, out_count, out_total, out_facet_counts, &submitted);
+    if (submitted) return rc;
+  }
   if (rt != SS_RT_COUNT && (k == 0 || !out_doc || !out_score)) return SS_EINVAL;
   if (n_sorts > SS_MAX_SORT_FIELDS) return SS_ENOTSUP;
   for (uint32_t f = 0; f < n_sorts; f++)
@@ -3373,6 +3430,210 @@ int ss_bm25_search_sorted_facets(ss_shard* s, uint32_t nq, const ss_bm25_query* 
   // SS_RT_COUNT: no docs, so no select -- the sort fields were checked above and play no further part
   return ss_bm25_search_facets(s, nq, queries, k, rt, n_filters, filters, n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases,
                                out_doc, out_score, out_count, out_total, out_facet_counts);
+}
+
+// ---- A batch whose queries each carry their OWN facet filters (ss_bm25_search_each): concurrent users of one page template share its
+// sorts and its query_facets and differ in their filters.  Per chunk of <= 64 queries ONE pass over the facet records writes an exclusion
+// row per distinct filter set (facet.hip facet_filter_rows_kernel), the match sets are built under the tombstones alone and every query's
+// row is taken off its set (match_exclude_rows_kernel); from there on the chunk is what a call with one filter for all would have made of
+// it.  The sorted half is ssi_bm25_search_sorted_locked with `each`; this is the other half: no sort fields, or SS_RT_COUNT.
+//   SS_RT_TOPKCOUNT  the facets counted on the match sets, ONE batched SS_RT_TOPK search with an exclusion bitmap per query, the totals
+//                    from the match sets -- where the chunk is the pruned kernel's (no phrase, no sparse-tier term, no field filter, no
+//                    all_terms_frequent mark, k <= 128, ...); any other chunk runs its searches query by query through
+//                    ss_bm25_search_filtered's direct path, which builds that query's own bitmap
+//   SS_RT_COUNT      no search at all: the totals are the match sets' sizes
+//   SS_RT_TOPK       every search through the direct path: what that entry leaves in *out_total for SS_RT_TOPK depends on the kernel
+//                    family that answered, and the contract is that entry's answer
+// A chunk whose match sets are refused (SS_ENOTSUP) fails the call when facets are wanted -- ss_bm25_search_facets refuses it as well --
+// and runs query by query when they are not: ss_bm25_search_filtered needs no match set.  One synchronisation per call on the batched route.
+// (Untuned: the batched search reads ONE bitmap per query, so every query's row is copied out beside the rows and the match sets -- three
+// [chunk][groups] arrays in the workspace, 1.25 MB each per query at 10 M docs; a row index in the search kernels' exclusion read would
+// spare the copy.)
+static int bm25_each_unsorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, const EachSets& each, const QueryFacets* qf,
+                                     uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
+  if (!s->d_post) return SS_ESTATE;
+  SS_HIP(hipSetDevice(s->device));
+  const bool any_set = each.filter_begin[nq] != each.filter_begin[0], use_rows = facet_records_cover(s);
+  if ((qf || any_set) && !use_rows) return SS_ESTATE;
+  if (qf && !facets_fit_records(s, *qf)) return SS_ESTATE;
+  const uint32_t kk = rt == SS_RT_COUNT ? 0u : k;
+  auto direct_one = [&](uint32_t i) {  // query i alone, as ss_bm25_search_filtered's direct path answers it
+    const uint32_t f0 = each.filter_begin[i], nf = each.filter_begin[i + 1] - f0;
+    return bm25_search_direct_locked(s, 1, q + i, k, rt, nf, nf ? each.filters + f0 : nullptr, out_doc ? out_doc + (size_t)i * kk : nullptr,
+                                     out_score ? out_score + (size_t)i * kk : nullptr, out_count + i, out_total + i);
+  };
+  if (!use_rows) {  // no facet records, and nothing that asks for them: plain searches
+    for (uint32_t i = 0; i < nq; i++) SS_TRY(direct_one(i));
+    return SS_OK;
+  }
+  const uint64_t groups = (uint64_t)s->bm_n_sub * (BM_SUB / 64);
+  const uint32_t CH = std::min<uint32_t>(nq, 64u);
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_q = 0, o_sub = o_q + al((size_t)CH * sizeof(ss_bm25_query)), o_ph = o_sub + al((size_t)CH * sizeof(ss_bm25_query)),
+               o_tot = o_ph + al((size_t)CH * sizeof(ss_bm25_query)), o_bits = o_tot + al((size_t)CH * 8), o_X = o_bits + al((size_t)CH * groups * 8),
+               o_Xq = o_X + al((size_t)CH * groups * 8), o_sets = o_Xq + al((size_t)CH * groups * 8), o_rowof = o_sets + al(each_sets_bytes(CH)),
+               o_stot = o_rowof + al((size_t)CH * 4), o_bounds = o_stot + al((size_t)CH * 8), o_cnt = o_bounds + al(qf ? qf->n_bounds * 8 : 0),
+               o_od = o_cnt + al(qf ? (size_t)nq * qf->stride * 8 : 0), o_os = o_od + al((size_t)nq * kk * 4), o_oc = o_os + al((size_t)nq * kk * 4),
+               o_ot = o_oc + al((size_t)nq * 4), need = o_ot + al((size_t)nq * 8);
+  SS_TRY(reserve(s, &s->d_facet_ws, &s->facet_ws_cap, need));
+  char* W = (char*)s->d_facet_ws;
+  ss_bm25_query* d_q = (ss_bm25_query*)(W + o_q);
+  unsigned long long *d_total = (unsigned long long*)(W + o_tot), *d_bits = (unsigned long long*)(W + o_bits), *d_counts = (unsigned long long*)(W + o_cnt);
+  uint64_t* d_bounds = (uint64_t*)(W + o_bounds);
+  std::vector<MatchChunk> plans((nq + CH - 1) / CH);  // (staged by asynchronous copies: they live until the call's synchronisation)
+  std::vector<EachChunk> each_plans(plans.size());
+  std::vector<uint8_t> batched(plans.size(), 0);
+  auto run = [&]() -> int {
+    if (qf) {
+      SS_HIP(hipMemsetAsync(d_counts, 0, (size_t)nq * qf->stride * 8, s->stream));
+      if (qf->n_bounds) SS_HIP(hipMemcpyAsync(d_bounds, qf->range_lower_bounds, qf->n_bounds * 8, hipMemcpyHostToDevice, s->stream));
+    }
+    for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
+      const uint32_t nb = std::min<uint32_t>(CH, nq - c0), ci = c0 / CH;
+      const ss_bm25_query* qc = q + c0;
+      MatchChunk& mc = plans[ci];
+      MatchBatchInfo b;
+      // (SS_RT_TOPK without facets: nothing reads a match set)
+      int rp = qf || rt != SS_RT_TOPK ? match_prepare(s, nb, qc, &mc, &b) : SS_ENOTSUP;
+      if (rp == SS_OK && b.gated) rp = SS_ENOTSUP;  // (a union under a field filter: the facet entries refuse it, the search runs it alone)
+      if (rp != SS_OK && (rp != SS_ENOTSUP || qf)) return rp;
+      const bool sets = rp == SS_OK;
+      const bool fast_search = sets && rt == SS_RT_TOPKCOUNT && !mc.tier.any_tiered && !mc.any_phrase() && !b.any_filter && !b.any_frequent;
+      const bool fast_count = sets && rt == SS_RT_COUNT;
+      if (sets && (qf || fast_search || fast_count)) {
+        SS_HIP(hipMemsetAsync(d_total, 0, (size_t)nb * 8, s->stream));
+        SS_HIP(hipMemsetAsync(d_bits, 0, (size_t)nb * groups * 8, s->stream));
+        SS_TRY(each_chunk_rows(s, nb, each.filter_begin + c0, each.filters, &each_plans[ci], W + o_sets, (uint32_t*)(W + o_X), (uint32_t*)(W + o_rowof), groups));
+        SS_TRY(match_enqueue(s, nb, qc, mc, 0, nullptr, false, d_q, (ss_bm25_query*)(W + o_sub), (ss_bm25_query*)(W + o_ph), d_bits, d_total));
+        SS_TRY(ssi_match_exclude_rows(s, nb, d_bits, (const unsigned long long*)(W + o_X), (const uint32_t*)(W + o_rowof), groups, d_total,
+                                      fast_search ? (unsigned long long*)(W + o_Xq) : nullptr, s->stream));
+        if (qf)
+          SS_TRY(ssi_facet_count_multi(s, nb, d_bits, qf->n_facets, qf->facet_offset, qf->facet_type, qf->n_buckets, qf->bases, d_bounds,
+                                       d_counts + (size_t)c0 * qf->stride, s->stream));
+      }
+      bool done = false;
+      if (fast_search) {  // ONE batched search, every query under its own exclusion bitmap
+        ExclSwap sw(s, (uint32_t*)(W + o_Xq), groups * 2);
+        sw.per_query();
+        const int rc = ssi_bm25_search(s, nb, d_q, k, SS_RT_TOPK, (uint32_t*)(W + o_od) + (size_t)c0 * k, (float*)(W + o_os) + (size_t)c0 * k,
+                                       (uint32_t*)(W + o_oc) + c0, (uint64_t*)(W + o_stot), b.has_and, b.has_or, b.nt_max, b.np_max, b.all_probed, s->stream,
+                                       b.any_frequent, false, b.any_filter, b.uniform, b.gated, b.nn_max);
+        if (rc != SS_OK && rc != SS_ENOTSUP) return rc;
+        done = rc == SS_OK;  // (SS_ENOTSUP: not the pruned kernel's batch -- query by query below)
+      } else if (fast_count) {
+        SS_HIP(hipMemsetAsync(W + o_oc + (size_t)c0 * 4, 0, (size_t)nb * 4, s->stream));
+        done = true;
+      }
+      if (done) SS_HIP(hipMemcpyAsync(W + o_ot + (size_t)c0 * 8, d_total, (size_t)nb * 8, hipMemcpyDeviceToDevice, s->stream));
+      else
+        for (uint32_t i = 0; i < nb; i++) SS_TRY(direct_one(c0 + i));
+      batched[ci] = done ? 1 : 0;
+    }
+    for (uint32_t c0 = 0; c0 < nq; c0 += CH) {
+      if (!batched[c0 / CH]) continue;
+      const uint32_t nb = std::min<uint32_t>(CH, nq - c0);
+      if (kk) {
+        SS_HIP(hipMemcpyAsync(out_doc + (size_t)c0 * kk, W + o_od + (size_t)c0 * kk * 4, (size_t)nb * kk * 4, hipMemcpyDeviceToHost, s->stream));
+        SS_HIP(hipMemcpyAsync(out_score + (size_t)c0 * kk, W + o_os + (size_t)c0 * kk * 4, (size_t)nb * kk * 4, hipMemcpyDeviceToHost, s->stream));
+      }
+      SS_HIP(hipMemcpyAsync(out_count + c0, W + o_oc + (size_t)c0 * 4, (size_t)nb * 4, hipMemcpyDeviceToHost, s->stream));
+      SS_HIP(hipMemcpyAsync(out_total + c0, W + o_ot + (size_t)c0 * 8, (size_t)nb * 8, hipMemcpyDeviceToHost, s->stream));
+    }
+    if (qf) SS_HIP(hipMemcpyAsync(qf->out_counts, d_counts, (size_t)nq * qf->stride * 8, hipMemcpyDeviceToHost, s->stream));
+    return SS_OK;
+  };
+  int rc = run();
+  if (hipStreamSynchronize(s->stream) != hipSuccess && rc == SS_OK) rc = SS_EDEVICE;  // (also on an error: the plans and the caller's arrays are being read)
+  return rc;
+}
+
+int ss_bm25_search_each(ss_shard* s, uint32_t nq, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts, uint32_t k, uint32_t rt,
+                        const uint32_t* filter_begin, const ss_facet_filter* filters, uint32_t n_facets, const uint32_t* facet_offset,
+                        const uint32_t* facet_type, const uint32_t* n_buckets, const uint64_t* range_lower_bounds, const ss_facet_point* bases,
+                        uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts) {
+  // the checks of ss_bm25_search_sorted_facets, in its order
+  if (rt > SS_RT_TOPKCOUNT) return SS_EINVAL;
+  if (!s || !queries || !out_count || !out_total || !filter_begin) return SS_EINVAL;
+  if (n_sorts && (nq == 0 || !sorts)) return SS_EINVAL;
+  if (rt != SS_RT_COUNT && (k == 0 || !out_doc || !out_score)) return SS_EINVAL;
+  if (n_sorts > SS_MAX_SORT_FIELDS) return SS_ENOTSUP;
+  for (uint32_t f = 0; f < n_sorts; f++)
+    if (sorts[f].facet_type > SS_FACET_POINT) return SS_EINVAL;
+  QueryFacets qf;
+  SS_TRY(query_facets_check(n_facets, facet_offset, facet_type, n_buckets, range_lower_bounds, bases, out_facet_counts, &qf));
+  for (uint32_t i = 0; i < nq; i++) {
+    if (filter_begin[i + 1] < filter_begin[i] || filter_begin[i + 1] - filter_begin[i] > SS_MAX_FACET_FILTERS) return SS_EINVAL;
+    if (filter_begin[i + 1] > filter_begin[i] && !filters) return SS_EINVAL;
+  }
+  if (!s->d_post) return SS_ESTATE;
+  if (nq == 0) return SS_OK;
+  const uint32_t kk = rt == SS_RT_COUNT ? 0u : k;
+  // who runs alone through the single-filter entry: everybody on a deep page, else the queries with an SS_FACET_IDS_EXTERN filter
+  const bool deep = rt != SS_RT_COUNT && k > SS_MAX_K;
+  std::vector<uint8_t> slow(nq, deep ? 1 : 0);
+  uint32_t n_slow = deep ? nq : 0;
+  if (!deep)
+    for (uint32_t i = 0; i < nq; i++) {
+      for (uint32_t j = filter_begin[i]; j < filter_begin[i + 1] && !slow[i]; j++) slow[i] = ssi_filter_is_extern(filters[j]) ? 1 : 0;
+      n_slow += slow[i];
+    }
+  if (n_slow < nq) {
+    const uint32_t n = nq - n_slow;
+    // the batched queries back to back (all of them, as a rule: then the caller's arrays serve as they are)
+    std::vector<ss_bm25_query> cq;
+    std::vector<uint32_t> cb, at, c_doc, c_cnt;
+    std::vector<ss_facet_filter> cf;
+    std::vector<float> c_score;
+    std::vector<uint64_t> c_tot, c_fc;
+    if (n_slow) {
+      cb.push_back(0);
+      for (uint32_t i = 0; i < nq; i++) {
+        if (slow[i]) continue;
+        at.push_back(i);
+        cq.push_back(queries[i]);
+        cf.insert(cf.end(), filters + filter_begin[i], filters + filter_begin[i + 1]);
+        cb.push_back((uint32_t)cf.size());
+      }
+      c_doc.resize((size_t)n * kk); c_score.resize((size_t)n * kk); c_cnt.resize(n); c_tot.resize(n); c_fc.resize((size_t)n * qf.stride);
+    }
+    const ss_bm25_query* q_ = n_slow ? cq.data() : queries;
+    const EachSets es{n_slow ? cb.data() : filter_begin, n_slow ? cf.data() : filters};
+    uint32_t* o_doc = n_slow ? c_doc.data() : out_doc;
+    float* o_score = n_slow ? c_score.data() : out_score;
+    uint32_t* o_cnt = n_slow ? c_cnt.data() : out_count;
+    uint64_t* o_tot = n_slow ? c_tot.data() : out_total;
+    QueryFacets qf_ = qf;
+    if (n_slow) qf_.out_counts = c_fc.data();
+    {
+      ShardLock g(s);  // (before the image is looked at: a commit swaps its arrays under this lock)
+      if (!s->d_post) return SS_ESTATE;
+      ss_sort_sources src;
+      if (n_sorts) SS_TRY(ssi_sort_resolve(s, n_sorts, sorts, &src));  // SS_ENOTSUP: a string field without a rank table
+      if (n_sorts && rt != SS_RT_COUNT)
+        SS_TRY(ssi_bm25_search_sorted_locked(s, n, q_, n_sorts, sorts, src, k, 0, nullptr, o_doc, o_score, o_cnt, o_tot, n_facets ? &qf_ : nullptr, &es));
+      else
+        SS_TRY(bm25_each_unsorted_locked(s, n, q_, k, rt, es, n_facets ? &qf_ : nullptr, o_doc, o_score, o_cnt, o_tot));
+    }
+    for (uint32_t j = 0; j < (n_slow ? n : 0u); j++) {
+      const uint32_t i = at[j];
+      if (kk) {
+        memcpy(out_doc + (size_t)i * kk, c_doc.data() + (size_t)j * kk, (size_t)kk * 4);
+        memcpy(out_score + (size_t)i * kk, c_score.data() + (size_t)j * kk, (size_t)kk * 4);
+      }
+      out_count[i] = c_cnt[j];
+      out_total[i] = c_tot[j];
+      if (n_facets) memcpy(out_facet_counts + (size_t)i * qf.stride, c_fc.data() + (size_t)j * qf.stride, qf.stride * 8);
+    }
+  }
+  for (uint32_t i = 0; i < nq; i++) {
+    if (!slow[i]) continue;
+    const uint32_t nf = filter_begin[i + 1] - filter_begin[i];
+    SS_TRY(ss_bm25_search_sorted_facets(s, 1, queries + i, n_sorts, sorts, k, rt, nf, nf ? filters + filter_begin[i] : nullptr, n_facets, facet_offset, facet_type,
+                                        n_buckets, range_lower_bounds, bases, out_doc ? out_doc + (size_t)i * kk : nullptr,
+                                        out_score ? out_score + (size_t)i * kk : nullptr, out_count + i, out_total + i,
+                                        n_facets ? out_facet_counts + (size_t)i * qf.stride : nullptr));
+  }
+  return SS_OK;
 }
 
 // The empty query of a shard (browse.hip; search_iterator_shard, iterator.rs:316-358).  Everything runs on s->stream: the match set of

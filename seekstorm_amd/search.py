@@ -1396,6 +1396,49 @@ class Shard:
             at += int(b) + 1
         return doc, score, cnt, tot, per
 
+    def search_lexical_each(self, queries, k, result_type, facet_filters_per_query, result_sort=None, query_facets=None):
+        """a batch whose queries each carry their OWN facet filters (ss_bm25_search_each): facet_filters_per_query[i] = the facet_filter
+        list of query i (None or [] = none), result_sort and query_facets are the batch's.  Query i gets exactly what
+        search_lexical_sorted_facets(queries[i:i + 1], ..., facet_filter=facet_filters_per_query[i]) returns -- so search_lexical_facets'
+        answer without result_sort, search_lexical_sorted_batch's / search_lexical_batch's without query_facets.
+        -> (doc, score, count, total, counts_per_facet)"""
+        n, arr = self._result_sorts(list(result_sort or []))
+        q = np.ascontiguousarray(queries)
+        query_facets = list(query_facets or [])
+        nq, nf_ = len(q), len(query_facets)
+        if len(facet_filters_per_query) != nq:
+            raise ValueError("one facet filter list per query")
+        flat, begin = [], [0]
+        for fl in facet_filters_per_query:
+            flat += list(fl or [])
+            begin.append(len(flat))
+        return self.search_lexical_each_raw(q, k, result_type, np.array(begin, np.uint32), flat, n, arr, query_facets)
+
+    def search_lexical_each_raw(self, q, k, result_type, filter_begin, flat_filters, n_sorts, sort_arr, query_facets):
+        """search_lexical_each with filter_begin as given (the C entry judges it)"""
+        nq, nf_ = len(q), len(query_facets)
+        kk = max(int(k), 1)
+        doc = np.full((nq, kk), N.SS_NO_DOC, np.uint32)
+        score = np.zeros((nq, kk), np.float32)
+        cnt = np.zeros(nq, np.uint32)
+        tot = np.zeros(nq, np.uint64)
+        off = ty = nb = allb = bases = out = None
+        if nf_:
+            off, ty, nb, allb, bases, stride = self._query_facet_args(query_facets)
+            out = np.zeros((nq, stride), np.uint64)
+        farr = self.facet_filters(flat_filters)[0] if flat_filters else None
+        fb = np.ascontiguousarray(filter_begin, np.uint32)
+        N.check(N.lib().ss_bm25_search_each(self._h, nq, q.ctypes.data_as(C.c_void_p), n_sorts, C.cast(sort_arr, C.c_void_p) if n_sorts else None, int(k),
+                                            int(result_type), N.ptr(fb, N.u32p), None if farr is None else C.cast(farr, C.c_void_p), nf_,
+                                            N.ptr(off, N.u32p), N.ptr(ty, N.u32p), N.ptr(nb, N.u32p), N.ptr(allb, N.u64p),
+                                            None if bases is None else C.cast(bases, C.c_void_p), N.ptr(doc, N.u32p), N.ptr(score, N.f32p),
+                                            N.ptr(cnt, N.u32p), N.ptr(tot, N.u64p), N.ptr(out, N.u64p)), "ss_bm25_search_each")
+        per, at = [], 0
+        for b in (nb if nf_ else []):
+            per.append(out[:, at:at + int(b) + 1])
+            at += int(b) + 1
+        return doc, score, cnt, tot, per
+
     def search_vector_batch(self, query_vectors, k, similarity_threshold=None, ann_mode=None, with_clusters=False,
                             field_filter=None, with_observed=False):
         """with_observed: -> (..., observed_cluster_count, observed_vector_count) per query (vector.rs:421, 1394, 1510)"""
@@ -1628,6 +1671,18 @@ class Shard:
         (ss_shard_set_coalescing; on by default, a batch size of 0 switches a kind off)"""
         N.check(N.lib().ss_shard_set_coalescing(self._h, int(max_lexical_batch), int(max_vector_batch), int(max_wait_us)),
                 "ss_shard_set_coalescing")
+
+    def set_coalescing_faceted(self, max_batch=64, max_wait_us=0):
+        """concurrent faceted, filtered and sorted searches of this shard (search_lexical_facets, search_lexical_sorted[_batch],
+        search_lexical_sorted_facets, search_lexical_batch with a facet_filter; at most 16 queries a call) share device batches of at most
+        64 queries, every query under its own caller's filters (ss_shard_set_coalescing_faceted); max_batch = 0 switches the kind off"""
+        N.check(N.lib().ss_shard_set_coalescing_faceted(self._h, int(max_batch), int(max_wait_us)), "ss_shard_set_coalescing_faceted")
+
+    def coalescing_stats_faceted(self):
+        """(batches, queries) served through the faceted kind of the coalescer so far"""
+        b, q = C.c_uint64(), C.c_uint64()
+        N.check(N.lib().ss_shard_coalescing_stats_faceted(self._h, C.byref(b), C.byref(q)), "ss_shard_coalescing_stats_faceted")
+        return int(b.value), int(q.value)
 
     def generic_batches(self):
         """sub-batches the generic galloping kernels answered (ss_bm25_shape_stats): shapes beyond the specialised kernels"""
