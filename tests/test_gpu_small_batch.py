@@ -6,6 +6,8 @@ agree with the CPU oracle -- unions / intersections of 1..4 terms, NOT terms, to
 import numpy as np
 import pytest
 
+from test_gpu_sparse_tier import _check_ids  # no doc twice, every doc a match, the id sets above the k-th score's tie band equal
+
 pytestmark = pytest.mark.gpu
 
 
@@ -135,6 +137,7 @@ def test_batches_outside_the_shape_take_the_staged_pipeline(S, O, world):
                 assert int(t[i]) == otot
             else:
                 assert int(c[i]) == len(od) and np.allclose(s[i][:c[i]], os_, rtol=1e-4)
+                _check_ids(osh, d[i], s[i], od, os_, otot, lists[i], O.OP_OR, (), (k, rt, i))
     # a call split by shape: 200 queries, every fifth one of 5 terms (staged), the others by launches of 64 -- answers in the callers' order
     lists = _queries(rng, 200, 3)[0]
     for j in range(0, 200, 5):
@@ -146,6 +149,7 @@ def test_batches_outside_the_shape_take_the_staged_pipeline(S, O, world):
     for i in list(range(0, 12)) + [63, 64, 65, 128, 198, 199]:
         od, os_, otot = osh.search_exhaustive(lists[i], O.OP_OR, 10)
         assert int(t[i]) == otot and int(c[i]) == len(od) and np.allclose(s[i][:c[i]], os_, rtol=1e-4), i
+        _check_ids(osh, d[i], s[i], od, os_, otot, lists[i], O.OP_OR, (), ("split by shape", i))
     # an invalid query keeps its error code on this path too (term id out of range)
     from seekstorm_amd import _native as N
     q = sh.make_queries([[0, 1]], S.QueryType.Union)
@@ -157,6 +161,7 @@ def test_batches_outside_the_shape_take_the_staged_pipeline(S, O, world):
     d, s, c, t = sh.search_lexical_batch(q, 10, S.ResultType.TopkCount, reference_shortcuts=False)
     od, os_, otot = osh.search_exhaustive([0, 1, 2], O.OP_OR, 10)
     assert int(t[0]) == otot and np.allclose(s[0][:c[0]], os_, rtol=1e-4)
+    _check_ids(osh, d[0], s[0], od, os_, otot, [0, 1, 2], O.OP_OR, (), "after an invalid query")
 
 
 def test_threshold_seeds_never_cost_a_result(S, O):
@@ -196,6 +201,8 @@ def test_threshold_seeds_never_cost_a_result(S, O):
                 assert int(seeded[3][i]) == int(exh[3][i]) == int(staged[3][i])
                 od, os_, otot = osh.search_exhaustive(tl, O.OP_OR, k)
                 assert c == len(od) and np.allclose(seeded[1][i][:c], os_, rtol=1e-4) and int(seeded[3][i]) == otot
+                for name, got in (("seeded", seeded), ("staged", staged), ("exhaustive", exh)):
+                    _check_ids(osh, got[0][i], got[1][i], od, os_, otot, tl, O.OP_OR, (), (name, k, tl))
     finally:
         sh.close()
 
@@ -307,6 +314,7 @@ def test_one_launch_on_a_tiered_image(S, O):
         for deleted in (False, True):
             sh.set_deleted(gone if deleted else [])
             osh.set_deleted([int(x) for x in gone] if deleted else [])
+            seen = {}  # (the queries' match sets under these tombstones, for _check_ids)
             for qt, oop in ((S.QueryType.Union, O.OP_OR), (S.QueryType.Intersection, O.OP_AND)):
                 shapes = [(1, 1, 1, 0, 0), (1, 3, 1, 0, 0), (7, 2, 1, 0, 0), (64, 3, 1, 0, 0), (33, 4, 2, 0, 0), (5, 4, 4, 0, 0), (16, 3, 2, 2, 0), (9, 2, 2, 1, 0)]
                 if qt == S.QueryType.Intersection:
@@ -333,6 +341,8 @@ def test_one_launch_on_a_tiered_image(S, O):
                                     assert int(got[3][i]) == otot, (qt, lists[i], nots[i], int(got[3][i]), otot)
                                 if c < k:
                                     assert set(got[0][i][:c].tolist()) == set(od.tolist())
+                                _check_ids(osh, got[0][i], got[1][i], od, os_, otot, lists[i], oop if len(lists[i]) > 1 else O.OP_OR, nots[i],
+                                           (qt, lists[i], nots[i], k, rt, deleted), seen)
         # outside the shape: a union with a SPARSE NOT term, k = 33 -- answered by the staged pipeline
         sh.set_deleted([]); osh.set_deleted([])
         for lists, nots, k in (([[0, 1]], [[nd + 2]], 10), ([[0, nd]], [[]], 33)):
@@ -341,6 +351,7 @@ def test_one_launch_on_a_tiered_image(S, O):
             assert sh.one_launch_batches() == before
             od, os_, otot = osh.search_exhaustive(lists[0], O.OP_OR, k, not_terms=nots[0])
             assert int(t[0]) == otot and int(c[0]) == len(od) and np.allclose(s_[0][:c[0]], os_, rtol=1e-4)
+            _check_ids(osh, d[0], s_[0], od, os_, otot, lists[0], O.OP_OR, nots[0], ("outside the shape", lists, nots, k))
     finally:
         sh.close()
 

@@ -132,6 +132,27 @@ def _tiered_shard(S, O, n_docs=150_000, seed=21):
     return sh, osh, nd, len(sp_n), hot, n_docs
 
 
+def _check_ids(osh, doc, score, od, os_, otot, terms, op, nots, what, cache=None):
+    """the doc ids of an answer whose count and scores agree with the oracle's top-k (od, os_): no doc twice, every doc a match of the
+    query, the id sets above the k-th score's tie band equal (the band as _check_topk has it).  cache: the match sets of the queries
+    seen so far, for a caller that asks again under the same tombstones"""
+    n = len(od)
+    d, s = doc[:n], score[:n]
+    assert len(set(map(int, d))) == n, ("a doc twice", what)
+    key = (tuple(terms), op, tuple(nots))
+    if cache is None or key not in cache:
+        matches = osh.search_exhaustive(terms, op, max(int(otot), 1), not_terms=nots)[0]
+        if cache is not None:
+            cache[key] = matches
+    else:
+        matches = cache[key]
+    assert len(matches) == otot and np.isin(d, matches).all(), ("a doc that does not match", what, [int(x) for x in d[~np.isin(d, matches)]])
+    if n:
+        band = abs(float(os_[-1])) * REL
+        clear = lambda dd, ss: {int(x) for x, y in zip(dd, ss) if y > os_[-1] + 2 * band}
+        assert clear(d, s) <= {int(x) for x in od} and clear(od, os_) <= {int(x) for x in d}, ("docs above the tie band differ", what)
+
+
 def _check_against(osh, O, S, out, cases, op, k, rt):
     d, s_, c, t = out
     for i, (terms, nots) in enumerate(cases):
@@ -143,6 +164,7 @@ def _check_against(osh, O, S, out, cases, op, k, rt):
         assert np.allclose(s_[i, :c[i]], os_, rtol=1e-4), (op, k, i, terms, nots)
         if len(od) < k:
             assert set(d[i, :c[i]].tolist()) == set(int(x) for x in od)
+        _check_ids(osh, d[i], s_[i], od, os_, otot, terms, op, nots, (op, k, i, terms, nots))
 
 
 def _same_answers(a, b):
@@ -185,6 +207,7 @@ def test_sparse_tier_queries_against_the_oracle(S, O):
         terms = [int(x) for x in rng.choice(nt_all, n, replace=False)]
         cases.append((terms, []))
     cases += [([nd + 3, nd + 4], []), ([nd + 5], []), ([0, nd], []), ([nd + 9, 4, 3], [2]), ([nd + 4, nd + 5, 1], [0])]
+    seen = {}  # (the queries' match sets, for _check_ids)
     for op, qt in ((O.OP_OR, S.QueryType.Union), (O.OP_AND, S.QueryType.Intersection)):
         tl = [c[0] for c in cases]
         nl = [c[1] for c in cases]
@@ -201,11 +224,13 @@ def test_sparse_tier_queries_against_the_oracle(S, O):
                     assert np.allclose(s_[i, :c[i]], os_, rtol=1e-4), (op, k, i, terms)
                     if len(od) < k:
                         assert set(d[i, :c[i]].tolist()) == set(int(x) for x in od)
+                    _check_ids(osh, d[i], s_[i], od, os_, otot, terms, op, nots, (op, k, i, terms, nots), seen)
     # a sparse NOT list inside an intersection (in a union: tests/test_gpu_round4.py)
     q = sh.make_queries([[3, nd + 8]], S.QueryType.Intersection, [[nd + 4]])
     d, s_, c, t = sh.search_lexical_batch(q, 10, reference_shortcuts=False)
     od, os_, otot = osh.search_exhaustive([3, nd + 8], O.OP_AND, 10, not_terms=[nd + 4])
-    assert int(t[0]) == otot and np.allclose(s_[0, :c[0]], os_, rtol=1e-4)
+    assert int(t[0]) == otot and c[0] == len(od) and np.allclose(s_[0, :c[0]], os_, rtol=1e-4)
+    _check_ids(osh, d[0], s_[0], od, os_, otot, [3, nd + 8], O.OP_AND, [nd + 4], "a sparse NOT list inside an intersection")
     # tombstones: neither counted nor ranked, in either part
     gone = [int(x) for x in hot[::3]]
     sh.set_deleted(gone)
@@ -217,6 +242,8 @@ def test_sparse_tier_queries_against_the_oracle(S, O):
         assert c[i] == len(od) and np.allclose(s_[i, :c[i]], os_, rtol=1e-4)
         if op == O.OP_AND or True:
             assert int(t[i]) == otot, (i, int(t[i]), otot)
+        _check_ids(osh, d[i], s_[i], od, os_, otot, terms, op, [], ("tombstones", i, terms))
+        assert not np.isin(d[i, :c[i]], gone).any()
     sh.close()
 
 
@@ -269,8 +296,9 @@ def test_sparse_tier_not_terms_in_unions_large_k_and_facet_filters(S, O):
                         if rt != S.ResultType.Topk:
                             _check_against(osh, O, S, out, [(terms, nots)], O.OP_OR, k, rt)
                         else:
-                            od, os_, _ = osh.search_exhaustive(terms, O.OP_OR, k, not_terms=nots)
+                            od, os_, otot = osh.search_exhaustive(terms, O.OP_OR, k, not_terms=nots)
                             assert out[2][0] == len(od) and np.allclose(out[1][0, :len(od)], os_, rtol=1e-4)
+                            _check_ids(osh, out[0][0], out[1][0], od, os_, otot, terms, O.OP_OR, nots, ("Topk", strat, k, terms, nots))
                     mixed = [([0, 1, 2], []), cases[0], ([nd + 4, 3], []), cases[2], ([4], [2]), cases[3], ([1, nd + 6], [3])]
                     if rt != S.ResultType.Topk:
                         out = sh.search_lexical_batch(sh.make_queries([c[0] for c in mixed], U, [c[1] for c in mixed]), k, rt, reference_shortcuts=False)
