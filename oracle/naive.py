@@ -170,6 +170,60 @@ def bm25_exact(n_docs, doclen_bytes, postings, op_and, not_docs=(), deleted=(), 
     return ids, sc[ids]
 
 
+def _bm25f_core(n_docs, doclen_fields, boost, entries, op_and, not_docs, deleted, field_filter):
+    dlf = np.asarray(doclen_fields, np.uint8).reshape(-1, n_docs)
+    n_fields = dlf.shape[0]
+    b = np.ones(n_fields, np.float32) if boost is None else np.asarray(boost, np.float32)
+    psum = int(DLC[dlf].astype(np.uint64).sum())  # positions_sum over ALL fields: one avgdl, one component cache
+    comp = component_cache(np.float32(psum) / np.float32(n_docs))
+    listed = np.zeros(n_fields, bool)
+    listed[[int(f) for f in field_filter]] = True
+    assert not listed.any() or op_and or len(entries) == 1, "field filter: intersections and single-term queries"
+    sc = np.zeros(n_docs, np.float64)
+    cnt = np.zeros(n_docs, np.int32)
+    low = np.zeros(n_docs, bool)  # some term's tf in the LOWEST field that holds the doc is < 10
+    for docs, fields, tfs in entries:
+        docs, fields = np.asarray(docs, np.int64), np.asarray(fields, np.int64)
+        assert np.all((docs[1:] > docs[:-1]) | ((docs[1:] == docs[:-1]) & (fields[1:] > fields[:-1]))), "entries sorted by (doc, field)"
+        first = np.ones(len(docs), bool)
+        first[1:] = docs[1:] != docs[:-1]
+        w_idf = np.float64(idf(n_docs, int(first.sum())))  # the docs that hold the term in ANY field
+        tf = np.asarray(tfs).astype(np.float32)
+        w = ((tf * (K + np.float32(1.0))) / (tf + comp[dlf[fields, docs]])).astype(np.float32)
+        np.add.at(sc, docs, b[fields].astype(np.float64) * w_idf * w.astype(np.float64))
+        low[docs[first & (tf < np.float32(10.0))]] = True
+        cnt[np.unique(docs[listed[fields]]) if listed.any() else docs[first]] += 1
+    m = (cnt == len(entries)) if op_and else (cnt > 0)
+    for d in not_docs:
+        m[np.asarray(d, np.int64)] = False
+    if len(deleted):
+        m[np.asarray(deleted, np.int64)] = False
+    return m, sc, low
+
+
+def bm25f_exact(n_docs, doclen_fields, boost, entries, op_and, not_docs=(), deleted=(), field_filter=()):
+    """bm25_exact over several indexed fields (BM25F, add_result.rs:1171-1426; ss_oracle.c fields_core restated): every match,
+    score = sum over the query's (term, field) entries of the doc of  boost[f] * idf * tf (K + 1) / (tf + comp[len byte(doc, f)])
+    -- f32 boost, f32 idf from the docs that hold the term in ANY field, f32 weight under the ONE component cache of the avgdl over
+    all fields (commit.rs:318-325), their product and the sum in float64.  An intersection asks for every term in some field.
+    doclen_fields: [n_fields][n_docs] length bytes; boost: [n_fields] or None (all 1); entries: (docs, fields, tfs) per query term,
+    sorted by (doc, field); not_docs: doc arrays of the NOT terms (any field); deleted: tombstones; field_filter: field ids -- a doc
+    is dropped unless EVERY term it is matched on stands in a listed field, the score still sums all fields (add_result.rs:3124-3136;
+    intersections and single terms).  -> (doc ids ascending, float64 scores); len(ids) = result_count_total."""
+    m, sc, _ = _bm25f_core(n_docs, doclen_fields, boost, entries, op_and, not_docs, deleted, field_filter)
+    ids = np.nonzero(m)[0].astype(np.uint32)
+    return ids, sc[ids]
+
+
+def bm25f_shortcut_exact(n_docs, doclen_fields, boost, entries, deleted=()):
+    """An intersection under all_terms_frequent over several indexed fields (add_result.rs:1595-1607, 3111-3122; ss_oracle.c
+    so_search_fields_shortcut): every match is counted, a doc is RANKED only if for every term the tf in the lowest field that holds
+    the doc is >= 10.  No NOT terms, no field filter (3116).  -> (ranked doc ids ascending, their float64 scores, result_count_total)"""
+    m, sc, low = _bm25f_core(n_docs, doclen_fields, boost, entries, True, (), deleted, ())
+    ids = np.nonzero(m & ~low)[0].astype(np.uint32)
+    return ids, sc[ids], int(m.sum())
+
+
 def topk_exact(ids, scores, k):
     """top-k of bm25_exact's answer by (score desc, doc asc)"""
     order = np.lexsort((ids, -np.asarray(scores, np.float64)))[:k]

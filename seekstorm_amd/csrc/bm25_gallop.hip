@@ -14,7 +14,9 @@
 // postings); a lane owns one driver posting.  A dense driver is walked by posting INDEX (shares are equal whatever the doc
 // distribution); the posting's sub-block is found in the term's directory row by binary search.
 // Scores: the fma chain in query-term order over the same 19-bit weight codes every other kernel reads -- bit-identical to the
-// specialised kernels where both can answer (tests/test_gpu_shape_sweep.py compares them).  HBM-latency bound (dependent loads),
+// specialised kernels where both can answer (tests/test_gpu_fields_edges.py compares them row for row: phrases at k = 128 | 129 and on
+// a shard without probe rows, all_terms_frequent intersections of 7 | 8 terms; the same file checks every answer doc for doc against
+// naive.bm25f_exact, tests/test_gpu_shape_sweep.py against the C oracle within a tolerance).  HBM-latency bound (dependent loads),
 // which is what rare shapes may cost: 1023 sub-queries of a 10-term filtered union run as ONE launch of this kernel.
 #include <algorithm>
 

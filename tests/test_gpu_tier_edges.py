@@ -27,8 +27,9 @@ SM_H_QUERIES, not 64) hands every query that fits to the one-launch kernel -- fo
 scored terms, no sparse NOT term in a union -- so the staged pipeline with seeds is reached by repeating the set beyond 256 queries
 (k <= 32), by any call at k > 32 and under the exhaustive strategy.  A 9- or 12-term intersection with a sparse term is NOT the generic
 galloping kernel's on an image with one indexed field (bm25_shape_of sends there only filtered / per-field / all_terms_frequent
-shapes): the sparse kernel drives it, generic_batches() stays.  NOT COVERED here: bm25_gallop.hip with a sparse driver -- it needs an
-image with several indexed fields (a field filter, or no merged lists), for which naive has no reference."""
+shapes): the sparse kernel drives it, generic_batches() stays.  Images with several indexed fields -- bm25_gallop.hip over per-field
+lists, and filtered queries naming a sparse term (the gate of bm25_sparse.hip) -- are tests/test_gpu_fields_edges.py's, against
+naive.bm25f_exact."""
 import types
 
 import numpy as np

@@ -919,3 +919,110 @@ def test_merge_exact_agrees_with_the_oracle_merge(seed):
             assert d.tolist() == od.tolist() and _bits(s_) == _bits(os_) and src.tolist() == osrc.tolist(), (seed, trial, mode)
             t = [(0 if lx is None else lx[2], 0 if vx is None else vx[2]) for lx, vx in lists]
             assert tot == sum(max(a, b) if mode == 2 else (a if mode == 0 else b) for a, b in t)
+
+
+# ---- naive.bm25f_exact: the exact reference of images with several indexed fields
+def _fields_world(seed, n_fields, n_docs=6000, tf_p=0.5):
+    """random entries (doc, field, tf) sorted by (doc, field) per term; two lists of df >= N / 2 (the shortcut's condition) first"""
+    rng = np.random.default_rng(seed)
+    dlf = np.array([[naive.int_to_byte4(int(x)) for x in rng.integers(4, 400, n_docs)] for _ in range(n_fields)], np.uint8)
+    boost = np.array([2.0, 1.0, 0.5][:n_fields], np.float32)
+    offs, D, F, T = [0], [], [], []
+    for df in (0.7, 0.55, 0.3, 0.05, 0.01, 0.002):
+        for d in np.sort(rng.choice(n_docs, int(df * n_docs), replace=False)):
+            for f in np.sort(rng.choice(n_fields, int(rng.integers(1, n_fields + 1)), replace=False)):
+                D.append(int(d)); F.append(int(f)); T.append(int(min(rng.geometric(tf_p), 500)))
+        offs.append(len(D))
+    return n_docs, dlf, boost, np.array(offs, np.uint64), np.array(D, np.uint32), np.array(F, np.uint8), np.array(T, np.uint16)
+
+
+def _entries(offs, D, F, T, t):
+    a, b = int(offs[t]), int(offs[t + 1])
+    return D[a:b], F[a:b], T[a:b]
+
+
+@pytest.mark.parametrize("seed,n_fields", [(11, 2), (12, 3)])
+def test_naive_bm25f_exact_agrees_with_the_oracle(seed, n_fields):
+    """naive.bm25f_exact (f32 factors, float64 products and sum) against so_search_fields_exhaustive / _filtered with k = n_docs: the
+    same match set, every score within REL (the project's bound) -- unions and intersections, NOT terms, tombstones, a field filter"""
+    from test_gpu_score_edges import REL
+    n, dlf, boost, offs, D, F, T = _fields_world(seed, n_fields)
+    gone = np.sort(np.random.default_rng(seed + 100).choice(n, 200, replace=False))
+    filters = [(), (0,), (1,)] + ([(1, 2)] if n_fields == 3 else [])
+    checked = dropped = 0
+    for dele in ((), gone):
+        for terms, nots in (([0], []), ([3], [2]), ([0, 1], []), ([0, 2, 3], [4]), ([1, 2], [3, 5]), ([2, 3, 4, 5], []), ([0, 1, 2], [])):
+            for op in (O.OP_OR, O.OP_AND):
+                for ff in filters:
+                    if ff and op == O.OP_OR and len(terms) > 1:
+                        continue  # (a filtered union of several terms is not a function of the doc alone: neither restatement models it)
+                    ids, sc = naive.bm25f_exact(n, dlf, boost, [_entries(offs, D, F, T, t) for t in terms], op == O.OP_AND,
+                                                not_docs=[_entries(offs, D, F, T, t)[0] for t in nots], deleted=dele, field_filter=ff)
+                    od, os_, otot, _ = O.search_fields_exhaustive(n, dlf, boost, offs, D, F, T, terms, op, n, not_terms=nots, deleted=dele,
+                                                                  field_filter=ff)
+                    assert otot == len(ids) == len(od)
+                    order = np.argsort(od)
+                    assert np.array_equal(od[order], ids)
+                    assert np.all(np.abs(os_[order].astype(np.float64) - sc) <= REL * sc)
+                    checked += 1
+                    if ff:
+                        dropped += len(naive.bm25f_exact(n, dlf, boost, [_entries(offs, D, F, T, t) for t in terms], op == O.OP_AND,
+                                                         not_docs=[_entries(offs, D, F, T, t)[0] for t in nots], deleted=dele)[0]) - len(ids)
+    assert checked > 50 and dropped > 100  # (the filter really removes docs)
+
+
+@pytest.mark.parametrize("seed,n_fields", [(21, 2), (22, 3)])
+def test_naive_bm25f_shortcut_agrees_with_the_oracle(seed, n_fields):
+    """the all_terms_frequent form: so_search_fields_shortcut ranks the docs naive.bm25f_shortcut_exact ranks, counts what it counts"""
+    from test_gpu_score_edges import REL
+    n, dlf, boost, offs, D, F, T = _fields_world(seed, n_fields, tf_p=0.12)   # (about a third of the entries have tf >= 10)
+    gone = np.arange(5, n, 37)
+    for dele in ((), gone):
+        for terms in ([0, 1], [1, 0], [0, 1, 2]):
+            ent = [_entries(offs, D, F, T, t) for t in terms]
+            ids, sc, total = naive.bm25f_shortcut_exact(n, dlf, boost, ent, deleted=dele)
+            all_ids, all_sc = naive.bm25f_exact(n, dlf, boost, ent, True, deleted=dele)
+            od, os_, otot = O.search_fields_shortcut(n, dlf, boost, offs, D, F, T, terms, n, deleted=dele)
+            assert otot == total == len(all_ids) and 0 < len(ids) < total
+            order = np.argsort(od)
+            assert np.array_equal(od[order], ids)
+            assert np.all(np.abs(os_[order].astype(np.float64) - sc) <= REL * sc)
+            assert np.array_equal(sc, all_sc[np.isin(all_ids, ids)])   # a ranked doc keeps its full score
+
+
+def test_naive_bm25f_exact_hand_computed():
+    """three docs, two fields, by hand: lengths (field 0; field 1) = (10; 20), (30; 0), (10; 10) -> positions_sum 80, avgdl 80 / 3;
+    term A = doc 0 field 0 tf 2, doc 0 field 1 tf 1, doc 2 field 1 tf 3 (df 2); term B = doc 0 field 1 tf 1, doc 1 field 0 tf 4 (df 2)"""
+    dlf = np.array([[10, 30, 10], [20, 0, 10]], np.uint8)   # (below 24 a length byte is the length)
+    boost = np.array([2.0, 0.5], np.float32)
+    A = (np.array([0, 0, 2]), np.array([0, 1, 1]), np.array([2, 1, 3]))
+    Bt = (np.array([0, 1]), np.array([1, 0]), np.array([1, 4]))
+    f32 = np.float32
+    avg = f32(80) / f32(3)
+    comp = lambda length: f32(1.2) * (f32(1) - f32(0.75) + f32(0.75) * (f32(length) / avg))
+    w = lambda tf, length: float((f32(tf) * f32(2.2)) / (f32(tf) + comp(length)))
+    idf2 = float(np.log((f32(3) - f32(2) + f32(0.5)) / (f32(2) + f32(0.5)) + f32(1), dtype=np.float32))
+    a0 = 2.0 * idf2 * w(2, 10) + 0.5 * idf2 * w(1, 20)
+    a2 = 0.5 * idf2 * w(3, 10)
+    b0 = 0.5 * idf2 * w(1, 20)
+    b1 = 2.0 * idf2 * w(4, 30)
+    ids, sc = naive.bm25f_exact(3, dlf, boost, [A, Bt], False)
+    assert ids.tolist() == [0, 1, 2] and np.allclose(sc, [a0 + b0, b1, a2], rtol=1e-15)
+    ids, sc = naive.bm25f_exact(3, dlf, boost, [A, Bt], True)
+    assert ids.tolist() == [0] and np.allclose(sc, [a0 + b0], rtol=1e-15)
+    # field 0 only: term B stands in doc 0's field 1 alone -- doc 0 leaves the intersection; a single term keeps its full score
+    assert naive.bm25f_exact(3, dlf, boost, [A, Bt], True, field_filter=(0,))[0].tolist() == []
+    ids, sc = naive.bm25f_exact(3, dlf, boost, [A], False, field_filter=(0,))
+    assert ids.tolist() == [0] and np.allclose(sc, [a0], rtol=1e-15)
+    ids, sc = naive.bm25f_exact(3, dlf, boost, [A], False, field_filter=(1,))
+    assert ids.tolist() == [0, 2] and np.allclose(sc, [a0, a2], rtol=1e-15)
+    assert naive.bm25f_exact(3, dlf, boost, [A], False, not_docs=[Bt[0]])[0].tolist() == [2]
+    assert naive.bm25f_exact(3, dlf, boost, [A], False, deleted=[2])[0].tolist() == [0]
+    assert naive.bm25f_exact(3, dlf, None, [A], False)[1][1] == idf2 * w(3, 10)   # no boosts: all 1
+    # the shortcut: every match counted, none ranked (tf < 10 in the lowest field); with tf 10 there, ranked
+    ids, sc, total = naive.bm25f_shortcut_exact(3, dlf, boost, [A, Bt])
+    assert len(ids) == 0 and total == 1
+    A10 = (A[0], A[1], np.array([10, 1, 3]))
+    B10 = (Bt[0], Bt[1], np.array([10, 4]))
+    ids, sc, total = naive.bm25f_shortcut_exact(3, dlf, boost, [A10, B10])
+    assert ids.tolist() == [0] and total == 1
