@@ -1,6 +1,8 @@
 // Internal to the C ABI layer (include/seekstorm_hip.h is the contract): what its files share.  Included by them only.
-//   ss_api.hip        shard life, image uploads and commits, lexical search and its routing, match sets with sorts, facets and browse, the
-//                     vector side, merge, profile hooks
+//   ss_api.hip        shard life, lexical search and its routing, match sets with sorts, facets and browse, the sharded searches, merge,
+//                     profile hooks
+//   api_vec.hip       the vector side: f32 and i8 images, their appends and side data, the host- and device-pointer searches
+//   api_image.hip     the lexical and facet images built and committed: uploads, level and sparse-tier commits, tombstones, string ranks
 //   api_coalesce.hip  the futex coalescer of concurrent callers, its SS_CO_TRACE report and its stats
 //   api_deep.hip      deep pages: lexical and vector searches of more than SS_MAX_K results, in passes
 // A function that one file defines and another calls is declared here, once, with its default arguments, under the ssi_ prefix and with
@@ -59,6 +61,21 @@ static int reserve(ss_shard* s, T** ptr, size_t* cap, size_t need, size_t alloc 
 static inline int ensure_qstage(ss_shard* s, size_t bytes) {
   return reserve(s, &s->d_qstage, &s->qstage_cap, bytes);
 }
+// the device lists of nq queries x k results (s->d_out_*)
+static inline int ensure_out(ss_shard* s, size_t nq, size_t k) {
+  size_t need = nq * std::max<size_t>(k, 1);
+  if (need <= s->out_cap && nq <= s->q_cap) return SS_OK;
+  void* ptrs[] = {s->d_out_doc, s->d_out_score, s->d_out_count, s->d_out_total};
+  for (void* p : ptrs) if (p) (void)hipFree(p);
+  s->d_out_doc = nullptr; s->d_out_score = nullptr; s->d_out_count = nullptr; s->d_out_total = nullptr;
+  s->out_cap = 0; s->q_cap = 0;
+  SS_HIP(hipMalloc(&s->d_out_doc, need * sizeof(uint32_t)));
+  SS_HIP(hipMalloc(&s->d_out_score, need * sizeof(float)));
+  SS_HIP(hipMalloc(&s->d_out_count, nq * sizeof(uint32_t)));
+  SS_HIP(hipMalloc(&s->d_out_total, nq * sizeof(uint64_t)));
+  s->out_cap = need; s->q_cap = nq;
+  return SS_OK;
+}
 
 // The shard mutex, as everybody but the coalescer's lane path takes it: with the lane streams drained (ss_common.h lstream) -- whoever
 // holds it may write the lexical image or enqueue writers on s->stream, and no lane kernel is in flight to meet them.
@@ -89,6 +106,10 @@ int ssi_bm25_search_sorted_locked(ss_shard* s, uint32_t nq, const ss_bm25_query*
                                   const ss_sort_sources& src, uint32_t k, uint32_t n_filters, const ss_facet_filter* filters,
                                   uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, const QueryFacets* qf = nullptr,
                                   const EachSets* each = nullptr);
+
+// ---- api_vec.hip: the image released (ss_shard_destroy; the shard's streams are idle), the host-pointer search as one call, up to the
+// device lists (the caller holds s->mu) and as a coalesced lane's pass
+void ssi_vec_free(ss_shard* s);
 int ssi_vec_search_host(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
                         float thr, const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                         uint64_t* out_total, uint32_t* out_clusters, const float* query_norm = nullptr);
@@ -97,6 +118,15 @@ int ssi_vec_search_host_lists(ss_shard* s, uint32_t nq, const void* queries, siz
                               const float* query_norm = nullptr, bool want_clusters = false, size_t out_slot = 0);
 int ssi_vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
                              uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total);
+
+// ---- api_image.hip: the lexical image released (ss_shard_destroy).  keep_tier: the dense image goes (a commit swaps in its successor),
+// the sparse tier stays
+void ssi_bm25_free(ss_shard* s, bool keep_tier = false);
+
+// ---- comm.hip: ssi_comm_exchange (ss_common.h) with the hybrid fusion on the host when host_fuse
+int ssi_comm_exchange_hf(ss_comm* c, uint32_t nq, int n_lists, const ss_dev_list* L, const uint64_t* d_tot_a, const uint64_t* d_tot_b,
+                         int local_rc, bool hybrid, uint32_t offset, uint32_t length, uint64_t* out_doc, float* out_score,
+                         uint8_t* out_source, uint32_t* out_count, uint64_t* out_total, hipStream_t st, bool host_fuse);
 
 // ---- api_deep.hip
 int ssi_bm25_search_deep_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,

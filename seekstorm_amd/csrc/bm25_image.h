@@ -57,7 +57,7 @@ struct ss_raw_level_mf {
 };
 // Those levels of a shard live beside it, keyed by it (as the sparse tier's level state does, sparse_levels.h): raw / boost are guarded
 // by the shard mutex; commit_mu is held across a commit, so that commits of one shard run one after the other.  The entry lives from
-// the shard's first commit until ssi_mf_levels_drop (ss_shard_destroy); an upload empties it (ss_api.hip free_raw_levels).
+// the shard's first commit until ssi_mf_levels_drop (ss_shard_destroy); an upload empties it (api_image.hip free_raw_levels).
 struct ss_mf_levels {
   std::vector<ss_raw_level_mf> raw;
   std::vector<float> boost;          // the fields' boosts of those levels

@@ -1,5 +1,5 @@
 // Facet records committed level by level, string ranks kept on the device, tombstones added in place (facet_commit.hip; the entry
-// points are ss_facet_append_level / _reserve / _info, ss_facet_set_string_ranks / _string_ranks and ss_add_deleted in ss_api.hip).
+// points are ss_facet_append_level / _reserve / _info, ss_facet_set_string_ranks / _string_ranks and ss_add_deleted in api_image.hip).
 //
 // What these need beyond ss_shard's d_facets / facet_docs / facet_record_size lives BESIDE the shard, as the multi-field levels do
 // (bm25_image.h ssi_mf_levels): from the first call that needs it until ssi_facet_side_drop (ss_shard_destroy, and ss_facet_upload,

@@ -12,7 +12,7 @@
 #include <cstdint>
 #include <vector>
 
-constexpr int MF_OK = 0, MF_EINVAL = -1, MF_ENOTSUP = -4;  // (= SS_OK, SS_EINVAL, SS_ENOTSUP; ss_api.hip asserts it)
+constexpr int MF_OK = 0, MF_EINVAL = -1, MF_ENOTSUP = -4;  // (= SS_OK, SS_EINVAL, SS_ENOTSUP; api_image.hip asserts it)
 constexpr uint32_t MF_POS_FIELD_SHIFT = 20u;               // (= BM_POS_FIELD_SHIFT)
 
 struct mf_level_host {

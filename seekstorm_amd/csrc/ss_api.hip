@@ -1,6 +1,8 @@
 // C ABI of the MI355X-native SeekStorm query hot path (see include/seekstorm_hip.h for the contract and the
-// reference seams each entry point replaces).  Host-side plumbing only; the kernels live in vec_scan.hip / bm25.hip.
-// The coalescer of concurrent callers stands in api_coalesce.hip, the deep pages in api_deep.hip; api_internal.h is what the three share.
+// reference seams each entry point replaces): shard life, lexical search and its routing, match sets with sorts, facets and browse, the
+// sharded searches, merge and the profile hooks.  Host-side plumbing only; the kernels live in bm25*.hip.
+// The vector side stands in api_vec.hip, the lexical and facet images (uploads and commits) in api_image.hip, the coalescer of concurrent
+// callers in api_coalesce.hip, the deep pages in api_deep.hip; api_internal.h is what the five share.
 #include <sched.h>
 #include <time.h>
 #include <unistd.h>
@@ -9,18 +11,15 @@
 #include <cfloat>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <iterator>
-#include <memory>
 #include <new>
 #include <type_traits>
 #include <unordered_map>
 
 #include "ss_common.h"
-#include "sparse_levels.h"
-#include "ss_threads.h"
 #include "facet_point.h"
-#include "bm25_build.h"
 #include "bm25_image.h"
 #include "bm25_match.h"
 #include "bm25_pack.h"
@@ -39,37 +38,6 @@ int with_facet_filter(ss_shard* s, uint32_t n_filters, const ss_facet_filter* fi
   if (rc) return rc;
   ExclSwap sw(s, s->d_filter_bits, (s->facet_docs + 31) / 32);
   return search();
-}
-
-// the postings of n_terms lists (CSR): offs non-decreasing; inside a list docs ascending and in [lo, hi), no tf of 0 (lists in parallel)
-bool postings_ok(uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, uint64_t lo, uint64_t hi) {
-  for (uint32_t t = 0; t < n_terms; t++)
-    if (offs[t + 1] < offs[t]) return false;
-  std::atomic<int> bad{0};
-  ss_parallel_for(n_terms, 64, [&](size_t a, size_t b, unsigned) {
-    for (size_t t = a; t < b; t++)
-      for (uint64_t j = offs[t]; j < offs[t + 1]; j++)
-        if (docs[j] < lo || docs[j] >= hi || tfs[j] == 0 || (j > offs[t] && docs[j] <= docs[j - 1])) { bad.store(1); return; }
-  });
-  return !bad.load();
-}
-
-// The positions a `_positions` upload needs are exactly sum(tf), and there: asked BEFORE anything is built or read, since the walk over
-// the postings indexes the positions by the running sum of the tfs.
-bool positions_needed(const uint64_t* offs, uint32_t n_terms, const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
-  if (!offs || n_terms == 0 || (offs[n_terms] && !tfs)) return false;
-  uint64_t need = 0;
-  for (uint64_t j = offs[0]; j < offs[n_terms]; j++) need += tfs[j];
-  return need == n_positions && (!need || positions);
-}
-
-// a commit brings the next level or replaces the last one (a re-commit); only the last level may be partial; doc ids stay under 2^32
-template <class Levels>
-int level_rules(uint32_t level, uint32_t n_level_docs, const Levels& levels) {
-  if (level > levels.size() || level + 1 < levels.size()) return SS_EINVAL;
-  if (level >= 1 && levels[level - 1].n_docs != 65536u) return SS_EINVAL;
-  if ((uint64_t)level * 65536u + n_level_docs > 0xFFFFFFFFull) return SS_ENOTSUP;
-  return SS_OK;
 }
 }  // namespace
 
@@ -143,103 +111,6 @@ int ss_shard_create(int device, ss_shard** out) {
   return SS_OK;
 }
 
-// RAII: a search on a stream other than the shard's own runs on that stream's set of scan buffers (swapped into the shard's
-// fields while the launches are enqueued -- under s->mu -- and back afterwards; buffers are allocated lazily by the scan code)
-struct VecWsBind {
-  ss_shard* s;
-  ss_vec_ws* w = nullptr;
-  VecWsBind(ss_shard* s_, hipStream_t st) : s(s_) {
-    if (st == s->stream) return;
-    w = &s->vec_ws[st];
-    swap();
-  }
-  ~VecWsBind() { if (w) swap(); }
-  void swap() {
-    std::swap(s->d_Qf, w->d_Qf);
-    std::swap(s->d_vstate, w->d_vstate);
-    std::swap(s->d_cand, w->d_cand);
-    std::swap(s->d_qaux, w->d_qaux);
-  }
-};
-
-// The ANN selection state (medoid scores, per-query cluster bitmaps, the tile list, the live counts) is ONE set of buffers per
-// shard: a search with an ss_ann_mode queued on another stream than the previous one first waits for that one to finish.
-// Caller holds s->mu.  (Searches without a mode touch none of it and stay concurrent across streams.)
-struct AnnStateGuard {
-  ss_shard* s;
-  hipStream_t st;
-  bool on;
-  AnnStateGuard(ss_shard* s_, hipStream_t st_, const ss_ann_mode* mode) : s(s_), st(st_), on(mode != nullptr) {
-    if (on && s->ann_ev_set && s->ann_ev_stream != st) (void)hipStreamWaitEvent(st, s->ann_ev, 0);
-  }
-  ~AnnStateGuard() {
-    if (!on) return;
-    if (!s->ann_ev && hipEventCreateWithFlags(&s->ann_ev, hipEventDisableTiming) != hipSuccess) { s->ann_ev = nullptr; s->ann_ev_set = false; return; }
-    s->ann_ev_set = hipEventRecord(s->ann_ev, st) == hipSuccess;
-    s->ann_ev_stream = st;
-  }
-};
-
-static void free_vec(ss_shard* s) {
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // a coalesced scan still running reads the arrays released below
-  for (auto& kv : s->vec_ws) {
-    void* wp[] = {kv.second.d_Qf, kv.second.d_vstate, kv.second.d_cand, kv.second.d_qaux};
-    for (void* p : wp) if (p) (void)hipFree(p);
-  }
-  s->vec_ws.clear();
-  void* ptrs[] = {s->d_X, s->d_X8, s->d_row_scale, s->d_row_doc, s->d_Qf, s->d_vstate, s->d_cand, s->d_row_field, s->d_row_norm, s->d_row_sq, s->d_qaux, s->d_vec_r2};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  s->d_X = nullptr; s->d_X8 = nullptr; s->d_row_scale = nullptr; s->d_row_doc = nullptr; s->d_Qf = nullptr;
-  s->d_row_norm = nullptr; s->d_row_sq = nullptr; s->d_qaux = nullptr; s->d_vec_r2 = nullptr;
-  s->d_vstate = nullptr; s->d_cand = nullptr; s->d_row_field = nullptr;
-  s->n_rows = s->n_rows_pad = 0; s->dim = s->dim_pad = s->dim_pad8 = 0; s->vec_multi_record = false; s->vec_rows_cap = 0;
-  ssi_vec_free_clusters(s);
-  if (s->ann_ev) (void)hipEventDestroy(s->ann_ev);
-  s->ann_ev = nullptr; s->ann_ev_set = false; s->ann_ev_stream = nullptr;
-}
-extern "C++" {
-// the levels of ss_bm25_commit_level_fields, beside their shards (bm25_image.h ss_mf_levels)
-static std::mutex g_mf_mu;
-static std::map<const ss_shard*, std::unique_ptr<ss_mf_levels>> g_mf;
-ss_mf_levels* ssi_mf_levels(const ss_shard* s, bool create) {
-  std::lock_guard<std::mutex> g(g_mf_mu);
-  auto it = g_mf.find(s);
-  if (it != g_mf.end()) return it->second.get();
-  if (!create) return nullptr;
-  return (g_mf[s] = std::make_unique<ss_mf_levels>()).get();
-}
-void ssi_mf_levels_drop(const ss_shard* s) {
-  std::lock_guard<std::mutex> g(g_mf_mu);
-  g_mf.erase(s);
-}
-}  // extern "C++"
-static void free_raw_levels(ss_shard* s) {
-  for (ss_raw_level& L : s->raw) raw_level_free(L);
-  s->raw.clear();
-  s->h_doclen.clear();
-  s->raw_f.clear();
-  s->raw_f_fields = 0;
-  if (ss_mf_levels* M = ssi_mf_levels(s, false)) {
-    for (ss_raw_level_mf& L : M->raw) raw_level_mf_free(L);
-    M->raw.clear();
-    M->boost.clear();
-  }
-}
-// keep_tier: the dense image goes (a commit swaps in its successor), the sparse tier stays
-static void free_bm25(ss_shard* s, bool keep_tier = false) {
-  free_raw_levels(s);
-  bm_image_arrays(s, [&](auto*& p) { if (p) { s->blocks.drop(p); (void)hipFree(p); } });
-  s->blocks.clear_idle();
-  ssi_bm25_drop_kth(s);
-  if (!keep_tier) {
-    for (void* p : {(void*)s->d_sp_base, (void*)s->d_sp_post, (void*)s->d_sp_pos, (void*)s->d_sp_pos_end}) if (p) (void)hipFree(p);
-    s->d_sp_base = nullptr; s->d_sp_post = nullptr; s->sp_n = 0; s->h_sp_base.clear();
-    s->d_sp_pos = nullptr; s->d_sp_pos_end = nullptr; s->sp_pos_n = 0; s->sp_pos_elem = 0;
-    ssi_bm25_sparse_levels_drop(s);
-  }
-  bm_image_clear_fields(s);
-}
-
 int ss_shard_destroy(ss_shard* s) {
   if (!s) return SS_EINVAL;
   ssi_co_trace_report();
@@ -248,8 +119,8 @@ int ss_shard_destroy(ss_shard* s) {
   if (s->vstream) (void)hipStreamSynchronize(s->vstream);
   for (hipStream_t st : s->lstream)
     if (st) (void)hipStreamSynchronize(st);
-  free_vec(s);
-  free_bm25(s);
+  ssi_vec_free(s);
+  ssi_bm25_free(s);
   ssi_mf_levels_drop(s);
   ssi_facet_side_drop(s);
   for (void* p_ : {(void*)s->d_vq, (void*)s->d_vdoc, (void*)s->d_vscore, (void*)s->d_vcount, (void*)s->d_vtotal}) if (p_) (void)hipFree(p_);
@@ -292,1044 +163,6 @@ int ss_shard_sync(ss_shard* s) {
   if (s->vstream) SS_HIP(hipStreamSynchronize(s->vstream));
   for (hipStream_t st : s->lstream)
     if (st) SS_HIP(hipStreamSynchronize(st));
-  return SS_OK;
-}
-
-// ------------------------------------------------------------------ staging helpers
-static int ensure_out(ss_shard* s, size_t nq, size_t k) {
-  size_t need = nq * std::max<size_t>(k, 1);
-  if (need <= s->out_cap && nq <= s->q_cap) return SS_OK;
-  void* ptrs[] = {s->d_out_doc, s->d_out_score, s->d_out_count, s->d_out_total};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  s->d_out_doc = nullptr; s->d_out_score = nullptr; s->d_out_count = nullptr; s->d_out_total = nullptr;
-  s->out_cap = 0; s->q_cap = 0;
-  SS_HIP(hipMalloc(&s->d_out_doc, need * sizeof(uint32_t)));
-  SS_HIP(hipMalloc(&s->d_out_score, need * sizeof(float)));
-  SS_HIP(hipMalloc(&s->d_out_count, nq * sizeof(uint32_t)));
-  SS_HIP(hipMalloc(&s->d_out_total, nq * sizeof(uint64_t)));
-  s->out_cap = need; s->q_cap = nq;
-  return SS_OK;
-}
-
-// ------------------------------------------------------------------ BM25
-int ss_bm25_upload(ss_shard* s, uint64_t n_docs, const uint8_t* doclen, uint32_t n_terms, const uint64_t* offs,
-                   const uint32_t* docs, const uint16_t* tfs) {
-  return ss_guard([&] { return ssi_bm25_upload(s, n_docs, doclen, n_terms, offs, docs, tfs, 0); }, SS_ENOMEM, SS_EDEVICE);
-}
-
-int ss_bm25_upload_positions(ss_shard* s, uint64_t n_docs, const uint8_t* doclen, uint32_t n_terms, const uint64_t* offs,
-                             const uint32_t* docs, const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
-  if (!positions_needed(offs, n_terms, tfs, positions, n_positions)) return SS_EINVAL;
-  return ss_guard([&]() -> int {
-    SS_TRY(ssi_bm25_upload(s, n_docs, doclen, n_terms, offs, docs, tfs, 0));
-    return ssi_bm25_attach_positions(s, offs, docs, tfs, positions, n_positions);
-  }, SS_ENOMEM, SS_EDEVICE);
-}
-
-}  // extern "C"
-
-// positions of the image just built (CSR order); a failure leaves no image behind
-int ssi_bm25_attach_positions(ss_shard* s, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, const uint16_t* positions,
-                              uint64_t n_positions, const uint16_t* npos) {
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  const int rc = ssi_bm25_upload_positions(s, offs, docs, tfs, positions, n_positions, npos);
-  if (rc) free_bm25(s);
-  return rc;
-}
-
-// the arrays of a whole-image upload -> device, validated on the way (terms in parallel); the image is built by the device kernels
-static int bm25_upload_device_build(ss_shard* s, const uint8_t* doclen, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
-                                    uint64_t positions_sum) {
-  const uint32_t nt = s->bm_n_terms;
-  const uint64_t nd = s->bm_n_docs, np = offs[nt] - offs[0];
-  if (!postings_ok(nt, offs, docs, tfs, 0, nd)) return SS_EINVAL;
-  ss_raw_level L;
-  L.n_docs = 0; L.n_terms = nt; L.n_post = np;
-  if (positions_sum) L.psum = positions_sum;
-  else {
-    std::vector<uint64_t> part(ss_loader_threads() + 1, 0);
-    ss_parallel_for(nd, 1u << 20, [&](size_t a, size_t b, unsigned w) { uint64_t c = 0; for (size_t d = a; d < b; d++) c += ss_byte4_to_int(doclen[d]); part[w] += c; });
-    for (uint64_t c : part) L.psum += c;
-  }
-  SS_TRY(raw_level_upload(L, offs, docs, tfs, nt, nullptr, s->stream));
-  std::vector<ss_raw_level> one{L};
-  const int rc = ssi_bm25_rebuild_from_raw(s, one, nt, doclen, nd, s, s->stream, true);
-  raw_level_free(L);
-  return rc;
-}
-
-int ssi_bm25_upload(ss_shard* s, uint64_t n_docs, const uint8_t* doclen, uint32_t n_terms, const uint64_t* offs,
-                    const uint32_t* docs, const uint16_t* tfs, uint64_t positions_sum) {
-  if (!s || !doclen || !offs || n_docs == 0 || n_terms == 0) return SS_EINVAL;
-  if (offs[n_terms] && (!docs || !tfs)) return SS_EINVAL;
-  if (n_docs > 0xFFFFFFFFull) return SS_ENOTSUP;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  free_bm25(s);
-  s->bm_n_docs = n_docs;
-  s->bm_n_terms = n_terms;
-  s->bm_n_sub = (uint32_t)((n_docs + BM_SUB - 1) >> BM_SUB_LOG2);
-  // One indexed field: the image is BUILT ON THE DEVICE from the decoded arrays (the kernels of the incremental rebuild, synth.hip
-  // ssi_bm25_rebuild_from_raw) -- the host validates and copies 6 bytes per posting instead of packing, sorting out segments and
-  // filling probe rows.  SS_BM25_HOST_BUILD=1 keeps the host builder (the two are compared by the tests).
-  constexpr bool host_build = false;  // (the host builder: images with several fields, and what the device builder was checked against)
-  int rc;
-  if (host_build) {
-    rc = ssi_bm25_build_from_host(s, doclen, offs, docs, tfs, positions_sum);
-  } else {
-    rc = bm25_upload_device_build(s, doclen, offs, docs, tfs, positions_sum);
-  }
-  if (rc) free_bm25(s);
-  return rc;
-}
-
-extern "C" {
-
-// Several indexed fields (BM25F, get_bm25f_multiterm_multifield add_result.rs:1171-1426): a posting = (term, doc, field, tf).
-// The image holds one posting list per (term, field); a query term is expanded over its fields on the device.
-int ss_bm25_upload_fields(ss_shard* s, uint64_t n_docs, uint32_t n_fields, const uint8_t* doclen, const float* boost,
-                          uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                          const uint16_t* tfs) {
-  return ss_guard([&] { return ssi_bm25_upload_fields(s, n_docs, n_fields, doclen, boost, n_terms, offs, docs, fields, tfs, 0); }, SS_ENOMEM, SS_EDEVICE);
-}
-
-// ... plus the positions of every (term, doc, field) entry: phrase queries over several indexed fields
-int ss_bm25_upload_fields_positions(ss_shard* s, uint64_t n_docs, uint32_t n_fields, const uint8_t* doclen, const float* boost,
-                                    uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                                    const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions) {
-  if (!positions_needed(offs, n_terms, tfs, positions, n_positions)) return SS_EINVAL;
-  return ss_guard([&] { return ssi_bm25_upload_fields_positions(s, n_docs, n_fields, doclen, boost, n_terms, offs, docs, fields, tfs, 0, positions, n_positions); },
-                  SS_ENOMEM, SS_EDEVICE);
-}
-
-}  // extern "C"
-
-int ssi_bm25_upload_fields_positions(ss_shard* s, uint64_t n_docs, uint32_t n_fields, const uint8_t* doclen, const float* boost,
-                                     uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                                     const uint16_t* tfs, uint64_t positions_sum, const uint16_t* positions, uint64_t n_positions, const uint16_t* npos) {
-  if (n_fields < 2) return SS_EINVAL;  // one indexed field: ss_bm25_upload_positions
-  static const bool trace = getenv("SS_LOAD_TRACE") != nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  int rc = ssi_bm25_upload_fields(s, n_docs, n_fields, doclen, boost, n_terms, offs, docs, fields, tfs, positions_sum);
-  if (rc) return rc;
-  const auto t1 = std::chrono::steady_clock::now();
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  rc = ssi_bm25_upload_positions_fields(s, n_terms, offs, docs, fields, tfs, positions, n_positions, npos);
-  if (trace) fprintf(stderr, "[load]   fields image %.0f ms, positions %.0f ms\n", std::chrono::duration<double, std::milli>(t1 - t0).count(),
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
-  if (rc) free_bm25(s);  // a failure leaves no image behind
-  return rc;
-}
-
-int ssi_bm25_upload_fields(ss_shard* s, uint64_t n_docs, uint32_t n_fields, const uint8_t* doclen, const float* boost,
-                           uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                           const uint16_t* tfs, uint64_t positions_sum) {
-  if (!s || !doclen || !offs || n_docs == 0 || n_terms == 0 || n_fields == 0 || n_fields > 8) return SS_EINVAL;
-  if (offs[n_terms] && (!docs || !fields || !tfs)) return SS_EINVAL;
-  // (term, field) lists: entries of a term are sorted by (doc, field); a stable split by field keeps each list sorted by doc.
-  // Two or more fields: one more list per term, the MERGED list (ss_common.h bm_merged) -- every doc of the term once.
-  std::vector<float> b(n_fields, 1.0f);
-  if (boost) b.assign(boost, boost + n_fields);
-  float bmax = 0.f;
-  bool boosts_ok = true;
-  for (float x : b) { boosts_ok = boosts_ok && x > 0.f && x < 1e30f; bmax = std::max(bmax, x); }
-  constexpr bool merged_off = false;
-  (void)bmax;
-  std::vector<uint64_t> df_real(n_terms, 0);
-  for (uint32_t t = 0; t < n_terms; t++)
-    if (offs[t + 1] < offs[t]) return SS_EINVAL;
-  {  // (per-term loops on the loader's worker threads, here and below: a term's entries and lists are its own)
-    std::atomic<int> bad{0};
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++)
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) {
-          if (fields[j] >= n_fields) { bad.store(1); return; }
-          if (j > offs[t] && (docs[j] < docs[j - 1] || (docs[j] == docs[j - 1] && fields[j] <= fields[j - 1]))) { bad.store(1); return; }
-          if (j == offs[t] || docs[j] != docs[j - 1]) df_real[t]++;  // docs containing the term in any field: the df of idf
-        }
-    });
-    if (bad.load()) return SS_EINVAL;
-  }
-  {  // a (term, field) weight the code cannot hold: refused before the present image is released (a re-upload of ss_bm25_append_level_fields
-     // keeps the image and levels it had)
-    const int rc_codable = ssi_bm25_fields_codable(n_docs, n_fields, doclen, n_terms, offs, fields, tfs, docs, positions_sum);
-    if (rc_codable) return rc_codable;
-  }
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  // with merged lists first; a corpus whose merged weights do not fit the weight code is built again without them
-  int rc = SS_OK;
-  for (int attempt = 0; attempt < 2; attempt++) {
-    const bool merged = attempt == 0 && n_fields > 1 && boosts_ok && !merged_off;
-    if (attempt == 0 && !merged) continue;
-    const uint32_t L = n_fields + (merged ? 1u : 0u);
-    if ((uint64_t)n_terms * L > 0x7FFFFFFFull) return SS_ENOTSUP;
-    const uint32_t nv = n_terms * L;
-    std::vector<uint64_t> voff((size_t)nv + 1, 0);
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++) {
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) voff[t * L + fields[j] + 1]++;
-        if (merged) voff[t * L + n_fields + 1] = df_real[t];
-      }
-    });
-    for (uint32_t v = 0; v < nv; v++) voff[v + 1] += voff[v];
-    std::vector<uint32_t> vdocs(voff[nv]);
-    std::vector<uint16_t> vtfs(voff[nv]);
-    std::vector<uint64_t> cur(voff.begin(), voff.end() - 1);
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++)
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) {
-          const uint64_t w = cur[t * L + fields[j]]++;
-          vdocs[w] = docs[j];
-          vtfs[w] = tfs[j];
-          if (merged && (j == offs[t] || docs[j] != docs[j - 1])) {
-            const uint64_t m = cur[t * L + n_fields]++;
-            vdocs[m] = docs[j];
-            vtfs[m] = 1;  // not a tf: the builder derives the merged weight from the field lists
-          }
-        }
-    });
-    free_bm25(s);
-    s->bm_n_docs = n_docs;
-    s->bm_n_fields = L;
-    s->bm_merged = merged;
-    s->bm_n_terms = nv;
-    s->bm_n_sub = (uint32_t)((n_docs + BM_SUB - 1) >> BM_SUB_LOG2);
-    float scale = 1.0f;
-    const auto tb0 = std::chrono::steady_clock::now();
-    rc = ssi_bm25_build_from_host_merged(s, doclen, voff.data(), vdocs.data(), vtfs.data(), positions_sum, merged ? b.data() : nullptr, &scale);
-    if (getenv("SS_LOAD_TRACE")) fprintf(stderr, "[load]     build_from_host_merged %.0f ms (attempt %d)\n",
-                                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count(), attempt);
-    if (rc == SS_MERGED_RANGE) continue;  // the merged weights span more than the code: again, without merged lists
-    if (rc == SS_OK) {
-      std::vector<float> bb = b;
-      if (merged) bb.push_back(scale);  // the merged list's "boost" gives the scale back through idf
-      if (hipMalloc(&s->d_boost, bb.size() * sizeof(float)) != hipSuccess ||
-          hipMemcpy(s->d_boost, bb.data(), bb.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = SS_EDEVICE;
-      s->h_df_real = df_real;
-      s->h_boost = bb;
-      s->bm_n_post = offs[n_terms];  // the postings of the index (the merged lists are a second copy)
-    }
-    break;
-  }
-  if (rc) free_bm25(s);
-  return rc;
-}
-
-extern "C" {
-
-int ss_synth_set_partition(ss_shard* s, uint32_t shard_id, uint32_t n_shards) {
-  if (!s || n_shards == 0 || shard_id >= n_shards) return SS_EINVAL;
-  ShardLock g(s);
-  s->synth_stride = n_shards;
-  s->synth_offset = shard_id;
-  return SS_OK;
-}
-
-int ss_bm25_synth(ss_shard* s, uint64_t seed, uint64_t n_docs, uint32_t n_terms, const uint32_t* thresh32,
-                  const uint8_t* len_table1024) {
-  if (!s || !thresh32 || !len_table1024 || n_docs == 0 || n_terms == 0) return SS_EINVAL;
-  if (n_docs > 0xFFFFFFFFull) return SS_ENOTSUP;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  free_bm25(s);
-  s->bm_n_docs = n_docs;
-  s->bm_n_terms = n_terms;
-  s->bm_n_sub = (uint32_t)((n_docs + BM_SUB - 1) >> BM_SUB_LOG2);
-  uint32_t* d_th = nullptr;
-  uint8_t* d_tab = nullptr;
-  SS_HIP(hipMalloc(&d_th, (size_t)n_terms * sizeof(uint32_t)));
-  SS_HIP(hipMalloc(&d_tab, 1024));
-  SS_HIP(hipMemcpy(d_th, thresh32, (size_t)n_terms * sizeof(uint32_t), hipMemcpyHostToDevice));
-  SS_HIP(hipMemcpy(d_tab, len_table1024, 1024, hipMemcpyHostToDevice));
-  int rc = ssi_bm25_synth(s, seed, d_th, d_tab, s->stream);
-  (void)hipFree(d_th);
-  (void)hipFree(d_tab);
-  if (rc) free_bm25(s);
-  return rc;
-}
-
-// Incremental commit.  The reference commits one 65 536-doc level at a time and rebuilds its in-RAM structures for it (commit.rs:142-148
-// commit -> warmup, 264-369 the level writer; index.rs:3796); a BM25 weight depends on avgdl, which every commit moves (commit.rs:318-325
-// refills bm25_component_cache), so no posting of the image survives a commit unchanged.  Here the decoded postings of every level stay
-// in HBM as they arrived (6 bytes per posting) and the image is rebuilt from them ON THE DEVICE (ssi_bm25_rebuild_from_raw: count,
-// scan, fill -- the raw postings read once, the image written once): a commit costs the level's H2D + a few milliseconds per GB of
-// image, not a host pass over the shard.  The new image is built beside the old one; searches keep running on the old image until the
-// swap, which waits for the searches in flight and releases the old arrays.
-static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, const uint64_t* offs,
-                             const uint32_t* docs, const uint16_t* tfs, bool with_pos, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
-  if (!s || !level_doclen || !offs || n_terms == 0 || n_level_docs == 0 || n_level_docs > 65536u) return SS_EINVAL;
-  if (offs[n_terms] && (!docs || !tfs)) return SS_EINVAL;
-  const auto t_begin = std::chrono::steady_clock::now();
-  SS_HIP(hipSetDevice(s->device));
-  std::vector<ss_raw_level> levels;
-  std::vector<uint8_t> doclen;
-  uint32_t nt_old = 0;
-  {
-    ShardLock g(s);
-    if (s->d_post && s->raw.empty()) return SS_ESTATE;       // an image that was not built level by level
-    // a sparse tier numbers its terms behind the dense ones: a grown dense vocabulary would shift them -- new terms of an image with a
-    // tier join the tier (ss_bm25_append_sparse_level), whose postings must come level by level too (their tfs are kept for re-coding)
-    if (s->sp_n && (!ssi_bm25_sparse_levels_has(s) || n_terms != s->bm_n_terms)) return SS_ENOTSUP;
-    // (a re-committed level only grows, commit.rs:204-206; a shrinking one would leave the tier's postings of the level pointing
-    // past the image until ss_bm25_append_sparse_level replaces them)
-    if (s->sp_n && level < s->raw.size() && n_level_docs < s->raw[level].n_docs) return SS_ENOTSUP;
-    SS_TRY(level_rules(level, n_level_docs, s->raw));
-    nt_old = s->raw.empty() ? 0u : s->bm_n_terms;
-    if (n_terms < nt_old) return SS_EINVAL;                    // the vocabulary only grows; new terms get the next ids
-    if (level > 0 && (s->raw[0].d_tpos != nullptr) != with_pos) return SS_EINVAL;  // positions for every level of an image, or for none
-    levels.assign(s->raw.begin(), s->raw.begin() + level);
-    doclen.assign(s->h_doclen.begin(), s->h_doclen.begin() + (size_t)level * 65536u);
-  }
-  // validation: docs of a term ascending and inside the level
-  const uint64_t d_lo = (uint64_t)level * 65536u, d_hi = d_lo + n_level_docs;
-  if (!postings_ok(n_terms, offs, docs, tfs, d_lo, d_hi)) return SS_EINVAL;
-  ss_raw_level L;
-  L.n_docs = n_level_docs; L.n_terms = n_terms; L.n_post = offs[n_terms] - offs[0];
-  for (uint32_t d = 0; d < n_level_docs; d++) L.psum += ss_byte4_to_int(level_doclen[d]);
-  // positions: per posting its count, the positions of the term's earlier postings of this level, per term its first position
-  std::vector<uint16_t> h_npos;
-  std::vector<uint32_t> h_prel;
-  std::vector<uint64_t> h_tpos;
-  if (with_pos) {
-    h_npos.resize(L.n_post); h_prel.resize(L.n_post); h_tpos.assign((size_t)n_terms + 1, 0);
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {  // a term's positions: the sum of its postings' counts
-      for (size_t t = ta; t < tb; t++) {
-        uint64_t c = 0;
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) c += npos ? npos[j] : tfs[j];
-        h_tpos[t + 1] = c;
-      }
-    });
-    for (uint32_t t = 0; t < n_terms; t++) h_tpos[t + 1] += h_tpos[t];
-    if (h_tpos[n_terms] != n_positions) return SS_EINVAL;
-    std::atomic<int> bad{SS_OK};
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++) {
-        const uint64_t at = h_tpos[t];
-        uint64_t rel = 0;
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) {
-          const uint32_t c = npos ? npos[j] : tfs[j];
-          if (rel >= (1ull << 32)) { bad.store(SS_ENOTSUP); return; }
-          h_npos[j - offs[0]] = (uint16_t)c; h_prel[j - offs[0]] = (uint32_t)rel;
-          for (uint32_t x = 1; x < c; x++)
-            if (positions[at + rel + x] <= positions[at + rel + x - 1]) { bad.store(SS_EINVAL); return; }  // ascending inside a posting
-          rel += c;
-        }
-      }
-    });
-    if (bad.load()) return bad.load();
-    L.n_pos = n_positions;
-  }
-  hipStream_t bst = nullptr;
-  std::unique_ptr<ss_shard> img(new ss_shard);
-  auto undo = [&]() {
-    raw_level_free(L);
-    bm_image_arrays(img.get(), [&](auto*& p) { if (p && !s->blocks.release(p)) (void)hipFree(p); });
-  };
-  CommitUndo<decltype(undo)> own{undo, bst};
-  if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
-  const raw_level_positions pos{h_npos.data(), h_prel.data(), h_tpos.data(), positions, n_positions};
-  if (const int rc_up = raw_level_upload(L, offs, docs, tfs, n_terms, with_pos ? &pos : nullptr, bst)) return rc_up;
-  levels.push_back(L);
-  doclen.insert(doclen.end(), level_doclen, level_doclen + n_level_docs);
-  const auto t_build = std::chrono::steady_clock::now();
-  int rc = ssi_bm25_rebuild_from_raw(s, levels, n_terms, doclen.data(), doclen.size(), img.get(), bst);
-  if (rc) return rc;
-  const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
-  int rc_recode = SS_OK;
-  {  // the swap: searches in flight finish on the old image, whose arrays are then released
-    ShardLock g(s);
-    if (level > s->raw.size() || level + 1 < s->raw.size()) return SS_ESTATE;  // another commit got in between (the caller's write lock forbids it)
-    (void)hipStreamSynchronize(s->stream);
-    for (auto& kv : s->bm_ws) (void)hipStreamSynchronize(kv.first);
-    if (s->sp_n) {  // the sparse postings under the new average length: a weight the code cannot hold refuses the commit before anything changes
-      const int rc_check = ssi_bm25_sparse_levels_check(s, img.get(), bst);
-      if (rc_check) return rc_check;
-    }
-    ss_raw_level replaced;
-    const bool replace = level < s->raw.size();
-    if (replace) replaced = s->raw[level];
-    std::vector<ss_raw_level> keep;
-    keep.reserve((size_t)level + 1);
-    keep.assign(s->raw.begin(), s->raw.begin() + level);
-    keep.push_back(L);
-    own.taken = true;  // from here on the level and the image are the shard's
-    s->raw.clear();  // (free_bm25 must not release the levels that stay)
-    {  // the old image's arrays go back to the block pool: the next commit builds into them
-      s->blocks.gen++;
-      bm_image_arrays(s, [&](auto*& p) { if (p && s->blocks.release(p)) p = nullptr; });  // (d_boost, d_pos32: null in an image built by levels)
-      std::vector<ss_block_pool::Idle> idle;
-      idle.swap(s->blocks.idle);   // (free_bm25 clears the idle list: these stay)
-      free_bm25(s, /*keep_tier=*/true);
-      s->blocks.idle.swap(idle);
-      s->blocks.trim(3);
-    }
-    if (replace) raw_level_free(replaced);
-    s->raw.swap(keep);
-    s->h_doclen.swap(doclen);
-    bm_image_take(s, img.get());
-    if (s->sp_n) {  // the average length moved: the sparse postings' codes follow (their docs of this level: ss_bm25_append_sparse_level)
-      rc_recode = ssi_bm25_sparse_levels_recode(s, s->stream);
-      if (rc_recode == SS_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc_recode = SS_EDEVICE;
-    }
-    s->raw_last_rebuild_ms = rebuild_ms;
-    s->raw_last_append_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  // the dense image is swapped in either way; a sparse tier that could not follow the new average length would score its terms with
-  // the old one: the caller hears about it, and commits again or rebuilds
-  return rc_recode;
-}
-
-int ss_bm25_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms, const uint64_t* offs,
-                         const uint32_t* docs, const uint16_t* tfs) {
-  return ss_guard([&] { return append_level_impl(s, level, n_level_docs, level_doclen, n_terms, offs, docs, tfs, false, nullptr, nullptr, 0); }, SS_ENOMEM, SS_EDEVICE);
-}
-// ... with the postings' POSITIONS (phrase queries on an image that grows by commits): positions = every posting's, in CSR order, tf of
-// them each -- or npos[i] where that is not the tf (npos may be NULL): the component terms of an n-gram key, whose own positions stand
-// behind its first component's postings.  Every level of an image brings positions, or none does.
-int ss_bm25_append_level_positions(ss_shard* s, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms,
-                                   const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions,
-                                   uint64_t n_positions) {
-  if (n_positions && !positions) return SS_EINVAL;
-  return ss_guard([&] { return append_level_impl(s, level, n_level_docs, level_doclen, n_terms, offs, docs, tfs, true, npos, positions, n_positions); }, SS_ENOMEM, SS_EDEVICE);
-}
-
-// INCREMENTAL COMMIT of an image with SEVERAL indexed fields (round 6; VERDICT r5 missing 6; commit.rs:142-148 -> the "(re)build device image"
-// seam).  The level's entries (term, doc, field, tf) and its docs' length bytes per field join the levels kept on the HOST; the shard's
-// postings are re-assembled term by term (a term's entries of level after level: doc ids ascend with the level) and the image is rebuilt
-// by the multi-field builder -- per-field lists, merged lists, probe rows --, i.e. a commit costs what an upload of the shard costs
-// (52 M entries/s), where the one-field form rebuilds on the device from levels kept in HBM.  Same level rules as ss_bm25_append_level.
-int ss_bm25_append_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost,
-                                uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields, const uint16_t* tfs) {
-  return ss_guard([&]() -> int {
-    if (!s || !level_doclen || !offs || n_terms == 0 || n_level_docs == 0 || n_level_docs > 65536u || n_fields < 2 || n_fields > 8) return SS_EINVAL;
-    if (offs[n_terms] && (!docs || !fields || !tfs)) return SS_EINVAL;
-    const auto t_begin = std::chrono::steady_clock::now();
-    std::vector<ss_raw_level_f> levels;
-    {
-      ShardLock g(s);
-      if ((s->d_post || !s->raw.empty()) && s->raw_f.empty()) return SS_ESTATE;  // an image that was not built this way
-      if (s->sp_n) return SS_ENOTSUP;                                            // (a sparse tier beside it: upload + ss_bm25_append_sparse_fields)
-      if (!s->raw_f.empty() && s->raw_f_fields != n_fields) return SS_EINVAL;
-      SS_TRY(level_rules(level, n_level_docs, s->raw_f));
-      if (!s->raw_f.empty() && n_terms < s->raw_f.back().n_terms && level == s->raw_f.size()) return SS_EINVAL;  // the vocabulary only grows
-      levels.assign(s->raw_f.begin(), s->raw_f.begin() + level);
-    }
-    const uint64_t d_lo = (uint64_t)level * 65536u, d_hi = d_lo + n_level_docs;
-    // (not postings_ok: a doc's entries follow each other field by field; their order is ssi_bm25_upload_fields' to judge)
-    for (uint32_t t = 0; t < n_terms; t++)
-      if (offs[t + 1] < offs[t]) return SS_EINVAL;
-    for (uint64_t j = offs[0]; j < offs[n_terms]; j++)
-      if (docs[j] < d_lo || docs[j] >= d_hi || tfs[j] == 0 || fields[j] >= n_fields) return SS_EINVAL;
-    ss_raw_level_f L;
-    L.n_docs = n_level_docs; L.n_terms = n_terms;
-    L.off.resize((size_t)n_terms + 1);
-    for (uint32_t t = 0; t <= n_terms; t++) L.off[t] = offs[t] - offs[0];
-    L.doc.assign(docs + offs[0], docs + offs[n_terms]);
-    L.field.assign(fields + offs[0], fields + offs[n_terms]);
-    L.tf.assign(tfs + offs[0], tfs + offs[n_terms]);
-    L.doclen.assign(level_doclen, level_doclen + (size_t)n_fields * n_level_docs);
-    levels.push_back(std::move(L));
-    // the whole shard, term by term
-    uint64_t n_docs = 0;
-    uint32_t nt_all = 0;
-    for (const ss_raw_level_f& l : levels) { n_docs += l.n_docs; nt_all = std::max(nt_all, l.n_terms); }
-    std::vector<uint64_t> off_all((size_t)nt_all + 1, 0);
-    for (const ss_raw_level_f& l : levels)
-      for (uint32_t t = 0; t < l.n_terms; t++) off_all[t + 1] += l.off[t + 1] - l.off[t];
-    for (uint32_t t = 0; t < nt_all; t++) off_all[t + 1] += off_all[t];
-    const uint64_t n_all = off_all[nt_all];
-    std::vector<uint32_t> doc_all(std::max<uint64_t>(n_all, 1));
-    std::vector<uint8_t> field_all(std::max<uint64_t>(n_all, 1));
-    std::vector<uint16_t> tf_all(std::max<uint64_t>(n_all, 1));
-    ss_parallel_for(nt_all, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++) {
-        uint64_t at = off_all[t];
-        for (const ss_raw_level_f& l : levels) {
-          if (t >= l.n_terms) continue;
-          const uint64_t a = l.off[t], n = l.off[t + 1] - a;
-          if (!n) continue;
-          memcpy(&doc_all[at], &l.doc[a], n * sizeof(uint32_t));
-          memcpy(&field_all[at], &l.field[a], n);
-          memcpy(&tf_all[at], &l.tf[a], n * sizeof(uint16_t));
-          at += n;
-        }
-      }
-    });
-    std::vector<uint8_t> dl_all((size_t)n_fields * n_docs);
-    for (uint32_t f = 0; f < n_fields; f++) {
-      uint64_t at = 0;
-      for (const ss_raw_level_f& l : levels) { memcpy(&dl_all[(size_t)f * n_docs + at], &l.doclen[(size_t)f * l.n_docs], l.n_docs); at += l.n_docs; }
-    }
-    const auto t_build = std::chrono::steady_clock::now();
-    // (the builder replaces the image in place under the shard mutex and drops every raw level: ours go back in afterwards)
-    const int rc = ssi_bm25_upload_fields(s, n_docs, n_fields, dl_all.data(), boost, nt_all, off_all.data(), doc_all.data(), field_all.data(), tf_all.data(), 0);
-    ShardLock g(s);
-    if (rc != SS_OK) return rc;  // (no image is left behind, and no levels: the caller starts over with an upload)
-    s->raw_f.swap(levels);
-    s->raw_f_fields = n_fields;
-    s->raw_last_rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
-    s->raw_last_append_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    return SS_OK;
-  }, SS_ENOMEM, SS_EDEVICE);
-}
-
-// ... with the levels in HBM and the image rebuilt ON THE DEVICE (ssi_bm25_rebuild_from_raw_fields), positions included: the shape of
-// append_level_impl.  The host makes one pass over the level's own entries (mf_level.h), the level goes up on a stream of the commit's
-// own, the image is built beside the serving one from the block pool and swapped in under ONE lock section together with the level
-// list.  Whatever fails before the swap frees what this call allocated; the shard answers as before.
-static_assert(MF_OK == SS_OK && MF_EINVAL == SS_EINVAL && MF_ENOTSUP == SS_ENOTSUP && MF_POS_FIELD_SHIFT == BM_POS_FIELD_SHIFT, "mf_level.h");
-static int commit_level_fields_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost,
-                                    uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields, const uint16_t* tfs,
-                                    const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
-  if (!s || !level_doclen || !offs || n_terms == 0 || n_level_docs == 0 || n_level_docs > 65536u || n_fields < 2 || n_fields > 8) return SS_EINVAL;
-  if (offs[n_terms] && (!docs || !fields || !tfs)) return SS_EINVAL;
-  if (n_positions && !positions) return SS_EINVAL;
-  const bool with_pos = positions != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  ss_mf_levels* const M = ssi_mf_levels(s, true);
-  std::lock_guard<std::mutex> commits(M->commit_mu);  // commits of one shard: one after the other
-  SS_HIP(hipSetDevice(s->device));
-  std::vector<float> b(n_fields, 1.0f);
-  if (boost) b.assign(boost, boost + n_fields);
-  std::vector<ss_raw_level_mf> levels;
-  {
-    ShardLock g(s);
-    // a tier of whole lists (ss_bm25_append_sparse_fields) keeps no tfs and cannot follow a commit.  A tier of levels
-    // (ss_bm25_commit_sparse_level_fields) numbers its terms behind the dense ones: new terms start rare; a re-committed level only grows
-    // (a shrinking one would leave the tier's postings of the level pointing past the image)
-    if (s->sp_n && (ssi_bm25_sparse_levels_fields(s) != n_fields || n_terms != s->bm_n_terms / s->bm_n_fields)) return SS_ENOTSUP;
-    if (s->sp_n && level < M->raw.size() && n_level_docs < M->raw[level].n_docs) return SS_ENOTSUP;
-    if ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()) return SS_ESTATE;  // an image that was not built this way
-    if (!M->raw.empty() && M->raw[0].n_fields != n_fields) return SS_EINVAL;
-    SS_TRY(level_rules(level, n_level_docs, M->raw));
-    if (level > 0 && n_terms < M->raw[level - 1].n_terms) return SS_EINVAL;                    // the vocabulary only grows
-    if (level > 0 && (M->raw[0].d_tpos != nullptr) != with_pos) return SS_EINVAL;             // positions for every level of an image, or for none
-    if (level > 0 && memcmp(M->boost.data(), b.data(), n_fields * sizeof(float)) != 0) return SS_EINVAL;  // ... and the same boosts
-    levels.assign(M->raw.begin(), M->raw.begin() + level);
-  }
-  mf_level_host H;
-  SS_TRY(mf_level_prepare(level, n_level_docs, n_fields, n_terms, offs, docs, fields, tfs, npos, positions, n_positions, &H));
-  ss_raw_level_mf L;
-  for (uint64_t d = 0; d < (uint64_t)n_fields * n_level_docs; d++) L.psum += ss_byte4_to_int(level_doclen[d]);
-  hipStream_t bst = nullptr;
-  std::unique_ptr<ss_shard> img(new ss_shard);
-  auto undo = [&]() {
-    raw_level_mf_free(L);
-    bm_image_arrays(img.get(), [&](auto*& p) { if (p && !s->blocks.release(p)) (void)hipFree(p); });
-  };
-  CommitUndo<decltype(undo)> own{undo, bst};
-  if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
-  if (const int rc_up = raw_level_mf_upload(L, H, level_doclen, bst)) return rc_up;
-  levels.push_back(L);  // (a copy of the handles: `L` stays the owner until the swap)
-  const auto t_build = std::chrono::steady_clock::now();
-  const int rc = ssi_bm25_rebuild_from_raw_fields(s, levels, n_fields, b.data(), img.get(), bst);
-  if (rc) return rc;
-  const double rebuild_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
-  int rc_recode = SS_OK;
-  {  // the swap: searches in flight finish on the old image, whose arrays are then released
-    ShardLock g(s);
-    const bool tier = s->sp_n != 0;
-    if (level > M->raw.size() || level + 1 < M->raw.size() || (tier && ssi_bm25_sparse_levels_fields(s) != n_fields) ||
-        ((s->d_post || !s->raw.empty() || !s->raw_f.empty()) && M->raw.empty()))
-      return SS_ESTATE;  // an upload got in between
-    (void)hipStreamSynchronize(s->stream);
-    for (auto& kv : s->bm_ws) (void)hipStreamSynchronize(kv.first);
-    if (tier) {  // the sparse postings under the new lengths, boosts and merged scale: refused before anything changes, never clamped
-      if (!img->bm_merged) return SS_ENOTSUP;  // (an image without merged lists has no tier)
-      const int rc_check = ssi_bm25_sparse_levels_check(s, img.get(), bst);
-      if (rc_check) return rc_check;
-    }
-    ss_raw_level_mf replaced;
-    const bool replace = level < M->raw.size();
-    if (replace) replaced = M->raw[level];
-    std::vector<ss_raw_level_mf> keep;
-    keep.reserve((size_t)level + 1);
-    keep.assign(M->raw.begin(), M->raw.begin() + level);
-    keep.push_back(L);
-    M->boost = b;
-    own.taken = true;  // from here on the level and the image are the shard's
-    M->raw.clear();  // (free_bm25 must not release the levels that stay)
-    {  // the old image's arrays go back to the block pool: the next commit builds into them
-      s->blocks.gen++;
-      bm_image_arrays(s, [&](auto*& p) { if (p && s->blocks.release(p)) p = nullptr; });
-      std::vector<ss_block_pool::Idle> idle;
-      idle.swap(s->blocks.idle);   // (free_bm25 clears the idle list: these stay)
-      free_bm25(s, /*keep_tier=*/tier);
-      s->blocks.idle.swap(idle);
-      s->blocks.trim(3);
-    }
-    if (replace) raw_level_mf_free(replaced);
-    M->raw.swap(keep);
-    bm_image_take_fields(s, img.get());
-    if (tier) {  // avgdl and the merged scale moved: the sparse postings' codes follow (their docs of this level: ss_bm25_commit_sparse_level_fields)
-      rc_recode = ssi_bm25_sparse_levels_recode(s, s->stream);
-      if (rc_recode == SS_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc_recode = SS_EDEVICE;
-    }
-    s->raw_last_rebuild_ms = rebuild_ms;
-    s->raw_last_append_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-  }
-  return rc_recode;  // (the dense image is swapped in either way, as in append_level_impl: the caller hears that the tier could not follow)
-}
-int ss_bm25_commit_level_fields(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t n_fields, const uint8_t* level_doclen, const float* boost,
-                                uint32_t n_terms, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields, const uint16_t* tfs,
-                                const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
-  return ss_guard([&] { return commit_level_fields_impl(s, level, n_level_docs, n_fields, level_doclen, boost, n_terms, offs, docs, fields, tfs, npos,
-                                                        positions, n_positions); }, SS_ENOMEM, SS_EDEVICE);
-}
-
-int ss_bm25_incremental_info(ss_shard* s, uint32_t* n_levels, uint64_t* raw_bytes, double* last_append_ms, double* last_rebuild_ms) {
-  if (!s) return SS_EINVAL;
-  ShardLock g(s);
-  uint64_t b = 0;
-  if (const ss_mf_levels* M = ssi_mf_levels(s, false)) {
-    for (const ss_raw_level_mf& L : M->raw) b += raw_level_mf_bytes(L);
-    if (n_levels && !M->raw.empty()) { *n_levels = (uint32_t)M->raw.size(); n_levels = nullptr; }
-  }
-  for (const ss_raw_level_f& L : s->raw_f) b += L.off.size() * 8u + L.doc.size() * 7u + L.doclen.size();
-  if (n_levels && !s->raw_f.empty()) { *n_levels = (uint32_t)s->raw_f.size(); n_levels = nullptr; }
-  for (const ss_raw_level& L : s->raw)
-    b += ((uint64_t)L.n_terms + 1) * 8u + L.n_post * 6u + (L.d_tpos ? ((uint64_t)L.n_terms + 1) * 8u + L.n_post * 6u + L.n_pos * 2u : 0u);
-  if (n_levels) *n_levels = (uint32_t)s->raw.size();
-  if (raw_bytes) *raw_bytes = b;
-  if (last_append_ms) *last_append_ms = s->raw_last_append_ms;
-  if (last_rebuild_ms) *last_rebuild_ms = s->raw_last_rebuild_ms;
-  return SS_OK;
-}
-
-// Tombstones: delete_hashset of the shard (index.rs:1594; filled from delete.bin, index.rs:3798-3809, and by
-// delete_document, index.rs:5110).  Replaces the whole set; n = 0 clears it.  Both search paths skip a deleted doc before
-// it counts or ranks (add_result.rs:3435, union.rs:975, vector.rs:1450).
-int ss_set_deleted(ss_shard* s, const uint64_t* doc_ids, uint64_t n) {
-  if (!s || (n && !doc_ids)) return SS_EINVAL;
-  uint64_t mx = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    if (doc_ids[i] >= 0xFFFFFFFFull) return SS_EINVAL;
-    mx = std::max(mx, doc_ids[i]);
-  }
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call replaces; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (s->d_deleted) { (void)hipFree(s->d_deleted); s->d_deleted = nullptr; }
-  s->deleted_words = 0;
-  s->n_deleted = 0;
-  if (n == 0) return SS_OK;
-  std::vector<uint32_t> bits((size_t)(mx >> 5) + 1, 0u);
-  uint64_t distinct = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    uint32_t& w = bits[(size_t)(doc_ids[i] >> 5)];
-    const uint32_t b = 1u << (doc_ids[i] & 31u);
-    distinct += !(w & b);
-    w |= b;
-  }
-  SS_HIP(hipMalloc(&s->d_deleted, bits.size() * sizeof(uint32_t)));
-  SS_HIP(hipMemcpy(s->d_deleted, bits.data(), bits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  s->deleted_words = bits.size();
-  s->n_deleted = distinct;
-  return SS_OK;
-}
-
-// ---- facet filter (facet.hip): facet.bin records on the device, a filtered search = the search with the filter's exclusion
-// bitmap standing in for the tombstone bitmap
-int ss_facet_upload(ss_shard* s, uint64_t n_docs, uint32_t record_size, const uint8_t* records) {
-  if (!s || !records || n_docs == 0 || record_size == 0 || n_docs > 0xFFFFFFFEull) return SS_EINVAL;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (s->d_facets) { (void)hipFree(s->d_facets); s->d_facets = nullptr; }
-  s->facet_docs = 0; s->facet_record_size = 0;
-  ssi_facet_side_drop(s);  // the reserved room and the rank tables described the image that went
-  SS_HIP(hipMalloc(&s->d_facets, (size_t)n_docs * record_size));
-  SS_HIP(hipMemcpy(s->d_facets, records, (size_t)n_docs * record_size, hipMemcpyHostToDevice));
-  s->facet_docs = n_docs;
-  s->facet_record_size = record_size;
-  return SS_OK;
-}
-
-// ---- the facet image committed level by level (facet_commit.h): the records of one 65 536-doc level behind (an append) or over (the
-// re-commit of the last level) the image's rows, every registered rank column extended with them.  O(level); nothing of the shard is
-// read but -- when the room is used up -- one device-to-device copy into an image half as large again.
-extern "C++" {
-namespace {
-// the shard's streams and the callers' own (filtered searches on their streams read the records) idle; caller holds the lock
-int facet_quiesce(ss_shard* s) {
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  SS_HIP(hipDeviceSynchronize());
-  return SS_OK;
-}
-struct DevBuf {  // a scratch device block freed when the call returns
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { SS_HIP(hipMalloc(&p, std::max<size_t>(bytes, 16))); return SS_OK; }
-};
-template <typename T>
-void swap_in(T*& dst, DevBuf& b) {  // the block becomes the shard's, the shard's old one is the DevBuf's to free
-  T* old = dst;
-  dst = (T*)b.p;
-  b.p = old;
-}
-}  // namespace
-}  // extern "C++"
-
-int ss_facet_append_level(ss_shard* s, uint32_t level, uint32_t n_level_docs, uint32_t record_size, const uint8_t* records) {
-  if (!s || !records || n_level_docs == 0 || n_level_docs > 65536u || record_size == 0) return SS_EINVAL;
-  ShardLock g(s);
-  const bool have = s->d_facets != nullptr;
-  const uint64_t old_docs = have ? s->facet_docs : 0, base_doc = (uint64_t)level * 65536u, new_docs = base_doc + n_level_docs;
-  if (have) {
-    if (record_size != s->facet_record_size) return SS_EINVAL;
-    const uint64_t last = (old_docs - 1) / 65536u;  // the last level held (an image holds at least one doc)
-    const bool last_full = old_docs % 65536u == 0;
-    if (level < last || level > last + 1) return SS_EINVAL;         // older than the last level, beyond the next one
-    if (level == last + 1 && !last_full) return SS_EINVAL;          // only the last level may be partial
-    if (level == last && new_docs < old_docs) return SS_EINVAL;     // a re-committed level never shrinks
-  } else if (level != 0) {
-    return SS_EINVAL;
-  }
-  if (new_docs > 0xFFFFFFFEull) return SS_ENOTSUP;
-  SS_TRY(facet_quiesce(s));
-  ss_facet_side* S = ssi_facet_side(s, true);
-  if (!S) return SS_ENOMEM;
-  const uint32_t n_ranks = have ? S->n_ranks : 0u;
-  // staged aside and checked: the level's records, and for every registered string facet the level's slice of the rank column.  The
-  // 64-bit counter of ids beyond a table stands at the HEAD of the block (hipMalloc's alignment: the gather kernel adds to it
-  // atomically, which wants 8 bytes' alignment whatever the level's size), records and column slices behind it at multiples of 256
-  const size_t level_bytes = (size_t)n_level_docs * record_size, o_rec = 256, o_cols = o_rec + ((level_bytes + 255) & ~(size_t)255);
-  DevBuf stage;
-  SS_TRY(stage.alloc(o_cols + (size_t)n_ranks * n_level_docs * 4));
-  unsigned long long* d_bad = (unsigned long long*)stage.p;
-  uint8_t* d_stage = (uint8_t*)stage.p + o_rec;
-  uint32_t* d_cols = (uint32_t*)((uint8_t*)stage.p + o_cols);
-  SS_HIP(hipMemcpyAsync(d_stage, records, level_bytes, hipMemcpyHostToDevice, s->stream));
-  SS_HIP(hipMemsetAsync(d_bad, 0, 8, s->stream));
-  for (uint32_t r = 0; r < n_ranks; r++) {
-    const ss_facet_rank& R = S->ranks[r];
-    SS_TRY(ssi_facet_rank_gather(d_stage, record_size, R.offset, R.type, n_level_docs, R.d_rank, R.n_ids,
-                                 d_cols + (size_t)r * n_level_docs, d_bad, s->stream));
-  }
-  unsigned long long bad = 0;
-  SS_HIP(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s->stream));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (bad) return SS_EINVAL;  // an id beyond a registered table: the table for the new id space comes first
-  // room: the arrays as they are, or -- all allocated before anything is swapped -- their successors with the old rows copied over
-  const uint64_t cap = have ? std::max<uint64_t>(S->cap_docs, old_docs) : 0;
-  uint64_t new_cap = cap;
-  uint8_t* img = s->d_facets;
-  DevBuf grown[1 + SS_MAX_STRING_RANKS];
-  if (new_docs > cap) {
-    new_cap = have ? std::max<uint64_t>(new_docs, cap + cap / 2) : std::max<uint64_t>(new_docs, S->cap_docs);
-    SS_TRY(grown[0].alloc((size_t)new_cap * record_size));
-    img = (uint8_t*)grown[0].p;
-    if (have) SS_HIP(hipMemcpyAsync(img, s->d_facets, (size_t)old_docs * record_size, hipMemcpyDeviceToDevice, s->stream));
-    for (uint32_t r = 0; r < n_ranks; r++) {
-      SS_TRY(grown[1 + r].alloc((size_t)new_cap * 4));
-      SS_HIP(hipMemcpyAsync(grown[1 + r].p, S->ranks[r].d_col, (size_t)old_docs * 4, hipMemcpyDeviceToDevice, s->stream));
-    }
-  }
-  // Everything that can be refused or run out of memory lies behind; what follows are device-to-device copies.  Into room that was
-  // free, or into the successors, they touch nothing a reader sees before the doc count moves; the re-commit of the last level writes
-  // over that level's rows IN PLACE, so a device error from here on (SS_EDEVICE: the device is lost to the shard anyway) may leave
-  // part of the new level under the old doc count -- the one exception to "a failed call changes nothing" (seekstorm_hip.h).
-  SS_HIP(hipMemcpyAsync(img + (size_t)base_doc * record_size, d_stage, level_bytes, hipMemcpyDeviceToDevice, s->stream));
-  for (uint32_t r = 0; r < n_ranks; r++) {
-    uint32_t* col = new_docs > cap ? (uint32_t*)grown[1 + r].p : S->ranks[r].d_col;
-    SS_HIP(hipMemcpyAsync(col + base_doc, d_cols + (size_t)r * n_level_docs, (size_t)n_level_docs * 4, hipMemcpyDeviceToDevice, s->stream));
-  }
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (new_docs > cap) {  // the swap: the old arrays leave with the DevBufs
-    swap_in(s->d_facets, grown[0]);
-    for (uint32_t r = 0; r < n_ranks; r++) swap_in(S->ranks[r].d_col, grown[1 + r]);
-  }
-  S->cap_docs = new_cap;
-  s->facet_docs = new_docs;
-  s->facet_record_size = record_size;
-  return SS_OK;
-}
-
-int ss_facet_reserve(ss_shard* s, uint64_t n_docs_cap) {
-  if (!s) return SS_EINVAL;
-  if (n_docs_cap > 0xFFFFFFFEull) return SS_ENOTSUP;
-  ShardLock g(s);
-  ss_facet_side* S = ssi_facet_side(s, true);
-  if (!S) return SS_ENOMEM;
-  if (!s->d_facets) {  // no image yet: the first level takes the room
-    S->cap_docs = std::max(S->cap_docs, n_docs_cap);
-    return SS_OK;
-  }
-  const uint64_t cap = std::max<uint64_t>(S->cap_docs, s->facet_docs);
-  if (n_docs_cap <= cap) { S->cap_docs = cap; return SS_OK; }
-  SS_TRY(facet_quiesce(s));
-  DevBuf grown[1 + SS_MAX_STRING_RANKS];
-  SS_TRY(grown[0].alloc((size_t)n_docs_cap * s->facet_record_size));
-  SS_HIP(hipMemcpy(grown[0].p, s->d_facets, (size_t)s->facet_docs * s->facet_record_size, hipMemcpyDeviceToDevice));
-  for (uint32_t r = 0; r < S->n_ranks; r++) {
-    SS_TRY(grown[1 + r].alloc((size_t)n_docs_cap * 4));
-    SS_HIP(hipMemcpy(grown[1 + r].p, S->ranks[r].d_col, (size_t)s->facet_docs * 4, hipMemcpyDeviceToDevice));
-  }
-  swap_in(s->d_facets, grown[0]);
-  for (uint32_t r = 0; r < S->n_ranks; r++) swap_in(S->ranks[r].d_col, grown[1 + r]);
-  S->cap_docs = n_docs_cap;
-  return SS_OK;
-}
-
-int ss_facet_info(ss_shard* s, uint64_t* n_docs, uint32_t* record_size, uint64_t* capacity_docs, uint32_t* n_rank_tables) {
-  if (!s) return SS_EINVAL;
-  ShardLock g(s);
-  const ss_facet_side* S = ssi_facet_side(s, false);
-  const uint64_t docs = s->d_facets ? s->facet_docs : 0;
-  if (n_docs) *n_docs = docs;
-  if (record_size) *record_size = s->d_facets ? s->facet_record_size : 0u;
-  if (capacity_docs) *capacity_docs = std::max<uint64_t>(S ? S->cap_docs : 0, docs);
-  if (n_rank_tables) *n_rank_tables = S && s->d_facets ? S->n_ranks : 0u;
-  return SS_OK;
-}
-
-// String sorts: the host's table id -> rank (O(distinct values)), the device's column doc -> rank (one gather per table or commit)
-int ss_facet_set_string_ranks(ss_shard* s, uint32_t facet_offset, uint32_t facet_type, uint32_t n_ids, const uint32_t* rank) {
-  if (!s || (n_ids && !rank)) return SS_EINVAL;
-  if (facet_type != SS_FACET_STRING16 && facet_type != SS_FACET_STRING32) return SS_EINVAL;
-  ShardLock g(s);
-  if (!s->d_facets) return SS_ESTATE;
-  if ((uint64_t)facet_offset + ssi_facet_width(facet_type) > s->facet_record_size) return SS_EINVAL;
-  ss_facet_side* S = ssi_facet_side(s, true);
-  if (!S) return SS_ENOMEM;
-  uint32_t at = 0;
-  while (at < S->n_ranks && !(S->ranks[at].offset == facet_offset && S->ranks[at].type == facet_type)) at++;
-  if (n_ids == 0) {  // forget the table
-    if (at == S->n_ranks) return SS_OK;
-    SS_TRY(facet_quiesce(s));
-    (void)hipFree(S->ranks[at].d_rank);
-    (void)hipFree(S->ranks[at].d_col);
-    for (uint32_t i = at; i + 1 < S->n_ranks; i++) S->ranks[i] = S->ranks[i + 1];
-    S->ranks[--S->n_ranks] = ss_facet_rank{};
-    return SS_OK;
-  }
-  if (at == S->n_ranks && S->n_ranks == SS_MAX_STRING_RANKS) return SS_ENOTSUP;
-  SS_TRY(facet_quiesce(s));
-  const uint64_t cap = std::max<uint64_t>(S->cap_docs, s->facet_docs);
-  DevBuf tab, col, cnt;  // built aside: the table and column in force stay until the new ones are whole
-  SS_TRY(tab.alloc((size_t)n_ids * 4));
-  SS_TRY(col.alloc((size_t)cap * 4));
-  SS_TRY(cnt.alloc(8));
-  SS_HIP(hipMemcpyAsync(tab.p, rank, (size_t)n_ids * 4, hipMemcpyHostToDevice, s->stream));
-  SS_HIP(hipMemsetAsync(cnt.p, 0, 8, s->stream));
-  SS_TRY(ssi_facet_rank_gather(s->d_facets, s->facet_record_size, facet_offset, facet_type, s->facet_docs, (const uint32_t*)tab.p, n_ids,
-                               (uint32_t*)col.p, (unsigned long long*)cnt.p, s->stream));
-  unsigned long long bad = 0;
-  SS_HIP(hipMemcpyAsync(&bad, cnt.p, 8, hipMemcpyDeviceToHost, s->stream));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (bad) return SS_EINVAL;  // a doc holds an id the table does not name (the crate would panic on it)
-  ss_facet_rank& R = S->ranks[at];
-  swap_in(R.d_rank, tab);
-  swap_in(R.d_col, col);
-  R.offset = facet_offset; R.type = facet_type; R.n_ids = n_ids;
-  if (at == S->n_ranks) S->n_ranks++;
-  S->cap_docs = cap;
-  return SS_OK;
-}
-
-int ss_facet_string_ranks(ss_shard* s, uint32_t n, const uint32_t* doc_ids, uint32_t facet_offset, uint32_t facet_type, uint32_t* out_rank) {
-  if (!s || (n && (!doc_ids || !out_rank))) return SS_EINVAL;
-  if (facet_type != SS_FACET_STRING16 && facet_type != SS_FACET_STRING32) return SS_EINVAL;
-  ShardLock g(s);
-  const uint32_t* d_col = s->d_facets ? ssi_facet_rank_column(s, facet_offset, facet_type) : nullptr;
-  if (!d_col) return SS_ESTATE;
-  if (n == 0) return SS_OK;
-  SS_HIP(hipSetDevice(s->device));
-  SS_TRY(ensure_qstage(s, (size_t)n * 8));
-  uint32_t *d_out = (uint32_t*)s->d_qstage, *d_docs = d_out + n;
-  SS_HIP(hipMemcpyAsync(d_docs, doc_ids, (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
-  SS_TRY(ssi_facet_rank_read(d_col, s->facet_docs, d_docs, n, d_out, s->stream));
-  SS_HIP(hipMemcpyAsync(out_rank, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  return SS_OK;
-}
-
-// delete_document / delete_documents (index.rs:5099-5140): docs ADDED to the tombstone set -- the ids go up, a scatter kernel ORs their
-// bits in and counts those that were clear, so n_deleted stays the number of distinct docs.  The bitmap grows when an id lies beyond
-// its words (then to cover every doc of the images, so that the deletes that follow find their words).
-int ss_add_deleted(ss_shard* s, const uint64_t* doc_ids, uint64_t n) {
-  if (!s || (n && !doc_ids)) return SS_EINVAL;
-  uint64_t mx = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    if (doc_ids[i] >= 0xFFFFFFFFull) return SS_EINVAL;
-    mx = std::max(mx, doc_ids[i]);
-  }
-  if (n == 0) return SS_OK;
-  std::vector<uint32_t> ids(doc_ids, doc_ids + n);
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call writes; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  const uint64_t old_words = s->d_deleted ? s->deleted_words : 0;
-  uint64_t words = old_words;
-  DevBuf stage, grown;
-  if ((mx >> 5) + 1 > old_words) {
-    const uint64_t docs = std::max<uint64_t>(std::max<uint64_t>(s->bm_n_docs, s->facet_docs), s->n_rows);
-    words = std::max<uint64_t>((mx >> 5) + 1, (docs + 31) / 32);
-    SS_TRY(grown.alloc((size_t)words * 4));
-    if (old_words) SS_HIP(hipMemcpyAsync(grown.p, s->d_deleted, (size_t)old_words * 4, hipMemcpyDeviceToDevice, s->stream));
-    SS_HIP(hipMemsetAsync((uint32_t*)grown.p + old_words, 0, (size_t)(words - old_words) * 4, s->stream));
-  }
-  SS_TRY(stage.alloc((size_t)n * 4 + 8));
-  unsigned long long* d_new = (unsigned long long*)stage.p;
-  SS_HIP(hipMemsetAsync(d_new, 0, 8, s->stream));
-  SS_HIP(hipMemcpyAsync(d_new + 1, ids.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->stream));
-  SS_TRY(ssi_deleted_scatter(grown.p ? (uint32_t*)grown.p : s->d_deleted, (const uint32_t*)(d_new + 1), n, d_new, s->stream));
-  unsigned long long fresh = 0;
-  SS_HIP(hipMemcpyAsync(&fresh, d_new, 8, hipMemcpyDeviceToHost, s->stream));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  // (Without growth the scatter wrote the live bitmap: had the read-back or the wait above failed, bits would stand that n_deleted
-  // does not count.  Harmless: a live bitmap means n_deleted != 0 -- ss_set_deleted frees it with the last doc --, which is all the
-  // kernels ask of the number, and a set bit only ever says "deleted", which the caller asked for.)
-  if (grown.p) swap_in(s->d_deleted, grown);  // (the old bitmap leaves with the DevBuf)
-  s->deleted_words = words;
-  s->n_deleted = (old_words ? s->n_deleted : 0) + fresh;
-  return SS_OK;
-}
-
-
-// Probe-index budget of the NEXT image build (bytes; 0 = half of the free device memory).  Rows (1.9 MB per posting list
-// at 10 M docs) go to the longest lists first; a query touching a list without a row is ranked by the scan kernels.
-int ss_bm25_set_probe_budget(ss_shard* s, uint64_t max_bytes) {
-  if (!s) return SS_EINVAL;
-  ShardLock g(s);
-  s->probe_budget = max_bytes;
-  return SS_OK;
-}
-
-// 1 per term whose posting lists (all fields) have probe rows: such queries can take the pruned strategy
-int ss_bm25_term_probed(ss_shard* s, uint32_t n, const uint32_t* terms, uint8_t* out) {
-  if (!s || !terms || !out) return SS_EINVAL;
-  if (!s->d_post) return SS_ESTATE;
-  for (uint32_t i = 0; i < n; i++) {
-    if (terms[i] >= s->bm_n_terms / s->bm_n_fields) return SS_EINVAL;
-    uint8_t ok = s->bm_probe_rows != 0;
-    for (uint32_t f = 0; ok && f < s->bm_n_fields; f++) {
-      const uint32_t v = terms[i] * s->bm_n_fields + f;
-      if (s->h_probe_row[v] == BM_NO_PROBE_ROW && s->h_df[v] != 0) ok = 0;
-      else if (s->probe_pool_rows && s->h_probe_row[v] >= s->probe_pool_begin && s->h_probe_row[v] < s->probe_pool_begin + s->probe_pool_rows)
-        ok = 2;  // a row from the pool: a later host-pointer batch may take it away
-    }
-    out[i] = ok;
-  }
-  return SS_OK;
-}
-
-int ss_bm25_set_strategy(ss_shard* s, int strategy) {
-  if (!s || strategy < SS_BM25_AUTO || strategy > SS_BM25_EXHAUSTIVE_F32) return SS_EINVAL;
-  ShardLock g(s);
-  s->bm_strategy = strategy;
-  return SS_OK;
-}
-
-int ss_bm25_fields_info(ss_shard* s, uint32_t* n_fields, uint32_t* merged_lists, uint32_t* positions) {
-  if (!s) return SS_EINVAL;
-  if (!s->d_post) return SS_ESTATE;
-  if (n_fields) *n_fields = bm_real_fields(s);
-  if (merged_lists) *merged_lists = s->bm_merged ? 1u : 0u;
-  if (positions) *positions = (s->bm_n_fields == 1 ? s->d_pos != nullptr : s->d_pos32 != nullptr) ? 1u : 0u;
-  return SS_OK;
-}
-int ss_bm25_info(ss_shard* s, uint64_t* n_docs, float* avgdl, uint32_t* n_terms, uint64_t* n_postings) {
-  if (!s) return SS_EINVAL;
-  if (!s->d_post) return SS_ESTATE;
-  if (n_docs) *n_docs = s->bm_n_docs;
-  if (avgdl) *avgdl = s->bm_avgdl;
-  if (n_terms) *n_terms = s->bm_n_terms / s->bm_n_fields;
-  if (n_postings) *n_postings = s->bm_n_post;
-  return SS_OK;
-}
-
-int ss_bm25_term_df(ss_shard* s, uint32_t n, const uint32_t* terms, uint64_t* df_out) {
-  if (!s || !terms || !df_out) return SS_EINVAL;
-  if (!s->d_post) return SS_ESTATE;
-  for (uint32_t i = 0; i < n; i++) {
-    const uint32_t n_dense = s->bm_n_terms / s->bm_n_fields;
-    if (terms[i] >= n_dense + s->sp_n) return SS_EINVAL;
-    if (terms[i] >= n_dense) df_out[i] = s->h_sp_base[terms[i] - n_dense + 1] - s->h_sp_base[terms[i] - n_dense];  // sparse tier
-    else df_out[i] = s->bm_n_fields > 1 ? s->h_df_real[terms[i]] : s->h_df[terms[i]];
-  }
-  return SS_OK;
-}
-
-int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
-                                const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
-  if (!s || !offs || n_lists == 0 || (offs[n_lists] > offs[0] && (!docs || !tfs))) return SS_EINVAL;
-  return ss_guard([&]() -> int {
-    ShardLock g(s);
-    if (s->raw.empty()) return SS_ESTATE;  // an image that grows level by level (ss_bm25_append_level)
-    SS_HIP(hipSetDevice(s->device));
-    SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays the level replaces
-    return ssi_bm25_append_sparse_level(s, level, n_lists, offs, docs, tfs, npos, positions, n_positions);
-  }, SS_ENOMEM, SS_EDEVICE);
-}
-// ... of an image with several indexed fields whose levels came through ss_bm25_commit_level_fields (include/seekstorm_hip.h)
-int ss_bm25_commit_sparse_level_fields(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                                       const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions) {
-  if (!s || !offs || n_lists == 0 || (offs[n_lists] > offs[0] && (!docs || !fields || !tfs)) || (n_positions && !positions)) return SS_EINVAL;
-  return ss_guard([&]() -> int {
-    ShardLock g(s);
-    if (!s->d_post) return SS_ESTATE;
-    SS_HIP(hipSetDevice(s->device));
-    SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays the level replaces
-    return ssi_bm25_commit_sparse_level_fields(s, level, n_lists, offs, docs, fields, tfs, npos, positions, n_positions);
-  }, SS_ENOMEM, SS_EDEVICE);
-}
-// Whole lists of rare terms behind the tier's: with_fields = entries (doc, field, tf) of an image with several indexed fields -- said
-// apart from `fields`, which postings present must bring then --; with_positions = the entry brings positions (none at all: still
-// a tier that carries them).  The first new list's term id continues behind the dense terms and the lists the tier holds.
-static int append_sparse(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, bool with_fields, const uint8_t* fields,
-                         const uint16_t* tfs, bool with_positions, const uint16_t* positions, uint64_t n_positions, const uint16_t* npos,
-                         uint32_t* first_term_id_out) {
-  if (!s || !offs || (n_lists && offs[n_lists] > offs[0] && (!docs || (with_fields && !fields) || !tfs)) || (with_positions && n_positions && !positions))
-    return SS_EINVAL;
-  return ss_guard([&]() -> int {
-    static const uint16_t none = 0;
-    if (with_positions && !positions) positions = &none;
-    ShardLock g(s);
-    SS_HIP(hipSetDevice(s->device));
-    SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams may still read the arrays an append replaces
-    const uint32_t first = s->bm_n_terms / std::max<uint32_t>(s->bm_n_fields, 1) + s->sp_n;
-    SS_TRY(with_fields ? ssi_bm25_append_sparse_fields(s, n_lists, offs, docs, fields, tfs, positions, n_positions, npos)
-                       : ssi_bm25_append_sparse(s, n_lists, offs, docs, tfs, positions, n_positions, npos));
-    if (first_term_id_out) *first_term_id_out = first;
-    return SS_OK;
-  }, SS_ENOMEM, SS_EDEVICE);
-}
-int ss_bm25_append_sparse(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
-                          uint32_t* first_term_id_out) {
-  return append_sparse(s, n_lists, offs, docs, false, nullptr, tfs, false, nullptr, 0, nullptr, first_term_id_out);
-}
-int ss_bm25_append_sparse_fields(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                                 const uint16_t* tfs, uint32_t* first_term_id_out) {
-  return append_sparse(s, n_lists, offs, docs, true, fields, tfs, false, nullptr, 0, nullptr, first_term_id_out);
-}
-int ss_bm25_append_sparse_positions(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs,
-                                    const uint16_t* positions, uint64_t n_positions, const uint16_t* npos, uint32_t* first_term_id_out) {
-  return append_sparse(s, n_lists, offs, docs, false, nullptr, tfs, true, positions, n_positions, npos, first_term_id_out);
-}
-int ss_bm25_append_sparse_fields_positions(ss_shard* s, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
-                                           const uint16_t* tfs, const uint16_t* positions, uint64_t n_positions, const uint16_t* npos,
-                                           uint32_t* first_term_id_out) {
-  return append_sparse(s, n_lists, offs, docs, true, fields, tfs, true, positions, n_positions, npos, first_term_id_out);
-}
-int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, uint64_t* bytes) {
-  if (!s) return SS_EINVAL;
-  ShardLock g(s);
-  const uint64_t np = s->h_sp_base.empty() ? 0 : s->h_sp_base.back();
-  if (n_lists) *n_lists = s->sp_n;
-  if (n_postings) *n_postings = np;
-  const uint32_t tf_row = ssi_bm25_sparse_levels_fields(s);  // (a tier of levels keeps the tf of every indexed field beside a posting)
-  if (bytes) *bytes = np * (8 + 2 * (uint64_t)tf_row) + ((uint64_t)s->sp_n + 1) * 8;
   return SS_OK;
 }
 
@@ -2765,14 +1598,6 @@ static int bm25_search_deep(ss_shard* s, uint32_t nq, const ss_bm25_query* q, ui
   return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); });
 }
 
-static int vec_search_host_deep(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
-                                const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
-                                uint32_t* out_clusters, const float* query_norm) {
-  if (nq == 0) return SS_OK;
-  ShardLock g(s);
-  return ssi_vec_search_deep_locked(s, nq, queries, elem, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total, out_clusters, query_norm);
-}
-
 int ss_bm25_search_filtered(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
                             const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
                             uint64_t* out_total) {
@@ -2865,10 +1690,6 @@ int ss_vec_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const float* que
 // SearchMode::Hybrid over shards on different GPUs: both shard tasks with (offset 0, length k = offset + length), ONE all-gather
 // of both lists, the two cross-shard concatenations sorted, RRF over them and sort / offset / length (search.rs:1962-2035,
 // 2098-2119) on the device; result_count_total = sum over the shards of max(lexical, vector) (1919-1921).
-// (comm.hip: the exchange with the hybrid fusion on the host when host_fuse)
-extern "C++" int ssi_comm_exchange_hf(ss_comm* c, uint32_t nq, int n_lists, const ss_dev_list* L, const uint64_t* d_tot_a, const uint64_t* d_tot_b,
-                         int local_rc, bool hybrid, uint32_t offset, uint32_t length, uint64_t* out_doc, float* out_score,
-                         uint8_t* out_source, uint32_t* out_count, uint64_t* out_total, hipStream_t st, bool host_fuse);
 int ss_hybrid_search_sharded(ss_shard* s, ss_comm* c, uint32_t nq, const ss_bm25_query* q, uint32_t rt, const float* queries, float thr,
                              uint32_t k, uint32_t offset, uint32_t length, uint64_t* out_doc, float* out_score, uint8_t* out_source,
                              uint32_t* out_count, uint64_t* out_total) {
@@ -3850,737 +2671,6 @@ int ss_bm25_search_filtered_dev(ss_shard* s, uint32_t nq, const ss_bm25_query* d
                            (ops_mask & 8u) != 0, (ops_mask & 16u) != 0, (ops_mask & 32u) != 0, (ops_mask & 64u) != 0, (ops_mask & 128u) != 0,
                            (ops_mask >> 24) & 0xFu ? (ops_mask >> 24) & 0xFu : 0xFFFFFFFFu);
   });
-}
-
-// ------------------------------------------------------------------ vectors
-// end of every vector-image build: the Euclidean side data (f32: the two augmented columns; i8: the records' sums of
-// squares), then the per-batch workspace
-static int vec_finish(ss_shard* s) {
-  if (s->vec_similarity == SS_SIM_EUCLIDEAN) {
-    int rc = s->d_X ? ssi_vec_augment(s, s->stream) : ssi_vec8_row_sq(s, s->stream);
-    if (rc) return rc;
-    SS_HIP(hipStreamSynchronize(s->stream));
-  }
-  return ssi_vec_alloc_ws(s);
-}
-
-static int vec_alloc(ss_shard* s, uint64_t n_rows, uint32_t dim) {
-  free_vec(s);
-  s->n_rows = n_rows;
-  s->dim = dim;
-  // Euclidean: the scan computes -|q - x|^2 as the dot product of [x, |x|^2, 1] with [2 q, -1, -|q|^2] -- two more columns
-  const uint32_t dim_img = dim + (s->vec_similarity == SS_SIM_EUCLIDEAN ? 2u : 0u);
-  s->dim_pad = (dim_img + VS_KC - 1) / VS_KC * VS_KC;
-  s->n_rows_pad = (n_rows + VS_TR - 1) / VS_TR * VS_TR;
-  const size_t bytes = (size_t)s->n_rows_pad * s->dim_pad * sizeof(float);
-  SS_HIP(hipMalloc(&s->d_X, bytes));
-  if (s->dim_pad != dim) SS_HIP(hipMemsetAsync(s->d_X, 0, bytes, s->stream));
-  else if (s->n_rows_pad != n_rows)
-    SS_HIP(hipMemsetAsync(s->d_X + (size_t)n_rows * s->dim_pad, 0, (size_t)(s->n_rows_pad - n_rows) * s->dim_pad * sizeof(float),
-                          s->stream));
-  return SS_OK;
-}
-
-int ss_vec_upload(ss_shard* s, uint64_t n_rows, uint32_t dim, const float* rows, const uint32_t* row_doc_ids) {
-  if (!s || !rows || n_rows == 0 || dim == 0) return SS_EINVAL;
-  if (n_rows > 0xFFFFFFFEull) return SS_ENOTSUP;
-  bool multi = false;
-  if (row_doc_ids) {  // several records per doc (one per field x chunk, vector.rs:561-576) -> dedup in the refine kernel
-    std::vector<uint32_t> tmp(row_doc_ids, row_doc_ids + n_rows);
-    std::sort(tmp.begin(), tmp.end());
-    multi = std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end();
-    if (!tmp.empty() && tmp.back() == SS_NO_DOC) return SS_EINVAL;
-  }
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  int rc = vec_alloc(s, n_rows, dim);
-  if (rc) { free_vec(s); return rc; }
-  SS_HIP(hipMemcpy2DAsync(s->d_X, (size_t)s->dim_pad * sizeof(float), rows, (size_t)dim * sizeof(float),
-                          (size_t)dim * sizeof(float), n_rows, hipMemcpyHostToDevice, s->stream));
-  s->vec_multi_record = multi;
-  if (row_doc_ids) {
-    SS_HIP(hipMalloc(&s->d_row_doc, n_rows * sizeof(uint32_t)));
-    SS_HIP(hipMemcpyAsync(s->d_row_doc, row_doc_ids, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  }
-  SS_HIP(hipStreamSynchronize(s->stream));
-  return vec_finish(s);
-}
-
-// the i8 image's rows ("i8 (quantised) vectors" below)
-static int vec8_alloc(ss_shard* s, uint64_t n_rows, uint32_t dim) {
-  free_vec(s);
-  s->n_rows = n_rows;
-  s->dim = dim;
-  s->dim_pad8 = (dim + 127u) / 128u * 128u;
-  if (s->dim_pad8 > 2560u) { free_vec(s); return SS_ENOTSUP; }  // the 64 queries stay in LDS: 64 x dim_pad8 <= 160 KB
-  s->n_rows_pad = (n_rows + VS_TR - 1) / VS_TR * VS_TR;
-  const size_t bytes = (size_t)s->n_rows_pad * s->dim_pad8;
-  SS_HIP(hipMalloc(&s->d_X8, bytes));
-  if (s->dim_pad8 != dim || s->n_rows_pad != n_rows) SS_HIP(hipMemsetAsync(s->d_X8, 0, bytes, s->stream));  // padding is interleaved
-  return SS_OK;
-}
-
-// vector.bin (writer vector.rs:1066-1094, reader 1279-1298): per level u32 cluster_count, cluster_count x u32 child_count,
-// then the records cluster after cluster, each a packed 24-byte VectorHeader (u16 doc_id first, vector.rs:62-73) + dim x f32.
-// Shard-local doc id of a record = (level << 16) | doc_id (vector.rs:1448).  The payloads go to HBM straight from the
-// file bytes with a strided copy per level; the cluster structure is kept for the ANN modes (vec_ann.hip).
-// i8 = Precision::I8 records (dim x i8 after the header); use_scale keeps VectorHeader.scale (f32 at byte 10) per record
-// for dot_i8_quantized (ScalarQuantizationI8 with Dot / Euclidean; Cosine scores are the raw integer dot, vector.rs:1331-1333)
-static int vec_bin_upload(ss_shard* s, const uint8_t* bytes, uint64_t len, uint32_t dim, bool i8, bool use_scale) {
-  if (!s || !bytes || dim == 0) return SS_EINVAL;
-  const uint64_t rec = 24u + (uint64_t)dim * (i8 ? 1u : 4u);
-  struct Lvl { uint64_t first, n; };
-  std::vector<Lvl> levels;
-  std::vector<uint32_t> ids, level_clusters, child_counts;
-  std::vector<uint16_t> fields;  // VectorHeader.field_id (u32 at byte 2); the reference compares it as u16 (vector.rs:1398)
-  std::vector<float> scales, norms;
-  uint64_t pos = 0;
-  while (pos < len) {
-    if (pos + 4 > len) return SS_EINVAL;
-    uint32_t clusters;
-    memcpy(&clusters, bytes + pos, 4);
-    pos += 4;
-    if (pos + (uint64_t)clusters * 4u > len) return SS_EINVAL;
-    uint64_t n = 0;
-    for (uint32_t c = 0; c < clusters; c++) {
-      uint32_t child;
-      memcpy(&child, bytes + pos + 4ull * c, 4);
-      n += child;
-      child_counts.push_back(child);
-    }
-    level_clusters.push_back(clusters);
-    pos += (uint64_t)clusters * 4u;
-    if (n > (len - pos) / rec || levels.size() >= 65536u) return SS_EINVAL;
-    for (uint64_t r = 0; r < n; r++) {
-      uint16_t d;
-      memcpy(&d, bytes + pos + r * rec, 2);
-      ids.push_back((uint32_t)(levels.size() << 16) | d);
-      uint32_t fid;
-      memcpy(&fid, bytes + pos + r * rec + 2, 4);
-      fields.push_back((uint16_t)fid);
-      if (use_scale) {
-        float sc;
-        memcpy(&sc, bytes + pos + r * rec + 10, 4);
-        scales.push_back(sc);
-        memcpy(&sc, bytes + pos + r * rec + 14, 4);  // VectorHeader.norm: euclidean_i8_quantized
-        norms.push_back(sc);
-      }
-    }
-    levels.push_back({pos, n});
-    pos += n * rec;
-  }
-  const uint64_t n_rows = ids.size();
-  if (n_rows == 0) return SS_EINVAL;
-  if (n_rows > 0xFFFFFFFEull) return SS_ENOTSUP;
-  std::vector<uint32_t> tmp(ids);
-  std::sort(tmp.begin(), tmp.end());
-  const bool multi = std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end();
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  int rc = i8 ? vec8_alloc(s, n_rows, dim) : vec_alloc(s, n_rows, dim);
-  if (rc) { free_vec(s); return rc; }
-  int8_t* stage = nullptr;  // i8: row-major staging on the device, permuted into fragment order afterwards
-  if (i8 && hipMalloc(&stage, (size_t)n_rows * dim) != hipSuccess) { free_vec(s); return SS_ENOMEM; }
-  uint64_t row = 0;
-  for (const Lvl& l : levels) {
-    if (l.n == 0) continue;
-    hipError_t e = i8 ? hipMemcpy2DAsync(stage + row * dim, (size_t)dim, bytes + l.first + 24u, rec, (size_t)dim, l.n,
-                                         hipMemcpyHostToDevice, s->stream)
-                      : hipMemcpy2DAsync(s->d_X + row * s->dim_pad, (size_t)s->dim_pad * sizeof(float), bytes + l.first + 24u, rec,
-                                         (size_t)dim * sizeof(float), l.n, hipMemcpyHostToDevice, s->stream);
-    if (e != hipSuccess) { if (stage) (void)hipFree(stage); free_vec(s); return SS_EDEVICE; }
-    row += l.n;
-  }
-  if (i8) {
-    rc = ssi_vec8_permute(s, stage, s->stream);
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipFree(stage);
-    if (rc) { free_vec(s); return rc; }
-    if (use_scale) {
-      SS_HIP(hipMalloc(&s->d_row_scale, n_rows * sizeof(float)));
-      SS_HIP(hipMemcpyAsync(s->d_row_scale, scales.data(), n_rows * sizeof(float), hipMemcpyHostToDevice, s->stream));
-      SS_HIP(hipMalloc(&s->d_row_norm, n_rows * sizeof(float)));
-      SS_HIP(hipMemcpyAsync(s->d_row_norm, norms.data(), n_rows * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    }
-  }
-  s->vec_multi_record = multi;
-  SS_HIP(hipMalloc(&s->d_row_doc, n_rows * sizeof(uint32_t)));
-  SS_HIP(hipMemcpyAsync(s->d_row_doc, ids.data(), n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  SS_HIP(hipMalloc(&s->d_row_field, n_rows * sizeof(uint16_t)));
-  SS_HIP(hipMemcpyAsync(s->d_row_field, fields.data(), n_rows * sizeof(uint16_t), hipMemcpyHostToDevice, s->stream));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  rc = ssi_vec_set_clusters(s, (uint32_t)level_clusters.size(), level_clusters.data(), child_counts.data());
-  if (rc != SS_OK && rc != SS_ENOTSUP) { free_vec(s); return rc; }  // ENOTSUP (an empty cluster): AnnMode::All only
-  return vec_finish(s);
-}
-
-int ss_vec_upload_vector_bin(ss_shard* s, const uint8_t* bytes, uint64_t len, uint32_t dim) {
-  return vec_bin_upload(s, bytes, len, dim, false, false);
-}
-
-int ss_vec_upload_vector_bin_i8(ss_shard* s, const uint8_t* bytes, uint64_t len, uint32_t dim, int use_record_scale) {
-  return vec_bin_upload(s, bytes, len, dim, true, use_record_scale != 0);
-}
-
-int ss_vec_synth(ss_shard* s, uint64_t seed, uint64_t n_rows, uint32_t dim) {
-  if (!s || n_rows == 0 || dim == 0) return SS_EINVAL;
-  if (n_rows > 0xFFFFFFFEull) return SS_ENOTSUP;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  int rc = vec_alloc(s, n_rows, dim);
-  if (rc) { free_vec(s); return rc; }
-  SS_TRY(ssi_vec_synth(s, seed, s->stream));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  return vec_finish(s);
-}
-
-int ss_vec_info(ss_shard* s, uint64_t* n_rows, uint32_t* dim) {
-  if (!s) return SS_EINVAL;
-  if (!s->d_X && !s->d_X8) return SS_ESTATE;
-  if (n_rows) *n_rows = s->n_rows;
-  if (dim) *dim = s->dim;
-  return SS_OK;
-}
-
-int ss_vec_read_rows(ss_shard* s, uint64_t r0, uint64_t n, float* out) {
-  if (!s || !out) return SS_EINVAL;
-  if (!s->d_X) return SS_ESTATE;
-  if (r0 + n > s->n_rows) return SS_EINVAL;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  SS_HIP(hipMemcpy2D(out, (size_t)s->dim * sizeof(float), s->d_X + r0 * s->dim_pad, (size_t)s->dim_pad * sizeof(float),
-                     (size_t)s->dim * sizeof(float), n, hipMemcpyDeviceToHost));
-  return SS_OK;
-}
-
-// the search up to the device lists (s->d_out_* on s->stream, counts checked on the host: an overflowed batch is re-run in
-// safe mode); caller holds s->mu.  h_count: nq words of host scratch.
-extern "C++" int ssi_vec_search_host_lists(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
-                                 float thr, const ss_ann_mode* mode, uint32_t* h_count, uint32_t** d_ncl_out,
-                                 const float* query_norm, bool want_clusters, size_t out_slot) {
-  SS_HIP(hipSetDevice(s->device));
-  SS_TRY(ensure_out(s, out_slot + nq, k));  // out_slot: the lists go behind those of `out_slot` earlier queries (hybrid)
-  uint32_t* const o_doc = s->d_out_doc + out_slot * k;
-  float* const o_score = s->d_out_score + out_slot * k;
-  uint32_t* const o_count = s->d_out_count + out_slot;
-  uint64_t* const o_total = s->d_out_total + out_slot;
-  const size_t qbytes = ((size_t)nq * s->dim * elem + 15) & ~(size_t)15;
-  const size_t sbytes = query_scale ? (size_t)nq * sizeof(float) : 0;
-  const size_t nbytes = query_norm ? (size_t)nq * sizeof(float) : 0;
-  SS_TRY(ensure_qstage(s, qbytes + sbytes + nbytes + (want_clusters ? (size_t)nq * 3 * sizeof(uint32_t) : 0)));  // (three words with SS_ANN_REPORT_OBSERVED)
-  float* d_qs = query_scale ? (float*)((char*)s->d_qstage + qbytes) : nullptr;
-  float* d_qn = query_norm ? (float*)((char*)s->d_qstage + qbytes + sbytes) : nullptr;
-  uint32_t* d_ncl = want_clusters ? (uint32_t*)((char*)s->d_qstage + qbytes + sbytes + nbytes) : nullptr;
-  if (d_ncl_out) *d_ncl_out = d_ncl;
-  int rc = SS_OK;
-  AnnStateGuard ann_guard(s, s->stream, mode);
-  for (int attempt = 0; attempt < 2; attempt++) {
-    if (hipMemcpyAsync(s->d_qstage, queries, (size_t)nq * s->dim * elem, hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = SS_EDEVICE; break; }
-    if (d_qs && hipMemcpyAsync(d_qs, query_scale, sbytes, hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = SS_EDEVICE; break; }
-    if (d_qn && hipMemcpyAsync(d_qn, query_norm, nbytes, hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = SS_EDEVICE; break; }
-    rc = ssi_vec_search(s, nq, s->d_qstage, d_qs, k, thr, o_doc, o_score, o_count, o_total, s->stream,
-                        attempt == 1, mode, d_ncl, d_qn);
-    if (rc) break;
-    if (hipMemcpyAsync(h_count, o_count, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream) != hipSuccess ||
-        hipStreamSynchronize(s->stream) != hipSuccess) { rc = SS_EDEVICE; break; }
-    bool ovf = false;
-    for (uint32_t i = 0; i < nq; i++) ovf |= h_count[i] == 0xFFFFFFFFu;
-    if (!ovf) break;
-    if (attempt == 1) { rc = SS_EDEVICE; break; }  // cannot overflow in safe mode
-  }
-  return rc;
-}
-
-// A COALESCED vector batch (AnnMode::All; f32 or i8 rows): queries from, and answers into, the lane's PINNED buffers; its own stream and
-// staging (ss_common.h vmu / vstream).  The shard mutex is held while the pass is enqueued -- the scan buffers of the stream are bound
-// into the shard's fields for that long (VecWsBind) -- and NOT while it runs: 9 ms at 10 M x 768, during which lexical searches of the
-// shard (a hybrid caller's first half) used to wait for the mutex, then for the stream.
-extern "C++" int ssi_vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k, float thr,
-                                uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
-  if (nq == 0) return SS_OK;
-  std::lock_guard<std::mutex> gv(s->vmu);
-  for (int attempt = 0; attempt < 2; attempt++) {
-    {
-      std::lock_guard<std::mutex> g(s->mu);  // (a vector pass neither writes nor reads what the lexical lanes' kernels touch: no drain)
-      SS_HIP(hipSetDevice(s->device));
-      if ((elem == sizeof(float)) ? !s->d_X : !s->d_X8) return SS_ESTATE;
-      const size_t qbytes = ((size_t)nq * s->dim * elem + 15) & ~(size_t)15, sbytes = query_scale ? (size_t)nq * sizeof(float) : 0;
-      if (qbytes + sbytes > s->vq_cap) {  // (vstream is idle: vmu is ours and the batch before synchronised it)
-        if (s->d_vq) (void)hipFree(s->d_vq);
-        s->d_vq = nullptr; s->vq_cap = 0;
-        SS_HIP(hipMalloc(&s->d_vq, (qbytes + sbytes) * 2));
-        s->vq_cap = (qbytes + sbytes) * 2;
-      }
-      if ((size_t)nq * k > s->vout_cap || nq > s->vq_rows_cap) {
-        for (void* p_ : {(void*)s->d_vdoc, (void*)s->d_vscore, (void*)s->d_vcount, (void*)s->d_vtotal}) if (p_) (void)hipFree(p_);
-        s->d_vdoc = nullptr; s->d_vscore = nullptr; s->d_vcount = nullptr; s->d_vtotal = nullptr; s->vout_cap = 0; s->vq_rows_cap = 0;
-        const size_t rows = std::max<size_t>(nq, SS_VEC_BATCH), cells = std::max<size_t>((size_t)nq * k, (size_t)SS_VEC_BATCH * k);
-        SS_HIP(hipMalloc(&s->d_vdoc, cells * sizeof(uint32_t)));
-        SS_HIP(hipMalloc(&s->d_vscore, cells * sizeof(float)));
-        SS_HIP(hipMalloc(&s->d_vcount, rows * sizeof(uint32_t)));
-        SS_HIP(hipMalloc(&s->d_vtotal, rows * sizeof(uint64_t)));
-        s->vout_cap = cells; s->vq_rows_cap = rows;
-      }
-      float* d_qs = query_scale ? (float*)((char*)s->d_vq + qbytes) : nullptr;
-      SS_HIP(hipMemcpyAsync(s->d_vq, queries, (size_t)nq * s->dim * elem, hipMemcpyHostToDevice, s->vstream));
-      if (d_qs) SS_HIP(hipMemcpyAsync(d_qs, query_scale, sbytes, hipMemcpyHostToDevice, s->vstream));
-      {
-        VecWsBind bind(s, s->vstream);
-        SS_TRY(ssi_vec_search(s, nq, s->d_vq, d_qs, k, thr, s->d_vdoc, s->d_vscore, s->d_vcount, s->d_vtotal, s->vstream, attempt == 1, nullptr, nullptr, nullptr));
-      }
-      SS_HIP(hipMemcpyAsync(out_count, s->d_vcount, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s->vstream));
-      SS_HIP(hipMemcpyAsync(out_doc, s->d_vdoc, (size_t)nq * k * sizeof(uint32_t), hipMemcpyDeviceToHost, s->vstream));
-      SS_HIP(hipMemcpyAsync(out_score, s->d_vscore, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, s->vstream));
-      SS_HIP(hipMemcpyAsync(out_total, s->d_vtotal, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost, s->vstream));
-      if (!s->vev) SS_HIP(hipEventCreateWithFlags(&s->vev, hipEventDisableTiming | hipEventBlockingSync));
-      SS_HIP(hipEventRecord(s->vev, s->vstream));
-    }
-    // the pass itself: nobody waits for us but this batch's callers.  The leader SLEEPS on a blocking-sync event: hipStreamSynchronize
-    // spins, and a thread that spins through 9 ms on a box whose 64 callers share 16 CPUs uses up its time slice and is descheduled just
-    // when the pass ends -- its whole batch then comes home a scheduling quantum late (one such batch per second or two was the p99 of the
-    // T = 64 vector and hybrid callers: 17.8 / 17.0 ms against a p50 of 9.6 / 10.8, gpurun_out/r6_bench_b.json)
-    SS_HIP(hipEventSynchronize(s->vev));
-    bool ovf = false;
-    for (uint32_t i = 0; i < nq; i++) ovf |= out_count[i] == 0xFFFFFFFFu;
-    if (!ovf) return SS_OK;  // (an adversarial row order overflowed the candidate slots: once more in safe mode)
-  }
-  return SS_EDEVICE;  // cannot overflow in safe mode
-}
-
-// host-pointer searches: queries (f32 or i8 rows) and scales are staged in the shard's grow-only buffer, out_clusters
-// (observed_cluster_count, ANN modes) rides behind them
-extern "C++" int ssi_vec_search_host(ss_shard* s, uint32_t nq, const void* queries, size_t elem, const float* query_scale, uint32_t k,
-                           float thr, const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count,
-                           uint64_t* out_total, uint32_t* out_clusters, const float* query_norm) {
-  if (nq == 0) return SS_OK;
-  ShardLock g(s);
-  uint32_t* d_ncl = nullptr;
-  int rc = ssi_vec_search_host_lists(s, nq, queries, elem, query_scale, k, thr, mode, out_count, &d_ncl, query_norm, out_clusters != nullptr);
-  if (rc == SS_OK) {
-    if (hipMemcpy(out_doc, s->d_out_doc, (size_t)nq * k * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(out_score, s->d_out_score, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(out_total, s->d_out_total, (size_t)nq * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess ||
-        (d_ncl && hipMemcpy(out_clusters, d_ncl, (size_t)nq * ((mode && (mode->flags & SS_ANN_REPORT_OBSERVED)) ? 3 : 1) * sizeof(uint32_t),
-                            hipMemcpyDeviceToHost) != hipSuccess))
-      rc = SS_EDEVICE;
-  }
-  return rc;
-}
-static bool ann_skips_clusters(const ss_ann_mode* m) { return m->n_probe != 0 || m->cluster_threshold_raw > -3.4028234663852886e38f; }
-// a mode that neither skips clusters nor filters fields is AnnMode::All
-static const ss_ann_mode* ann_effective(const ss_ann_mode* m) {
-  return (m && (ann_skips_clusters(m) || m->field_mask || (m->flags & SS_ANN_REPORT_OBSERVED))) ? m : nullptr;
-}
-static int ann_mode_ok(const ss_shard* s, const ss_ann_mode* mode) {
-  if (!mode) return SS_OK;
-  if (mode->cluster_threshold_raw != mode->cluster_threshold_raw) return SS_EINVAL;
-  if (ann_skips_clusters(mode) && !s->d_row_cluster) return SS_ESTATE;
-  if (mode->field_mask && !s->d_row_field) return SS_ESTATE;
-  return SS_OK;
-}
-
-int ss_vec_search_ann(ss_shard* s, uint32_t nq, const float* queries, uint32_t k, float thr, const ss_ann_mode* mode,
-                      uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total, uint32_t* out_clusters) {
-  if (!s || !queries || !out_doc || !out_score || !out_count || !out_total) return SS_EINVAL;
-  if (k == 0) return SS_EINVAL;
-  if (!s->d_X) return SS_ESTATE;
-  SS_TRY(ann_mode_ok(s, mode));
-  mode = ann_effective(mode);
-  if (k > SS_MAX_K)  // (a page deeper than SS_MAX_K results: passes under per-query exclusion bitmaps, api_deep.hip)
-    return vec_search_host_deep(s, nq, queries, sizeof(float), nullptr, k, thr, mode, out_doc, out_score, out_count, out_total, mode ? out_clusters : nullptr, nullptr);
-  if (!mode && nq != 0 && nq <= SS_COALESCE_MAX_REQUEST && s->co_vec.max_batch) {  // AnnMode::All from concurrent callers: one pass serves them
-    ss_co_req r;
-    r.q = queries; r.nq = nq; r.k = k; r.elem = (uint32_t)sizeof(float); r.thr = thr;
-    r.out_doc = out_doc; r.out_score = out_score; r.out_count = out_count; r.out_total = out_total;
-    return ssi_co_submit(s, s->co_vec, false, &r);
-  }
-  return ssi_vec_search_host(s, nq, queries, sizeof(float), nullptr, k, thr, mode, out_doc, out_score, out_count, out_total,
-                         mode ? out_clusters : nullptr);
-}
-int ss_vec_search(ss_shard* s, uint32_t nq, const float* queries, uint32_t k, float thr, uint32_t* out_doc,
-                  float* out_score, uint32_t* out_count, uint64_t* out_total) {
-  return ss_vec_search_ann(s, nq, queries, k, thr, nullptr, out_doc, out_score, out_count, out_total, nullptr);
-}
-
-// a DEEP page on a device-pointer vector entry: the passes are steered from the host, so the queries (and their scales / norms) make one
-// trip there and the call is synchronous; the page is left in the caller's device arrays, ordered on `st`.  Caller holds the shard lock.
-static int vec_search_deep_dev_locked(ss_shard* s, uint32_t nq, const void* d_queries, size_t elem, const float* d_qscale, const float* d_qnorm, uint32_t k, float thr,
-                                      const ss_ann_mode* mode, uint32_t* d_out_doc, float* d_out_score, uint32_t* d_out_count, uint64_t* d_out_total,
-                                      uint32_t* d_out_clusters, hipStream_t st) {
-  if (nq == 0) return SS_OK;
-  const uint32_t ocw = (mode && (mode->flags & SS_ANN_REPORT_OBSERVED)) ? 3u : 1u;
-  std::vector<char> hq((size_t)nq * s->dim * elem);
-  std::vector<float> hs(d_qscale ? nq : 0), hn(d_qnorm ? nq : 0);
-  SS_HIP(hipMemcpyAsync(hq.data(), d_queries, hq.size(), hipMemcpyDeviceToHost, st));
-  if (d_qscale) SS_HIP(hipMemcpyAsync(hs.data(), d_qscale, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-  if (d_qnorm) SS_HIP(hipMemcpyAsync(hn.data(), d_qnorm, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-  SS_HIP(hipStreamSynchronize(st));
-  std::vector<uint32_t> h_doc((size_t)nq * k), h_cnt(nq), h_ncl(d_out_clusters ? (size_t)nq * ocw : 0);
-  std::vector<float> h_score((size_t)nq * k);
-  std::vector<uint64_t> h_tot(nq);
-  SS_TRY(ssi_vec_search_deep_locked(s, nq, hq.data(), elem, d_qscale ? hs.data() : nullptr, k, thr, mode, h_doc.data(), h_score.data(), h_cnt.data(), h_tot.data(),
-                                d_out_clusters ? h_ncl.data() : nullptr, d_qnorm ? hn.data() : nullptr));
-  SS_HIP(hipMemcpyAsync(d_out_doc, h_doc.data(), h_doc.size() * 4, hipMemcpyHostToDevice, st));
-  SS_HIP(hipMemcpyAsync(d_out_score, h_score.data(), h_score.size() * 4, hipMemcpyHostToDevice, st));
-  SS_HIP(hipMemcpyAsync(d_out_count, h_cnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
-  SS_HIP(hipMemcpyAsync(d_out_total, h_tot.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
-  if (d_out_clusters) SS_HIP(hipMemcpyAsync(d_out_clusters, h_ncl.data(), h_ncl.size() * 4, hipMemcpyHostToDevice, st));
-  SS_HIP(hipStreamSynchronize(st));
-  return SS_OK;
-}
-
-int ss_vec_search_ann_dev(ss_shard* s, uint32_t nq, const float* d_queries, uint32_t k, float thr, const ss_ann_mode* mode,
-                          uint32_t* d_out_doc, float* d_out_score, uint32_t* d_out_count, uint64_t* d_out_total,
-                          uint32_t* d_out_clusters, void* stream) {
-  if (!s || !d_queries || !d_out_doc || !d_out_score || !d_out_count || !d_out_total) return SS_EINVAL;
-  if (k == 0) return SS_EINVAL;
-  if (!s->d_X) return SS_ESTATE;
-  SS_TRY(ann_mode_ok(s, mode));
-  mode = ann_effective(mode);
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  if (k > SS_MAX_K)
-    return vec_search_deep_dev_locked(s, nq, d_queries, sizeof(float), nullptr, nullptr, k, thr, mode, d_out_doc, d_out_score, d_out_count, d_out_total,
-                                      mode ? d_out_clusters : nullptr, st);
-  VecWsBind bind(s, st);
-  AnnStateGuard ann_guard(s, st, mode);
-  return ssi_vec_search(s, nq, d_queries, nullptr, k, thr, d_out_doc, d_out_score, d_out_count, d_out_total, st, false, mode,
-                        mode ? d_out_clusters : nullptr);
-}
-int ss_vec_search_dev(ss_shard* s, uint32_t nq, const float* d_queries, uint32_t k, float thr, uint32_t* d_out_doc,
-                      float* d_out_score, uint32_t* d_out_count, uint64_t* d_out_total, void* stream) {
-  return ss_vec_search_ann_dev(s, nq, d_queries, k, thr, nullptr, d_out_doc, d_out_score, d_out_count, d_out_total, nullptr, stream);
-}
-
-// ---- VectorSimilarity of the image (vector_similarity.rs:118-345): must precede the upload (layout of the f32 image)
-int ss_vec_set_similarity(ss_shard* s, int similarity) {
-  if (!s || (similarity != SS_SIM_DOT && similarity != SS_SIM_EUCLIDEAN)) return SS_EINVAL;
-  ShardLock g(s);
-  if ((s->d_X || s->d_X8) && similarity != s->vec_similarity) return SS_ESTATE;
-  s->vec_similarity = similarity;
-  return SS_OK;
-}
-int ss_vec_set_row_norms(ss_shard* s, uint64_t n_rows, const float* row_norm) {
-  if (!s || !row_norm) return SS_EINVAL;
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call replaces; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  if (!s->d_X8) return SS_ESTATE;
-  if (n_rows != s->n_rows) return SS_EINVAL;
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (!s->d_row_norm) SS_HIP(hipMalloc(&s->d_row_norm, std::max<uint64_t>(n_rows, s->vec_rows_cap) * sizeof(float)));
-  SS_HIP(hipMemcpy(s->d_row_norm, row_norm, n_rows * sizeof(float), hipMemcpyHostToDevice));
-  return SS_OK;
-}
-
-// ---- cluster structure of the vector image (ANN modes, vec_ann.hip)
-int ss_vec_set_clusters(ss_shard* s, uint32_t n_levels, const uint32_t* level_clusters, const uint32_t* child_count) {
-  if (!s) return SS_EINVAL;
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call replaces; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  return ssi_vec_set_clusters(s, n_levels, level_clusters, child_count);
-}
-int ss_vec_set_fields(ss_shard* s, uint64_t n_rows, const uint16_t* row_field) {
-  if (!s || !row_field) return SS_EINVAL;
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call replaces; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  if (!s->d_X && !s->d_X8) return SS_ESTATE;
-  if (n_rows != s->n_rows) return SS_EINVAL;
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (!s->d_row_field) SS_HIP(hipMalloc(&s->d_row_field, std::max<uint64_t>(n_rows, s->vec_rows_cap) * sizeof(uint16_t)));
-  SS_HIP(hipMemcpy(s->d_row_field, row_field, n_rows * sizeof(uint16_t), hipMemcpyHostToDevice));
-  return SS_OK;
-}
-int ss_vec_cluster_info(ss_shard* s, uint32_t* n_levels, uint32_t* n_clusters) {
-  if (!s) return SS_EINVAL;
-  // no lock: two words that only an image (re)build changes, read by every vector search of the host mirrors -- behind s->mu each
-  // such read queued up with the batch in flight (64 concurrent callers: mean merged batch 1.3, p99 0.6 s; bench round 3)
-  if (n_levels) *n_levels = s->vec_n_levels;
-  if (n_clusters) *n_clusters = s->vec_n_clusters;
-  return SS_OK;
-}
-
-// ------------------------------------------------------------------ i8 (quantised) vectors
-// i8 image: rows as the reference stores them for Precision::I8 (quantize_f32_to_i8, vector_similarity.rs:1226-1232, or a
-// per-record scale = VectorHeader.scale with ScalarQuantizationI8).  Score = dot_i8 as f32 (vector_similarity.rs:1011-1016)
-// or, with scales, dot_i8_quantized = dot as f32 * query_scale * embedding_scale (1754-1758).
-int ss_vec_upload_i8(ss_shard* s, uint64_t n_rows, uint32_t dim, const int8_t* rows, const float* row_scale,
-                     const uint32_t* row_doc_ids) {
-  if (!s || !rows || n_rows == 0 || dim == 0) return SS_EINVAL;
-  if (n_rows > 0xFFFFFFFEull) return SS_ENOTSUP;
-  bool multi = false;
-  if (row_doc_ids) {
-    std::vector<uint32_t> tmp(row_doc_ids, row_doc_ids + n_rows);
-    std::sort(tmp.begin(), tmp.end());
-    multi = std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end();
-    if (!tmp.empty() && tmp.back() == SS_NO_DOC) return SS_EINVAL;
-  }
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  int rc = vec8_alloc(s, n_rows, dim);
-  if (rc) { free_vec(s); return rc; }
-  {  // row-major staging on the device, then into fragment order
-    int8_t* stage = nullptr;
-    SS_HIP(hipMalloc(&stage, (size_t)n_rows * dim));
-    if (hipMemcpyAsync(stage, rows, (size_t)n_rows * dim, hipMemcpyHostToDevice, s->stream) != hipSuccess) { (void)hipFree(stage); free_vec(s); return SS_EDEVICE; }
-    rc = ssi_vec8_permute(s, stage, s->stream);
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipFree(stage);
-    if (rc) { free_vec(s); return rc; }
-  }
-  s->vec_multi_record = multi;
-  if (row_scale) {
-    SS_HIP(hipMalloc(&s->d_row_scale, n_rows * sizeof(float)));
-    SS_HIP(hipMemcpyAsync(s->d_row_scale, row_scale, n_rows * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  }
-  if (row_doc_ids) {
-    SS_HIP(hipMalloc(&s->d_row_doc, n_rows * sizeof(uint32_t)));
-    SS_HIP(hipMemcpyAsync(s->d_row_doc, row_doc_ids, n_rows * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  }
-  SS_HIP(hipStreamSynchronize(s->stream));
-  return vec_finish(s);
-}
-
-// ------------------------------------------------------------------ append of one committed level of vector records
-// The reference commits 65 536 docs at a time and writes the level's clusters and records behind the earlier ones
-// (vector.rs:1066-1094); a rebuild of the whole image per commit would cost O(shard).  Rows are independent, so the new records are
-// written behind the image's rows IN PLACE (f32: a strided copy; i8: through a row-major staging and the fragment-order scatter of the
-// rows' range), the Euclidean side data is computed for the new range only, the per-row side arrays (doc ids, scales, norms, field
-// ids) are extended, and the cluster structure -- if the image has one -- is declared again with the level added (O(rows) words, not
-// O(image bytes)).  The image and the side arrays grow by half when their room is used up (one device-to-device copy, amortised).
-// room for new_cap rows in the image and every per-row array it carries (caller holds s->mu, the device is idle).  ALL OR NOTHING:
-// every new array is allocated before anything is copied or swapped, so a failure (SS_ENOMEM) leaves the shard as it was.
-// grow_image = false: the image already has the room (its row padding), only the side arrays follow.
-static int vec_grow(ss_shard* s, uint64_t new_cap, bool grow_image = true) {
-  const bool i8 = s->d_X8 != nullptr;
-  const size_t row_bytes = i8 ? (size_t)s->dim_pad8 : (size_t)s->dim_pad * sizeof(float);
-  const uint64_t old_n = s->n_rows;
-  struct G { void** p; size_t elem; uint64_t old_rows; bool zero_tail; void* q; };
-  // the image: rows [0, n_rows_pad) are data + zero padding, the room behind them starts as padding (zero)
-  G gs[] = {{i8 ? (void**)&s->d_X8 : (void**)&s->d_X, row_bytes, s->n_rows_pad, true, nullptr},
-            {(void**)&s->d_row_doc, sizeof(uint32_t), old_n, false, nullptr},   {(void**)&s->d_row_scale, sizeof(float), old_n, false, nullptr},
-            {(void**)&s->d_row_norm, sizeof(float), old_n, false, nullptr},     {(void**)&s->d_row_sq, sizeof(int32_t), old_n, false, nullptr},
-            {(void**)&s->d_row_field, sizeof(uint16_t), old_n, false, nullptr}};
-  int rc = SS_OK;
-  for (size_t i = grow_image ? 0 : 1; i < sizeof(gs) / sizeof(gs[0]) && rc == SS_OK; i++) {
-    G& g = gs[i];
-    if (!*g.p) continue;
-    const hipError_t e = hipMalloc(&g.q, (size_t)new_cap * g.elem);
-    if (e != hipSuccess) { g.q = nullptr; rc = e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE; break; }
-    if (hipMemcpy(g.q, *g.p, (size_t)g.old_rows * g.elem, hipMemcpyDeviceToDevice) != hipSuccess ||
-        (g.zero_tail && hipMemset((char*)g.q + (size_t)g.old_rows * g.elem, 0, (size_t)(new_cap - g.old_rows) * g.elem) != hipSuccess))
-      rc = SS_EDEVICE;
-  }
-  if (rc != SS_OK) {
-    for (G& g : gs) if (g.q) (void)hipFree(g.q);
-    return rc;
-  }
-  for (G& g : gs)
-    if (g.q) { (void)hipFree(*g.p); *g.p = g.q; }
-  s->vec_rows_cap = new_cap;
-  return SS_OK;
-}
-
-int ss_vec_reserve_rows(ss_shard* s, uint64_t n_rows_cap) {
-  if (!s) return SS_EINVAL;
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call replaces; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  if (!s->d_X && !s->d_X8) return SS_ESTATE;
-  if (n_rows_cap > 0xFFFFFFFEull) return SS_ENOTSUP;
-  const uint64_t cap = s->vec_rows_cap ? s->vec_rows_cap : s->n_rows_pad, want = (n_rows_cap + VS_TR - 1) / VS_TR * VS_TR;
-  if (want <= cap && s->vec_rows_cap) return SS_OK;
-  SS_HIP(hipDeviceSynchronize());
-  return vec_grow(s, std::max(want, cap));
-}
-
-int ss_vec_append_rows(ss_shard* s, const ss_vec_level* lv) {
-  if (!s || !lv || !lv->rows || lv->n_rows == 0) return SS_EINVAL;
-  const uint64_t n_new = lv->n_rows;
-  bool multi = false;
-  if (lv->row_doc_ids) {  // (a level's records share doc ids only among themselves: (level << 16) | doc_id, vector.rs:1448)
-    std::vector<uint32_t> tmp(lv->row_doc_ids, lv->row_doc_ids + n_new);
-    std::sort(tmp.begin(), tmp.end());
-    multi = std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end();
-    if (tmp.back() == SS_NO_DOC) return SS_EINVAL;
-  }
-  ShardLock g(s);
-  if (s->vstream) (void)hipStreamSynchronize(s->vstream);  // (a coalesced scan in flight reads what this call replaces; none starts while mu is ours)
-  SS_HIP(hipSetDevice(s->device));
-  if (!s->d_X && !s->d_X8) return SS_ESTATE;
-  const bool i8 = s->d_X8 != nullptr;
-  if ((lv->elem_i8 != 0) != i8) return SS_EINVAL;
-  // what the image carries per row, the level must bring -- and nothing else
-  if ((s->d_row_doc != nullptr) != (lv->row_doc_ids != nullptr) || (s->d_row_scale != nullptr) != (lv->row_scale != nullptr) ||
-      (s->d_row_norm != nullptr) != (lv->row_norm != nullptr) || (s->d_row_field != nullptr) != (lv->row_field != nullptr) ||
-      (s->vec_n_clusters != 0) != (lv->n_clusters != 0))
-    return SS_EINVAL;
-  if (lv->n_clusters) {
-    if (!lv->child_count) return SS_EINVAL;
-    uint64_t sum = 0;
-    for (uint32_t c = 0; c < lv->n_clusters; c++) { if (lv->child_count[c] == 0) return SS_ENOTSUP; sum += lv->child_count[c]; }
-    if (sum != n_new) return SS_EINVAL;
-  }
-  const uint64_t old_n = s->n_rows, new_n = old_n + n_new;
-  if (new_n > 0xFFFFFFFEull) return SS_ENOTSUP;
-  const uint64_t new_pad = (new_n + VS_TR - 1) / VS_TR * VS_TR;
-  SS_HIP(hipDeviceSynchronize());  // searches on the callers' own streams read the arrays that are written / replaced here
-  const uint64_t cap = s->vec_rows_cap ? s->vec_rows_cap : s->n_rows_pad;
-  // (an opener that expects commits reserves the room once: ss_vec_reserve_rows).  Otherwise: what is needed plus a bounded headroom
-  // -- half of what there is, at most 4 M rows: old and new image are both live during the copy -- and on the FIRST append only the side
-  // arrays (allocated for exactly n_rows) when the level still fits the image's own row padding
-  if (new_pad > cap)
-    SS_TRY(vec_grow(s, (std::max<uint64_t>(new_pad, std::min<uint64_t>(cap + cap / 2, new_pad + (4u << 20))) + VS_TR - 1) / VS_TR * VS_TR));
-  else if (!s->vec_rows_cap)
-    SS_TRY(vec_grow(s, cap, /*grow_image=*/false));
-  if (!i8) {
-    SS_HIP(hipMemcpy2DAsync(s->d_X + (size_t)old_n * s->dim_pad, (size_t)s->dim_pad * sizeof(float), lv->rows, (size_t)s->dim * sizeof(float),
-                            (size_t)s->dim * sizeof(float), n_new, hipMemcpyHostToDevice, s->stream));
-  } else {
-    int8_t* stage = nullptr;
-    SS_HIP(hipMalloc(&stage, (size_t)n_new * s->dim));
-    int rc = hipMemcpyAsync(stage, lv->rows, (size_t)n_new * s->dim, hipMemcpyHostToDevice, s->stream) == hipSuccess ? SS_OK : SS_EDEVICE;
-    if (rc == SS_OK) rc = ssi_vec8_permute_range(s, stage, old_n, n_new, s->stream);
-    (void)hipStreamSynchronize(s->stream);
-    (void)hipFree(stage);
-    if (rc) return rc;
-  }
-  if (lv->row_doc_ids) SS_HIP(hipMemcpyAsync(s->d_row_doc + old_n, lv->row_doc_ids, n_new * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  if (lv->row_scale) SS_HIP(hipMemcpyAsync(s->d_row_scale + old_n, lv->row_scale, n_new * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  if (lv->row_norm) SS_HIP(hipMemcpyAsync(s->d_row_norm + old_n, lv->row_norm, n_new * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  if (lv->row_field) SS_HIP(hipMemcpyAsync(s->d_row_field + old_n, lv->row_field, n_new * sizeof(uint16_t), hipMemcpyHostToDevice, s->stream));
-  s->n_rows = new_n;
-  s->n_rows_pad = new_pad;
-  s->vec_multi_record = s->vec_multi_record || multi;
-  if (s->vec_similarity == SS_SIM_EUCLIDEAN) SS_TRY(s->d_X ? ssi_vec_augment(s, s->stream, old_n) : ssi_vec8_row_sq(s, s->stream, old_n));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (lv->n_clusters) {  // the structure with the level added, declared again (row -> cluster words, the new medoids, tile lists)
-    std::vector<uint32_t> lc = s->h_level_clusters, cc = s->h_child_count;
-    lc.push_back(lv->n_clusters);
-    cc.insert(cc.end(), lv->child_count, lv->child_count + lv->n_clusters);
-    SS_TRY(ssi_vec_set_clusters(s, (uint32_t)lc.size(), lc.data(), cc.data()));
-  }
-  return SS_OK;
-}
-
-// bench / test utility: the synthetic f32 corpus of ss_vec_synth quantised on the device with quantize_f32_to_i8
-int ss_vec_synth_i8(ss_shard* s, uint64_t seed, uint64_t n_rows, uint32_t dim) {
-  if (!s || n_rows == 0 || dim == 0) return SS_EINVAL;
-  if (n_rows > 0xFFFFFFFEull) return SS_ENOTSUP;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  int rc = vec_alloc(s, n_rows, dim);  // f32 rows first ...
-  if (rc) { free_vec(s); return rc; }
-  SS_TRY(ssi_vec_synth(s, seed, s->stream));
-  float* x32 = s->d_X;
-  const uint32_t pad32 = s->dim_pad;
-  s->d_X = nullptr;  // ... kept aside while the i8 image is allocated (free_vec must not release them)
-  rc = vec8_alloc(s, n_rows, dim);
-  if (rc) { (void)hipFree(x32); return rc; }
-  s->d_X = x32;
-  s->dim_pad = pad32;
-  rc = ssi_vec8_quantize(s, s->stream);
-  (void)hipStreamSynchronize(s->stream);
-  (void)hipFree(x32);
-  s->d_X = nullptr;
-  s->dim_pad = 0;
-  if (rc) { free_vec(s); return rc; }
-  return vec_finish(s);
-}
-
-int ss_vec_read_rows_i8(ss_shard* s, uint64_t r0, uint64_t n, int8_t* out) {
-  if (!s || !out) return SS_EINVAL;
-  if (!s->d_X8) return SS_ESTATE;
-  if (r0 + n > s->n_rows) return SS_EINVAL;
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  SS_HIP(hipStreamSynchronize(s->stream));
-  if (n == 0) return SS_OK;
-  int8_t* tmp = nullptr;
-  SS_HIP(hipMalloc(&tmp, (size_t)n * s->dim));
-  int rc = ssi_vec8_gather_rows(s, r0, n, tmp, s->stream);
-  if (rc == SS_OK && hipMemcpyAsync(out, tmp, (size_t)n * s->dim, hipMemcpyDeviceToHost, s->stream) != hipSuccess) rc = SS_EDEVICE;
-  (void)hipStreamSynchronize(s->stream);
-  (void)hipFree(tmp);
-  return rc;
-}
-
-// euclidean_i8_quantized (scales present) = max(0, n1 + n2 - 2 dot s1 s2) needs BOTH norms: the reference always carries
-// VectorHeader.norm / QuantizedVector.norm.  Without them the ranking would silently be that of -max(0, -2 dot s1 s2).
-static int vec8_euclid_norms_ok(const ss_shard* s, bool have_qscale, bool have_qnorm) {
-  if (s->vec_similarity != SS_SIM_EUCLIDEAN || (!s->d_row_scale && !have_qscale)) return SS_OK;
-  if (!s->d_row_norm) return SS_ESTATE;  // ss_vec_set_row_norms
-  return have_qnorm ? SS_OK : SS_EINVAL;
-}
-int ss_vec_search_i8_euclid(ss_shard* s, uint32_t nq, const int8_t* queries, const float* query_scale, const float* query_norm,
-                            uint32_t k, float thr, const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count,
-                            uint64_t* out_total, uint32_t* out_clusters) {
-  if (!s || !queries || !out_doc || !out_score || !out_count || !out_total) return SS_EINVAL;
-  if (k == 0) return SS_EINVAL;
-  if (!s->d_X8) return SS_ESTATE;
-  SS_TRY(vec8_euclid_norms_ok(s, query_scale != nullptr, query_norm != nullptr));
-  SS_TRY(ann_mode_ok(s, mode));
-  mode = ann_effective(mode);
-  if (k > SS_MAX_K)  // (deep pages)
-    return vec_search_host_deep(s, nq, queries, 1, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total, mode ? out_clusters : nullptr, query_norm);
-  if (!mode && !query_norm && nq != 0 && nq <= SS_COALESCE_MAX_REQUEST && s->co_vec.max_batch) {
-    ss_co_req r;
-    r.q = queries; r.qscale = query_scale; r.nq = nq; r.k = k; r.elem = 1; r.thr = thr;
-    r.out_doc = out_doc; r.out_score = out_score; r.out_count = out_count; r.out_total = out_total;
-    return ssi_co_submit(s, s->co_vec, false, &r);
-  }
-  return ssi_vec_search_host(s, nq, queries, 1, query_scale, k, thr, mode, out_doc, out_score, out_count, out_total,
-                         mode ? out_clusters : nullptr, query_norm);
-}
-int ss_vec_search_i8_ann(ss_shard* s, uint32_t nq, const int8_t* queries, const float* query_scale, uint32_t k, float thr,
-                         const ss_ann_mode* mode, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total,
-                         uint32_t* out_clusters) {
-  return ss_vec_search_i8_euclid(s, nq, queries, query_scale, nullptr, k, thr, mode, out_doc, out_score, out_count, out_total, out_clusters);
-}
-int ss_vec_search_i8(ss_shard* s, uint32_t nq, const int8_t* queries, const float* query_scale, uint32_t k, float thr,
-                     uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total) {
-  return ss_vec_search_i8_ann(s, nq, queries, query_scale, k, thr, nullptr, out_doc, out_score, out_count, out_total, nullptr);
-}
-
-int ss_vec_search_i8_ann_dev(ss_shard* s, uint32_t nq, const int8_t* d_queries, const float* d_query_scale, uint32_t k, float thr,
-                             const ss_ann_mode* mode, uint32_t* d_out_doc, float* d_out_score, uint32_t* d_out_count,
-                             uint64_t* d_out_total, uint32_t* d_out_clusters, void* stream) {
-  return ss_vec_search_i8_euclid_dev(s, nq, d_queries, d_query_scale, nullptr, k, thr, mode, d_out_doc, d_out_score, d_out_count,
-                                     d_out_total, d_out_clusters, stream);
-}
-int ss_vec_search_i8_euclid_dev(ss_shard* s, uint32_t nq, const int8_t* d_queries, const float* d_query_scale, const float* d_query_norm,
-                                uint32_t k, float thr, const ss_ann_mode* mode, uint32_t* d_out_doc, float* d_out_score,
-                                uint32_t* d_out_count, uint64_t* d_out_total, uint32_t* d_out_clusters, void* stream) {
-  if (!s || !d_queries || !d_out_doc || !d_out_score || !d_out_count || !d_out_total) return SS_EINVAL;
-  if (k == 0) return SS_EINVAL;
-  if (!s->d_X8) return SS_ESTATE;
-  SS_TRY(vec8_euclid_norms_ok(s, d_query_scale != nullptr, d_query_norm != nullptr));
-  SS_TRY(ann_mode_ok(s, mode));
-  mode = ann_effective(mode);
-  ShardLock g(s);
-  SS_HIP(hipSetDevice(s->device));
-  hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  if (k > SS_MAX_K)
-    return vec_search_deep_dev_locked(s, nq, d_queries, 1, d_query_scale, d_query_norm, k, thr, mode, d_out_doc, d_out_score, d_out_count, d_out_total,
-                                      mode ? d_out_clusters : nullptr, st);
-  VecWsBind bind(s, st);
-  AnnStateGuard ann_guard(s, st, mode);
-  return ssi_vec_search(s, nq, d_queries, d_query_scale, k, thr, d_out_doc, d_out_score, d_out_count, d_out_total, st, false, mode,
-                        mode ? d_out_clusters : nullptr, d_query_norm);
-}
-int ss_vec_search_i8_dev(ss_shard* s, uint32_t nq, const int8_t* d_queries, const float* d_query_scale, uint32_t k, float thr,
-                         uint32_t* d_out_doc, float* d_out_score, uint32_t* d_out_count, uint64_t* d_out_total, void* stream) {
-  return ss_vec_search_i8_ann_dev(s, nq, d_queries, d_query_scale, k, thr, nullptr, d_out_doc, d_out_score, d_out_count,
-                                  d_out_total, nullptr, stream);
 }
 
 // ------------------------------------------------------------------ cross-shard merge + RRF (search.rs:1875-2119)

@@ -1,5 +1,5 @@
 """Return codes of the entries that upload a BM25 image or commit to one, for bad inputs alone and in pairs, and what a refusal leaves
-behind (csrc/ss_api.hip; -m gpu).
+behind (csrc/api_image.hip; -m gpu).
 
 ss_bm25_upload[_positions], ss_bm25_upload_fields[_positions], ss_bm25_append_level[_positions], ss_bm25_append_level_fields,
 ss_bm25_append_sparse_level and the four ss_bm25_append_sparse* check their arguments, the shard's state and the postings in an order
