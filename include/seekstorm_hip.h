@@ -426,6 +426,26 @@ int ss_bm25_append_level_positions(ss_shard* s, uint32_t level, uint32_t n_level
  * (ss_bm25_append_sparse) takes no levels, and this one no whole lists (SS_ESTATE).  SS_EINVAL leaves the tier as it was. */
 int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs /*[n_lists+1]*/, const uint32_t* doc_ids,
                                 const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions);
+/* index.bin opened LEVEL BY LEVEL, ready to commit to: the end of open_shard (index.rs:3796) for a shard that commits afterwards
+ * (commit.rs:142-148).  Where ss_bm25_upload_index_bin builds an image that keeps no levels (the first ss_bm25_append_level after it
+ * answers SS_ESTATE), this entry makes one raw level per level of the file -- n_docs of the last from indexed_doc_count, every
+ * level's length sum the difference of the file's cumulative positions_sum_normalized, so the average length is the one
+ * ss_bm25_upload_index_bin computes -- and builds the image from them with ONE device rebuild.  Without positions the blocks are decoded
+ * ON THE DEVICE: the file's bytes are staged in HBM one level at a time and every posting is decoded by its own lane straight into its
+ * level's arrays (csrc/ref_decode_dev.hip); with_positions != 0 takes postings and positions from the host decoder of
+ * ss_bm25_upload_index_bin_positions and cuts them per level.  A tiered ix (ss_index_bin_tier) gives a sparse tier that TAKES
+ * LEVELS: its postings keep their tfs, its last level is the file's last.  Afterwards ss_bm25_incremental_info reports the file's
+ * level count, and ss_bm25_append_level[_positions] / ss_bm25_append_sparse_level accept the next level -- or the last one again, if it
+ * was incomplete, which replaces exactly what that level brought.  Term ids are those of ss_index_bin_term_keys at the time of the
+ * call; keys that later commits bring take the next ids (rare ones behind the tier's), so the host keeps its key -> id map from then on.
+ * One indexed field, SingleTerm and n-gram keys.  Returns SS_ENOTSUP for an index of several indexed fields, a Delta container
+ * (also where the same file holds a malformed block), a weight the code cannot hold; SS_EINVAL for an ix without dense terms
+ * (ss_index_bin_tier left none), a key whose blocks do not ascend by level (a key head in two segments of one level), or a
+ * malformed block (docs not ascending, a count that is not
+ * its container's, tf 0 or above 65 535, a doc at or past its level's doc count, a pointer or record outside the key bodies -- no byte
+ * outside them is read).  On any failure the shard is exactly as before: image, levels and tier are built aside and swapped in under
+ * the shard lock. */
+int ss_bm25_open_index_bin_levels(ss_shard* s, const ss_index_bin* ix, int with_positions);
 /* ... on an image of SEVERAL INDEXED FIELDS whose levels came through ss_bm25_commit_level_fields: after the dense commit of `level`
  * (the level the dense image committed last), the entries (doc, field, tf) of the RARE terms in that level, sorted by (doc, field)
  * inside a list, doc ids inside the level, tf >= 1, field < n_fields.  List i continues sparse list i (term id = dense terms + i);

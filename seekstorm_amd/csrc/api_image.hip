@@ -45,6 +45,43 @@ int level_rules(uint32_t level, uint32_t n_level_docs, const Levels& levels) {
 }
 }  // namespace
 
+// The positions of a level's postings as raw_level_upload takes them (a commit, and the open level by level of ref_decode_dev.hip): per
+// posting its count -- npos, or its tf --, the positions of the term's earlier postings of this level, per term its first position.
+// SS_EINVAL: the counts do not add up to n_positions, or a posting's positions do not ascend; SS_ENOTSUP: 2^32 positions in one term.
+int ssi_level_positions_prepare(uint32_t n_terms, const uint64_t* offs, const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions,
+                                uint64_t n_positions, LevelPositions* out) {
+  const uint64_t n_post = offs[n_terms] - offs[0];
+  std::vector<uint16_t>& h_npos = out->npos;
+  std::vector<uint32_t>& h_prel = out->prel;
+  std::vector<uint64_t>& h_tpos = out->tpos;
+  h_npos.resize(n_post); h_prel.resize(n_post); h_tpos.assign((size_t)n_terms + 1, 0);
+  ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {  // a term's positions: the sum of its postings' counts
+    for (size_t t = ta; t < tb; t++) {
+      uint64_t c = 0;
+      for (uint64_t j = offs[t]; j < offs[t + 1]; j++) c += npos ? npos[j] : tfs[j];
+      h_tpos[t + 1] = c;
+    }
+  });
+  for (uint32_t t = 0; t < n_terms; t++) h_tpos[t + 1] += h_tpos[t];
+  if (h_tpos[n_terms] != n_positions) return SS_EINVAL;
+  std::atomic<int> bad{SS_OK};
+  ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
+    for (size_t t = ta; t < tb; t++) {
+      const uint64_t at = h_tpos[t];
+      uint64_t rel = 0;
+      for (uint64_t j = offs[t]; j < offs[t + 1]; j++) {
+        const uint32_t c = npos ? npos[j] : tfs[j];
+        if (rel >= (1ull << 32)) { bad.store(SS_ENOTSUP); return; }
+        h_npos[j - offs[0]] = (uint16_t)c; h_prel[j - offs[0]] = (uint32_t)rel;
+        for (uint32_t x = 1; x < c; x++)
+          if (positions[at + rel + x] <= positions[at + rel + x - 1]) { bad.store(SS_EINVAL); return; }  // ascending inside a posting
+        rel += c;
+      }
+    }
+  });
+  return bad.load();
+}
+
 extern "C" {
 
 extern "C++" {
@@ -371,37 +408,9 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   ss_raw_level L;
   L.n_docs = n_level_docs; L.n_terms = n_terms; L.n_post = offs[n_terms] - offs[0];
   for (uint32_t d = 0; d < n_level_docs; d++) L.psum += ss_byte4_to_int(level_doclen[d]);
-  // positions: per posting its count, the positions of the term's earlier postings of this level, per term its first position
-  std::vector<uint16_t> h_npos;
-  std::vector<uint32_t> h_prel;
-  std::vector<uint64_t> h_tpos;
+  LevelPositions P;
   if (with_pos) {
-    h_npos.resize(L.n_post); h_prel.resize(L.n_post); h_tpos.assign((size_t)n_terms + 1, 0);
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {  // a term's positions: the sum of its postings' counts
-      for (size_t t = ta; t < tb; t++) {
-        uint64_t c = 0;
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) c += npos ? npos[j] : tfs[j];
-        h_tpos[t + 1] = c;
-      }
-    });
-    for (uint32_t t = 0; t < n_terms; t++) h_tpos[t + 1] += h_tpos[t];
-    if (h_tpos[n_terms] != n_positions) return SS_EINVAL;
-    std::atomic<int> bad{SS_OK};
-    ss_parallel_for(n_terms, 64, [&](size_t ta, size_t tb, unsigned) {
-      for (size_t t = ta; t < tb; t++) {
-        const uint64_t at = h_tpos[t];
-        uint64_t rel = 0;
-        for (uint64_t j = offs[t]; j < offs[t + 1]; j++) {
-          const uint32_t c = npos ? npos[j] : tfs[j];
-          if (rel >= (1ull << 32)) { bad.store(SS_ENOTSUP); return; }
-          h_npos[j - offs[0]] = (uint16_t)c; h_prel[j - offs[0]] = (uint32_t)rel;
-          for (uint32_t x = 1; x < c; x++)
-            if (positions[at + rel + x] <= positions[at + rel + x - 1]) { bad.store(SS_EINVAL); return; }  // ascending inside a posting
-          rel += c;
-        }
-      }
-    });
-    if (bad.load()) return bad.load();
+    SS_TRY(ssi_level_positions_prepare(n_terms, offs, tfs, npos, positions, n_positions, &P));
     L.n_pos = n_positions;
   }
   hipStream_t bst = nullptr;
@@ -412,7 +421,7 @@ static int append_level_impl(ss_shard* s, uint32_t level, uint32_t n_level_docs,
   };
   CommitUndo<decltype(undo)> own{undo, bst};
   if (const hipError_t e = hipStreamCreateWithFlags(&bst, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
-  const raw_level_positions pos{h_npos.data(), h_prel.data(), h_tpos.data(), positions, n_positions};
+  const raw_level_positions pos{P.npos.data(), P.prel.data(), P.tpos.data(), positions, n_positions};
   if (const int rc_up = raw_level_upload(L, offs, docs, tfs, n_terms, with_pos ? &pos : nullptr, bst)) return rc_up;
   levels.push_back(L);
   doclen.insert(doclen.end(), level_doclen, level_doclen + n_level_docs);
@@ -1113,3 +1122,22 @@ int ss_bm25_sparse_info(ss_shard* s, uint32_t* n_lists, uint64_t* n_postings, ui
 }
 
 }  // extern "C"
+
+// An image opened level by level (ref_decode_dev.hip ss_bm25_open_index_bin_levels) becomes the shard's: the raw levels, the length
+// bytes, the image built from them beside the serving one and -- tier != nullptr -- the sparse tier that takes levels.  One lock
+// section, as the swap of append_level_impl: searches in flight finish on what they read, which is then released.  The caller still
+// owns everything until this returns SS_OK.
+int ssi_bm25_install_levels(ss_shard* s, std::vector<ss_raw_level>& levels, std::vector<uint8_t>& doclen, ss_shard* img, ss_sparse_tier_built* tier,
+                            double rebuild_ms, double open_ms) {
+  ShardLock g(s);
+  SS_HIP(hipSetDevice(s->device));
+  SS_HIP(hipDeviceSynchronize());  // (searches on the callers' own streams may still read the image and the tier that go)
+  ssi_bm25_free(s);  // image, levels of every kind, tier and its level state; the new image's arrays stay with the block pool
+  s->raw.swap(levels);
+  s->h_doclen.swap(doclen);
+  bm_image_take(s, img);
+  if (tier) ssi_bm25_sparse_tier_take(s, tier);
+  s->raw_last_rebuild_ms = rebuild_ms;
+  s->raw_last_append_ms = open_ms;
+  return SS_OK;
+}

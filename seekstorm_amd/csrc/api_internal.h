@@ -5,6 +5,7 @@
 //   api_image.hip     the lexical and facet images built and committed: uploads, level and sparse-tier commits, tombstones, string ranks
 //   api_coalesce.hip  the futex coalescer of concurrent callers, its SS_CO_TRACE report and its stats
 //   api_deep.hip      deep pages: lexical and vector searches of more than SS_MAX_K results, in passes
+//   ref_decode_dev.hip  index.bin opened level by level, its blocks decoded on the device (ss_bm25_open_index_bin_levels)
 // A function that one file defines and another calls is declared here, once, with its default arguments, under the ssi_ prefix and with
 // C++ linkage (as in ss_common.h); everything else is static in its file.  The helpers defined here are static too: every file gets its
 // own copy and the library exports none of them.
@@ -122,6 +123,16 @@ int ssi_vec_search_host_lane(ss_shard* s, uint32_t nq, const void* queries, size
 // ---- api_image.hip: the lexical image released (ss_shard_destroy).  keep_tier: the dense image goes (a commit swaps in its successor),
 // the sparse tier stays
 void ssi_bm25_free(ss_shard* s, bool keep_tier = false);
+
+// the positions of a level's postings as raw_level_upload (bm25_image.h) takes them, prepared on the host: what a commit with positions
+// and the open level by level share
+struct LevelPositions { std::vector<uint16_t> npos; std::vector<uint32_t> prel; std::vector<uint64_t> tpos; };
+int ssi_level_positions_prepare(uint32_t n_terms, const uint64_t* offs, const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions,
+                                uint64_t n_positions, LevelPositions* out);
+// levels + length bytes + the image built from them (+ a sparse tier that takes levels) become the shard's, in one lock section
+struct ss_sparse_tier_built;  // sparse_levels.h
+int ssi_bm25_install_levels(ss_shard* s, std::vector<ss_raw_level>& levels, std::vector<uint8_t>& doclen, ss_shard* img, ss_sparse_tier_built* tier,
+                            double rebuild_ms, double open_ms);
 
 // ---- comm.hip: ssi_comm_exchange (ss_common.h) with the hybrid fusion on the host when host_fuse
 int ssi_comm_exchange_hf(ss_comm* c, uint32_t nq, int n_lists, const ss_dev_list* L, const uint64_t* d_tot_a, const uint64_t* d_tot_b,

@@ -1,0 +1,497 @@
+// index.bin opened LEVEL BY LEVEL, its blocks decoded ON THE DEVICE, ready to commit to (ss_bm25_open_index_bin_levels; the seam is the
+// end of open_shard, index.rs:3796, followed by commits, commit.rs:142-148).
+//
+// A block of index.bin is one (key, 65 536-doc level) pair and a raw level of an incremental image (ss_raw_level) is the per-term
+// (doc, tf) CSR of one level: the file is already cut the way the incremental image wants it, and a posting decodes independently of
+// every other posting of its block (ref_block_decode.h).  So the file's bytes go to HBM one level at a time, a descriptor per block
+// says where its postings belong -- a dense term's in its level's d_doc / d_tf, a rare term's in the sparse tier's whole lists --, the
+// kernels below write them there, and ONE ssi_bm25_rebuild_from_raw builds the image over all levels.
+//
+// Work goes by POSTING, not by block: on a text-shaped index nearly every block holds 1 - 5 postings.  rbd_flat_kernel: a lane takes
+// posting p of a launch and finds its (Array) block by binary search over the blocks' first postings.  Bitmap and Rle blocks are few and
+// long: rbd_wg_kernel gives each a workgroup, which scans the words' popcounts / the runs' lengths in LDS and then writes ranks.
+#include <atomic>
+#include <chrono>
+#include <cstring>
+#include <memory>
+
+#include "ref_block_decode.h"
+#include "ref_index_bin.h"
+#include "sparse_levels.h"
+#include "bm25_image.h"
+#include "api_internal.h"
+
+namespace {
+
+static_assert(RBD_EINVAL == SS_EINVAL && RBD_ENOTSUP == SS_ENOTSUP, "ref_block_decode.h");
+
+// one block of a launch
+struct RbdDesc {
+  uint64_t body;        // the segment's key bodies: offset in the staged bytes
+  uint64_t dst;         // its first posting's index in the destination arrays
+  uint32_t body_len;    // byte_array_len
+  uint32_t ctp;         // compression_type_pointer
+  uint32_t first;       // flat launch: postings of the launch's blocks before this one
+  uint16_t count_m1, pivot;
+  uint8_t n_comp, comp;
+  uint8_t sparse;       // 1: a rare key, its postings go to the tier's whole lists
+  uint8_t pad;
+};
+// where a launch writes: a level's arrays (dense terms) and the tier's (rare terms; a posting's upper word is coded later)
+struct RbdDst {
+  uint32_t* doc; uint16_t* tf;
+  uint64_t* sp_post; uint16_t* sp_tf;
+  uint32_t doc_base, level_docs;  // first doc of the level, docs it holds
+};
+constexpr uint32_t RBD_CHUNK = 2048;  // items (bitmap words, runs) a workgroup scans at a time; the writer's Rle containers hold at most
+                                      // that many runs (compress_postinglist.rs:256-332), longer ones take several rounds
+
+__device__ __forceinline__ rbd_block rbd_block_of(const uint8_t* __restrict__ bytes, const RbdDesc& d) {
+  rbd_block b;
+  b.a = bytes + d.body; b.len = d.body_len; b.ctp = d.ctp; b.count = (uint32_t)d.count_m1 + 1u; b.pivot = d.pivot;
+  b.n_comp = d.n_comp; b.comp = d.comp;
+  return b;
+}
+// (the largest code wins: a file that holds a Delta container AND a malformed block answers SS_ENOTSUP, where the host decoder answers
+// with whichever it meets first)
+__device__ __forceinline__ void rbd_fail(uint32_t* status, int rc) { atomicMax(status, (uint32_t)(-rc)); }
+__device__ __forceinline__ void rbd_store(const RbdDst& D, const RbdDesc& d, uint32_t r, uint32_t doc, uint32_t tf) {
+  if (d.sparse) { D.sp_post[d.dst + r] = (uint64_t)(D.doc_base + doc); D.sp_tf[d.dst + r] = (uint16_t)tf; }
+  else { D.doc[d.dst + r] = D.doc_base + doc; D.tf[d.dst + r] = (uint16_t)tf; }
+}
+
+// Array blocks, one lane per posting
+__global__ void __launch_bounds__(256) rbd_flat_kernel(const uint8_t* __restrict__ bytes, const RbdDesc* __restrict__ desc, uint32_t n_blocks,
+                                                       uint32_t n_post, RbdDst D, uint32_t* __restrict__ status) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_post) return;
+  uint32_t lo = 0u, hi = n_blocks;  // the block with first <= p < the next block's first
+  while (hi - lo > 1u) {
+    const uint32_t m = (lo + hi) >> 1;
+    if (desc[m].first <= p) lo = m; else hi = m;
+  }
+  const RbdDesc d = desc[lo];
+  const uint32_t r = p - d.first;
+  const rbd_block b = rbd_block_of(bytes, d);
+  rbd_head h;
+  uint32_t doc = 0u, tf = 0u;
+  int rc = rbd_head_check(b, &h);
+  if (rc == RBD_OK && (h.ctype != 1u || r >= b.count)) rc = RBD_EINVAL;  // (the host sends Array blocks here, with their counts)
+  if (rc == RBD_OK) rc = rbd_doc(b, h, nullptr, r, D.level_docs, &doc);
+  if (rc == RBD_OK) rc = rbd_tf(b, h, r, &tf);
+  if (rc != RBD_OK) { rbd_fail(status, rc); return; }
+  rbd_store(D, d, r, doc, tf);
+}
+
+// Bitmap / Rle blocks (and whatever else the head names: refused), one workgroup per block.  The items -- 64-bit bitmap words / runs --
+// go through the LDS table RBD_CHUNK at a time (a Bitmap is one chunk; an Rle container of more runs than that, which the writer would
+// have made a Bitmap, takes several): their sizes are scanned, then the chunk's ranks are written.  A store is guarded by the key
+// head's count; count != popcount / sum of runs is known after the last chunk, and the arrays written are nobody's until the call succeeds.
+__global__ void __launch_bounds__(256) rbd_wg_kernel(const uint8_t* __restrict__ bytes, const RbdDesc* __restrict__ desc, RbdDst D,
+                                                     uint32_t* __restrict__ status) {
+  __shared__ uint32_t prefix[RBD_CHUNK + 1];
+  __shared__ uint32_t wave_sum[4];
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const RbdDesc d = desc[blockIdx.x];
+  const rbd_block b = rbd_block_of(bytes, d);
+  rbd_head h;
+  int rc = rbd_head_check(b, &h);  // (uniform over the workgroup)
+  if (rc == RBD_OK && h.ctype == 1u) rc = RBD_EINVAL;  // (Array blocks go to the flat kernel)
+  if (rc != RBD_OK) { if (tid == 0) rbd_fail(status, rc); return; }
+  const bool bitmap = h.ctype == 2u;
+  const uint32_t per = bitmap ? RBD_BITMAP_WORDS / 256u : RBD_CHUNK / 256u, n_items = bitmap ? RBD_BITMAP_WORDS : h.runs;
+  uint32_t base = 0u;  // postings of the chunks before (uniform)
+  for (uint32_t c0 = 0; c0 < n_items; c0 += per * 256u) {
+    const uint32_t m = min(per * 256u, n_items - c0);  // items of this chunk
+    uint32_t size[RBD_CHUNK / 256u], mine = 0u;
+    for (uint32_t k = 0; k < RBD_CHUNK / 256u; k++) {
+      const uint32_t i = tid * per + k;
+      size[k] = 0u;
+      if (k < per && i < m) {
+        if (bitmap) size[k] = rbd_popcount64(rbd_bitmap_word(b, h, i));
+        else {
+          uint32_t s, l;
+          rbd_rle_run(b, h, c0 + i, &s, &l);
+          size[k] = l + 1u;
+          if (rbd_rle_run_check(b, h, c0 + i)) rbd_fail(status, RBD_EINVAL);  // out of the level, or not behind the run before
+        }
+      }
+      mine += size[k];
+    }
+    uint32_t incl = mine;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(incl, o); if ((int)lane >= o) incl += x; }
+    if (lane == 63u) wave_sum[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - mine;
+    for (uint32_t w = 0; w < wave; w++) run += wave_sum[w];
+    for (uint32_t k = 0; k < per; k++) {
+      const uint32_t i = tid * per + k;
+      if (i < m) prefix[i] = run;
+      run += size[k];
+    }
+    const uint32_t total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+    if (tid == 0) prefix[m] = total;
+    __syncthreads();
+    for (uint32_t q = tid; q < total && base + q < b.count; q += 256u) {  // rank base + q of the block = rank q of the chunk
+      uint32_t doc, tf = 0u;
+      if (bitmap) doc = rbd_doc_bitmap(b, h, prefix, q);
+      else {
+        const uint32_t i = rbd_prefix_find(prefix, m, q);
+        uint32_t s, l;
+        rbd_rle_run(b, h, c0 + i, &s, &l);
+        doc = s + (q - prefix[i]);
+      }
+      rc = doc >= D.level_docs ? (int)RBD_EINVAL : rbd_tf(b, h, base + q, &tf);
+      if (rc != RBD_OK) { rbd_fail(status, rc); continue; }
+      rbd_store(D, d, base + q, doc, tf);
+    }
+    base += total;
+    __syncthreads();  // (the next chunk overwrites the table)
+  }
+  if (base != b.count && tid == 0) rbd_fail(status, RBD_EINVAL);  // count != popcount / sum of runs
+}
+
+struct DevBuf {  // a device block freed when the call returns
+  void* p = nullptr;
+  size_t cap = 0;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int reserve(size_t bytes) {
+    if (bytes <= cap) return SS_OK;
+    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    SS_HIP(hipMalloc(&p, bytes + bytes / 4 + 256));
+    cap = bytes + bytes / 4 + 256;
+    return SS_OK;
+  }
+};
+
+inline uint64_t rd64(const uint8_t* p) { uint64_t v; std::memcpy(&v, p, 8); return v; }
+
+// what the open builds before the swap: released on every way out until the shard has taken it
+struct OpenState {
+  std::vector<ss_raw_level> levels;
+  ss_sparse_tier_built tier;
+  std::unique_ptr<ss_shard> img{new ss_shard};
+  ss_shard* owner = nullptr;
+  hipStream_t st = nullptr;
+  bool taken = false;
+  ~OpenState() {
+    if (!taken) {
+      for (ss_raw_level& L : levels) raw_level_free(L);
+      ssi_bm25_sparse_tier_drop(&tier);
+      bm_image_arrays(img.get(), [&](auto*& p) { if (p && !owner->blocks.release(p)) (void)hipFree(p); });
+    }
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+// a block of the file as the walk found it, with what its level's launch needs: read once in term order, written to its level's run,
+// so that the per-level pass below reads its blocks in a row (the block table itself is in term order: 40 bytes a block, a cache miss each)
+struct LevelEntry { RbdDesc d; const uint8_t* body; uint32_t term; };
+
+// the device decoder: every level's postings of the dense terms into the level's arrays, the rare terms' into the tier's
+int decode_levels_device(const ss_index_bin* ix, uint32_t n_dense, uint32_t n_all, const std::vector<uint32_t>& level_docs, OpenState& O) {
+  static const bool trace = getenv("SS_LOAD_TRACE") != nullptr;
+  const auto t_0 = std::chrono::steady_clock::now();
+  const uint32_t nl = (uint32_t)level_docs.size();
+  hipStream_t st = O.st;
+  // ---- the blocks, level by level, in term order; a rare term's postings follow each other level after level in its list
+  std::vector<uint64_t> lvl_first((size_t)nl + 1, 0);
+  for (const ss_index_bin::Blk& e : ix->blocks) {
+    if (e.b.block_id >= nl) return SS_EINVAL;
+    lvl_first[e.b.block_id + 1]++;
+  }
+  for (uint32_t l = 0; l < nl; l++) lvl_first[l + 1] += lvl_first[l];
+  NoInitVec<LevelEntry> ent(ix->blocks.size());
+  ss_sparse_tier_built& T = O.tier;
+  const uint32_t n_rare = n_all - n_dense;
+  {
+    std::vector<uint64_t> at(lvl_first.begin(), lvl_first.end() - 1);
+    if (n_rare) { T.h_base.assign((size_t)n_rare + 1, 0); T.h_last_n.assign(n_rare, 0); }
+    uint64_t sp_at = 0;
+    for (uint32_t t = 0; t < n_all; t++) {
+      for (uint64_t bi = ix->term_block_off[t]; bi < ix->term_block_off[t + 1]; bi++) {
+        const ss_index_bin::Blk& e = ix->blocks[bi];
+        const ss_ref_block& b = e.b;
+        const uint32_t n = (uint32_t)b.posting_count_m1 + 1u;
+        if (b.byte_array_len > 0xFFFFFFFFull) return SS_EINVAL;
+        LevelEntry& E = ent[at[b.block_id]++];
+        E.d = RbdDesc{};
+        E.d.dst = t < n_dense ? 0ull : sp_at;
+        E.d.body_len = (uint32_t)b.byte_array_len;
+        E.d.ctp = b.compression_type_pointer;
+        E.d.count_m1 = b.posting_count_m1; E.d.pivot = b.pointer_pivot_p_docid;
+        E.d.n_comp = e.n_comp; E.d.comp = e.comp;
+        E.d.sparse = t < n_dense ? 0 : 1;
+        E.body = b.byte_array;
+        E.term = t;
+        if (t >= n_dense) {
+          sp_at += n;
+          if (b.block_id == nl - 1u) T.h_last_n[t - n_dense] = n;
+        }
+      }
+      if (t >= n_dense) T.h_base[t - n_dense + 1] = sp_at;
+    }
+  }
+  if (n_rare) {
+    const uint64_t tot = T.h_base[n_rare];
+    T.n_lists = n_rare; T.last_level = nl - 1u;
+    SS_HIP(hipMalloc(&T.d_base, ((size_t)n_rare + 1) * sizeof(uint64_t)));
+    SS_HIP(hipMalloc(&T.d_post, std::max<uint64_t>(tot, 1) * sizeof(uint64_t)));
+    SS_HIP(hipMalloc(&T.d_tf, std::max<uint64_t>(tot, 1) * sizeof(uint16_t)));
+    SS_HIP(hipMemcpyAsync(T.d_base, T.h_base.data(), ((size_t)n_rare + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  }
+  DevBuf d_stage, d_flat, d_wg, d_status;
+  SS_TRY(d_status.reserve(sizeof(uint32_t)));
+  SS_HIP(hipMemsetAsync(d_status.p, 0, sizeof(uint32_t), st));
+  std::vector<uint64_t> offs((size_t)n_dense + 1);
+  NoInitVec<RbdDesc> flat, wg;
+  double ms_host = 0, ms_dev = 0;
+  uint64_t n_post_all = 0, n_bytes_all = 0;
+  O.levels.resize(nl);
+  for (uint32_t l = 0; l < nl; l++) {
+    const auto t_a = std::chrono::steady_clock::now();
+    // the level's bytes: from its length bytes to the next level's (the last one: to the end of the file)
+    const uint8_t* lv_begin = ix->doclen[l];
+    const uint8_t* lv_end = l + 1 < nl ? ix->doclen[l + 1] : ix->bytes + ix->len;
+    const uint64_t lv_bytes = (uint64_t)(lv_end - lv_begin);
+    const LevelEntry* E = ent.data() + lvl_first[l];
+    const uint64_t ne = lvl_first[l + 1] - lvl_first[l];
+    // the level's CSR over the dense terms
+    std::fill(offs.begin(), offs.end(), 0ull);
+    for (uint64_t i = 0; i < ne && E[i].term < n_dense; i++) offs[E[i].term + 1] = (uint64_t)E[i].d.count_m1 + 1u;
+    for (uint32_t t = 0; t < n_dense; t++) offs[t + 1] += offs[t];
+    flat.clear(); wg.clear();
+    uint64_t n_flat_post = 0;
+    for (uint64_t i = 0; i < ne; i++) {
+      if (E[i].body < lv_begin || E[i].body + E[i].d.body_len > lv_end) return SS_EINVAL;
+      RbdDesc d = E[i].d;
+      d.body = (uint64_t)(E[i].body - lv_begin);
+      if (!d.sparse) d.dst = offs[E[i].term];
+      if ((d.ctp >> 30) == 1u) {
+        if (n_flat_post + 65536u > 0xFFFFFFFFull) return SS_ENOTSUP;  // (2^32 postings in the Array blocks of one level)
+        d.first = (uint32_t)n_flat_post;
+        n_flat_post += (uint64_t)d.count_m1 + 1u;
+        flat.push_back(d);
+      } else {
+        wg.push_back(d);
+      }
+    }
+    ss_raw_level& L = O.levels[l];
+    L.n_docs = level_docs[l]; L.n_terms = n_dense; L.n_post = offs[n_dense];
+    const uint64_t np1 = std::max<uint64_t>(L.n_post, 1);
+    SS_HIP(hipMalloc(&L.d_off, ((size_t)n_dense + 1) * sizeof(uint64_t)));
+    SS_HIP(hipMalloc(&L.d_doc, np1 * sizeof(uint32_t)));
+    SS_HIP(hipMalloc(&L.d_tf, np1 * sizeof(uint16_t)));
+    SS_TRY(d_stage.reserve(lv_bytes));
+    SS_TRY(d_flat.reserve(std::max<size_t>(flat.size(), 1) * sizeof(RbdDesc)));
+    SS_TRY(d_wg.reserve(std::max<size_t>(wg.size(), 1) * sizeof(RbdDesc)));
+    const auto t_b = std::chrono::steady_clock::now();
+    SS_HIP(hipMemcpyAsync(L.d_off, offs.data(), ((size_t)n_dense + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SS_HIP(hipMemcpyAsync(d_stage.p, lv_begin, lv_bytes, hipMemcpyHostToDevice, st));
+    if (!flat.empty()) SS_HIP(hipMemcpyAsync(d_flat.p, flat.data(), flat.size() * sizeof(RbdDesc), hipMemcpyHostToDevice, st));
+    if (!wg.empty()) SS_HIP(hipMemcpyAsync(d_wg.p, wg.data(), wg.size() * sizeof(RbdDesc), hipMemcpyHostToDevice, st));
+    RbdDst D{L.d_doc, L.d_tf, T.d_post, T.d_tf, l << 16, level_docs[l]};
+    if (n_flat_post)
+      rbd_flat_kernel<<<(uint32_t)((n_flat_post + 255u) / 256u), 256, 0, st>>>((const uint8_t*)d_stage.p, (const RbdDesc*)d_flat.p, (uint32_t)flat.size(),
+                                                                             (uint32_t)n_flat_post, D, (uint32_t*)d_status.p);
+    if (!wg.empty())
+      rbd_wg_kernel<<<(uint32_t)wg.size(), 256, 0, st>>>((const uint8_t*)d_stage.p, (const RbdDesc*)d_wg.p, D, (uint32_t*)d_status.p);
+    SS_HIP(hipGetLastError());
+    SS_HIP(hipStreamSynchronize(st));  // (the host arrays and the staging serve the next level)
+    const auto t_c = std::chrono::steady_clock::now();
+    ms_host += std::chrono::duration<double, std::milli>(t_b - t_a).count();
+    ms_dev += std::chrono::duration<double, std::milli>(t_c - t_b).count();
+    for (const RbdDesc& d : wg) n_post_all += (uint64_t)d.count_m1 + 1u;
+    n_post_all += n_flat_post;
+    n_bytes_all += lv_bytes;
+  }
+  uint32_t status = 0;
+  SS_HIP(hipMemcpy(&status, d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (trace)
+    fprintf(stderr, "[load] open levels: block lists %.0f ms; %u levels, %llu postings, %llu file bytes: descriptors %.0f ms, copies + decode kernels %.0f ms\n",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_0).count() - ms_host - ms_dev, nl,
+            (unsigned long long)n_post_all, (unsigned long long)n_bytes_all, ms_host, ms_dev);
+  if (status) return status == (uint32_t)(-SS_ENOTSUP) ? SS_ENOTSUP : SS_EINVAL;
+  return SS_OK;
+}
+
+// with positions: the host decoder's postings and positions, cut per level (dense terms) / taken whole (rare terms)
+int decode_levels_host_positions(const ss_index_bin* ix, uint32_t n_dense, uint32_t n_all, const std::vector<uint32_t>& level_docs, OpenState& O) {
+  const uint32_t nl = (uint32_t)level_docs.size();
+  hipStream_t st = O.st;
+  {
+    DecodedRange D;
+    SS_TRY(ssi_index_bin_decode_range(ix, 0, n_dense, true, &D));
+    // a term's first position in D.pos, and per (term, level) where its postings and positions begin: the blocks tell the postings
+    std::vector<uint64_t> tpos((size_t)n_dense + 1, 0);
+    ss_parallel_for(n_dense, 256, [&](size_t a, size_t b, unsigned) {
+      for (size_t t = a; t < b; t++) {
+        uint64_t c = 0;
+        for (uint64_t j = D.offs[t]; j < D.offs[t + 1]; j++) c += D.npos[j];
+        tpos[t + 1] = c;
+      }
+    });
+    for (uint32_t t = 0; t < n_dense; t++) tpos[t + 1] += tpos[t];
+    if (tpos[n_dense] != D.pos.size()) return SS_EINVAL;
+    const uint64_t nb = ix->term_block_off[n_dense];
+    std::vector<uint64_t> blk_post(nb), blk_pos(nb), blk_npos(nb);  // per block of a dense term
+    std::atomic<int> bad{0};
+    ss_parallel_for(n_dense, 256, [&](size_t a, size_t b, unsigned) {
+      for (size_t t = a; t < b; t++) {
+        uint64_t j = D.offs[t], p = tpos[t];
+        for (uint64_t bi = ix->term_block_off[t]; bi < ix->term_block_off[t + 1]; bi++) {
+          const uint64_t n = (uint64_t)ix->blocks[bi].b.posting_count_m1 + 1u;
+          if (ix->blocks[bi].b.block_id >= nl || j + n > D.offs[t + 1]) { bad.store(1); return; }
+          uint64_t c = 0;
+          for (uint64_t x = j; x < j + n; x++) c += D.npos[x];
+          blk_post[bi] = j; blk_pos[bi] = p; blk_npos[bi] = c;
+          j += n; p += c;
+        }
+      }
+    });
+    if (bad.load()) return SS_EINVAL;
+    std::vector<uint64_t> cur(ix->term_block_off.begin(), ix->term_block_off.begin() + n_dense);  // every term's next block
+    std::vector<uint64_t> offs((size_t)n_dense + 1), poff((size_t)n_dense + 1);
+    std::vector<uint32_t> docs;
+    std::vector<uint16_t> tfs, npos, pos;
+    O.levels.resize(nl);
+    for (uint32_t l = 0; l < nl; l++) {
+      offs[0] = 0; poff[0] = 0;
+      for (uint32_t t = 0; t < n_dense; t++) {
+        const bool here = cur[t] < ix->term_block_off[t + 1] && ix->blocks[cur[t]].b.block_id == l;
+        offs[t + 1] = offs[t] + (here ? (uint64_t)ix->blocks[cur[t]].b.posting_count_m1 + 1u : 0u);
+        poff[t + 1] = poff[t] + (here ? blk_npos[cur[t]] : 0u);
+      }
+      docs.resize(std::max<uint64_t>(offs[n_dense], 1)); tfs.resize(docs.size()); npos.resize(docs.size());
+      pos.resize(std::max<uint64_t>(poff[n_dense], 1));
+      ss_parallel_for(n_dense, 256, [&](size_t a, size_t b, unsigned) {
+        for (size_t t = a; t < b; t++) {
+          const uint64_t n = offs[t + 1] - offs[t];
+          if (!n) continue;
+          const uint64_t bi = cur[t];
+          std::memcpy(&docs[offs[t]], D.docs.data() + blk_post[bi], n * sizeof(uint32_t));
+          std::memcpy(&tfs[offs[t]], D.tfs.data() + blk_post[bi], n * sizeof(uint16_t));
+          std::memcpy(&npos[offs[t]], D.npos.data() + blk_post[bi], n * sizeof(uint16_t));
+          if (blk_npos[bi]) std::memcpy(&pos[poff[t]], D.pos.data() + blk_pos[bi], blk_npos[bi] * sizeof(uint16_t));
+        }
+      });
+      for (uint32_t t = 0; t < n_dense; t++)
+        if (offs[t + 1] > offs[t]) cur[t]++;
+      LevelPositions P;
+      SS_TRY(ssi_level_positions_prepare(n_dense, offs.data(), tfs.data(), npos.data(), pos.data(), poff[n_dense], &P));
+      ss_raw_level& L = O.levels[l];
+      L.n_docs = level_docs[l]; L.n_terms = n_dense; L.n_post = offs[n_dense]; L.n_pos = poff[n_dense];
+      const raw_level_positions rp{P.npos.data(), P.prel.data(), P.tpos.data(), pos.data(), poff[n_dense]};
+      SS_TRY(raw_level_upload(L, offs.data(), docs.data(), tfs.data(), n_dense, &rp, st));
+    }
+  }
+  if (n_dense == n_all) return SS_OK;
+  // the rare keys: whole lists with their tfs and positions; what the last level brought is what a re-commit of it replaces
+  DecodedRange R;
+  SS_TRY(ssi_index_bin_decode_range(ix, n_dense, n_all, true, &R));
+  const uint32_t n_rare = n_all - n_dense;
+  const uint64_t tot = R.offs[n_rare], d_last = (uint64_t)(nl - 1u) << 16;
+  ss_sparse_tier_built& T = O.tier;
+  T.n_lists = n_rare; T.last_level = nl - 1u; T.with_pos = true;
+  T.h_base.assign(R.offs.begin(), R.offs.end());
+  T.h_pbase.assign((size_t)n_rare + 1, 0);
+  T.h_last_n.assign(n_rare, 0); T.h_last_pos.assign(n_rare, 0);
+  NoInitVec<uint64_t> post(std::max<uint64_t>(tot, 1)), pend(std::max<uint64_t>(tot, 1));
+  ss_parallel_for(n_rare, 4096, [&](size_t a, size_t b, unsigned) {
+    for (size_t i = a; i < b; i++) {
+      uint64_t c = 0;
+      for (uint64_t j = R.offs[i]; j < R.offs[i + 1]; j++) c += R.npos[j];
+      T.h_pbase[i + 1] = c;
+    }
+  });
+  for (uint32_t i = 0; i < n_rare; i++) T.h_pbase[i + 1] += T.h_pbase[i];
+  if (T.h_pbase[n_rare] != R.pos.size()) return SS_EINVAL;
+  ss_parallel_for(n_rare, 4096, [&](size_t a, size_t b, unsigned) {
+    for (size_t i = a; i < b; i++) {
+      uint64_t run = T.h_pbase[i];
+      for (uint64_t j = R.offs[i]; j < R.offs[i + 1]; j++) {
+        run += R.npos[j];
+        post[j] = R.docs[j]; pend[j] = run;
+        if (R.docs[j] >= d_last) { T.h_last_n[i]++; T.h_last_pos[i] += R.npos[j]; }
+      }
+    }
+  });
+  T.pos_n = R.pos.size();
+  SS_HIP(hipMalloc(&T.d_base, ((size_t)n_rare + 1) * sizeof(uint64_t)));
+  SS_HIP(hipMalloc(&T.d_post, post.size() * sizeof(uint64_t)));
+  SS_HIP(hipMalloc(&T.d_tf, post.size() * sizeof(uint16_t)));
+  SS_HIP(hipMalloc(&T.d_pos_end, post.size() * sizeof(uint64_t)));
+  SS_HIP(hipMalloc(&T.d_pos, std::max<uint64_t>(T.pos_n, 1) * sizeof(uint16_t)));
+  SS_HIP(hipMemcpyAsync(T.d_base, T.h_base.data(), ((size_t)n_rare + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if (tot) {
+    SS_HIP(hipMemcpyAsync(T.d_post, post.data(), tot * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SS_HIP(hipMemcpyAsync(T.d_tf, R.tfs.data(), tot * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    SS_HIP(hipMemcpyAsync(T.d_pos_end, pend.data(), tot * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  }
+  if (T.pos_n) SS_HIP(hipMemcpyAsync(T.d_pos, R.pos.data(), T.pos_n * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+  SS_HIP(hipStreamSynchronize(st));  // (the host arrays die with this frame)
+  return SS_OK;
+}
+
+int open_levels_impl(ss_shard* s, const ss_index_bin* ix, bool with_positions) {
+  const auto t_begin = std::chrono::steady_clock::now();
+  static const bool trace = getenv("SS_LOAD_TRACE") != nullptr;
+  const uint32_t n_all = (uint32_t)ix->keys.size(), n_dense = std::min<uint32_t>(ix->n_dense, n_all);  // ss_index_bin_tier
+  if (n_dense == 0) return SS_EINVAL;  // the dense image needs at least one list
+  const uint32_t nl = (uint32_t)ix->doclen.size();
+  if (nl == 0 || ix->n_docs > 0xFFFFFFFFull || ix->n_docs <= (uint64_t)(nl - 1u) * 65536u || ix->n_docs > (uint64_t)nl * 65536u) return SS_EINVAL;
+  // every level's docs and the sum of their lengths as the file states it: indexed_doc_count / positions_sum_normalized are cumulative
+  // (commit.rs:298-311), so the levels' shares add up to what ss_bm25_upload_index_bin divides (index.rs:3480-3482)
+  std::vector<uint32_t> level_docs(nl);
+  std::vector<uint64_t> level_psum(nl);
+  std::vector<uint8_t> doclen(ix->n_docs);
+  uint64_t cum = 0;
+  for (uint32_t l = 0; l < nl; l++) {
+    level_docs[l] = (uint32_t)std::min<uint64_t>(65536u, ix->n_docs - (uint64_t)l * 65536u);
+    const uint64_t c = rd64(ix->doclen[l] + 65536u + 8u);
+    if (c < cum) return SS_EINVAL;
+    level_psum[l] = c - cum;
+    cum = c;
+    std::memcpy(doclen.data() + (size_t)l * 65536u, ix->doclen[l], level_docs[l]);
+  }
+  // a term holds at most one block per level, levels ascending (ss_bm25_upload_ref_blocks asks the same): a key head that stands in two
+  // segments of one level would send two blocks to one destination -- refused here, before anything is staged or launched
+  {
+    std::atomic<int> bad{0};
+    ss_parallel_for(n_all, 16384, [&](size_t a, size_t b, unsigned) {
+      for (size_t t = a; t < b; t++)
+        for (uint64_t bi = ix->term_block_off[t]; bi < ix->term_block_off[t + 1]; bi++)
+          if (ix->blocks[bi].b.block_id >= nl || (bi > ix->term_block_off[t] && ix->blocks[bi].b.block_id <= ix->blocks[bi - 1].b.block_id)) { bad.store(1); return; }
+    });
+    if (bad.load()) return SS_EINVAL;
+  }
+  SS_HIP(hipSetDevice(s->device));
+  OpenState O;
+  O.owner = s;
+  if (const hipError_t e = hipStreamCreateWithFlags(&O.st, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
+  SS_TRY(with_positions ? decode_levels_host_positions(ix, n_dense, n_all, level_docs, O) : decode_levels_device(ix, n_dense, n_all, level_docs, O));
+  for (uint32_t l = 0; l < nl; l++) O.levels[l].psum = level_psum[l];
+  const auto t_build = std::chrono::steady_clock::now();
+  // ONE rebuild over all levels, beside the serving image (commits of one shard are the caller's to serialise, as for ss_bm25_append_level)
+  SS_TRY(ssi_bm25_rebuild_from_raw(s, O.levels, n_dense, doclen.data(), doclen.size(), O.img.get(), O.st));
+  const auto t_tier = std::chrono::steady_clock::now();
+  const bool tier = n_dense < n_all;
+  if (tier) SS_TRY(ssi_bm25_sparse_tier_code(&O.tier, O.img.get(), O.st));  // a weight the code cannot hold: SS_ENOTSUP, nothing changed
+  const auto t_swap = std::chrono::steady_clock::now();
+  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  SS_TRY(ssi_bm25_install_levels(s, O.levels, doclen, O.img.get(), tier ? &O.tier : nullptr, ms(t_build, t_tier), ms(t_begin, std::chrono::steady_clock::now())));
+  O.taken = true;
+  if (trace)
+    fprintf(stderr, "[load] open levels: decode %.0f ms, rebuild %.0f ms, tier codes %.0f ms, swap %.0f ms\n", ms(t_begin, t_build), ms(t_build, t_tier),
+            ms(t_tier, t_swap), ms(t_swap, std::chrono::steady_clock::now()));
+  return SS_OK;
+}
+
+}  // namespace
+
+extern "C" int ss_bm25_open_index_bin_levels(ss_shard* s, const ss_index_bin* ix, int with_positions) {
+  if (!s || !ix) return SS_EINVAL;
+  if (ix->keys.empty() || ix->n_docs == 0) return SS_EINVAL;
+  if (ix->n_fields > 1) return SS_ENOTSUP;  // several indexed fields: ss_bm25_upload_index_bin_fields (their decode on the device is not built)
+  return ss_guard([&] { return open_levels_impl(s, ix, with_positions != 0); }, SS_ENOMEM, SS_EDEVICE);
+}

@@ -20,6 +20,7 @@
 
 #include "ss_common.h"
 #include "ss_threads.h"
+#include "ref_index_bin.h"
 
 namespace {
 
@@ -590,26 +591,6 @@ extern "C" int ss_bm25_upload_ref_blocks(ss_shard* s, uint64_t n_docs, const uin
 //   key head (compress_postinglist.rs:339-409): u64 key_hash @0 (low 3 bits = NgramType), u16 posting_count - 1 @8,
 //     u16 max_docid @10, u16 max_p_docid @12, n-gram df bytes @14.., u16 pointer_pivot_p_docid @size-6,
 //     u32 compression_type_pointer @size-4
-struct ss_index_bin {
-  const uint8_t* bytes = nullptr;
-  uint64_t len = 0;
-  uint32_t n_fields = 1, key_head_size = 20, seg_bits = 11;
-  uint64_t n_docs = 0, positions_sum = 0;
-  uint32_t n_ngram_keys = 0;
-  uint16_t longest_field_id = 0;
-  std::vector<const uint8_t*> doclen;  // per level: indexed_field_count arrays of 65 536 bytes
-  struct Blk {
-    uint64_t key;
-    ss_ref_block b;
-    uint8_t n_comp, comp;              // n-gram key: one entry per component term (2 or 3), SingleTerm: 1 / 0
-    uint8_t df_byte;                   // posting_count_ngram_{comp+1}_compressed of the key head
-  };                                   // (trivially constructible: see NoInitAlloc)
-  std::vector<Blk, NoInitAlloc<Blk>> blocks;  // sorted by (key, component, block_id)
-  std::vector<uint64_t> keys;          // ascending; term id = index.  An n-gram key appears once per component, in order
-  std::vector<uint8_t> term_comp, term_ncomp, term_df_byte;  // per term; df byte of the LAST level (commit.rs:646-653)
-  std::vector<uint64_t> term_block_off;
-  uint32_t n_dense = 0xFFFFFFFFu;      // ss_index_bin_tier: terms [0, n_dense) go to the dense image, the rest to the sparse tier
-};
 
 namespace {
 inline uint64_t rd64(const uint8_t* p) { uint64_t v; std::memcpy(&v, p, 8); return v; }
@@ -923,20 +904,6 @@ namespace {
 // per-posting counts).  A term's posting count is known from its key heads, so docs / tfs / counts are decoded straight into their
 // final places; only the positions, whose number the heads do not tell, are gathered per chunk and copied once.  The arrays are
 // NOT value-initialised (a vector would zero a gigabyte on one thread first): the worker that decodes a range touches its pages.
-template <class T>
-struct RawBuf {
-  std::unique_ptr<T[]> p;
-  size_t n = 0;
-  void alloc(size_t m) { p.reset(new T[std::max<size_t>(m, 1)]); n = m; }
-  T* data() { return p.get(); }
-  const T* data() const { return p.get(); }
-  size_t size() const { return n; }
-};
-struct DecodedRange {
-  std::vector<uint64_t> offs;  // [t1 - t0 + 1]
-  RawBuf<uint32_t> docs;
-  RawBuf<uint16_t> tfs, pos, npos;
-};
 int index_bin_decode_range(const ss_index_bin* ix, uint32_t t0, uint32_t t1, bool with_positions, DecodedRange* out) {
   if (ix->n_fields != 1) return SS_ENOTSUP;
   const size_t nt = t1 - t0;
@@ -1284,3 +1251,8 @@ int upload_index_bin_single(ss_shard* s, const ss_index_bin* ix, bool with_posit
   return rc;
 }
 }  // namespace
+
+// the decoder of a range of terms for the other translation units (ref_index_bin.h)
+int ssi_index_bin_decode_range(const ss_index_bin* ix, uint32_t t0, uint32_t t1, bool with_positions, DecodedRange* out) {
+  return index_bin_decode_range(ix, t0, t1, with_positions, out);
+}

@@ -29,3 +29,26 @@ int ssi_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, 
 // weight the code cannot hold.  Caller holds s->mu, the device is idle.
 int ssi_bm25_commit_sparse_level_fields(ss_shard* s, uint32_t level, uint32_t n_lists, const uint64_t* offs, const uint32_t* docs, const uint8_t* fields,
                                         const uint16_t* tfs, const uint16_t* npos, const uint16_t* positions, uint64_t n_positions);
+
+// A tier that takes levels, built ASIDE from whole lists (ss_bm25_open_index_bin_levels: the rare keys of an index.bin, their docs from
+// the first level on) and swapped in with the image it was coded against.  d_post holds the docs (its codes: ssi_bm25_sparse_tier_code);
+// h_last_n / h_last_pos = per list what `last_level` brought, which a re-commit of that level replaces (ss_bm25_append_sparse_level).
+struct ss_sparse_tier_built {
+  uint32_t n_lists = 0;
+  std::vector<uint64_t> h_base;      // [n_lists + 1]
+  uint64_t* d_base = nullptr;        // [n_lists + 1]
+  uint64_t* d_post = nullptr;        // [postings]
+  uint16_t* d_tf = nullptr;          // [postings]
+  bool with_pos = false;             // positions (u16): per posting the END of its positions in the pool, the pool, the lists' starts
+  uint64_t* d_pos_end = nullptr;
+  uint16_t* d_pos = nullptr;
+  uint64_t pos_n = 0;
+  std::vector<uint64_t> h_pbase;     // [n_lists + 1]
+  uint32_t last_level = 0;
+  std::vector<uint32_t> h_last_n, h_last_pos;
+};
+// every posting's code under the length bytes and component cache of `img` (SS_ENOTSUP: a weight the code cannot hold)
+int ssi_bm25_sparse_tier_code(ss_sparse_tier_built* T, const ss_shard* img, hipStream_t st);
+// the tier becomes the shard's (whose own is gone: ssi_bm25_free); T is left empty.  Caller holds s->mu, the device is idle.
+void ssi_bm25_sparse_tier_take(ss_shard* s, ss_sparse_tier_built* T);
+void ssi_bm25_sparse_tier_drop(ss_sparse_tier_built* T);  // frees what T still owns

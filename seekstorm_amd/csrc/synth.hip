@@ -1448,6 +1448,30 @@ static int sparse_levels_recode(ss_shard* s, hipStream_t st, const ss_shard* img
 int ssi_bm25_sparse_levels_recode(ss_shard* s, hipStream_t st) { return sparse_levels_recode(s, st, s, true); }
 int ssi_bm25_sparse_levels_check(ss_shard* s, const ss_shard* img, hipStream_t st) { return sparse_levels_recode(s, st, img, false); }
 
+// ---- a tier built aside from whole lists (sparse_levels.h ss_sparse_tier_built)
+int ssi_bm25_sparse_tier_code(ss_sparse_tier_built* T, const ss_shard* img, hipStream_t st) {
+  return sp_recode_run(T->d_post, T->d_tf, T->h_base.empty() ? 0 : T->h_base.back(), 1, img, st, true);
+}
+void ssi_bm25_sparse_tier_drop(ss_sparse_tier_built* T) {
+  for (void* p : {(void*)T->d_base, (void*)T->d_post, (void*)T->d_tf, (void*)T->d_pos_end, (void*)T->d_pos}) if (p) (void)hipFree(p);
+  T->d_base = nullptr; T->d_post = nullptr; T->d_tf = nullptr; T->d_pos_end = nullptr; T->d_pos = nullptr;
+}
+void ssi_bm25_sparse_tier_take(ss_shard* s, ss_sparse_tier_built* T) {
+  s->d_sp_base = T->d_base; s->d_sp_post = T->d_post; s->sp_n = T->n_lists;
+  s->h_sp_base.swap(T->h_base);
+  if (T->with_pos) { s->d_sp_pos_end = T->d_pos_end; s->d_sp_pos = T->d_pos; s->sp_pos_n = T->pos_n; s->sp_pos_elem = (uint32_t)sizeof(uint16_t); }
+  std::lock_guard<std::mutex> g(g_spl_mu);
+  SparseLevels& E = g_spl[s];
+  if (E.d_tf) (void)hipFree(E.d_tf);
+  E.d_tf = T->d_tf;
+  E.n_fields = 1;
+  E.h_pbase.swap(T->h_pbase);
+  E.last_level = T->last_level;
+  E.h_last_n.swap(T->h_last_n);
+  E.h_last_pos.swap(T->h_last_pos);
+  T->d_base = nullptr; T->d_post = nullptr; T->d_tf = nullptr; T->d_pos_end = nullptr; T->d_pos = nullptr;
+}
+
 // What a level brings to the tier, however many fields: list i's postings off[i] .. off[i + 1] (from 0) of doc / tf (rows of F); with
 // positions, per posting the END of its positions counted from its list's first of the level (pend), the lists' first positions in the
 // level's pool (pbase [n_lists + 1]) and the pool itself (elements of sp_level_install's P).

@@ -158,6 +158,16 @@ int ssh_open_index_bin(ssh_index* ix, int shard, const uint8_t* bytes, uint64_t 
   return (int)keys.size();
 }
 
+// ... opened level by level, ready to commit to (Shard::open_index_bin with levels = true)
+int ssh_open_index_bin_levels(ssh_index* ix, int shard, const uint8_t* bytes, uint64_t len, uint32_t key_head_size, int with_positions,
+                              uint64_t* keys_out, uint32_t cap) {
+  std::vector<uint64_t> keys;
+  const int rc = ix->shards[shard]->open_index_bin(bytes, len, key_head_size, &keys, with_positions != 0, true);
+  if (rc) return rc;
+  for (size_t i = 0; i < keys.size() && i < cap; i++) keys_out[i] = keys[i];
+  return (int)keys.size();
+}
+
 // Index::search; returns the number of results written (<= cap)
 int ssh_search(ssh_index* ix, const uint32_t* terms, uint32_t n_terms, const float* query_vector, uint32_t query_type,
                int search_mode, uint32_t offset, uint32_t length, uint32_t result_type, int has_threshold, float threshold,

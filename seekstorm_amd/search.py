@@ -626,6 +626,16 @@ class Shard:
         self.lexical_field_count = int(ix.indexed_field_count)
         self._df_cache.clear()
 
+    def open_index_bin_levels(self, ix: "IndexBin", positions=False):
+        """index.bin opened level by level, ready to commit to (ss_bm25_open_index_bin_levels; one indexed field): one raw level per
+        level of the file, its blocks decoded on the device, one rebuild -- commit_level then takes the next level, or the last one again
+        if it was incomplete.  A tiered ix (IndexBin.tier) gives a sparse tier that takes levels.  positions: also every posting's
+        positions (phrase queries), through the host decoder"""
+        N.check(N.lib().ss_bm25_open_index_bin_levels(self._h, ix._h, 1 if positions else 0), "ss_bm25_open_index_bin_levels")
+        self.indexed_doc_count = int(ix.indexed_doc_count)
+        self.lexical_field_count = 1
+        self._df_cache.clear()
+
     def upload_vector_bin(self, data, dim, i8=False, use_record_scale=False):
         """vector.bin as the reference writes it: f32 records, or Precision::I8 records (i8=True)"""
         buf = np.frombuffer(bytes(data), np.uint8)
