@@ -62,6 +62,8 @@ __global__ void __launch_bounds__(256) bm_qbound_kernel(const bm_vquery* __restr
 }
 
 // (FILT / SKIP and the body itself: bm25_probe_body.h pb_wave)
+constexpr int PB_STAGED_G = 4;  // chunks of 64 driver postings per group in the staged kernel
+static_assert(PB_WAVES * pb_wave_lds(4, PB_STAGED_G) <= 53 * 1024, "three workgroups of the staged kernel must fit a CU's LDS");
 template <int NT, int KPL, bool FILT, bool SKIP>
 __global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
     const uint32_t* __restrict__ post, const unsigned long long* __restrict__ term_base, const uint32_t* __restrict__ sub_off,
@@ -82,7 +84,7 @@ __global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
 #define PB_STAGED_KTHB 0
 #endif
   // (PB_STAGED_KTHB: rank 0 of every partition's output list as its best-so-far key, zeroed by bm_expand_kernel -- measurement switch)
-  const BmTop<KPL> T = pb_wave<NT, KPL, FILT, SKIP, false, 4, PB_STAGED_KTHB != 0>(post, term_base, sub_off, probe, probe_z, probe_row, umax, pmax, qbound, PbQueryMem{qs + qi}, tau, del,
+  const BmTop<KPL> T = pb_wave<NT, KPL, FILT, SKIP, false, PB_STAGED_G, PB_STAGED_KTHB != 0>(post, term_base, sub_off, probe, probe_z, probe_row, umax, pmax, qbound, PbQueryMem{qs + qi}, tau, del,
                                                     del_words, n_sub, n_terms, P, k, count, qi, part, w, lane, 0.f,
                                                     (PB_STAGED_KTHB != 0 && k <= 64u && P >= k && k != 0u) ? part_keys + (size_t)qi * P * (64 * KPL) : nullptr, 64u * KPL);
 
@@ -96,7 +98,13 @@ template <int NT, int KPL, bool FILT, bool SKIP>
 static int launch_probe(const BmParams& p, const uint2* probe, const uint32_t* probe_z, const uint32_t* probe_row, const float* umax,
                         const float* pmax, const float* qbound, hipStream_t st) {
   const uint32_t A = p.nq * p.P;
-  bm25_probe_kernel<NT, KPL, FILT, SKIP><<<(A + PB_WAVES - 1) / PB_WAVES, PB_WAVES * 64, PB_WAVES * PB_QCAP * 12, st>>>(
+#if PB_STATS
+  void* stats = nullptr;
+  SS_HIP(hipGetSymbolAddress(&stats, HIP_SYMBOL(pb_stats_dev)));
+  SS_HIP(hipMemsetAsync(stats, 0, sizeof(pb_stats_dev), st));
+#endif
+  // LDS: 36 KB with the second queue of >= 3 terms, 30 KB without -- three workgroups a CU (occupancy 6) fit its 160 KB
+  bm25_probe_kernel<NT, KPL, FILT, SKIP><<<(A + PB_WAVES - 1) / PB_WAVES, PB_WAVES * 64, PB_WAVES * pb_wave_lds(NT, PB_STAGED_G), st>>>(
       p.post, p.term_base, p.sub_off, probe, probe_z, probe_row, umax, pmax, qbound, p.q, p.part_keys, p.total, p.tau, p.del, p.del_words, p.n_sub, p.n_terms, p.nq, p.P, p.k,
       p.count);
   return SS_OK;
@@ -249,3 +257,12 @@ int ssi_bm25_launch_probe(const BmParams& p, const uint2* probe, const uint32_t*
 #undef SS_P
   return SS_ENOTSUP;
 }
+
+#if PB_STATS
+// experiment builds (-DPB_STATS=1) only: the counters of the LAST staged launch (bm25_probe_body.h pb_stats_dev), read after the device is idle
+extern "C" int ssi_dbg_pb_stats(unsigned long long* out3) {
+  SS_HIP(hipDeviceSynchronize());
+  SS_HIP(hipMemcpyFromSymbol(out3, HIP_SYMBOL(pb_stats_dev), 3 * sizeof(unsigned long long)));
+  return SS_OK;
+}
+#endif

@@ -8,9 +8,28 @@
 #include "bm25_dev.h"
 
 constexpr int PB_WAVES = 8;
-// survivor queue entries per wave: < 64 left over + one group of G x 64 pushed (G = chunks of 64 driver postings evaluated together)
-constexpr int pb_qcap(int G) { return 64 * G + 64; }
-constexpr int PB_QCAP = pb_qcap(4);
+// PB_TWO_PHASE (measurement switch, on): bodies of >= 3 terms split their sparse stage in two (pb_wave: phase 1 / phase 2) and keep a
+// SECOND queue between them, three dwords an entry like the first (doc, driver weight, one rank byte per list)
+#ifndef PB_TWO_PHASE
+#define PB_TWO_PHASE 1
+#endif
+constexpr bool pb_two_phase(int NT) { return PB_TWO_PHASE != 0 && NT >= 3; }
+// Survivor queue entries per wave: < 64 left over + one group of G x 64 pushed (G = chunks of 64 driver postings evaluated together).
+// Where there is a second queue it lives in the SAME three arrays and grows down from their top: it holds < 64 entries whenever the first
+// is pushed to, and a phase-1 batch moves <= 64 entries from one to the other, so first + second <= 64 G + 126 at all times -- 64 entries
+// more than the first queue alone needs, not a second region of 128.
+constexpr int pb_qcap(int NT, int G) { return 64 * G + (pb_two_phase(NT) ? 128 : 64); }
+// bytes of LDS one wave of the body owns: the body's offsets, the launchers' sizes and bm25_small_kernel's region all come from here
+constexpr int pb_wave_lds(int NT, int G) { return pb_qcap(NT, G) * 12; }
+#ifndef PB_STATS
+#define PB_STATS 0
+#endif
+#if PB_STATS
+// experiment builds only: [0] entries pushed to the first queue, [1] entries that pass the bound of the sparse stage (phase 1; the one-phase
+// body: its round-3 bound), [2] postings of the first probed list fetched -- summed per wave, added once at the wave's end (one copy per
+// translation unit; bm25_probe.hip zeroes its own before every launch and reads it back)
+static __device__ unsigned long long pb_stats_dev[3];
+#endif
 
 // weight of one posting: it is IN the posting (ss_common.h) -- the same decode as the scan kernels'
 __device__ __forceinline__ float pb_weight(uint32_t p) { return bm_weight(p); }
@@ -225,9 +244,17 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
   // other term probed -- wait here until 64 of them can take the SPARSE stage together (posting fetch of the probed
   // term, remaining probes, score).  After the first probe only a few percent of the lanes are still alive; without
   // the queue every later gather round trip would be paid for a handful of lanes.
-  constexpr uint32_t QCAP = pb_qcap(G);
-  const uint32_t q_doc = (uint32_t)w * (QCAP * 12u), q_w0 = q_doc + QCAP * 4u, q_pos = q_w0 + QCAP * 4u;
+  constexpr uint32_t QCAP = pb_qcap(NT, G);
+  const uint32_t q_doc = (uint32_t)w * (uint32_t)pb_wave_lds(NT, G), q_w0 = q_doc + QCAP * 4u, q_pos = q_w0 + QCAP * 4u;
   uint32_t qn = 0;
+  // Second queue (>= 3 terms): what the first queue's entries become once the bit records of the REMAINING lists are known -- the docs whose
+  // bound over the lists they are actually in still reaches the threshold.  Only they pay for rank-table entries and postings.
+  // Entry j lies at element QCAP - 1 - j of the first queue's arrays (pb_qcap), its rank bytes where the first queue keeps the rank in A.
+  constexpr bool TWO = pb_two_phase(NT);
+  uint32_t q2n = 0;
+#if PB_STATS
+  uint32_t st_push = 0u, st_pass = 0u, st_apost = 0u;
+#endif
 
   // one driver stream: the postings of processing term J inside this partition's sub-block range
   auto stream = [&](auto Jc) {
@@ -241,7 +268,108 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
     // counts its own matches.)
     if (J == 0 && !is_and && k && !(count && nt == 1) && SU[0] < cur_thr() * 0.99999f) return;
 
-    // ---- sparse stage: the LAST n queue entries (n <= 64), one per lane
+    // ---- sparse stage, phase 2 (>= 3 terms): the LAST n entries of the second queue (n <= 64), one per lane.  Round 1: the rank-table
+    // entries of every list the doc is in, A and the further ones, at once; round 2: their postings at once; then filters, score, offer.
+    // Everything it needs comes from LDS: nothing of phase 1 stays live across it.
+    auto fetch = [&](uint32_t n) {
+      const float thr = cur_thr();
+      bool alive = (uint32_t)lane < n;
+      const uint32_t eb = (QCAP - 1u - (q2n - n + (uint32_t)lane)) * 4u;  // (dead lanes compute an offset they never use)
+      const uint32_t doc = alive ? lds_ld32(q_doc + eb) : 0u;
+      const uint32_t rks = alive ? lds_ld32(q_pos + eb) : 0xFFFFFFFFu;  // byte t: rank of the doc inside its group of list t, 0xFF = not in it
+      float wv[NT];
+#pragma unroll
+      for (int t = 0; t < NT; t++) wv[t] = 0.f;
+      wv[J] = alive ? lds_ldf(q_w0 + eb) : 0.f;
+      uint32_t pres = 1u << J;
+      const uint32_t gidx = (doc >> BM_SUB_LOG2) * (uint32_t)(BM_SUB / 64) + ((doc & (BM_SUB - 1)) >> 6);
+      uint32_t zt[NT];
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        zt[t] = 0u;
+        if (t == J || (uint32_t)t >= nt) continue;
+        zt[t] = zrow[t][((rks >> (8 * t)) & 0xFFu) != 0xFFu ? gidx : 0u];  // unconditional loads (lanes without a hit: element 0)
+      }
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        if (t == J || (uint32_t)t >= nt) continue;
+        const uint32_t rk = (rks >> (8 * t)) & 0xFFu;
+        if (rk != 0xFFu) {
+          wv[t] = pb_weight(tptr[t][zt[t] + rk]);
+          pres |= 1u << t;
+        }
+      }
+#if PB_STATS
+      st_apost += (uint32_t)__popcll(__ballot(((rks >> (8 * A)) & 0xFFu) != 0xFFu));
+#endif
+      if (FILT && del && __ballot(alive)) alive = alive && !is_deleted(alive, doc);
+      if (FILT && n_not && !(count && is_and) && k) alive = alive && combine(wv, pres) >= thr;  // probe the NOT lists for real candidates only
+      if (FILT && n_not && __ballot(alive)) alive = alive && !in_not_list(alive, doc);
+      if (__ballot(alive)) {
+        if (count && is_and) T.matched += __popcll(__ballot(alive));
+        if (k) {
+          const float score = combine(wv, pres);
+          offer(alive && score >= thr && score > 0.f, score, doc);
+        }
+      }
+      q2n -= n;
+    };
+
+    // ---- sparse stage, phase 1 (>= 3 terms): the LAST n entries of the first queue (n <= 64), one per lane
+    auto sift = [&](uint32_t n) {
+      // the bit records of the remaining lists and NOTHING else.  A survivor of the dense stage was let through on the bounds of
+      // every further list, whether or not it is in them; here the bound is summed over the lists the doc IS in, and most survivors end
+      // before a rank-table entry or a posting has been fetched for them.
+      const float thr = cur_thr();
+      bool alive = (uint32_t)lane < n;
+      const uint32_t qb = (qn - n + (uint32_t)lane) * 4u;
+      const uint32_t doc = alive ? lds_ld32(q_doc + qb) : 0u;
+      const uint32_t pos = alive ? lds_ld32(q_pos + qb) : 0xFFFFFFFFu;  // rank inside the group of A, or no hit
+      const float w0 = alive ? lds_ldf(q_w0 + qb) : 0.f;
+      const uint32_t d = doc & (BM_SUB - 1);
+      const uint32_t gidx = (doc >> BM_SUB_LOG2) * (uint32_t)(BM_SUB / 64) + (d >> 6);
+      uint2 rb[NT];
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        rb[t] = make_uint2(0u, 0u);
+        if (t == J || t == A || (uint32_t)t >= nt) continue;
+        rb[t] = prow[t][alive ? gidx : 0u];  // unconditional loads (dead lanes: element 0), no exec-masked branches
+      }
+      const bool hit_a = pos != 0xFFFFFFFFu;
+      float ub = idf[J] * w0 + (hit_a ? U[A] : 0.f);
+      uint32_t rks = 0xFFFFFFFFu ^ ((hit_a ? (pos ^ 0xFFu) : 0u) << (8 * A));
+      bool hit[NT];
+#pragma unroll
+      for (int t = 0; t < NT; t++) {
+        hit[t] = false;
+        if (t == J || t == A || (uint32_t)t >= nt) continue;
+        const u64 bits = ((u64)rb[t].y << 32) | rb[t].x;
+        hit[t] = alive && ((bits >> (d & 63u)) & 1ull);
+        if (is_and) alive = hit[t];
+        else if (t < J && hit[t]) { alive = false; }  // evaluated in the earlier term's stream
+        const uint32_t rk = (uint32_t)__popcll(bits & ((1ull << (d & 63u)) - 1ull));
+        if (hit[t]) { rks ^= (rk ^ 0xFFu) << (8 * t); ub += U[t]; }
+      }
+      if (!is_and && k) alive = alive && ub >= thr * 0.99999f;
+      const u64 m = __ballot(alive);
+      if (m) {
+        if (alive) {
+          // (the slots written lie above the first queue's entries that remain, and the ones being moved are in registers: pb_qcap)
+          const uint32_t at = (QCAP - 1u - (q2n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)))) * 4u;
+          lds_st32(q_doc + at, doc);
+          lds_stf(q_w0 + at, w0);
+          lds_st32(q_pos + at, rks);
+        }
+        q2n += (uint32_t)__popcll(m);
+      }
+#if PB_STATS
+      st_pass += (uint32_t)__popcll(m);
+#endif
+      qn -= n;
+      while (q2n >= 64u) fetch(64u);
+    };
+
+    // ---- sparse stage in one piece (<= 2 terms: there is no further list): the LAST n queue entries (n <= 64), one per lane
     auto drain = [&](uint32_t n) {
       const float thr = cur_thr();
       bool alive = (uint32_t)lane < n;
@@ -295,6 +423,10 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
       // round 3: postings of the other hits (skipped when the bounds already rule the doc out)
       float rest = SU[0] - U[J] - ((uint32_t)A < nt ? U[A] : 0.f);
       if (!is_and && k) alive = alive && (known + rest) >= thr * 0.99999f;
+#if PB_STATS
+      st_pass += (uint32_t)__popcll(__ballot(alive));
+      st_apost += (uint32_t)__popcll(__ballot(hit_a));
+#endif
 #pragma unroll
       for (int t = 0; t < NT; t++) {
         if (t == J || t == A || (uint32_t)t >= nt) continue;
@@ -444,11 +576,20 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
             lds_st32(q_pos + at * 4u, pos);
           }
           qn += (uint32_t)__popcll(m);
+#if PB_STATS
+          st_push += (uint32_t)__popcll(m);
+#endif
         }
       }
-      while (qn >= 64u) drain(64u);
+      if constexpr (TWO) { while (qn >= 64u) sift(64u); }
+      else { while (qn >= 64u) drain(64u); }
     }
-    if (qn) drain(qn);
+    if constexpr (TWO) {  // (both queues are empty between streams and when the body returns)
+      if (qn) sift(qn);
+      if (q2n) fetch(q2n);
+    } else {
+      if (qn) drain(qn);
+    }
   };
   // drivers: unions -> every term in upper-bound order (a stream ends as soon as its term is non-essential);
   // intersections -> the shortest list only
@@ -460,5 +601,12 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
     if (NT > 3 && nt > 3) stream(std::integral_constant<int, (NT > 3 ? 3 : 0)>{});
   }
 
+#if PB_STATS
+  if (lane == 0) {
+    atomicAdd(&pb_stats_dev[0], (unsigned long long)st_push);
+    atomicAdd(&pb_stats_dev[1], (unsigned long long)st_pass);
+    atomicAdd(&pb_stats_dev[2], (unsigned long long)st_apost);
+  }
+#endif
   return T;
 }

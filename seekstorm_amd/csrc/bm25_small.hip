@@ -384,7 +384,8 @@ __global__ void __launch_bounds__(PB_WAVES * 64, 4) bm25_small_kernel(const PbSm
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t nq = fz->nq, PB = fz->PB, CB = fz->CB, SB = TIER ? fz->SB : 0u, LPQ = PB + SB, k = fz->k, b = blockIdx.x;
   constexpr uint32_t KS = 64u * KPL;
-  constexpr uint32_t WREG = pb_qcap(SM_G) * 12u;  // a wave's LDS region (its survivor queue while it probes, its list afterwards)
+  // a wave's LDS region: its survivor queues while it probes (both are empty when pb_wave returns), its list afterwards
+  constexpr uint32_t WREG = (uint32_t)pb_wave_lds(NT, SM_G);
   // What one workgroup hands to another (partition lists, counts) travels in device-scope atomic accesses -- they meet at the
   // coherence point of the 8 XCDs' L2s by themselves.  No __threadfence(): on this part an agent-scope fence writes back and
   // invalidates the XCD's L2, and one per wave made a batch of 64 TopkCount queries take 595 us instead of 230.
@@ -810,7 +811,7 @@ int ssi_bm25_small_launch(ss_shard* s, void* ws, uint32_t nq, const ss_bm25_quer
   const uint32_t NT = sh.np_max <= 2 ? 2u : sh.np_max;
   const bool filt = sh.any_not || a.del != nullptr || TIER != 0;  // (the tiered instances are built with the filters in)
   const dim3 grid(nq * (PB + CB + a.SB)), block(PB_WAVES * 64);
-  const size_t lds = (size_t)PB_WAVES * pb_qcap(SM_G) * 12;
+  const size_t lds = (size_t)PB_WAVES * pb_wave_lds((int)NT, SM_G);  // (60 KB with the second queue of >= 3 terms, 54 KB without)
   bool launched = false;
 #define SS_S(NT_, KPL_)                                                                                  \
   if (!launched && TIER == 0 && NT == NT_ && KPL == KPL_) {                                              \
