@@ -5,11 +5,8 @@
 #include <cstdlib>
 
 #include "bm25_dev.h"
+#include "bm25_hist.h"
 #include "bm25_pack.h"
-
-#ifndef PB_STAGED_KTHB
-#define PB_STAGED_KTHB 0  // (bm25_probe.hip)
-#endif
 
 
 // ---------------------------------------------------------------- merge of partition-local lists (bitonic in LDS)
@@ -186,12 +183,13 @@ __device__ __forceinline__ void bm_expand_one(const QV Q, bm_vquery& V, uint32_t
                               const float* __restrict__ boost, unsigned long long* __restrict__ total, uint32_t* __restrict__ tau,
                               uint32_t claim, uint32_t n_vterms, const uint32_t* __restrict__ probe_row, uint32_t merged, uint32_t keep_tau,
                               const float* __restrict__ kthw, uint32_t kth_sel, unsigned long long* __restrict__ best_slots, uint32_t best_P,
-                              uint32_t best_KS) {
+                              uint32_t best_KS, const float* __restrict__ hist_umax) {
   // rank 0 of every partition's list doubles as the partition's BEST-SO-FAR key while the many-list scan runs (bm25_scan16m_kernel
   // derives the query's threshold from the k-th largest of them): they start from "none"
   if (best_slots)
     for (uint32_t p_ = 0; p_ < best_P; p_++) best_slots[((size_t)i * best_P + p_) * best_KS] = 0ull;
   total[i] = 0ull;                      // per-query match count and shared threshold start from zero (no separate memset launch)
+  if (hist_umax) { tau[(size_t)i * BM_TAU_STRIDE + BM_TAU_HIST_LO] = 0u; tau[(size_t)i * BM_TAU_STRIDE + BM_TAU_HIST_SHIFT] = 0u; }
   if (!keep_tau) tau[(size_t)i * BM_TAU_STRIDE] = 0u;  // (keep_tau: an experiment -- the same batch again with the thresholds it ended on)
                                                        // (a union without exclusions raises it to its seed at the end of the expansion)
   const uint32_t np = Q.n_terms(), n_not = bm_q_nnot(Q.op());
@@ -286,10 +284,22 @@ __device__ __forceinline__ void bm_expand_one(const QV Q, bm_vquery& V, uint32_t
   // threshold seed (bm_kth_kernel): a union -- every list adds to the score of a doc that holds it -- with nothing that could take a
   // doc away again (the caller passes kthw only when no tombstone / filter bitmap is in force; NOT terms, field filters, a phrase's position test --
   // a phrase of ONE unique term is a "union" of one list here --: none of them)
+  float seed = 0.f;
   if (kthw && kth_sel < 3u && !keep_tau && !is_and && !q_is_phrase && !gated && n_not == 0u && filt == 0u && n == n_scored) {
-    float seed = 0.f;
     for (uint32_t j = 0; j < n; j++) seed = fmaxf(seed, V.idf[j] * kthw[(size_t)V.term[j] * 4u + kth_sel]);
     tau[(size_t)i * BM_TAU_STRIDE] = __float_as_uint(seed);
+  }
+  // the bucket rule of the query's score histogram (bm25_hist.h; the staged pruned kernel, pb_publish_hist): BM_HIST_B equal steps in
+  // float-bit space from lo = the seed -- nothing below it can matter -- to hi = the most a doc can score.  Without a seed (tombstones,
+  // NOT terms, filters, lists shorter than the seed's rank) lo is a fixed share of hi: scores below it go uncounted, which costs nothing
+  // but the bound they would have given.
+  if (hist_umax) {
+    float hi = 0.f;
+    for (uint32_t j = 0; j < n_scored; j++) hi += V.idf[j] * hist_umax[V.term[j]];
+    const float lo = seed > 0.f ? seed : hi * BM_HIST_SEEDLESS_LO;
+    const uint32_t lo_bits = __float_as_uint(lo), hi_bits = max(lo_bits, __float_as_uint(hi));
+    tau[(size_t)i * BM_TAU_STRIDE + BM_TAU_HIST_LO] = lo_bits;
+    tau[(size_t)i * BM_TAU_STRIDE + BM_TAU_HIST_SHIFT] = bm_hist_shift(lo_bits, hi_bits);
   }
 }
 
@@ -304,16 +314,17 @@ __global__ void __launch_bounds__(BM_EXPAND_THREADS) bm_expand_kernel(const void
                                  unsigned long long* __restrict__ total, uint32_t* __restrict__ tau, uint32_t claim,
                                  uint32_t n_vterms, const uint32_t* __restrict__ probe_row, uint32_t merged, uint32_t keep_tau = 0u,
                                  const float* __restrict__ kthw = nullptr, uint32_t kth_sel = 3u,
-                                 unsigned long long* __restrict__ best_slots = nullptr, uint32_t best_P = 0u, uint32_t best_KS = 0u) {
+                                 unsigned long long* __restrict__ best_slots = nullptr, uint32_t best_P = 0u, uint32_t best_KS = 0u,
+                                 unsigned long long* __restrict__ hist = nullptr /* [nq][BM_HIST_B / 2]: zeroed here */, const float* __restrict__ hist_umax = nullptr) {
   __shared__ __attribute__((aligned(16))) bm_vquery sv[BM_EXPAND_THREADS];
   const uint32_t i0 = blockIdx.x * BM_EXPAND_THREADS, i = i0 + threadIdx.x;
   if (i < nq) {
     if constexpr (PACKED)
       bm_expand_one(BmQPacked{(const uint32_t*)q + (size_t)i * bm_pack_stride(packed_w), packed_w}, sv[threadIdx.x], i, n_lists, term_base, boost,
-                    total, tau, claim, n_vterms, probe_row, merged, keep_tau, kthw, kth_sel, best_slots, best_P, best_KS);
+                    total, tau, claim, n_vterms, probe_row, merged, keep_tau, kthw, kth_sel, best_slots, best_P, best_KS, hist ? hist_umax : nullptr);
     else
       bm_expand_one(BmQFull{(const ss_bm25_query*)q + i}, sv[threadIdx.x], i, n_lists, term_base, boost, total, tau, claim, n_vterms, probe_row,
-                    merged, keep_tau, kthw, kth_sel, best_slots, best_P, best_KS);
+                    merged, keep_tau, kthw, kth_sel, best_slots, best_P, best_KS, hist ? hist_umax : nullptr);
   }
   __syncthreads();
   // records [i0, i0 + n_here) of vq: vq + i0 is 16-byte aligned (hipMalloc, and a block's records are whole 16-byte words)
@@ -322,6 +333,9 @@ __global__ void __launch_bounds__(BM_EXPAND_THREADS) bm_expand_kernel(const void
   uint4* dst4 = (uint4*)(vq + i0);
   for (uint32_t w = threadIdx.x; w < dwords / 4u; w += BM_EXPAND_THREADS) dst4[w] = src4[w];
   for (uint32_t w = (dwords & ~3u) + threadIdx.x; w < dwords; w += BM_EXPAND_THREADS) ((uint32_t*)(vq + i0))[w] = ((const uint32_t*)sv)[w];
+  // the block's queries' score histograms start from zero (no separate memset launch): two counters a store
+  if (hist)
+    for (uint32_t w = threadIdx.x; w < n_here * (BM_HIST_B / 2u); w += BM_EXPAND_THREADS) hist[(size_t)i0 * (BM_HIST_B / 2u) + w] = 0ull;
 }
 
 // a threshold seed from outside the batch's own lists (ss_common.h d_ext_seed): the query's shared threshold starts at least there
@@ -540,9 +554,6 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   // imbalance is gone and fewer, longer assignments win again: 1.08 ms at 8 partitions per query, 1.10 at 10 / 12, 1.11 at 16, 1.15 at
   // 24 (tools/probes/psweep.sh).  Workgroups made of the partitions of ONE query instead of 8 queries of one partition were tried as
   // well (profiles/r3_map_sweep.log): no better, for the pruned kernel neither.)
-  // the probe kernel reads rank 0 of its partitions' lists as best-so-far keys only in builds with -DPB_STAGED_KTHB=1 (bm25_probe.hip,
-  // a measurement switch): only then does the expansion zero them -- the kernel writes every rank of every list itself
-  constexpr bool staged_kthb = PB_STAGED_KTHB != 0;
   const bool scan16m = scan16 && (np_max > 6 || (np_max > 4 && KPL == 2));  // the many-list instance (its waves share their best keys)
   const uint32_t resident = (pruned || phrase) ? 6144u : scan16 ? 4096u : 2048u, rounds = (pruned || phrase) ? 4u : 2u;
   uint32_t P = (rounds * resident) / nq;
@@ -568,7 +579,10 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   const size_t tau_words = (size_t)nq * BM_TAU_STRIDE / 2;  // u64 words: one 128-byte line per query
   // u64 words: 4 floats per (query, partition) + one float per (query, sub-block) -- the pruned kernel's block-max bounds
   const size_t pmax_words = (size_t)nq * P * 2 + ((size_t)nq * s->bm_n_sub + 1) / 2;
-  const size_t need = (size_t)nq * P * KS * 2 + nq + tau_words + pmax_words;  // two ping-pong merge buffers + totals + tau + bounds
+  // u64 words: BM_HIST_B counters per query -- the staged pruned kernel's histogram of accepted scores (bm25_hist.h), beside tau
+  // (a batch of intersections only, or one that ranks nothing, has none: they publish nothing)
+  const size_t hist_words = (pruned && has_or && k) ? (size_t)nq * (BM_HIST_B / 2u) : 0u;
+  const size_t need = (size_t)nq * P * KS * 2 + nq + tau_words + hist_words + pmax_words;  // two ping-pong merge buffers + totals + tau + histograms + bounds
   ss_bm_ws& W = s->bm_ws[st];  // this stream's workspace: searches on other streams of the shard run beside this one
   if (need > W.part_cap) {
     SS_HIP(hipStreamSynchronize(st));  // earlier searches of this stream may still use the old buffer
@@ -582,7 +596,8 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   u64* bufB = bufA + (size_t)nq * P * KS;
   u64* total = bufB + (size_t)nq * P * KS;
   uint32_t* tau = (uint32_t*)(total + nq);
-  float* pmax_ws = (float*)(total + nq + tau_words);
+  u64* hist = hist_words ? total + nq + tau_words : nullptr;
+  float* pmax_ws = (float*)(total + nq + tau_words + hist_words);
 
   // queries over (term, field) posting lists
   if ((size_t)nq * sizeof(bm_vquery) > W.vq_cap) {
@@ -601,17 +616,17 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
                          (std::min(np_max / F, 255u) << 16);
   {
     const float* seeds = (s->n_deleted || s->del_per_query || k == 0) ? nullptr : s->d_kthw;
-    u64* best = (scan16m || (pruned && staged_kthb)) ? bufA : nullptr;
+    u64* best = scan16m ? bufA : nullptr;  // (the many-list scan reads rank 0 of its partitions' lists as best-so-far keys: they start from zero)
     const uint32_t grid = (nq + BM_EXPAND_THREADS - 1u) / BM_EXPAND_THREADS;
     const uint32_t keep_tau = 0u;  // (the ceiling experiment of round 3, tools/probes/tau_ceiling.py)
     if (packed_w)
       bm_expand_kernel<true><<<grid, BM_EXPAND_THREADS, 0, st>>>(d_q, packed_w, (bm_vquery*)W.d_vq, nq, s->bm_n_fields, (const unsigned long long*)s->d_term_base,
                                                                 s->d_boost, total, tau, claim, s->bm_n_terms, s->d_probe_row, s->bm_merged ? 1u : 0u, keep_tau,
-                                                                seeds, bm_kth_sel(k), best, P, KS);
+                                                                seeds, bm_kth_sel(k), best, P, KS, hist, s->d_umax);
     else
       bm_expand_kernel<false><<<grid, BM_EXPAND_THREADS, 0, st>>>(d_q, 0u, (bm_vquery*)W.d_vq, nq, s->bm_n_fields, (const unsigned long long*)s->d_term_base,
                                                                  s->d_boost, total, tau, claim, s->bm_n_terms, s->d_probe_row, s->bm_merged ? 1u : 0u, keep_tau,
-                                                                 seeds, bm_kth_sel(k), best, P, KS);
+                                                                 seeds, bm_kth_sel(k), best, P, KS, hist, s->d_umax);
   }
 
   if (s->d_ext_seed && s->ext_seed_n == nq && k) {  // (a sub-batch the tiered search split further runs without: its rows moved)
@@ -627,6 +642,7 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   p.part_keys = bufA;
   p.total = total;
   p.tau = tau;
+  p.hist = (uint32_t*)hist;
   p.del = s->n_deleted ? s->d_deleted : nullptr;
   p.del_words = (uint32_t)s->deleted_words;
   if (s->del_per_query) {  // one exclusion bitmap per query (ss_bm25_search_sorted): the pruned kernel's filtered instances read them

@@ -16,6 +16,7 @@ struct BmParams {
   unsigned long long* part_keys;   // [nq][P][KS]
   unsigned long long* total;       // [nq] exact match counts
   uint32_t* tau;                   // [nq] shared admission threshold: bits of the best k-th score any partition holds
+  uint32_t* hist;                  // [nq][BM_HIST_B] counters of accepted scores (the staged pruned kernel: bm25_hist.h), or null: no histogram
   const uint32_t* del;             // tombstone bitmap (bit doc & 31 of word doc >> 5), null = no deleted docs
   uint32_t del_words;
   uint32_t n_sub, n_terms, nq, P, k, count;

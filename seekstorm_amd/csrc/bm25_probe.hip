@@ -64,13 +64,16 @@ __global__ void __launch_bounds__(256) bm_qbound_kernel(const bm_vquery* __restr
 // (FILT / SKIP and the body itself: bm25_probe_body.h pb_wave)
 constexpr int PB_STAGED_G = 4;  // chunks of 64 driver postings per group in the staged kernel
 static_assert(PB_WAVES * pb_wave_lds(4, PB_STAGED_G) <= 53 * 1024, "three workgroups of the staged kernel must fit a CU's LDS");
-template <int NT, int KPL, bool FILT, bool SKIP>
+// HIST: the batch holds unions and ranks (k >= 1): their partitions share a histogram of accepted scores (pb_publish_hist).  A separate
+// instantiation: a batch of intersections only, which publishes nothing, runs the code it ran before (the call's registers cost the
+// two-term kernel a wave per SIMD: 72 -> 74 VGPRs)
+template <int NT, int KPL, bool FILT, bool SKIP, bool HIST>
 __global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
     const uint32_t* __restrict__ post, const unsigned long long* __restrict__ term_base, const uint32_t* __restrict__ sub_off,
     const uint2* __restrict__ probe, const uint32_t* __restrict__ probe_z,
     const uint32_t* __restrict__ probe_row, const float* __restrict__ umax, const float* __restrict__ pmax, const float* __restrict__ qbound,
     const bm_vquery* __restrict__ qs, unsigned long long* __restrict__ part_keys, unsigned long long* __restrict__ total,
-    uint32_t* tau, const uint32_t* __restrict__ del, uint32_t del_words, uint32_t n_sub, uint32_t n_terms,
+    uint32_t* tau, uint32_t* hist, const uint32_t* __restrict__ del, uint32_t del_words, uint32_t n_sub, uint32_t n_terms,
     uint32_t nq, uint32_t P, uint32_t k, uint32_t count) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem != 0u) __builtin_trap();
@@ -80,13 +83,9 @@ __global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
   const uint32_t a = blockIdx.x * PB_WAVES + w;
   if (a >= nq * P) return;
   const uint32_t qi = a % nq, part = a / nq;
-#ifndef PB_STAGED_KTHB
-#define PB_STAGED_KTHB 0
-#endif
-  // (PB_STAGED_KTHB: rank 0 of every partition's output list as its best-so-far key, zeroed by bm_expand_kernel -- measurement switch)
-  const BmTop<KPL> T = pb_wave<NT, KPL, FILT, SKIP, false, PB_STAGED_G, PB_STAGED_KTHB != 0>(post, term_base, sub_off, probe, probe_z, probe_row, umax, pmax, qbound, PbQueryMem{qs + qi}, tau, del,
-                                                    del_words, n_sub, n_terms, P, k, count, qi, part, w, lane, 0.f,
-                                                    (PB_STAGED_KTHB != 0 && k <= 64u && P >= k && k != 0u) ? part_keys + (size_t)qi * P * (64 * KPL) : nullptr, 64u * KPL);
+  const BmTop<KPL> T = pb_wave<NT, KPL, FILT, SKIP, false, PB_STAGED_G, false, false, HIST>(
+      post, term_base, sub_off, probe, probe_z, probe_row, umax, pmax, qbound, PbQueryMem{qs + qi}, tau, del, del_words, n_sub, n_terms, P, k, count, qi, part,
+      w, lane, 0.f, nullptr, 1u, HIST ? hist + (size_t)qi * BM_HIST_B : nullptr);
 
   u64* out = part_keys + ((size_t)qi * P + part) * (64 * KPL);
 #pragma unroll
@@ -94,7 +93,7 @@ __global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
   if (lane == 0 && T.matched) atomicAdd(&total[qi], T.matched);
 }
 
-template <int NT, int KPL, bool FILT, bool SKIP>
+template <int NT, int KPL, bool FILT, bool SKIP, bool HIST>
 static int launch_probe(const BmParams& p, const uint2* probe, const uint32_t* probe_z, const uint32_t* probe_row, const float* umax,
                         const float* pmax, const float* qbound, hipStream_t st) {
   const uint32_t A = p.nq * p.P;
@@ -104,8 +103,8 @@ static int launch_probe(const BmParams& p, const uint2* probe, const uint32_t* p
   SS_HIP(hipMemsetAsync(stats, 0, sizeof(pb_stats_dev), st));
 #endif
   // LDS: 36 KB with the second queue of >= 3 terms, 30 KB without -- three workgroups a CU (occupancy 6) fit its 160 KB
-  bm25_probe_kernel<NT, KPL, FILT, SKIP><<<(A + PB_WAVES - 1) / PB_WAVES, PB_WAVES * 64, PB_WAVES * pb_wave_lds(NT, PB_STAGED_G), st>>>(
-      p.post, p.term_base, p.sub_off, probe, probe_z, probe_row, umax, pmax, qbound, p.q, p.part_keys, p.total, p.tau, p.del, p.del_words, p.n_sub, p.n_terms, p.nq, p.P, p.k,
+  bm25_probe_kernel<NT, KPL, FILT, SKIP, HIST><<<(A + PB_WAVES - 1) / PB_WAVES, PB_WAVES * 64, PB_WAVES * pb_wave_lds(NT, PB_STAGED_G), st>>>(
+      p.post, p.term_base, p.sub_off, probe, probe_z, probe_row, umax, pmax, qbound, p.q, p.part_keys, p.total, p.tau, p.hist, p.del, p.del_words, p.n_sub, p.n_terms, p.nq, p.P, p.k,
       p.count);
   return SS_OK;
 }
@@ -247,22 +246,24 @@ int ssi_bm25_launch_probe(const BmParams& p, const uint2* probe, const uint32_t*
   if (!probe || !probe_z || !probe_row || !umax || nt_max == 0 || nt_max > 4 || (KPL != 1 && KPL != 2)) return SS_ENOTSUP;
   const int NT = nt_max <= 2 ? 2 : (int)nt_max;
   const bool filt = any_not || p.del != nullptr;
+#define SS_L(NT_, KPL_, F_, S_) \
+  (p.hist ? launch_probe<NT_, KPL_, F_, S_, true>(p, probe, probe_z, probe_row, umax, pmax, qbound, st) \
+          : launch_probe<NT_, KPL_, F_, S_, false>(p, probe, probe_z, probe_row, umax, pmax, qbound, st))
 #define SS_P(NT_, KPL_)                                                                          \
   if (NT == NT_ && KPL == KPL_)                                                                  \
-    return qbound ? (filt ? launch_probe<NT_, KPL_, true, true>(p, probe, probe_z, probe_row, umax, pmax, qbound, st)   \
-                          : launch_probe<NT_, KPL_, false, true>(p, probe, probe_z, probe_row, umax, pmax, qbound, st)) \
-                  : (filt ? launch_probe<NT_, KPL_, true, false>(p, probe, probe_z, probe_row, umax, pmax, qbound, st)  \
-                          : launch_probe<NT_, KPL_, false, false>(p, probe, probe_z, probe_row, umax, pmax, qbound, st));
+    return qbound ? (filt ? SS_L(NT_, KPL_, true, true) : SS_L(NT_, KPL_, false, true))          \
+                  : (filt ? SS_L(NT_, KPL_, true, false) : SS_L(NT_, KPL_, false, false));
   SS_P(2, 1) SS_P(3, 1) SS_P(4, 1) SS_P(2, 2) SS_P(3, 2) SS_P(4, 2)
 #undef SS_P
+#undef SS_L
   return SS_ENOTSUP;
 }
 
 #if PB_STATS
 // experiment builds (-DPB_STATS=1) only: the counters of the LAST staged launch (bm25_probe_body.h pb_stats_dev), read after the device is idle
-extern "C" int ssi_dbg_pb_stats(unsigned long long* out3) {
+extern "C" int ssi_dbg_pb_stats(unsigned long long* out4) {
   SS_HIP(hipDeviceSynchronize());
-  SS_HIP(hipMemcpyFromSymbol(out3, HIP_SYMBOL(pb_stats_dev), 3 * sizeof(unsigned long long)));
+  SS_HIP(hipMemcpyFromSymbol(out4, HIP_SYMBOL(pb_stats_dev), 4 * sizeof(unsigned long long)));
   return SS_OK;
 }
 #endif

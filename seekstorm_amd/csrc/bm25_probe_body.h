@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "bm25_dev.h"
+#include "bm25_hist.h"
 
 constexpr int PB_WAVES = 8;
 // PB_TWO_PHASE (measurement switch, on): bodies of >= 3 terms split their sparse stage in two (pb_wave: phase 1 / phase 2) and keep a
@@ -27,8 +28,15 @@ constexpr int pb_wave_lds(int NT, int G) { return pb_qcap(NT, G) * 12; }
 #if PB_STATS
 // experiment builds only: [0] entries pushed to the first queue, [1] entries that pass the bound of the sparse stage (phase 1; the one-phase
 // body: its round-3 bound), [2] postings of the first probed list fetched -- summed per wave, added once at the wave's end (one copy per
-// translation unit; bm25_probe.hip zeroes its own before every launch and reads it back)
-static __device__ unsigned long long pb_stats_dev[3];
+// translation unit; bm25_probe.hip zeroes its own before every launch and reads it back), [3] times a wave read its query's histogram
+// (pb_publish_hist)
+static __device__ unsigned long long pb_stats_dev[4];
+#endif
+// PB_HIST_READ (measurement switch): when a wave that has just counted its accepted keys also READS the query's counters and publishes
+// a bound from them -- 1 (the product): only once its own list is full -- before that its accepts are the cheap early ones and the
+// partitions that are ahead publish for it; 0: every time (prunes a little more, measured slower: DESIGN section 5)
+#ifndef PB_HIST_READ
+#define PB_HIST_READ 1
 #endif
 
 // weight of one posting: it is IN the posting (ss_common.h) -- the same decode as the scan kernels'
@@ -101,6 +109,39 @@ __device__ __attribute__((noinline)) void pb_publish_kth_best2(unsigned long lon
   if (kth && lane == 0) bm_publish_tau(tau_q, __uint_as_float((uint32_t)(kth >> 32)));
 }
 
+// The query's threshold from a HISTOGRAM of the scores its partitions have accepted (the staged kernel, unions, k >= 1): `hist_q` holds
+// BM_HIST_B counters of the query, zeroed by bm_expand_kernel, which also leaves the bucket rule (lo_bits, shift: bm25_hist.h) in the
+// query's tau line.  Every lane whose key was accepted past its wave's worst adds 1 to the bucket of its score; the wave then reads the
+// counters, one per lane, and publishes the edge of the highest bucket b whose suffix sum (buckets >= b) reaches k.
+// Why the answers cannot change:
+//   * a doc is offered at most once per query: a driver's doc that also lies in an earlier stream's list is dropped (in the dense stage
+//     for A, in sift / drain for the others), and partitions are disjoint doc ranges;
+//   * offers happen after the tombstone and NOT-list tests;
+//   * so the counters in buckets >= b count distinct, valid docs whose true score is >= edge(b) -- a bit pattern, edge(bucket(s)) <= s
+//     exactly -- and when there are k of them the query's k-th best score is >= edge(b).  A reader that misses increments in flight
+//     sees fewer docs, a lower bound all the same;
+//   * the bound tests drop only docs whose upper bound lies below the threshold; ties on the k-th score are still offered (score >= thr).
+// Against the partitions' OWN k-th best (bm_offer_lane_keys), roughly the (16 k)-th best score of a query in 16 partitions, this is the
+// k-th best over all of them, rounded down to a bucket edge.  Out of line: the probe loop keeps its registers.
+__device__ __attribute__((noinline)) void pb_publish_hist(uint32_t* hist_q, uint32_t* tau_q, u64 key, uint32_t k, bool read) {
+  const uint32_t lo_bits = tau_q[BM_TAU_HIST_LO], shift = tau_q[BM_TAU_HIST_SHIFT];  // (written before this launch, never after)
+  if (key) {
+    const uint32_t b = bm_hist_bucket((uint32_t)(key >> 32), lo_bits, shift);
+    if (b != BM_HIST_NONE) (void)__hip_atomic_fetch_add(hist_q + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (!read) return;
+  const int lane = __lane_id();
+  uint32_t c = __hip_atomic_load(hist_q + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // suffix sums across the lanes: c of lane l = counters of buckets l .. 63
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t x = __shfl_down(c, o);
+    if (lane + o < 64) c += x;
+  }
+  const u64 m = __ballot(c >= k);  // (a prefix of the lanes: suffix sums fall with the lane)
+  if (m && lane == 0) bm_publish_tau(tau_q, __uint_as_float(bm_hist_edge(63u - (uint32_t)__builtin_clzll(m), lo_bits, shift)));
+}
+
 // FILT: tombstones and / or NOT terms are present (a separate instantiation: the unfiltered kernel pays nothing for them)
 // SKIP: the driver streams jump over sub-blocks whose block-max bound (qbound) lies below the threshold.  A separate
 // instantiation: the few registers the skip needs pushed the common kernel into scratch (C2: 0.55 -> 0.80 ms per 1000 queries).
@@ -109,14 +150,16 @@ __device__ __attribute__((noinline)) void pb_publish_kth_best2(unsigned long lon
 // for occupancy; 8 in the one-launch kernel of small batches, which is bound by the number of dependent round trips per wave)
 // KTHB: the partitions publish their best keys and derive the query's threshold from them (pb_publish_kth_best; `bests` + `bests_stride`)
 // EXT: the query's shared threshold may rise from OUTSIDE these lists while they are read (bm25_small.hip, the tiered instances)
-template <int NT, int KPL, bool FILT, bool SKIP, bool SEEDED, int G, bool KTHB, bool EXT = false, typename QV>
+// HIST: the partitions count their accepted scores in the query's histogram and publish its bound (pb_publish_hist; `hist_q`, or null)
+template <int NT, int KPL, bool FILT, bool SKIP, bool SEEDED, int G, bool KTHB, bool EXT = false, bool HIST = false, typename QV>
 __device__ __forceinline__ BmTop<KPL> pb_wave(
     const uint32_t* __restrict__ post, const unsigned long long* __restrict__ term_base, const uint32_t* __restrict__ sub_off,
     const uint2* __restrict__ probe, const uint32_t* __restrict__ probe_z,
     const uint32_t* __restrict__ probe_row, const float* __restrict__ umax, const float* __restrict__ pmax, const float* __restrict__ qbound,
     const QV Q, uint32_t* tau, const uint32_t* __restrict__ del, uint32_t del_words, uint32_t n_sub, uint32_t n_terms,
     uint32_t P, uint32_t k, uint32_t count, const uint32_t qi, const uint32_t part, const int w, const int lane, const float thr0 = 0.f,
-    unsigned long long* bests = nullptr /* KTHB: best key of partition p of the query at bests[p * bests_stride] */, const uint32_t bests_stride = 1u) {
+    unsigned long long* bests = nullptr /* KTHB: best key of partition p of the query at bests[p * bests_stride] */, const uint32_t bests_stride = 1u,
+    uint32_t* hist_q = nullptr /* HIST: the query's BM_HIST_B counters */) {
   // del_words bit 31: ONE exclusion bitmap PER QUERY, del_words words each, back to back (ss_bm25_search_sorted: every query of the
   // batch is searched inside its own doc set)
   if (FILT && (del_words >> 31)) { del_words &= 0x7FFFFFFFu; del += (size_t)qi * del_words; }
@@ -195,12 +238,22 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
     return score;
   };
 
+#if PB_STATS
+  uint32_t st_hist = 0u;
+#endif
   auto offer = [&](bool cand, float score, uint32_t doc) {
     if (__ballot(cand)) {
       const u64 key = cand ? (((u64)__float_as_uint(score) << 32) | (u64)(0xFFFFFFFFu - doc)) : 0ull;
       const u64 key2 = key > T.worst ? key : 0ull;
       if (__ballot(key2 != 0ull)) {
         T = bm_offer_lane_keys<KPL>(T, key2, k, tau_q);
+        if (HIST && hist_q && !is_and) {  // (intersections: the driver list is read whatever the threshold)
+          const bool read = PB_HIST_READ == 0 || T.worst != 0ull;
+          pb_publish_hist(hist_q, tau_q, key2, k, read);
+#if PB_STATS
+          st_hist += read ? 1u : 0u;
+#endif
+        }
         if (KTHB && KPL == 1) {  // (k <= 64: one key per lane)
           const u64 best = rdlane64(T.keys[0], 0);
           // (intersections: the driver list is read whatever the threshold -- nothing to gain there)
@@ -606,6 +659,7 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
     atomicAdd(&pb_stats_dev[0], (unsigned long long)st_push);
     atomicAdd(&pb_stats_dev[1], (unsigned long long)st_pass);
     atomicAdd(&pb_stats_dev[2], (unsigned long long)st_apost);
+    atomicAdd(&pb_stats_dev[3], (unsigned long long)st_hist);
   }
 #endif
   return T;

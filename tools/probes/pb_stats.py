@@ -6,8 +6,9 @@
     SEEKSTORM_HIP_LIB=$PWD/seekstorm_amd/lib_stats/libseekstorm_hip.so python tools/probes/pb_stats.py [batches] [docs]
 
 Prints, per 1000-query batch (bench.py's rotation: batch 0 = make_c2_queries' default seed) and per query of it: entries pushed to the first
-queue, entries that pass the sparse stage's bound, postings of the first probed list fetched; then one JSON line with the means.  Each
-batch is searched three times and the last launch is read: the counts depend on how the partitions' thresholds interleave."""
+queue, entries that pass the sparse stage's bound, postings of the first probed list fetched, times a wave read its query's score histogram
+(pb_publish_hist; a library from before the histogram leaves that counter at 0); then one JSON line with the means.  Each batch is searched
+three times and the last launch is read: the counts depend on how the partitions' thresholds interleave."""
 import ctypes as C
 import json
 import os
@@ -41,12 +42,12 @@ def main():
         q = sh.make_queries(tl, S.QueryType.Union)
         for _ in range(3):
             sh.search_lexical_batch(q, 10, S.ResultType.Topk, reference_shortcuts=False)
-        out = np.zeros(3, np.uint64)
+        out = np.zeros(4, np.uint64)
         N.check(L.ssi_dbg_pb_stats(out.ctypes.data_as(C.c_void_p)), "ssi_dbg_pb_stats")
         rows.append([int(x) for x in out])
-        print(f"batch {b}: pushed {out[0]} ({out[0] / 1000:.0f} / query)  passed {out[1]} ({out[1] / 1000:.0f})  A postings {out[2]} ({out[2] / 1000:.0f})", flush=True)
+        print(f"batch {b}: pushed {out[0]} ({out[0] / 1000:.0f} / query)  passed {out[1]} ({out[1] / 1000:.0f})  A postings {out[2]} ({out[2] / 1000:.0f})  histogram reads {out[3]} ({out[3] / 1000:.0f})", flush=True)
     m = np.mean(np.asarray(rows, np.float64), axis=0) / 1000.0
-    print(json.dumps({"batches": nb, "docs": docs, "per_query_mean": {"pushed": m[0], "passed": m[1], "a_postings": m[2]}, "per_batch": rows}))
+    print(json.dumps({"batches": nb, "docs": docs, "per_query_mean": {"pushed": m[0], "passed": m[1], "a_postings": m[2], "hist_reads": m[3]}, "per_batch": rows}))
     sh.close()
 
 
