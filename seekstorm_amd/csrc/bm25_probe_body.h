@@ -41,6 +41,13 @@ static __device__ unsigned long long pb_stats_dev[4];
 
 // weight of one posting: it is IN the posting (ss_common.h) -- the same decode as the scan kernels'
 __device__ __forceinline__ float pb_weight(uint32_t p) { return bm_weight(p); }
+// a value every lane of the wave holds alike, told to the compiler: it moves to a scalar register
+__device__ __forceinline__ uint32_t pb_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+template <typename T>
+__device__ __forceinline__ const T* pb_uniform(const T* p) {
+  const unsigned long long v = (unsigned long long)(uintptr_t)p;
+  return (const T*)(uintptr_t)(((unsigned long long)pb_uniform((uint32_t)(v >> 32)) << 32) | pb_uniform((uint32_t)v));
+}
 
 // How the body reads its query: the expanded query in device memory (bm_expand_kernel's bm_vquery) ...
 struct PbQueryMem {
@@ -310,10 +317,20 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
 #endif
 
   // one driver stream: the postings of processing term J inside this partition's sub-block range
-  auto stream = [&](auto Jc) {
+  // (SINGLE: the query has one term -- no probe, no queue; told at compile time so that the other streams' loop holds no branch for it:
+  // with one, the compiler moved the probe gathers under it, behind the wait for the threshold)
+  auto stream = [&](auto Jc, auto Sc) {
     constexpr int J = decltype(Jc)::value;
+    constexpr bool SINGLE = decltype(Sc)::value;
     constexpr int A = J == 0 ? 1 : 0;  // the first other term in probe order
-    const uint32_t x_begin = rowp[J][s_begin] * 4u, x_end = rowp[J][s_end] * 4u;  // dword range of the stream
+    // Streams after the first: nearly always non-essential before they begin -- tested before anything of the list is
+    // read, its boundaries included.  (They run for unions with k >= 1 only: below.)
+    if (J > 0 && !is_and && k && SU[J] < cur_thr() * 0.99999f) return;
+    // The stream's base and range are the same in every lane, but they come out of the sort above and out of loads the compiler cannot
+    // prove uniform.  Said here once: the descriptor and the loop's offsets then live in scalar registers and a driver load is ONE
+    // instruction -- with a descriptor in vector registers each one sat in a loop over the lanes' values (a "waterfall"), and the compiler
+    // waited for all loads in flight around every such loop.
+    const uint32_t x_begin = pb_uniform(rowp[J][s_begin]) * 4u, x_end = pb_uniform(rowp[J][s_end]) * 4u;  // dword range of the stream
     if (x_begin == x_end) return;
     // J = 0 and a threshold above SU[0]: NO list is essential -- the threshold came from outside these lists (a tiered query's sparse lists,
     // whose docs carry the rare terms' idf: bm25_small.hip role 3 while this runs, or the staged tiered pipeline's seeds before it,
@@ -502,7 +519,7 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
       qn -= n;
     };
 
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)tptr[J], 0, (int)(x_end * 4u), BM_RSRC_FLAGS);
+    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)pb_uniform(tptr[J]), 0, (int)(x_end * 4u), BM_RSRC_FLAGS);
     // sub-block boundaries of the driver (dword offsets), 64 per block load: lane i = sub-block blk0 + i
     uint32_t blk0 = s_begin;
     uint32_t vb = rowp[J][min(blk0 + (uint32_t)lane, s_end)] * 4u;
@@ -517,8 +534,17 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
     uint32_t pn[G];            // driver postings of the NEXT group (prefetched)
 #pragma unroll
     for (int g = 0; g < G; g++) pn[g] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4 + g * 256, (int)(x_begin * 4u), 0);
+    // Order of an iteration's loads (vmcnt retires in order, so the order decides what a wait covers):
+    //   the sub-block walk first -- its rare boundary reload waits for everything, and nothing is pending there;
+    //   then the threshold, the bit records of the CURRENT group and, last, the postings of the NEXT group.
+    // The dense stage waits for all but the last G loads: the prefetch stays in flight under it and one round trip a group is paid, not two.
+    // Where the threshold decides BEFORE the group is read (the break test of the later streams and of the EXT instances, the block skip)
+    // it is loaded and waited for at the top, as before; records and prefetch follow in the same order.
+    constexpr bool THR_FIRST = J > 0 || EXT || SKIP;
     for (uint32_t x = x_begin; x < x_end; x += 64u * G) {
-      const float thr = cur_thr();
+      float thr = 0.f;
+      // (as a scalar: tests against a vector register would make x, the offset of every driver load, lane-varying for the compiler)
+      if constexpr (THR_FIRST) thr = __uint_as_float(pb_uniform(__float_as_uint(cur_thr())));
       // this and all later terms are non-essential now
       // (J = 0 is tested inside the loop by the EXT instances only -- the test in the first, longest stream of every query cost the C2
       // headline 11 %, 0.567 -> 0.631 ms per 1000 queries, profiles/r6_break_ab.log; the others test it once, before the stream: above)
@@ -526,6 +552,7 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
       if constexpr (SKIP) if (skip_blocks) {
         // block-max skip: while the sub-block holding position x cannot contain a doc that reaches thr, jump to the next one
         bool moved = false;
+        const float thr_s = thr * 0.99999f;
         for (;;) {
           if (s_cur + 1u - blk0 >= 64u) {
             blk0 = s_cur;
@@ -535,7 +562,7 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
           if (s_cur + 1u > s_end) break;
           const uint32_t b1 = bnd(s_cur + 1u);
           if (b1 <= x) { s_cur++; continue; }  // x lies beyond this sub-block
-          if (__uint_as_float(__builtin_amdgcn_readlane(vqb, s_cur - blk0)) >= thr * 0.99999f) break;
+          if (__uint_as_float(__builtin_amdgcn_readlane(vqb, s_cur - blk0)) >= thr_s) break;
           x = b1;  // nothing in the rest of this sub-block can enter the top-k
           s_cur++;
           moved = true;
@@ -552,10 +579,6 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
       for (int g = 0; g < G; g++) {
         pg[g] = pn[g];
         tile[g] = s_cur;
-      }
-      if (x + 64u * G < x_end) {
-#pragma unroll
-        for (int g = 0; g < G; g++) pn[g] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4 + g * 256, (int)((x + 64u * G) * 4u), 0);
       }
       // each lane's sub-block: count the boundaries at or before its stream position
       const uint32_t x_hi = min(x + 64u * G, x_end);
@@ -577,6 +600,7 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
       bool alive[G];
       float w0[G];
       uint2 rec[G];
+      if constexpr (!THR_FIRST) thr = cur_thr();
 #pragma unroll
       for (int g = 0; g < G; g++) {
         alive[g] = pg[g] != 0u;
@@ -584,11 +608,15 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
         // The probe of the first other term is issued NOW, for every real posting and before its weight is known: the
         // weight lookups and bound tests below then run under the gather's latency instead of in front of it (postings the
         // bound test would have spared cost a cached read).  Unconditional load: NULL lanes read record 0.
-        if (NT > 1) rec[g] = prow[A][alive[g] ? tile[g] * (uint32_t)(BM_SUB / 64) + (dg[g] >> 6) : 0u];
+        if (!SINGLE) rec[g] = prow[A][alive[g] ? tile[g] * (uint32_t)(BM_SUB / 64) + (dg[g] >> 6) : 0u];
       }
+      // The next group's postings, issued LAST and on every iteration: a branch around them would make the waits below wait for
+      // everything.  Past the stream's end the offset stops AT the end, where every lane is out of the descriptor's range: zeros, no access.
+#pragma unroll
+      for (int g = 0; g < G; g++) pn[g] = __builtin_amdgcn_raw_buffer_load_b32(rs, lane4 + g * 256, (int)(x_hi * 4u), 0);
 #pragma unroll
       for (int g = 0; g < G; g++) w0[g] = alive[g] ? pb_weight(pg[g]) : 0.f;
-      if (nt == 1) {  // single-term query: the driver posting is the whole score
+      if constexpr (SINGLE) {  // single-term query: the driver posting is the whole score
 #pragma unroll
         for (int g = 0; g < G; g++) {
           if (__ballot(alive[g]) == 0ull) continue;
@@ -604,40 +632,41 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
             offer(cand, score, doc1);
           }
         }
-        continue;
-      }
-      const float rest0 = SU[0] - U[J];
+      } else {
+        const float rest0 = SU[0] - U[J];
 #pragma unroll
-      for (int g = 0; g < G; g++)
-        if (!is_and && k) alive[g] = alive[g] && (idf[J] * w0[g] + rest0) >= thr * 0.99999f;
+        for (int g = 0; g < G; g++)
+          if (!is_and && k) alive[g] = alive[g] && (idf[J] * w0[g] + rest0) >= thr * 0.99999f;
 #pragma unroll
-      for (int g = 0; g < G; g++) {
-        const u64 bits = ((u64)rec[g].y << 32) | rec[g].x;
-        bool hit = alive[g] && ((bits >> (dg[g] & 63u)) & 1ull);
-        uint32_t pos = 0xFFFFFFFFu;
-        if (is_and) alive[g] = hit;
-        else if (A < J && hit) { alive[g] = false; hit = false; }  // evaluated in the earlier term's stream
-        else if (!hit && k) alive[g] = alive[g] && (idf[J] * w0[g] + rest0 - U[A]) >= thr * 0.99999f;
-        if (hit) pos = (uint32_t)__popcll(bits & ((1ull << (dg[g] & 63u)) - 1ull));  // rank inside the group
-        // push the survivors of this chunk
-        const u64 m = __ballot(alive[g]);
-        if (m) {
-          if (alive[g]) {
-            const uint32_t at = qn + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            lds_st32(q_doc + at * 4u, (tile[g] << BM_SUB_LOG2) + dg[g]);
-            lds_stf(q_w0 + at * 4u, w0[g]);
-            lds_st32(q_pos + at * 4u, pos);
-          }
-          qn += (uint32_t)__popcll(m);
+        for (int g = 0; g < G; g++) {
+          const u64 bits = ((u64)rec[g].y << 32) | rec[g].x;
+          bool hit = alive[g] && ((bits >> (dg[g] & 63u)) & 1ull);
+          uint32_t pos = 0xFFFFFFFFu;
+          if (is_and) alive[g] = hit;
+          else if (A < J && hit) { alive[g] = false; hit = false; }  // evaluated in the earlier term's stream
+          else if (!hit && k) alive[g] = alive[g] && (idf[J] * w0[g] + rest0 - U[A]) >= thr * 0.99999f;
+          if (hit) pos = (uint32_t)__popcll(bits & ((1ull << (dg[g] & 63u)) - 1ull));  // rank inside the group
+          // push the survivors of this chunk
+          const u64 m = __ballot(alive[g]);
+          if (m) {
+            if (alive[g]) {
+              const uint32_t at = qn + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+              lds_st32(q_doc + at * 4u, (tile[g] << BM_SUB_LOG2) + dg[g]);
+              lds_stf(q_w0 + at * 4u, w0[g]);
+              lds_st32(q_pos + at * 4u, pos);
+            }
+            qn += (uint32_t)__popcll(m);
 #if PB_STATS
-          st_push += (uint32_t)__popcll(m);
+            st_push += (uint32_t)__popcll(m);
 #endif
+          }
         }
+        if constexpr (TWO) { while (qn >= 64u) sift(64u); }
+        else { while (qn >= 64u) drain(64u); }
       }
-      if constexpr (TWO) { while (qn >= 64u) sift(64u); }
-      else { while (qn >= 64u) drain(64u); }
     }
-    if constexpr (TWO) {  // (both queues are empty between streams and when the body returns)
+    if constexpr (SINGLE) {  // (pushes nothing)
+    } else if constexpr (TWO) {  // (both queues are empty between streams and when the body returns)
       if (qn) sift(qn);
       if (q2n) fetch(q2n);
     } else {
@@ -647,11 +676,12 @@ __device__ __forceinline__ BmTop<KPL> pb_wave(
   // drivers: unions -> every term in upper-bound order (a stream ends as soon as its term is non-essential);
   // intersections -> the shortest list only
   // (a union whose top-k is not wanted has nothing to do here: its count comes from bm25_union_count_kernel)
-  if (k || is_and || nt == 1) stream(std::integral_constant<int, 0>{});
+  if (nt == 1) stream(std::integral_constant<int, 0>{}, std::true_type{});
+  else if (k || is_and) stream(std::integral_constant<int, 0>{}, std::false_type{});
   if (!is_and && k) {
-    if (NT > 1 && nt > 1) stream(std::integral_constant<int, (NT > 1 ? 1 : 0)>{});
-    if (NT > 2 && nt > 2) stream(std::integral_constant<int, (NT > 2 ? 2 : 0)>{});
-    if (NT > 3 && nt > 3) stream(std::integral_constant<int, (NT > 3 ? 3 : 0)>{});
+    if (NT > 1 && nt > 1) stream(std::integral_constant<int, (NT > 1 ? 1 : 0)>{}, std::false_type{});
+    if (NT > 2 && nt > 2) stream(std::integral_constant<int, (NT > 2 ? 2 : 0)>{}, std::false_type{});
+    if (NT > 3 && nt > 3) stream(std::integral_constant<int, (NT > 3 ? 3 : 0)>{}, std::false_type{});
   }
 
 #if PB_STATS
