@@ -535,7 +535,9 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   // Partitions per query (one wave each).  The grid is a whole number of "rounds" of resident waves: a partially
   // filled last round costs its full duration (measured on C2: 550K q/s at 1.95 rounds vs 477K at 2.44).  Exhaustive
   // scan: 2048 resident waves (LDS-bound), ~2 rounds; pruned: 6144 resident waves, ~4 rounds of shorter assignments
-  // balance its more uneven work (driver streams differ 4x in length between queries).
+  // balance its more uneven work (driver streams differ 4x in length between queries).  (The phrase kernel's figure.  The staged pruned
+  // kernel runs in workgroups of 2 waves since: its registers allow 7 waves per SIMD, which 8-wave workgroups could not fill -- a
+  // fourth one needed 8 --, so up to 7168 are resident and each gives its slot back when IT ends; its partition rule is below.)
   // Exact counts (Count / TopkCount).  Pruned: the probe kernel counts intersections and single lists while it ranks them,
   // unions are popcounted from the bit records.  Scan kernels under AUTO with a probe index: every count comes from the
   // bit records and the scan runs without its count mode (which scans every sub-block: 5.8 instead of 1.8 ms per 1000 C2
@@ -569,8 +571,14 @@ int ssi_bm25_search(ss_shard* s, uint32_t nq, const ss_bm25_query* d_q, uint32_t
   // 2-term ANDs 1.035 ms at 16 partitions, 0.975 at 24, 0.947 at 48, 0.972 at 64)
   // (heavy queries want more partitions: a head-heavy mix of 4.2 M postings per query 3.68 ms per 1000 at 16 partitions, 3.34 at 48; C2's
   // 1.35 M per query is best at 16 -- where the host has seen the queries, about one partition per 84 K postings)
+  // The staged kernel in workgroups of 2 waves (bm25_probe.hip PB_STAGED_WAVES; a workgroup of 8 held its wave slots and LDS until its
+  // longest wave ended): shorter assignments no longer wait behind a long neighbour, and unions want at least 24 partitions instead of 16.
+  // Per launch of 1000 C2 queries 400 / 389 / 381 / 380 / 375 us at 16 / 20 / 24 / 28 / 32 partitions (8-wave workgroups on the same
+  // machine: 441 / 432 / 427 / 432 / 431); host-pointer calls 2.06 / 2.10 / 2.14 / 2.15 / 2.16 M q/s; device-resident calls of 256 queries
+  // 0.190 / 0.184 / 0.175 / 0.192 / 0.190 ms, of 500 0.283 / 0.267 / 0.258 / 0.254 / 0.248 ms, of 1000 0.425 / 0.414 / 0.406 / 0.404 /
+  // 0.400 ms (profiles/pshape_grid.md).  24: the best of the 256-query call, within 1 % of the best of the others.
   if (pruned) {
-    uint32_t floor_p = has_and ? 48u : 16u;
+    uint32_t floor_p = has_and ? 48u : 24u;
     if (s->bm_batch_postings) floor_p = std::max<uint32_t>(floor_p, (uint32_t)std::min<uint64_t>(64u, s->bm_batch_postings / 84000u));
     P = std::max<uint32_t>(floor_p, std::min<uint32_t>(64u, 4096u / std::max<uint32_t>(nq, 1u)));
   }

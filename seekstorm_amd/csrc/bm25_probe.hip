@@ -63,12 +63,42 @@ __global__ void __launch_bounds__(256) bm_qbound_kernel(const bm_vquery* __restr
 
 // (FILT / SKIP and the body itself: bm25_probe_body.h pb_wave)
 constexpr int PB_STAGED_G = 4;  // chunks of 64 driver postings per group in the staged kernel
-static_assert(PB_WAVES * pb_wave_lds(4, PB_STAGED_G) <= 53 * 1024, "three workgroups of the staged kernel must fit a CU's LDS");
+// The staged kernel's launch shape.  Its waves never meet: no barrier, a private LDS slice each (pb_wave: q_doc = w * pb_wave_lds), so
+// the workgroup size is free -- unlike bm25_small_kernel, whose PB_WAVES waves share a tournament and arrival counters.  A workgroup
+// gives its LDS and its wave slots back when its LONGEST wave ends, and its waves serve different queries, whose driver lists differ
+// 4x in length: in workgroups of 8 a third of the resident wave slots stood idle behind a neighbour.
+//   PB_STAGED_WAVES      waves per workgroup: 1, 2, 4 or 8
+//   PB_STAGED_MIN_WAVES  waves per SIMD the register budget is cut for, where an instantiation fits it (pb_staged_min_waves): 6 or 8
+// Measured on 1000 C2 queries at 16 partitions, microseconds per launch (DESIGN 3.2 has the grid at 12 .. 24 partitions):
+//   waves per workgroup        8      4      2      1
+//   budget for 6 per SIMD    449    416    409    414
+//   budget for 8 per SIMD    451    440    436    440
+// Two waves at the budget of 6 ship.  The instructions are the ones the 8-wave workgroup ran; only the grid and the LDS size changed.  At
+// the budget of 8 the scalar registers fall from 106 to 78 and the spills to vector lanes land inside the first stream's loop (v_readlane
+// 68 -> 138 there in the headline instantiation): slower in every cell.  Both stay experiment switches (-DPB_STAGED_WAVES=,
+// -DPB_STAGED_MIN_WAVES= through SS_HIPCC_FLAGS).
+#ifndef PB_STAGED_WAVES
+#define PB_STAGED_WAVES 2
+#endif
+#ifndef PB_STAGED_MIN_WAVES
+#define PB_STAGED_MIN_WAVES 6
+#endif
+static_assert(PB_STAGED_WAVES == 1 || PB_STAGED_WAVES == 2 || PB_STAGED_WAVES == 4 || PB_STAGED_WAVES == 8, "PB_STAGED_WAVES");
+static_assert(PB_STAGED_MIN_WAVES == 6 || PB_STAGED_MIN_WAVES == 8, "PB_STAGED_MIN_WAVES");
+static_assert((32 / PB_STAGED_WAVES) * (PB_STAGED_WAVES * pb_wave_lds(4, PB_STAGED_G)) <= 160 * 1024,
+              "8 waves per SIMD of the staged kernel (32 / PB_STAGED_WAVES workgroups) must fit a CU's LDS");
+// The second launch-bound argument (waves per SIMD): PB_STAGED_MIN_WAVES where the instantiation compiles under it without a vector
+// register spill and with no more scratch than under 6, 6 otherwise.  At 8 the budget is 64 VGPRs: every KPL = 2 instantiation spills
+// 1 .. 19 registers there or needs 12 bytes of scratch instead of 8 and stays at 6, as does <4, 1, false, false, true>, which spills
+// one (profiles/pshape_resources.md).
+constexpr int pb_staged_min_waves(int NT, int KPL, bool FILT, bool SKIP, bool HIST) {
+  return KPL == 1 && !(NT == 4 && !FILT && !SKIP && HIST) ? PB_STAGED_MIN_WAVES : 6;
+}
 // HIST: the batch holds unions and ranks (k >= 1): their partitions share a histogram of accepted scores (pb_publish_hist).  A separate
 // instantiation: a batch of intersections only, which publishes nothing, runs the code it ran before (the call's registers cost the
 // two-term kernel a wave per SIMD: 72 -> 74 VGPRs)
 template <int NT, int KPL, bool FILT, bool SKIP, bool HIST>
-__global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
+__global__ void __launch_bounds__(PB_STAGED_WAVES * 64, pb_staged_min_waves(NT, KPL, FILT, SKIP, HIST)) bm25_probe_kernel(
     const uint32_t* __restrict__ post, const unsigned long long* __restrict__ term_base, const uint32_t* __restrict__ sub_off,
     const uint2* __restrict__ probe, const uint32_t* __restrict__ probe_z,
     const uint32_t* __restrict__ probe_row, const float* __restrict__ umax, const float* __restrict__ pmax, const float* __restrict__ qbound,
@@ -80,8 +110,8 @@ __global__ void __launch_bounds__(PB_WAVES * 64, 6) bm25_probe_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  const uint32_t a = blockIdx.x * PB_WAVES + w;
-  if (a >= nq * P) return;
+  const uint32_t a = blockIdx.x * PB_STAGED_WAVES + w;
+  if (a >= nq * P) return;  // (the grid's tail: before anything touches LDS or the outputs)
   const uint32_t qi = a % nq, part = a / nq;
   const BmTop<KPL> T = pb_wave<NT, KPL, FILT, SKIP, false, PB_STAGED_G, false, false, HIST>(
       post, term_base, sub_off, probe, probe_z, probe_row, umax, pmax, qbound, PbQueryMem{qs + qi}, tau, del, del_words, n_sub, n_terms, P, k, count, qi, part,
@@ -102,8 +132,9 @@ static int launch_probe(const BmParams& p, const uint2* probe, const uint32_t* p
   SS_HIP(hipGetSymbolAddress(&stats, HIP_SYMBOL(pb_stats_dev)));
   SS_HIP(hipMemsetAsync(stats, 0, sizeof(pb_stats_dev), st));
 #endif
-  // LDS: 36 KB with the second queue of >= 3 terms, 30 KB without -- three workgroups a CU (occupancy 6) fit its 160 KB
-  bm25_probe_kernel<NT, KPL, FILT, SKIP, HIST><<<(A + PB_WAVES - 1) / PB_WAVES, PB_WAVES * 64, PB_WAVES * pb_wave_lds(NT, PB_STAGED_G), st>>>(
+  // LDS per wave: 4.5 KB with the second queue of >= 3 terms, 3.75 KB without -- 32 waves a CU fit its 160 KB in any workgroup size
+  bm25_probe_kernel<NT, KPL, FILT, SKIP, HIST><<<(A + PB_STAGED_WAVES - 1) / PB_STAGED_WAVES, PB_STAGED_WAVES * 64,
+                                                 PB_STAGED_WAVES * pb_wave_lds(NT, PB_STAGED_G), st>>>(
       p.post, p.term_base, p.sub_off, probe, probe_z, probe_row, umax, pmax, qbound, p.q, p.part_keys, p.total, p.tau, p.hist, p.del, p.del_words, p.n_sub, p.n_terms, p.nq, p.P, p.k,
       p.count);
   return SS_OK;
