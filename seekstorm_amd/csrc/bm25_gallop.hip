@@ -59,6 +59,7 @@ __device__ __forceinline__ uint32_t gp_sub_of(const uint32_t* __restrict__ r, ui
 
 // PHRASE: the position check of bm25_phrase.hip / bm25_sparse_phrase_kernel over up to GP_NT unique terms; PT: u16 (one indexed field)
 // or u32 (merged lists: field << 20 | position)
+// (one of five copies of the check; tests/test_gpu_phrase_positions.py drives all five over one world of position edges)
 template <int KPL, bool PHRASE, typename PT>
 __global__ void __launch_bounds__(GP_WAVES * 64) bm25_gallop_kernel(const GpArgs A) {
   const int lane = threadIdx.x & 63;

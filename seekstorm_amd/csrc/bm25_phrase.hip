@@ -11,7 +11,8 @@
 // of the doc's posting in that term).  For the survivors -- the intersection -- each lane checks the phrase over the
 // positions of ITS doc: the starts offered by the first word's positions, every other word looked up by binary search in
 // its own (ascending) position list.  That decides exactly what the reference's merge decides (some start carries word i at
-// start + i for every i; tests/test_oracle_kat.py pins the restated loop against this definition).  Under ResultType::Topk
+// start + i for every i; tests/test_oracle_kat.py pins the restated loop against this definition).  The check is written out in
+// five kernels; tests/test_gpu_phrase_positions.py drives all five over one world of position edges.  Under ResultType::Topk
 // a doc whose BM25 cannot enter the list skips the position check, as the reference does (add_result.rs:3573-3583).
 // Positions in HBM: d_pos (u16 pool in image order), d_pos_off (end offset per padded posting slot, relative to the term),
 // d_pos_base (first position of a term) -- ss_bm25_upload_positions.

@@ -14,6 +14,7 @@
 // lie (pointer + count per term, in LDS: a register array indexed by the running word would live in scratch) and runs the phrase check
 // the ranking kernels run: a start offered by the first word's positions, word i by binary search at start + i, SS_PHRASE_SKIP places
 // passed over; PT = uint32_t (several indexed fields, merged lists): the start's field tag tested against the query's field filter.
+// (One of five copies of the check; tests/test_gpu_phrase_positions.py drives all five over one world of position edges.)
 // A failed doc's bit is cleared in the wave's LDS copy of the words.  Global writes: the refined word (a plain store by the lane that
 // loaded it) and one atomic add per wave, which takes the cleared docs off the query's count.  Queries of the batch that are no phrases are not touched.
 #include <algorithm>

@@ -152,6 +152,8 @@ __global__ void __launch_bounds__(QW * 64) bm25_sparse_kernel(
 // in d_sp_pos (sp_pos_end), a dense posting's in the image's pool (pos_off by slot).  Each lane then checks ITS doc: a start offered
 // by the first word's positions, every other word by binary search at start + its place (places inside an n-gram key: SS_PHRASE_SKIP).
 // PT = uint32_t: several indexed fields -- merged lists, positions tagged with their field, the field filter a test on the start's tag.
+// (one of five copies of the check -- sm_phrase_wave of bm25_small.hip is this body for <= 4 unique terms -- and
+// tests/test_gpu_phrase_positions.py drives all five over one world of position edges)
 template <int KPL, int QW, typename PT>
 __global__ void __launch_bounds__(QW * 64) bm25_sparse_phrase_kernel(
     const uint32_t* __restrict__ post, const unsigned long long* __restrict__ term_base, const uint32_t* __restrict__ sub_off, uint32_t n_sub,
