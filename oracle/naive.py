@@ -431,3 +431,91 @@ def vec_offcentre(seed, n, dim, c, sigma):
     u /= np.linalg.norm(u)
     rng = np.random.default_rng(seed)
     return (c * u[None, :] + sigma * rng.standard_normal((n, dim))).astype(np.float32)
+
+
+# ---- Point (geo) facets: geo_search.rs, in numpy float64, every operation in the reference's order.  numpy's add, subtract, multiply,
+# divide and sqrt are correctly rounded IEEE operations; cos is the one routine that may differ from another libm in the last place.
+GEO_EARTH_KM = 6371.0087714  # geo_search.rs:109
+GEO_EARTH_MI = 3_958.761_315_801_475  # geo_search.rs:110
+GEO_DEG2RAD = 0.017_453_292_519_943_295  # geo_search.rs:111
+_GEO_SCALE = 10_000_000.0
+
+
+def _geo_as_i32(v):
+    """Rust's `f64 as i32`: toward zero, saturating at the type's ends, NaN -> 0 (int64 holding the i32 values)"""
+    v = np.asarray(v, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.trunc(np.where(v != v, 0.0, np.clip(v, -2147483648.0, 2147483647.0))).astype(np.int64)
+
+
+def _geo_spread(x):  # encode_morton_64_bit, geo_search.rs:12-21
+    x = x.astype(np.uint64)
+    for sh, mask in ((16, 0x0000FFFF0000FFFF), (8, 0x00FF00FF00FF00FF), (4, 0x0F0F0F0F0F0F0F0F), (2, 0x3333333333333333),
+                     (1, 0x5555555555555555)):  # (the first line, x | x << 32 under the low mask, leaves a u32 as it is)
+        x = (x | (x << np.uint64(sh))) & np.uint64(mask)
+    return x
+
+
+def geo_encode(lat, lon):
+    """encode_morton_2_d (geo_search.rs:27-41): lat x 1e7 as i32 as u32 in the even bits, lon in the odd ones -> uint64 codes"""
+    with np.errstate(all="ignore"):
+        x = _geo_as_i32(np.asarray(lat, np.float64) * _GEO_SCALE) & 0xFFFFFFFF
+        y = _geo_as_i32(np.asarray(lon, np.float64) * _GEO_SCALE) & 0xFFFFFFFF
+    return (_geo_spread(np.atleast_1d(y)) << np.uint64(1)) | _geo_spread(np.atleast_1d(x))
+
+
+def _geo_squeeze(x):  # decode_morton_64_bit, geo_search.rs:45-53
+    x = x & np.uint64(0x5555555555555555)
+    for sh, mask in ((1, 0x3333333333333333), (2, 0x0F0F0F0F0F0F0F0F), (4, 0x00FF00FF00FF00FF), (8, 0x0000FFFF0000FFFF),
+                     (16, 0x00000000FFFFFFFF)):
+        x = (x ^ (x >> np.uint64(sh))) & np.uint64(mask)
+    return x.astype(np.uint32)
+
+
+def geo_decode(codes):
+    """decode_morton_2_d (geo_search.rs:58-79): codes -> (lat, lon), each (u32 as i32) as f64 / 1e7"""
+    c = np.atleast_1d(np.asarray(codes, np.uint64))
+    lat = _geo_squeeze(c).view(np.int32).astype(np.float64) / _GEO_SCALE
+    lon = _geo_squeeze(c >> np.uint64(1)).view(np.int32).astype(np.float64) / _GEO_SCALE
+    return lat, lon
+
+
+def geo_distance(codes, base, unit):
+    """unit "km" | "miles": euclidian_distance(point1 = base, point2 = doc) (geo_search.rs:115-124, called so at add_result.rs:462-478
+    and 605-618); "sortkey": simplified_distance(point1 = doc, point2 = base) (geo_search.rs:82-87 under morton_ordering, 96-100)"""
+    lat, lon = geo_decode(codes)
+    b0, b1 = np.float64(base[0]), np.float64(base[1])
+    with np.errstate(all="ignore"):
+        if unit == "sortkey":
+            x = (b1 - lon) * np.cos(GEO_DEG2RAD * (lat + b0) / 2.0)
+            y = b0 - lat
+            return x * x + y * y
+        r = {"km": GEO_EARTH_KM, "miles": GEO_EARTH_MI}[unit]
+        x = GEO_DEG2RAD * (lon - b1) * np.cos(GEO_DEG2RAD * (b0 + lat) / 2.0)
+        y = GEO_DEG2RAD * (lat - b0)
+        return r * np.sqrt(x * x + y * y)
+
+
+def geo_morton_range(base, distance, unit):
+    """point_distance_to_morton_range (geo_search.rs:128-144) -> (morton_min, morton_max), the ends of a Range<u64>"""
+    r = np.float64({"km": GEO_EARTH_KM, "miles": GEO_EARTH_MI}[unit])
+    b0, b1, d = np.float64(base[0]), np.float64(base[1]), np.float64(distance)
+    with np.errstate(all="ignore"):
+        lat_delta = d / (GEO_DEG2RAD * r)
+        lon_delta = d / (GEO_DEG2RAD * r * np.cos(GEO_DEG2RAD * b0))
+        return int(geo_encode(b0 - lat_delta, b1 - lon_delta)[0]), int(geo_encode(b0 + lat_delta, b1 + lon_delta)[0])
+
+
+def geo_pass(codes, base, lo, hi, unit, flags=0):
+    """FilterSparse::Point (add_result.rs:462-478): the code inside the Z-order range of (base, hi) -- an unsigned Range<u64>, empty when
+    its ends are out of order -- AND the distance inside [lo, hi).  Under "sortkey" (the pivots of a sort by distance: no reference
+    filter has that unit) there is no Z range, and the flags turn the ends around as in facet_pass.  -> bool per code"""
+    c = np.atleast_1d(np.asarray(codes, np.uint64))
+    d = geo_distance(c, base, unit)
+    above = d > lo if flags & FACET_LO_EXCLUSIVE else d >= lo
+    below = d <= hi if flags & FACET_HI_INCLUSIVE else d < hi
+    keep = above & below
+    if unit != "sortkey":
+        m0, m1 = geo_morton_range(base, hi, unit)
+        keep &= (c >= np.uint64(m0)) & (c < np.uint64(m1))
+    return keep
