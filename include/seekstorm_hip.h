@@ -432,8 +432,17 @@ int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, c
  * level's length sum the difference of the file's cumulative positions_sum_normalized, so the average length is the one
  * ss_bm25_upload_index_bin computes -- and builds the image from them with ONE device rebuild.  Without positions the blocks are decoded
  * ON THE DEVICE: the file's bytes are staged in HBM one level at a time and every posting is decoded by its own lane straight into its
- * level's arrays (csrc/ref_decode_dev.hip); with_positions != 0 takes postings and positions from the host decoder of
- * ss_bm25_upload_index_bin_positions and cuts them per level.  A tiered ix (ss_index_bin_tier) gives a sparse tier that TAKES
+ * level's arrays (csrc/ref_decode_dev.hip).  with_positions is a MODE: SS_OPEN_NO_POSITIONS (0); SS_OPEN_POSITIONS (1), positions by the
+ * path the library prefers; SS_OPEN_POSITIONS_HOST (2), postings and positions from the host decoder of
+ * ss_bm25_upload_index_bin_positions, cut per level on the host and uploaded; SS_OPEN_POSITIONS_DEVICE (3), the positions decoded on
+ * the device as well: every posting's count in the same sweep, a 64-bit scan for the destinations, a lane per posting of up to 64
+ * positions and a wave per longer one, the tier's pool in a second sweep over the bytes kept in HBM.  Modes 1, 2 and 3 leave
+ * bit-identical images, levels and tiers; any other value is SS_EINVAL.  SS_OPEN_POSITIONS takes the DEVICE path: on the 1 M-doc
+ * text-shaped index of tools/probes/open_levels_time.py its median is below the host path's (profiles/open_levels_positions_time.json).
+ * A file with several defects may be refused with another of their codes by the device path (the largest) than by the host path (the
+ * first).  Beyond the refusals below, with positions: a position above 65 535 is SS_ENOTSUP; a record's count of 0 or above 65 535,
+ * positions running past the key bodies, or a block whose position counts add up to more than byte_array_len + 4 * 65 536 (pointers
+ * sharing bytes; refused before anything is sized by the sum) are SS_EINVAL.  A tiered ix (ss_index_bin_tier) gives a sparse tier that TAKES
  * LEVELS: its postings keep their tfs, its last level is the file's last.  Afterwards ss_bm25_incremental_info reports the file's
  * level count, and ss_bm25_append_level[_positions] / ss_bm25_append_sparse_level accept the next level -- or the last one again, if it
  * was incomplete, which replaces exactly what that level brought.  Term ids are those of ss_index_bin_term_keys at the time of the
@@ -445,7 +454,25 @@ int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, c
  * its container's, tf 0 or above 65 535, a doc at or past its level's doc count, a pointer or record outside the key bodies -- no byte
  * outside them is read).  On any failure the shard is exactly as before: image, levels and tier are built aside and swapped in under
  * the shard lock. */
+enum { SS_OPEN_NO_POSITIONS = 0, SS_OPEN_POSITIONS = 1, SS_OPEN_POSITIONS_HOST = 2, SS_OPEN_POSITIONS_DEVICE = 3 };
 int ss_bm25_open_index_bin_levels(ss_shard* s, const ss_index_bin* ix, int with_positions);
+/* What the shard's last successful ss_bm25_open_index_bin_levels did: the mode that ran (SS_OPEN_POSITIONS resolved to 2 or 3), the
+ * postings and positions its kernels decoded, the positions the host decoder brought.  Null pointers are skipped.  SS_ESTATE: no such
+ * open yet. */
+int ss_bm25_open_info(ss_shard* s, int* mode_ran, uint64_t* n_postings_dev, uint64_t* n_positions_dev, uint64_t* n_positions_host);
+/* The raw arrays of one kept level (ss_bm25_incremental_info counts them) for its dense terms [t0, t1), as an open or a commit
+ * (ss_bm25_append_level[_positions]) left them in HBM: offs_out [t1 - t0 + 1] relative to the first posting read, shard-local docs, tfs,
+ * positions per posting and the positions themselves in posting order.  A synchronous copy under the shard lock.  *n_post / *n_pos are
+ * always set; a null array is skipped (all null: sizes only); post_cap / pos_cap below them with an array to fill is SS_EINVAL.  A
+ * level without positions gives *n_pos = 0 and leaves npos_out alone.  SS_EINVAL also: no such level, t0 > t1, t1 beyond the level's
+ * terms. */
+int ss_bm25_level_read(ss_shard* s, uint32_t level, uint32_t t0, uint32_t t1, uint64_t* offs_out, uint32_t* docs_out, uint16_t* tfs_out,
+                       uint16_t* npos_out, uint16_t* pos_out, uint64_t post_cap, uint64_t pos_cap, uint64_t* n_post, uint64_t* n_pos);
+/* ... of the lists [l0, l1) of a sparse tier of ONE indexed field that keeps its tfs (one that takes levels: ss_bm25_open_index_bin_levels
+ * of a tiered ix, ss_bm25_append_sparse_level); docs are the low words of its postings, npos the distances of the pool's ends.
+ * SS_ESTATE: no such tier. */
+int ss_bm25_sparse_read(ss_shard* s, uint32_t l0, uint32_t l1, uint64_t* offs_out, uint32_t* docs_out, uint16_t* tfs_out, uint16_t* npos_out,
+                        uint16_t* pos_out, uint64_t post_cap, uint64_t pos_cap, uint64_t* n_post, uint64_t* n_pos);
 /* ... on an image of SEVERAL INDEXED FIELDS whose levels came through ss_bm25_commit_level_fields: after the dense commit of `level`
  * (the level the dense image committed last), the entries (doc, field, tf) of the RARE terms in that level, sorted by (doc, field)
  * inside a list, doc ids inside the level, tf >= 1, field < n_fields.  List i continues sparse list i (term id = dense terms + i);

@@ -9,14 +9,19 @@
 //   rbd_doc_*        doc of rank r: Array directly; Bitmap / Rle by select over prefixes the CALLER supplies (a workgroup scans them in
 //                    LDS, a host loop calls rbd_prefix_build)
 //   rbd_tf           tf of rank r from its rank/position pointer
+//   rbd_npos         ... and how many positions the posting carries (an n-gram key's stand behind its first component)
+//   rbd_positions    the posting's positions, absolute, from an embedded pointer or from the record behind the pointer
+//   rbd_chunk_*      a record's position bytes taken 64 at a time (a wave of the device; a host loop in the tests)
 // Codes are those of include/seekstorm_hip.h: RBD_EINVAL = SS_EINVAL, RBD_ENOTSUP = SS_ENOTSUP (Delta containers).
 #pragma once
 #include <stdint.h>
 
 #if defined(__HIPCC__)
 #define RBD_FN __host__ __device__ inline
+#define RBD_FN_FLAT __host__ __device__ inline __attribute__((always_inline))  // small helpers with out-parameters: inlined, so that those stay in registers
 #else
 #define RBD_FN inline
+#define RBD_FN_FLAT inline
 #endif
 
 enum { RBD_OK = 0, RBD_EINVAL = -1, RBD_ENOTSUP = -4 };
@@ -213,4 +218,139 @@ RBD_FN int rbd_tf(const rbd_block& b, const rbd_head& h, uint32_t r, uint32_t* t
   if (tf == 0u || tf > 65535u) return RBD_EINVAL;  // positions_count >= 1 always; component tfs likewise
   *tf_out = tf;
   return RBD_OK;
+}
+
+// ---- positions of rank r (decode_positions_multiterm_singlefield's embedded_positions / positions_pointer, add_result.rs:2036-2197)
+// a POSITION of a record (compress_positions, compress_postinglist.rs:948-976; get_next_position_singlefield / _multifield,
+// add_result.rs:36-88): one and two bytes like the VINT above, but the THREE-byte form keeps bit 13 twice -- the writer stores
+// delta >> 13, (delta >> 7) & 0x7F, delta & 0x7F and the reader ORs b0 << 13 | b1 << 7 | b2 -- so it is not the count's VINT
+RBD_FN uint32_t rbd_position_value(uint32_t b0, uint32_t b1, uint32_t b2, uint32_t size) {  // b2 = the value's last byte, b1 / b0 those before
+  return size == 1u ? (b2 & 0x7Fu) : size == 2u ? ((b1 << 7) | (b2 & 0x7Fu)) : ((b0 << 13) | (b1 << 7) | (b2 & 0x7Fu));
+}
+RBD_FN bool rbd_read_position(const uint8_t* a, uint64_t len, uint64_t pos, uint32_t* out, uint32_t* size) {
+  if (pos >= len) return false;
+  const uint32_t v = a[pos];
+  if (v & 0x80u) { *out = rbd_position_value(0u, 0u, v, 1u); *size = 1u; return true; }
+  if (pos + 1u >= len) return false;
+  const uint32_t b2 = a[pos + 1u];
+  if (b2 & 0x80u) { *out = rbd_position_value(0u, v, b2, 2u); *size = 2u; return true; }
+  if (pos + 2u >= len) return false;
+  *out = rbd_position_value(v, b2, a[pos + 2u], 3u);
+  *size = 3u;
+  return true;
+}
+// the rank/position pointer of rank r: 2 bytes below the pivot, 3 from it on
+RBD_FN_FLAT int rbd_pointer(const rbd_block& b, const rbd_head& h, uint32_t r, uint32_t* p, bool* wide) {
+  if (r < b.pivot) {
+    const uint64_t at = h.range + (uint64_t)r * 2u;
+    if (at + 2u > b.len) return RBD_EINVAL;
+    *p = rbd_rd16(b.a + at);
+    *wide = false;
+  } else {
+    const uint64_t at = h.range + (uint64_t)r * 3u - b.pivot;
+    if (at + 3u > b.len) return RBD_EINVAL;
+    *p = rbd_rd24(b.a + at);
+    *wide = true;
+  }
+  return RBD_OK;
+}
+RBD_FN bool rbd_pointer_embedded(uint32_t p, bool wide) { return (p & (wide ? 0x800000u : 0x8000u)) != 0u; }
+// the record behind a non-embedded pointer: where its positions begin (behind the component tfs of an n-gram key and the count) and
+// how many there are (1 .. 65 535)
+RBD_FN_FLAT int rbd_record_area(const rbd_block& b, const rbd_head& h, uint32_t p, bool wide, uint64_t* at, uint32_t* count) {
+  const uint64_t back = p & (wide ? 0x7FFFFFu : 0x7FFFu);
+  if (back > h.range) return RBD_EINVAL;
+  uint64_t pos = h.range - back;
+  uint32_t v = 0u, size;
+  for (uint32_t c = 0; c <= (b.n_comp > 1u ? b.n_comp : 0u); c++) {  // (component tfs,) the count
+    if (!rbd_read_vint(b.a, b.len, pos, &v, &size)) return RBD_EINVAL;
+    pos += size;
+  }
+  if (v == 0u || v > 65535u) return RBD_EINVAL;
+  *at = pos;
+  *count = v;
+  return RBD_OK;
+}
+// tf as rbd_tf gives it, and the posting's own positions: the tf for a SingleTerm key; an n-gram key's positions_count behind its first
+// component, none behind the others
+RBD_FN_FLAT int rbd_npos(const rbd_block& b, const rbd_head& h, uint32_t r, uint32_t* tf_out, uint32_t* npos_out) {
+  int rc = rbd_tf(b, h, r, tf_out);
+  if (rc != RBD_OK) return rc;
+  if (b.n_comp == 1u) { *npos_out = *tf_out; return RBD_OK; }
+  *npos_out = 0u;
+  if (b.comp != 0u) return RBD_OK;
+  uint32_t p;
+  bool wide;
+  uint64_t at;
+  if ((rc = rbd_pointer(b, h, r, &p, &wide)) != RBD_OK) return rc;
+  return rbd_record_area(b, h, p, wide, &at, npos_out);  // (rbd_tf refused an embedded pointer of an n-gram key)
+}
+// The positions of rank r, ABSOLUTE (the first as stored, every later one previous + stored + 1), at most cap of them: *n = how many.
+// RBD_ENOTSUP: a position above 65 535; RBD_EINVAL: everything else, more than cap positions among it.  (Component lists of an n-gram
+// key other than the first: none.)
+RBD_FN int rbd_positions(const rbd_block& b, const rbd_head& h, uint32_t r, uint16_t* out, uint32_t cap, uint32_t* n_out) {
+  *n_out = 0u;
+  if (b.n_comp > 1u && b.comp != 0u) return RBD_OK;
+  uint32_t p, n = 0u, at = 0u;
+  bool wide;
+  int rc = rbd_pointer(b, h, r, &p, &wide);
+  if (rc != RBD_OK) return rc;
+  if (rbd_pointer_embedded(p, wide)) {
+    if (b.n_comp > 1u) return RBD_EINVAL;
+    // widths as decode_positions_multiterm_singlefield unpacks them: 14 | 7 + 7; 21 | 10 + 11 | 7 + 7 + 7 | 5 + 5 + 5 + 6
+    uint32_t tf, d0, d1 = 0u, d2 = 0u, d3 = 0u;
+    if (!wide) {
+      if ((p >> 14) == 2u) { tf = 1u; d0 = p & 0x3FFFu; }
+      else { tf = 2u; d0 = (p >> 7) & 0x7Fu; d1 = p & 0x7Fu; }
+    } else {
+      tf = (p >> 21) - 3u;
+      if (tf == 1u) { d0 = p & 0x1FFFFFu; }
+      else if (tf == 2u) { d0 = (p >> 11) & 0x3FFu; d1 = p & 0x7FFu; }
+      else if (tf == 3u) { d0 = (p >> 14) & 0x7Fu; d1 = (p >> 7) & 0x7Fu; d2 = p & 0x7Fu; }
+      else { d0 = (p >> 16) & 0x1Fu; d1 = (p >> 11) & 0x1Fu; d2 = (p >> 6) & 0x1Fu; d3 = p & 0x3Fu; }
+    }
+    if (tf > cap) return RBD_EINVAL;
+    at = d0;
+    if (at > 65535u) return RBD_ENOTSUP;
+    out[n++] = (uint16_t)at;
+    if (tf > 1u) { at += d1 + 1u; out[n++] = (uint16_t)at; }  // (7 + 11 + ... bits: far below 65 536)
+    if (tf > 2u) { at += d2 + 1u; out[n++] = (uint16_t)at; }
+    if (tf > 3u) { at += d3 + 1u; out[n++] = (uint16_t)at; }
+    *n_out = n;
+    return RBD_OK;
+  }
+  uint64_t pos;
+  uint32_t count;
+  if ((rc = rbd_record_area(b, h, p, wide, &pos, &count)) != RBD_OK) return rc;
+  for (uint32_t i = 0; i < count; i++) {
+    uint32_t v, size;
+    if (!rbd_read_position(b.a, b.len, pos, &v, &size)) return RBD_EINVAL;
+    pos += size;
+    at = i == 0u ? v : at + v + 1u;
+    if (at > 65535u) return RBD_ENOTSUP;
+    if (n >= cap) return RBD_EINVAL;
+    out[n++] = (uint16_t)at;
+    *n_out = n;
+  }
+  return RBD_OK;
+}
+
+// ---- a record's position bytes, up to 64 consecutive ones at a time.  stops: bit i = byte i of the chunk has bit 7 set; carry: the
+// bytes of an unfinished value in front of the chunk (0 .. 2).  A value ends at a stop byte, or at the third byte of a value without
+// one (read_position looks at no stop bit there); it is made of that byte and the at most two before it, back to the previous end.
+// rbd_chunk_size: bytes of the value that ends at byte i (1 .. 3), 0 where none ends
+RBD_FN uint32_t rbd_chunk_size(uint64_t stops, uint32_t i, uint32_t carry) {
+  const uint64_t below = i ? stops & (~0ull >> (64u - i)) : 0ull;
+  // bytes since the last stop byte (or since the chunk began, plus the carry): whole values of three among them
+  const uint32_t d = below ? i - (64u - (uint32_t)__builtin_clzll((unsigned long long)below)) : i + carry;
+  if ((stops >> i) & 1ull) return d % 3u + 1u;
+  return d % 3u == 2u ? 3u : 0u;
+}
+// the carry behind a chunk of n bytes (1 .. 64)
+RBD_FN uint32_t rbd_chunk_carry(uint64_t stops, uint32_t n, uint32_t carry) {
+  const uint32_t i = n - 1u;
+  if (rbd_chunk_size(stops, i, carry)) return 0u;
+  const uint64_t below = i ? stops & (~0ull >> (64u - i)) : 0ull;
+  const uint32_t d = below ? i - (64u - (uint32_t)__builtin_clzll((unsigned long long)below)) : i + carry;
+  return d % 3u + 1u;
 }

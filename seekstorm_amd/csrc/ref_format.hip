@@ -21,6 +21,7 @@
 #include "ss_common.h"
 #include "ss_threads.h"
 #include "ref_index_bin.h"
+#include "ref_block_decode.h"
 
 namespace {
 
@@ -41,19 +42,11 @@ inline bool read_vint(const uint8_t* a, uint64_t len, uint64_t pos, uint32_t* ou
   return true;
 }
 
-// a POSITION of a record (compress_positions, compress_postinglist.rs:948-976; get_next_position_singlefield / _multifield,
-// add_result.rs:36-88): one and two bytes like the VINT above, but the THREE-byte form keeps bit 13 twice -- the writer stores
-// delta >> 13, (delta >> 7) & 0x7F, delta & 0x7F and the reader ORs b0 << 13 | b1 << 7 | b2 -- so it is not the count's VINT
+// a POSITION of a record: rbd_read_position of ref_block_decode.h, the one copy host and device share (its three-byte form is not the
+// count's VINT)
 inline bool read_position(const uint8_t* a, uint64_t len, uint64_t pos, uint32_t* out) {
-  if (pos >= len) return false;
-  const uint32_t v = a[pos];
-  if (v & 0x80u) { *out = v & 0x7Fu; return true; }
-  if (pos + 1 >= len) return false;
-  const uint32_t b2 = a[pos + 1];
-  if (b2 & 0x80u) { *out = (v << 7) | (b2 & 0x7Fu); return true; }
-  if (pos + 2 >= len) return false;
-  *out = (v << 13) | (b2 << 7) | (a[pos + 2] & 0x7Fu);
-  return true;
+  uint32_t size;
+  return rbd_read_position(a, len, pos, out, &size);
 }
 
 }  // namespace

@@ -11,6 +11,8 @@
 bool ssi_bm25_sparse_levels_has(const ss_shard* s);
 // the tf row of its postings: 0 = no such tier, 1 = one indexed field, else the indexed fields of ssi_bm25_commit_sparse_level_fields
 uint32_t ssi_bm25_sparse_levels_fields(const ss_shard* s);
+// the tf of every posting of a tier of ONE indexed field that takes levels (device, [postings]); nullptr: no such tier
+const uint16_t* ssi_bm25_sparse_levels_tf(const ss_shard* s);
 void ssi_bm25_sparse_levels_drop(const ss_shard* s);
 // every sparse posting's code again from its tf, the image's d_doclen and d_comp (after a commit moved the average length)
 // (SS_ENOTSUP: a weight the code cannot hold, bm_w_codable)

@@ -419,6 +419,10 @@ struct ss_shard {
   uint32_t raw_f_fields = 0;
   std::vector<uint8_t> h_doclen;     // the length bytes of every doc committed so far
   double raw_last_append_ms = 0.0, raw_last_rebuild_ms = 0.0;
+  // what the last successful ss_bm25_open_index_bin_levels did (ss_bm25_open_info): its mode (0 = no such open yet: -1), the postings
+  // and positions its kernels decoded, the positions the host decoder brought
+  int open_mode_ran = -1;
+  uint64_t open_post_dev = 0, open_pos_dev = 0, open_pos_host = 0;
   // bm25 workspace
   void* d_bq = nullptr; size_t bq_cap = 0;       // staged queries
   // ... and their way there: PINNED host staging the asynchronous copy reads from (the callers' own arrays -- pageable, often a local

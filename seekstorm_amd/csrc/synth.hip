@@ -1398,6 +1398,11 @@ uint32_t ssi_bm25_sparse_levels_fields(const ss_shard* s) {
   auto it = g_spl.find(s);
   return it == g_spl.end() ? 0u : it->second.n_fields;
 }
+const uint16_t* ssi_bm25_sparse_levels_tf(const ss_shard* s) {
+  std::lock_guard<std::mutex> g(g_spl_mu);
+  auto it = g_spl.find(s);
+  return it == g_spl.end() || it->second.n_fields != 1 ? nullptr : it->second.d_tf;
+}
 void ssi_bm25_sparse_levels_drop(const ss_shard* s) {
   std::lock_guard<std::mutex> g(g_spl_mu);
   auto it = g_spl.find(s);

@@ -162,7 +162,7 @@ int ssh_open_index_bin(ssh_index* ix, int shard, const uint8_t* bytes, uint64_t 
 int ssh_open_index_bin_levels(ssh_index* ix, int shard, const uint8_t* bytes, uint64_t len, uint32_t key_head_size, int with_positions,
                               uint64_t* keys_out, uint32_t cap) {
   std::vector<uint64_t> keys;
-  const int rc = ix->shards[shard]->open_index_bin(bytes, len, key_head_size, &keys, with_positions != 0, true);
+  const int rc = ix->shards[shard]->open_index_bin(bytes, len, key_head_size, &keys, with_positions, true);
   if (rc) return rc;
   for (size_t i = 0; i < keys.size() && i < cap; i++) keys_out[i] = keys[i];
   return (int)keys.size();

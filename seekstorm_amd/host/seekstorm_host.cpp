@@ -173,7 +173,7 @@ int Shard::upload_vectors(uint64_t n_rows, uint32_t dim, const float* rows, cons
 }
 
 int Shard::open_index_bin(const uint8_t* bytes, uint64_t len, uint32_t key_head_size, std::vector<uint64_t>* term_keys,
-                          bool with_positions, bool levels) {
+                          int with_positions, bool levels) {
   if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
   lexical_fields_ = 1;
   ss_index_bin* ix = nullptr;
@@ -192,7 +192,7 @@ int Shard::open_index_bin(const uint8_t* bytes, uint64_t len, uint32_t key_head_
   ngram_component_.assign(n_terms, 0);
   ngram_component_df_.assign(n_terms, 0);
   if (n_terms) ss_index_bin_term_ngram(ix, ngram_components_.data(), ngram_component_.data(), ngram_component_df_.data());
-  if (levels) rc = ss_bm25_open_index_bin_levels(h_, ix, with_positions ? 1 : 0);
+  if (levels) rc = ss_bm25_open_index_bin_levels(h_, ix, with_positions);  // (the mode as it came: SS_OPEN_*)
   else rc = with_positions ? ss_bm25_upload_index_bin_positions(h_, ix) : ss_bm25_upload_index_bin(h_, ix);
   ss_index_bin_close(ix);
   n_docs_ = rc == SS_OK ? n_docs : 0;

@@ -197,8 +197,10 @@ class Shard {
   // levels: the image is opened level by level (ss_bm25_open_index_bin_levels: its blocks decoded on the device, one raw level per
   // level of the file) -- for a shard that will be COMMITTED to: ss_bm25_append_level then takes the next level, or the last one again
   // if it was incomplete.  Term ids are term_keys' at this call; keys that commits bring take the next ids, so the host keeps the map.
+  // With levels, with_positions is the entry's mode: SS_OPEN_NO_POSITIONS (0 / false), SS_OPEN_POSITIONS (1 / true: the path the library
+  // prefers), SS_OPEN_POSITIONS_HOST (2), SS_OPEN_POSITIONS_DEVICE (3: positions decoded on the device as well); the same image each.
   int open_index_bin(const uint8_t* bytes, uint64_t len, uint32_t key_head_size, std::vector<uint64_t>* term_keys,
-                     bool with_positions = false, bool levels = false);
+                     int with_positions = 0, bool levels = false);
   int open_vector_bin(const uint8_t* bytes, uint64_t len, uint32_t dim, bool i8 = false, bool use_record_scale = false);
   // Precision::I8 records; queries given as f32 are quantised with quantize_f32_to_i8 like the reference's
   int upload_vectors_i8(uint64_t n_rows, uint32_t dim, const int8_t* rows, const float* row_scale, const uint32_t* row_doc_ids);

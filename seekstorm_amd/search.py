@@ -630,11 +630,42 @@ class Shard:
         """index.bin opened level by level, ready to commit to (ss_bm25_open_index_bin_levels; one indexed field): one raw level per
         level of the file, its blocks decoded on the device, one rebuild -- commit_level then takes the next level, or the last one again
         if it was incomplete.  A tiered ix (IndexBin.tier) gives a sparse tier that takes levels.  positions: also every posting's
-        positions (phrase queries), through the host decoder"""
-        N.check(N.lib().ss_bm25_open_index_bin_levels(self._h, ix._h, 1 if positions else 0), "ss_bm25_open_index_bin_levels")
+        positions (phrase queries): True by the path the library prefers, "host" through the host decoder, "device" decoded on the
+        device like the postings -- all three leave the same image"""
+        modes = {False: 0, True: 1, "host": 2, "device": 3}
+        mode = modes[positions] if isinstance(positions, (bool, str)) and positions in modes else int(positions)
+        N.check(N.lib().ss_bm25_open_index_bin_levels(self._h, ix._h, mode), "ss_bm25_open_index_bin_levels")
         self.indexed_doc_count = int(ix.indexed_doc_count)
         self.lexical_field_count = 1
         self._df_cache.clear()
+
+    def open_info(self):
+        """what the last open_index_bin_levels did: (mode that ran: 0 none, 2 host, 3 device; postings decoded on the device; positions
+        decoded on the device; positions brought by the host decoder)"""
+        m, a, b, c = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        N.check(N.lib().ss_bm25_open_info(self._h, C.byref(m), C.byref(a), C.byref(b), C.byref(c)), "ss_bm25_open_info")
+        return int(m.value), int(a.value), int(b.value), int(c.value)
+
+    def _read_raw(self, fn, name, which, a, b):
+        n_post, n_pos = C.c_uint64(), C.c_uint64()
+        N.check(fn(self._h, which, a, b, None, None, None, None, None, 0, 0, C.byref(n_post), C.byref(n_pos)) if which is not None else
+                fn(self._h, a, b, None, None, None, None, None, 0, 0, C.byref(n_post), C.byref(n_pos)), name)
+        np_, npz = int(n_post.value), int(n_pos.value)
+        offs, docs, tfs = np.zeros(b - a + 1, np.uint64), np.zeros(max(np_, 1), np.uint32), np.zeros(max(np_, 1), np.uint16)
+        npos, pos = np.zeros(max(np_, 1), np.uint16), np.zeros(max(npz, 1), np.uint16)
+        args = (N.ptr(offs, N.u64p), N.ptr(docs, N.u32p), N.ptr(tfs, N.u16p), N.ptr(npos, N.u16p), N.ptr(pos, N.u16p), np_, npz, C.byref(n_post),
+                C.byref(n_pos))
+        N.check(fn(self._h, which, a, b, *args) if which is not None else fn(self._h, a, b, *args), name)
+        return offs, docs[:np_], tfs[:np_], npos[:np_], pos[:npz]
+
+    def read_level(self, level, t0, t1):
+        """the raw arrays of one kept level for its dense terms [t0, t1), as an open or a commit left them in HBM: (offsets relative to
+        the first posting, docs, tfs, positions per posting, positions in posting order); a level without positions: no positions"""
+        return self._read_raw(N.lib().ss_bm25_level_read, "ss_bm25_level_read", int(level), int(t0), int(t1))
+
+    def read_sparse(self, l0, l1):
+        """... of the lists [l0, l1) of a sparse tier that takes levels (one indexed field)"""
+        return self._read_raw(N.lib().ss_bm25_sparse_read, "ss_bm25_sparse_read", None, int(l0), int(l1))
 
     def upload_vector_bin(self, data, dim, i8=False, use_record_scale=False):
         """vector.bin as the reference writes it: f32 records, or Precision::I8 records (i8=True)"""

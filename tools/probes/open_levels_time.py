@@ -9,26 +9,45 @@ SS_LOAD_TRACE=1 in the environment the library's own splits go to stderr.  SS_LO
 (leg (a) decodes on them; the library otherwise takes what the machine shows): the JSON records it.  --only b: leg (b) once and nothing
 else (for a kernel trace of the decode kernels in a run of its own); --kernel-stats CSV: adds that trace's rows of the decode kernels
 (rocprofv3 --kernel-trace --stats) to the JSON at --out and does nothing else.
-    python tools/probes/open_levels_time.py [--out FILE] [--docs 1000000] [--rounds 5] [--only b] [--kernel-stats CSV]"""
+--positions: the POSITIONS leg instead, on the same index (every index.bin carries positions), into profiles/open_levels_positions_time.json:
+  (2) ss_bm25_open_index_bin_levels, SS_OPEN_POSITIONS_HOST    -- unchanged code: the parent commit's open with positions
+  (3) ss_bm25_open_index_bin_levels, SS_OPEN_POSITIONS_DEVICE  -- positions decoded on the device
+one untimed warm-up round, then --rounds rounds alternating (2) and (3); median (min .. max); "mode_1_takes_device" is the rule the
+library's SS_OPEN_POSITIONS follows: the device path unless its median is above (2)'s by more than (2)'s own spread (max - min).  In
+the same run one shard opened in mode 3 answers a phrase set (pairs and triples of the most frequent dense terms, pairs with the most
+frequent rare terms) exactly as one opened in mode 2.  --positions --only 3: mode 3 once (for a kernel trace in a run of its own);
+--positions --kernel-stats CSV adds that trace's rows of the decode, scan and position kernels.
+    python tools/probes/open_levels_time.py [--out FILE] [--docs 1000000] [--rounds 5] [--only b] [--kernel-stats CSV] [--positions]"""
 import argparse, json, os, sys, time
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default=os.path.join(HERE, "..", "..", "profiles", "open_levels_time.json"))
+ap.add_argument("--out", default="")
 ap.add_argument("--docs", type=int, default=1_000_000)
 ap.add_argument("--vocab", type=int, default=1_000_000)
 ap.add_argument("--dense-min", type=int, default=1000)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--only", default="")
 ap.add_argument("--kernel-stats", default="")
+ap.add_argument("--positions", action="store_true")
 args = ap.parse_args()
+args.out = args.out or os.path.join(HERE, "..", "..", "profiles", "open_levels_positions_time.json" if args.positions else "open_levels_time.json")
+KERNELS = ("rbd_flat_kernel", "rbd_wg_kernel")
+if args.positions:
+    KERNELS += ("rbd_scan_sums_kernel", "rbd_scan_tiles_kernel", "rbd_scan_write_kernel", "rbd_tpos_kernel", "rbd_guard_kernel", "rbd_pos_kernel",
+                "rbd_pos_long_kernel", "rbd_tier_gather_kernel")
 if args.kernel_stats:
     import csv
     out = json.load(open(args.out))
-    rows = {k: r for r in csv.DictReader(open(args.kernel_stats)) for k in ("rbd_flat_kernel", "rbd_wg_kernel") if k + "(" in r["Name"]}
+    rows = {}
+    for r in csv.DictReader(open(args.kernel_stats)):  # (a templated kernel: one row per instantiation)
+        for k in KERNELS:
+            if k + "(" in r["Name"] or k + "<" in r["Name"]:
+                e = rows.setdefault(k, {"Calls": 0, "TotalDurationNs": 0})
+                e["Calls"] += int(r["Calls"]); e["TotalDurationNs"] += int(r["TotalDurationNs"])
     ns = sum(int(r["TotalDurationNs"]) for r in rows.values())
-    out["decode_kernels"] = {"source": "rocprofv3 --kernel-trace --stats, leg (b) once, a run of its own",
+    out["decode_kernels"] = {"source": "rocprofv3 --kernel-trace --stats, %s once, a run of its own" % ("mode 3" if args.positions else "leg (b)"),
                              "kernels": {k: {"calls": int(r["Calls"]), "total_ms": int(r["TotalDurationNs"]) / 1e6} for k, r in rows.items()},
                              "total_ms": ns / 1e6, "postings_decoded": out.get("postings_decoded"),
                              "postings_per_s": (out["postings_decoded"] / (ns / 1e9)) if out.get("postings_decoded") else None,
@@ -48,12 +67,61 @@ data = T.write_index_bin(key_head_size=23)
 ix = S.IndexBin(data, 1, key_head_size=23)
 n_dense = ix.tier(args.dense_min)
 out = {"docs": args.docs, "index_bin_bytes": len(data), "postings": int(T.n_postings), "terms": int(ix.term_count), "dense_terms": int(n_dense),
-       "levels": int(ix.level_count), "dense_min": args.dense_min, "positions": False, "write_and_walk_s": time.perf_counter() - t0,
+       "levels": int(ix.level_count), "dense_min": args.dense_min, "positions": bool(args.positions), "write_and_walk_s": time.perf_counter() - t0,
        "cpus_visible": len(os.sched_getaffinity(0)), "loader_threads": int(os.environ.get("SS_LOADER_THREADS", 0)) or None}
 a_, b_ = C.c_uint64(), C.c_uint64()
 N.check(N.lib().ss_index_bin_decode_stats(ix._h, 0, C.byref(a_), C.byref(b_)), "ss_index_bin_decode_stats")
 out["postings_decoded"] = int(a_.value)  # (an n-gram key's postings once per component term)
 print(out, flush=True)
+
+
+def leg_positions(mode, keep=False):
+    sh = S.Shard(0)
+    t = time.perf_counter()
+    sh.open_index_bin_levels(ix, positions=mode)
+    dt = time.perf_counter() - t
+    info = sh.open_info()
+    assert sh.incremental_info()[0] == ix.level_count and info[0] == {"host": 2, "device": 3}[mode]
+    if keep:
+        return dt, sh, info
+    sh.close()
+    return dt, None, info
+
+
+if args.positions:
+    if args.only == "3":
+        print("mode 3:", leg_positions("device")[0])
+        sys.exit(0)
+    leg_positions("host"); leg_positions("device")  # warm-up, untimed
+    h, d = [], []
+    for r in range(args.rounds):
+        h.append(leg_positions("host")[0]); d.append(leg_positions("device")[0])
+        print(f"round {r}: mode 2 (host) {h[-1]:.3f} s, mode 3 (device) {d[-1]:.3f} s", flush=True)
+    stat = lambda v: {"median_s": float(np.median(v)), "min_s": float(min(v)), "max_s": float(max(v)), "runs_s": [float(x) for x in v]}
+    out["mode_2_host"], out["mode_3_device"] = stat(h), stat(d)
+    spread = max(h) - min(h)
+    out["mode_1_takes_device"] = {"rule": "mode 3's median <= mode 2's median + mode 2's spread (max - min)",
+                                  "mode_2_median_plus_spread_s": float(np.median(h) + spread), "mode_3_median_s": float(np.median(d)),
+                                  "holds": bool(np.median(d) <= np.median(h) + spread)}
+    # one shard of each mode: the same counts, the same answers to a phrase set
+    _, sh2, info2 = leg_positions("host", keep=True)
+    _, sh3, info3 = leg_positions("device", keep=True)
+    out["position_counts"] = {"decoded_on_the_device": info3[2], "brought_by_the_host_decoder": info2[3], "postings_decoded_on_the_device": info3[1]}
+    assert info3[2] == info2[3] and info3[3] == 0
+    df = np.asarray(sh2.posting_count(np.arange(ix.term_count, dtype=np.uint32)), np.int64)
+    top = [int(t) for t in np.argsort(-df[:n_dense])[:12]]
+    rare = [int(n_dense + t) for t in np.argsort(-df[n_dense:])[:4]]
+    phrases = [[a, b] for a, b in zip(top, top[1:])] + [[b, a] for a, b in zip(top, top[1:])] + [list(top[i:i + 3]) for i in range(0, 9, 3)] + \
+        [[top[i], r] for i, r in enumerate(rare)] + [[r, top[i]] for i, r in enumerate(rare)]
+    ans = [s.search_lexical_batch(s.make_queries(phrases, S.QueryType.Phrase), 10, S.ResultType.TopkCount) for s in (sh2, sh3)]
+    same = all(np.array_equal(np.asarray(x).view(np.uint32) if np.asarray(x).dtype == np.float32 else x, np.asarray(y).view(np.uint32) if np.asarray(y).dtype == np.float32 else y)
+               for x, y in zip(*ans))
+    out["phrase_set"] = {"phrases": len(phrases), "matching_docs": int(np.asarray(ans[0][3]).sum()), "mode_3_equals_mode_2": bool(same)}
+    sh2.close(); sh3.close()
+    print(json.dumps(out, indent=1))
+    json.dump(out, open(args.out, "w"), indent=1)
+    assert same, "a shard opened in mode 3 answers the phrase set differently from one opened in mode 2"
+    sys.exit(0)
 
 
 def leg_a():
