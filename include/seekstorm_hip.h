@@ -456,7 +456,37 @@ int ss_bm25_append_sparse_level(ss_shard* s, uint32_t level, uint32_t n_lists, c
  * the shard lock. */
 enum { SS_OPEN_NO_POSITIONS = 0, SS_OPEN_POSITIONS = 1, SS_OPEN_POSITIONS_HOST = 2, SS_OPEN_POSITIONS_DEVICE = 3 };
 int ss_bm25_open_index_bin_levels(ss_shard* s, const ss_index_bin* ix, int with_positions);
-/* What the shard's last successful ss_bm25_open_index_bin_levels did: the mode that ran (SS_OPEN_POSITIONS resolved to 2 or 3), the
+/* ... of an index of SEVERAL INDEXED FIELDS (2 .. 8), ready for ss_bm25_commit_level_fields: one level kept in HBM per level of the
+ * file -- per-field lists, merged entries with the tf of every field, the level's length bytes [n_fields][level docs], n_docs and the
+ * length sums as above --, ONE device rebuild over all of them (per-field lists, merged lists, their positions), image, levels and
+ * boosts (NULL: all 1) swapped in under the shard lock.  Afterwards ss_bm25_incremental_info reports the file's level count and
+ * ss_bm25_commit_level_fields accepts the next level with the same n_fields, boosts and positions-or-none -- or the last one again if it
+ * was incomplete, which replaces exactly what that level brought.  Term ids are those of ss_index_bin_term_keys.  with_positions:
+ * SS_OPEN_NO_POSITIONS (0) decodes the FIELD VECTORS ON THE DEVICE: a posting of a block is one merged entry, a lane decodes its doc and
+ * the tf of every field (ref_block_decode.h rbd_field_vec), and a 64-bit scan over per-(term, field, rank) flags places the entries of
+ * the per-field lists -- no host pass over the entries.  SS_OPEN_POSITIONS_HOST (2): entries and positions from the host decoder of
+ * ss_bm25_upload_index_bin_fields_positions, cut per level on the host and uploaded; SS_OPEN_POSITIONS (1) takes that path;
+ * SS_OPEN_POSITIONS_DEVICE (3) answers SS_ENOTSUP: field-tagged positions decoded on the device are not built.  Any other value is
+ * SS_EINVAL.  Modes 0 and 2 leave bit-identical postings arrays in every level.  SS_ENOTSUP also: more than 8 fields, a tiered ix
+ * (ss_index_bin_tier left rare keys: a multi-field tier that takes levels is not built from whole lists), a Delta container, and what
+ * ss_bm25_commit_level_fields refuses (a weight the code cannot hold, positions on boosts that keep the merged lists from being built,
+ * 2^32 positions of a term).  SS_EINVAL also: one indexed field (ss_bm25_open_index_bin_levels), a key head in two segments of one
+ * level, a malformed block as above, or a field vector the host decoder refuses: more than 8 entries, a field >= n_fields, fields not
+ * ascending, tf 0 or above 65 535, an embedded pointer of an n-gram key.  The device path answers with the largest code of a file's
+ * defects.  On any failure the shard is exactly as before. */
+int ss_bm25_open_index_bin_levels_fields(ss_shard* s, const ss_index_bin* ix, const float* boost /*[n_fields] or NULL*/, int with_positions);
+/* The arrays of one level of SEVERAL indexed fields kept in HBM, as ss_bm25_open_index_bin_levels_fields or ss_bm25_commit_level_fields
+ * left them, for its terms [t0, t1): foff_out [(t1 - t0) * n_fields + 1] and moff_out / tpos_out [t1 - t0 + 1] relative to the first
+ * element read; fdoc / ftf the (term, field) lists; mdoc, mtf [*n_ment][n_fields] the merged entries; with positions mnpos per merged
+ * entry and pos (field << 20 | position); doclen_out [n_fields][n_docs] the whole level's length bytes.  A synchronous copy under the
+ * shard lock.  The five counts are always set; a null array is skipped; a cap below its count with an array to fill is SS_EINVAL.  A
+ * level without positions gives *n_pos = 0 and leaves mnpos_out / tpos_out / pos_out alone.  SS_ESTATE: the shard keeps no such levels;
+ * SS_EINVAL also: no such level, t0 > t1, t1 beyond the level's terms. */
+int ss_bm25_level_read_fields(ss_shard* s, uint32_t level, uint32_t t0, uint32_t t1, uint64_t* foff_out, uint32_t* fdoc_out, uint16_t* ftf_out,
+                              uint64_t* moff_out, uint32_t* mdoc_out, uint16_t* mtf_out, uint32_t* mnpos_out, uint64_t* tpos_out, uint32_t* pos_out,
+                              uint8_t* doclen_out, uint64_t ent_cap, uint64_t ment_cap, uint64_t pos_cap, uint64_t doclen_cap, uint64_t* n_ent,
+                              uint64_t* n_ment, uint64_t* n_pos, uint32_t* n_fields, uint32_t* n_docs);
+/* What the shard's last successful ss_bm25_open_index_bin_levels[_fields] did: the mode that ran (SS_OPEN_POSITIONS resolved to 2 or 3), the
  * postings and positions its kernels decoded, the positions the host decoder brought.  Null pointers are skipped.  SS_ESTATE: no such
  * open yet. */
 int ss_bm25_open_info(ss_shard* s, int* mode_ran, uint64_t* n_postings_dev, uint64_t* n_positions_dev, uint64_t* n_positions_host);

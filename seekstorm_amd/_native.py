@@ -126,6 +126,9 @@ SYMBOLS = [
     ("ss_bm25_upload_index_bin", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ss_bm25_upload_index_bin_positions", C.c_int, [C.c_void_p, C.c_void_p]),
     ("ss_bm25_open_index_bin_levels", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("ss_bm25_open_index_bin_levels_fields", C.c_int, [C.c_void_p, C.c_void_p, f32p, C.c_int]),
+    ("ss_bm25_level_read_fields", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, u16p, u64p, u32p, u16p, u32p, u64p, u32p, u8p,
+                                            C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u32p, u32p]),
     ("ss_bm25_open_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), u64p, u64p, u64p]),
     ("ss_bm25_level_read", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u64p, u32p, u16p, u16p, u16p, C.c_uint64, C.c_uint64, u64p, u64p]),
     ("ss_bm25_sparse_read", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u64p, u32p, u16p, u16p, u16p, C.c_uint64, C.c_uint64, u64p, u64p]),

@@ -1141,3 +1141,19 @@ int ssi_bm25_install_levels(ss_shard* s, std::vector<ss_raw_level>& levels, std:
   s->raw_last_append_ms = open_ms;
   return SS_OK;
 }
+// ... of SEVERAL indexed fields (ss_bm25_open_index_bin_levels_fields): the levels become those ss_bm25_commit_level_fields continues,
+// with the boosts its later calls must repeat.  The caller holds the levels' commit_mu, as a commit does.
+int ssi_bm25_install_levels_fields(ss_shard* s, std::vector<ss_raw_level_mf>& levels, const std::vector<float>& boost, ss_shard* img, double rebuild_ms,
+                                   double open_ms) {
+  ss_mf_levels* const M = ssi_mf_levels(s, true);
+  ShardLock g(s);
+  SS_HIP(hipSetDevice(s->device));
+  SS_HIP(hipDeviceSynchronize());
+  ssi_bm25_free(s);  // (empties M->raw and M->boost among the rest)
+  M->raw.swap(levels);
+  M->boost = boost;
+  bm_image_take_fields(s, img);
+  s->raw_last_rebuild_ms = rebuild_ms;
+  s->raw_last_append_ms = open_ms;
+  return SS_OK;
+}

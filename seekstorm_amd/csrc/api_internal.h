@@ -134,6 +134,11 @@ struct ss_sparse_tier_built;  // sparse_levels.h
 int ssi_bm25_install_levels(ss_shard* s, std::vector<ss_raw_level>& levels, std::vector<uint8_t>& doclen, ss_shard* img, ss_sparse_tier_built* tier,
                             double rebuild_ms, double open_ms);
 
+// ... of an image of SEVERAL indexed fields: the levels become ssi_mf_levels(s)->raw, with their boosts (the caller holds commit_mu)
+struct ss_raw_level_mf;  // bm25_image.h
+int ssi_bm25_install_levels_fields(ss_shard* s, std::vector<ss_raw_level_mf>& levels, const std::vector<float>& boost, ss_shard* img, double rebuild_ms,
+                                   double open_ms);
+
 // ---- comm.hip: ssi_comm_exchange (ss_common.h) with the hybrid fusion on the host when host_fuse
 int ssi_comm_exchange_hf(ss_comm* c, uint32_t nq, int n_lists, const ss_dev_list* L, const uint64_t* d_tot_a, const uint64_t* d_tot_b,
                          int local_rc, bool hybrid, uint32_t offset, uint32_t length, uint64_t* out_doc, float* out_score,

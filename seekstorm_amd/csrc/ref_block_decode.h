@@ -12,6 +12,7 @@
 //   rbd_npos         ... and how many positions the posting carries (an n-gram key's stand behind its first component)
 //   rbd_positions    the posting's positions, absolute, from an embedded pointer or from the record behind the pointer
 //   rbd_chunk_*      a record's position bytes taken 64 at a time (a wave of the device; a host loop in the tests)
+//   rbd_field_vec    several indexed fields: the tf of every field of rank r (rbd_tf .. rbd_chunk_* above read one-field blocks only)
 // Codes are those of include/seekstorm_hip.h: RBD_EINVAL = SS_EINVAL, RBD_ENOTSUP = SS_ENOTSUP (Delta containers).
 #pragma once
 #include <stdint.h>
@@ -332,6 +333,122 @@ RBD_FN int rbd_positions(const rbd_block& b, const rbd_head& h, uint32_t r, uint
     out[n++] = (uint16_t)at;
     *n_out = n;
   }
+  return RBD_OK;
+}
+
+// ---- SEVERAL indexed fields: the field vector of rank r -- the tf of every field, 0 where the posting does not hold the key there
+// (decode_block_fields / read_field_vec of ref_format.hip restated rank by rank; add_result.rs:1485-2034, 2200-2293).  The vector is
+// kept PACKED while it is decoded, 16 bits a field in two 64-bit words (fields 0 - 3, 4 - 7): an array indexed by a field id read from
+// the bytes would live in scratch memory on the device.
+RBD_FN uint32_t rbd_field_id_bits(uint32_t n_fields) {  // bit length of n_fields - 1 (index.rs:2569-2570)
+  uint32_t bits = 0u;
+  while ((1u << bits) < n_fields) bits++;
+  return bits;
+}
+struct rbd_fvec { uint64_t lo, hi; int32_t last; };  // last: the highest field stored so far (-1: none)
+RBD_FN uint32_t rbd_fvec_tf(const rbd_fvec& v, uint32_t f) { return (uint32_t)((f < 4u ? v.lo >> (16u * f) : v.hi >> (16u * (f - 4u))) & 0xFFFFu); }
+// an entry joins the vector: its field inside n_fields and behind the entry before, its tf 1 .. 65 535
+RBD_FN_FLAT bool rbd_fvec_put(rbd_fvec* v, uint32_t field, uint32_t tf, uint32_t n_fields) {
+  if (field >= n_fields || (int32_t)field <= v->last || tf == 0u || tf > 65535u) return false;
+  if (field < 4u) v->lo |= (uint64_t)tf << (16u * field); else v->hi |= (uint64_t)tf << (16u * (field - 4u));
+  v->last = (int32_t)field;
+  return true;
+}
+// One written field vector at *pos (read_multifield_vec): only the longest field -- 0x40 set, the count in 6 + 7 (+ 7) bits --, or up to
+// eight (field, tf) values of 1 - 3 bytes with FIELD_STOP_BIT_1 / _2 on the last.  *pos moves behind it.  keep: the entries join *v
+// and are judged; else the vector is only stepped over, as the host decoder steps over the components in front of the wanted one.
+RBD_FN_FLAT bool rbd_read_field_vec(const uint8_t* a, uint64_t len, uint64_t* pos_io, uint32_t id_bits, uint32_t n_fields, uint32_t longest, bool keep,
+                                    rbd_fvec* v) {
+  uint64_t pos = *pos_io;
+  if (pos >= len) return false;
+  if (a[pos] & 0x40u) {
+    uint32_t c = a[pos++];
+    if (c & 0x80u) c &= 0x3Fu;
+    else {
+      if (pos >= len) return false;
+      c = (c & 0x3Fu) << 7;
+      const uint32_t c2 = a[pos++];
+      if (c2 & 0x80u) c |= c2 & 0x7Fu;
+      else {
+        if (pos >= len) return false;
+        c = (c << 7) | ((c2 & 0x7Fu) << 7) | (a[pos++] & 0x7Fu);
+      }
+    }
+    if (keep && !rbd_fvec_put(v, longest, c, n_fields)) return false;
+  } else {
+    bool first = true, ok = true;
+    for (uint32_t n = 0;; n++) {
+      if (pos >= len || n >= 8u) return false;
+      uint32_t b = a[pos++];
+      const bool field_stop = (b & (first ? 0x20u : 0x40u)) != 0u;
+      uint32_t x = b & (first ? 0x1Fu : 0x3Fu);
+      if (!(b & 0x80u)) {
+        if (pos >= len) return false;
+        b = a[pos++];
+        x = (x << 7) | (b & 0x7Fu);
+        if (!(b & 0x80u)) {
+          if (pos >= len) return false;
+          b = a[pos++];
+          x = (x << 7) | (b & 0x7Fu);
+        }
+      }
+      // (a vector that is malformed as bytes is refused before one whose entries are: both answer RBD_EINVAL)
+      if (keep && ok) ok = rbd_fvec_put(v, x & ((1u << id_bits) - 1u), x >> id_bits, n_fields);
+      first = false;
+      if ((b & 0x80u) && field_stop) break;
+    }
+    if (!ok) return false;
+  }
+  *pos_io = pos;
+  return true;
+}
+// The field vector of rank r, packed.  A record behind a non-embedded pointer: the vectors of the components 0 .. comp of an n-gram key
+// one after the other, the last one kept (SingleTerm: the posting's own).  Embedded pointers (never an n-gram key's): the 2-byte tags
+// 0x8 .. 0xF and the 3-byte tags 0x10 .. 0x1F, field ids in id_bits-wide slots below the tag.
+RBD_FN_FLAT int rbd_field_vec_packed(const rbd_block& b, const rbd_head& h, uint32_t r, uint32_t n_fields, uint32_t longest, rbd_fvec* out) {
+  if (n_fields < 2u || n_fields > 8u || longest >= n_fields) return RBD_EINVAL;
+  const uint32_t id_bits = rbd_field_id_bits(n_fields), id_mask = (1u << id_bits) - 1u;
+  rbd_fvec v{0ull, 0ull, -1};
+  uint32_t p;
+  bool wide;
+  const int rc = rbd_pointer(b, h, r, &p, &wide);
+  if (rc != RBD_OK) return rc;
+  bool ok;
+  if (!rbd_pointer_embedded(p, wide)) {
+    const uint64_t back = p & (wide ? 0x7FFFFFu : 0x7FFFu);
+    if (back > h.range) return RBD_EINVAL;
+    uint64_t at = h.range - back;
+    ok = true;
+    for (uint32_t c = 0; ok && c <= (b.n_comp > 1u ? b.comp : 0u); c++)
+      ok = rbd_read_field_vec(b.a, b.len, &at, id_bits, n_fields, longest, c == (b.n_comp > 1u ? b.comp : 0u), &v);
+  } else if (b.n_comp > 1u) {
+    return RBD_EINVAL;  // n-gram postings are never embedded (index_posting.rs:445)
+  } else if (!wide) {  // tag = bits 15 .. 12 (add_result.rs:1606-1737)
+    const uint32_t tag = p >> 12, pb = 12u - id_bits, pb2 = 12u - 2u * id_bits;
+    if (tag >= 0xCu) ok = rbd_fvec_put(&v, longest, tag >= 0xEu ? 2u : 1u, n_fields);
+    else if (tag <= 0xAu) ok = rbd_fvec_put(&v, (p >> pb) & id_mask, tag - 7u, n_fields);
+    else ok = rbd_fvec_put(&v, (p >> (pb2 + id_bits)) & id_mask, 1u, n_fields) && rbd_fvec_put(&v, (p >> pb2) & id_mask, 1u, n_fields);
+  } else {  // tag = bits 23 .. 19 (add_result.rs:1738-2017)
+    const uint32_t tag = p >> 19, pb = 19u - id_bits, pb2 = 19u - 2u * id_bits, pb3 = 19u - 3u * id_bits;
+    if (tag >= 0x18u) ok = rbd_fvec_put(&v, longest, ((tag - 0x18u) >> 1) + 1u, n_fields);
+    else if (tag <= 0x13u) ok = rbd_fvec_put(&v, (p >> pb) & id_mask, tag - 0x0Fu, n_fields);
+    else if (tag <= 0x16u)
+      ok = rbd_fvec_put(&v, (p >> (pb2 + id_bits)) & id_mask, tag == 0x16u ? 2u : 1u, n_fields) &&
+           rbd_fvec_put(&v, (p >> pb2) & id_mask, tag == 0x15u ? 2u : 1u, n_fields);
+    else
+      ok = rbd_fvec_put(&v, (p >> (pb3 + 2u * id_bits)) & id_mask, 1u, n_fields) && rbd_fvec_put(&v, (p >> (pb3 + id_bits)) & id_mask, 1u, n_fields) &&
+           rbd_fvec_put(&v, (p >> pb3) & id_mask, 1u, n_fields);
+  }
+  if (!ok) return RBD_EINVAL;
+  *out = v;
+  return RBD_OK;
+}
+// ... as the tf of every field: tf_out[f] for f < n_fields, 0 = absent; the entries behind n_fields are 0
+RBD_FN int rbd_field_vec(const rbd_block& b, const rbd_head& h, uint32_t r, uint32_t n_fields, uint32_t longest_field_id, uint32_t tf_out[8]) {
+  rbd_fvec v;
+  const int rc = rbd_field_vec_packed(b, h, r, n_fields, longest_field_id, &v);
+  if (rc != RBD_OK) return rc;
+  for (uint32_t f = 0; f < 8u; f++) tf_out[f] = rbd_fvec_tf(v, f);
   return RBD_OK;
 }
 

@@ -13,6 +13,10 @@
 // more than its bytes can hold BEFORE anything is sized by the sum; then rbd_pos_kernel (a lane per posting of at most 64 positions) and
 // rbd_pos_long_kernel (a wave per longer posting, its record's bytes 64 at a time) write the positions.
 //
+// SEVERAL indexed fields go the same way (ss_bm25_open_index_bin_levels_fields, further down): a posting is a merged entry of its level,
+// the fields instantiations of the two decode kernels write its doc and the tf of every field, and a scan over per-field flags places
+// the per-field lists.
+//
 // Work goes by POSTING, not by block: on a text-shaped index nearly every block holds 1 - 5 postings.  rbd_flat_kernel: a lane takes
 // posting p of a launch and finds its (Array) block by binary search over the blocks' first postings.  Bitmap and Rle blocks are few and
 // long: rbd_wg_kernel gives each a workgroup, which scans the words' popcounts / the runs' lengths in LDS and then writes ranks.
@@ -49,7 +53,13 @@ struct RbdDst {
   uint64_t* sp_post; uint16_t* sp_tf;
   uint16_t* npos; uint16_t* sp_npos;  // the positions instantiation: every posting's count, beside its tf
   uint32_t doc_base, level_docs;  // first doc of the level, docs it holds
+  // the fields instantiation (several indexed fields; a posting = one merged entry of its level): its doc, the tf of every field, and
+  // per field a flag "held there" in (term, field, rank) order -- the order of the level's (term, field) lists
+  uint32_t* mdoc; uint16_t* mtf; uint16_t* flag;
+  uint32_t n_fields, longest;
 };
+// what a decode kernel takes from a posting beside its doc: the tf; tf + position count; the field vector
+enum { RBD_TF = 0, RBD_TF_NPOS = 1, RBD_FIELDS = 2 };
 constexpr uint32_t RBD_CHUNK = 2048;  // items (bitmap words, runs) a workgroup scans at a time; the writer's Rle containers hold at most
                                       // that many runs (compress_postinglist.rs:256-332), longer ones take several rounds
 
@@ -73,8 +83,32 @@ __device__ __forceinline__ void rbd_store(const RbdDst& D, const RbdDesc& d, uin
   }
 }
 
-// Array blocks, one lane per posting (POS: with the posting's position count)
-template <bool POS>
+// the posting of rank r behind its doc, decoded and stored
+template <int KIND>
+__device__ __forceinline__ int rbd_posting(const RbdDst& D, const RbdDesc& d, const rbd_block& b, const rbd_head& h, uint32_t r, uint32_t doc) {
+  if constexpr (KIND == RBD_FIELDS) {
+    rbd_fvec v;
+    const int rc = rbd_field_vec_packed(b, h, r, D.n_fields, D.longest, &v);
+    if (rc != RBD_OK) return rc;
+    const uint64_t j = d.dst + r, n = (uint64_t)d.count_m1 + 1u;  // (r < n: the callers' guard)
+    D.mdoc[j] = D.doc_base + doc;
+    for (uint32_t f = 0; f < D.n_fields; f++) {
+      const uint32_t tf = rbd_fvec_tf(v, f);
+      D.mtf[j * D.n_fields + f] = (uint16_t)tf;
+      D.flag[d.dst * D.n_fields + f * n + r] = tf ? 1u : 0u;
+    }
+    return RBD_OK;
+  } else {
+    uint32_t tf = 0u, np = 0u;
+    const int rc = KIND == RBD_TF_NPOS ? rbd_npos(b, h, r, &tf, &np) : rbd_tf(b, h, r, &tf);
+    if (rc != RBD_OK) return rc;
+    rbd_store<KIND == RBD_TF_NPOS>(D, d, r, doc, tf, np);
+    return RBD_OK;
+  }
+}
+
+// Array blocks, one lane per posting
+template <int KIND>
 __global__ void __launch_bounds__(256) rbd_flat_kernel(const uint8_t* __restrict__ bytes, const RbdDesc* __restrict__ desc, uint32_t n_blocks,
                                                        uint32_t n_post, RbdDst D, uint32_t* __restrict__ status) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
@@ -88,20 +122,19 @@ __global__ void __launch_bounds__(256) rbd_flat_kernel(const uint8_t* __restrict
   const uint32_t r = p - d.first;
   const rbd_block b = rbd_block_of(bytes, d);
   rbd_head h;
-  uint32_t doc = 0u, tf = 0u, np = 0u;
+  uint32_t doc = 0u;
   int rc = rbd_head_check(b, &h);
   if (rc == RBD_OK && (h.ctype != 1u || r >= b.count)) rc = RBD_EINVAL;  // (the host sends Array blocks here, with their counts)
   if (rc == RBD_OK) rc = rbd_doc(b, h, nullptr, r, D.level_docs, &doc);
-  if (rc == RBD_OK) rc = POS ? rbd_npos(b, h, r, &tf, &np) : rbd_tf(b, h, r, &tf);
-  if (rc != RBD_OK) { rbd_fail(status, rc); return; }
-  rbd_store<POS>(D, d, r, doc, tf, np);
+  if (rc == RBD_OK) rc = rbd_posting<KIND>(D, d, b, h, r, doc);
+  if (rc != RBD_OK) rbd_fail(status, rc);
 }
 
 // Bitmap / Rle blocks (and whatever else the head names: refused), one workgroup per block.  The items -- 64-bit bitmap words / runs --
 // go through the LDS table RBD_CHUNK at a time (a Bitmap is one chunk; an Rle container of more runs than that, which the writer would
 // have made a Bitmap, takes several): their sizes are scanned, then the chunk's ranks are written.  A store is guarded by the key
 // head's count; count != popcount / sum of runs is known after the last chunk, and the arrays written are nobody's until the call succeeds.
-template <bool POS>
+template <int KIND>
 __global__ void __launch_bounds__(256) rbd_wg_kernel(const uint8_t* __restrict__ bytes, const RbdDesc* __restrict__ desc, RbdDst D,
                                                      uint32_t* __restrict__ status) {
   __shared__ uint32_t prefix[RBD_CHUNK + 1];
@@ -148,7 +181,7 @@ __global__ void __launch_bounds__(256) rbd_wg_kernel(const uint8_t* __restrict__
     if (tid == 0) prefix[m] = total;
     __syncthreads();
     for (uint32_t q = tid; q < total && base + q < b.count; q += 256u) {  // rank base + q of the block = rank q of the chunk
-      uint32_t doc, tf = 0u, np = 0u;
+      uint32_t doc;
       if (bitmap) doc = rbd_doc_bitmap(b, h, prefix, q);
       else {
         const uint32_t i = rbd_prefix_find(prefix, m, q);
@@ -156,9 +189,8 @@ __global__ void __launch_bounds__(256) rbd_wg_kernel(const uint8_t* __restrict__
         rbd_rle_run(b, h, c0 + i, &s, &l);
         doc = s + (q - prefix[i]);
       }
-      rc = doc >= D.level_docs ? (int)RBD_EINVAL : POS ? rbd_npos(b, h, base + q, &tf, &np) : rbd_tf(b, h, base + q, &tf);
-      if (rc != RBD_OK) { rbd_fail(status, rc); continue; }
-      rbd_store<POS>(D, d, base + q, doc, tf, np);
+      rc = doc >= D.level_docs ? (int)RBD_EINVAL : rbd_posting<KIND>(D, d, b, h, base + q, doc);
+      if (rc != RBD_OK) rbd_fail(status, rc);
     }
     base += total;
     __syncthreads();  // (the next chunk overwrites the table)
@@ -232,6 +264,39 @@ __global__ void __launch_bounds__(256) rbd_scan_write_kernel(const uint16_t* __r
 __global__ void __launch_bounds__(256) rbd_tpos_kernel(const uint64_t* __restrict__ off, uint32_t n_terms, const uint64_t* __restrict__ scan, uint64_t* __restrict__ tpos) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
   if (t <= n_terms) tpos[t] = scan[off[t]];
+}
+
+// ---- several indexed fields: the (term, field) lists of a level from its merged entries.  scan [n_ment * F + 1] = the exclusive scan
+// of the flags the fields instantiation wrote, in (term, field, rank) order: entries of the level in front of every flag.
+// d_foff: the scan at every list's first flag (a lane per list; the last entry: all the level's entries)
+__global__ void __launch_bounds__(256) rbd_foff_kernel(const uint64_t* __restrict__ moff, uint32_t n_terms, uint32_t n_fields, const uint64_t* __restrict__ scan,
+                                                       uint64_t* __restrict__ foff) {
+  const uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x, n = (uint64_t)n_terms * n_fields;
+  if (v > n) return;
+  if (v == n) { foff[v] = scan[moff[n_terms] * n_fields]; return; }
+  const uint64_t t = v / n_fields, f = v - t * n_fields, m0 = moff[t];
+  foff[v] = scan[m0 * n_fields + f * (moff[t + 1] - m0)];
+}
+// d_fdoc / d_ftf: a lane per merged entry finds its term (the last one that begins at or before it) and writes the entry of every
+// field it holds where the scan says; nothing is written at or behind n_ent
+__global__ void __launch_bounds__(256) rbd_fsplit_kernel(const uint64_t* __restrict__ moff, uint32_t n_terms, uint32_t n_fields, uint64_t n_ment,
+                                                         const uint32_t* __restrict__ mdoc, const uint16_t* __restrict__ mtf, const uint64_t* __restrict__ scan,
+                                                         uint32_t* __restrict__ fdoc, uint16_t* __restrict__ ftf, uint64_t n_ent) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (j >= n_ment) return;
+  uint32_t lo = 0u, hi = n_terms;
+  while (hi - lo > 1u) {
+    const uint32_t m = lo + ((hi - lo) >> 1);
+    if (moff[m] <= j) lo = m; else hi = m;
+  }
+  const uint64_t m0 = moff[lo], cnt = moff[lo + 1u] - m0, r = j - m0;
+  const uint32_t doc = mdoc[j];
+  for (uint32_t f = 0; f < n_fields; f++) {
+    const uint16_t tf = mtf[j * n_fields + f];
+    if (!tf) continue;
+    const uint64_t w = scan[m0 * n_fields + f * cnt + r];
+    if (w < n_ent) { fdoc[w] = doc; ftf[w] = tf; }
+  }
 }
 
 // where the positions of a launch's postings go: posting i (a level's d_npos index / the tier's posting index) has cnt[i] positions from
@@ -552,15 +617,15 @@ int decode_levels_device(const ss_index_bin* ix, uint32_t n_dense, uint32_t n_al
     SS_HIP(hipMemcpyAsync(stage.p, lv_begin, lv_bytes, hipMemcpyHostToDevice, st));
     if (!flat.empty()) SS_HIP(hipMemcpyAsync(d_flat.p, flat.data(), flat.size() * sizeof(RbdDesc), hipMemcpyHostToDevice, st));
     if (!wg.empty()) SS_HIP(hipMemcpyAsync(d_wg.p, wg.data(), wg.size() * sizeof(RbdDesc), hipMemcpyHostToDevice, st));
-    RbdDst D{L.d_doc, L.d_tf, T.d_post, T.d_tf, L.d_npos, (uint16_t*)d_sp_cnt.p, l << 16, level_docs[l]};
+    RbdDst D{L.d_doc, L.d_tf, T.d_post, T.d_tf, L.d_npos, (uint16_t*)d_sp_cnt.p, l << 16, level_docs[l], nullptr, nullptr, nullptr, 1u, 0u};
     const uint8_t* d_bytes = (const uint8_t*)stage.p;
     const uint32_t flat_grid = (uint32_t)((n_flat_post + 255u) / 256u);
     if (n_flat_post && pos)
-      rbd_flat_kernel<true><<<flat_grid, 256, 0, st>>>(d_bytes, (const RbdDesc*)d_flat.p, (uint32_t)flat.size(), (uint32_t)n_flat_post, D, (uint32_t*)d_status.p);
+      rbd_flat_kernel<RBD_TF_NPOS><<<flat_grid, 256, 0, st>>>(d_bytes, (const RbdDesc*)d_flat.p, (uint32_t)flat.size(), (uint32_t)n_flat_post, D, (uint32_t*)d_status.p);
     else if (n_flat_post)
-      rbd_flat_kernel<false><<<flat_grid, 256, 0, st>>>(d_bytes, (const RbdDesc*)d_flat.p, (uint32_t)flat.size(), (uint32_t)n_flat_post, D, (uint32_t*)d_status.p);
-    if (!wg.empty() && pos) rbd_wg_kernel<true><<<(uint32_t)wg.size(), 256, 0, st>>>(d_bytes, (const RbdDesc*)d_wg.p, D, (uint32_t*)d_status.p);
-    else if (!wg.empty()) rbd_wg_kernel<false><<<(uint32_t)wg.size(), 256, 0, st>>>(d_bytes, (const RbdDesc*)d_wg.p, D, (uint32_t*)d_status.p);
+      rbd_flat_kernel<RBD_TF><<<flat_grid, 256, 0, st>>>(d_bytes, (const RbdDesc*)d_flat.p, (uint32_t)flat.size(), (uint32_t)n_flat_post, D, (uint32_t*)d_status.p);
+    if (!wg.empty() && pos) rbd_wg_kernel<RBD_TF_NPOS><<<(uint32_t)wg.size(), 256, 0, st>>>(d_bytes, (const RbdDesc*)d_wg.p, D, (uint32_t*)d_status.p);
+    else if (!wg.empty()) rbd_wg_kernel<RBD_TF><<<(uint32_t)wg.size(), 256, 0, st>>>(d_bytes, (const RbdDesc*)d_wg.p, D, (uint32_t*)d_status.p);
     SS_HIP(hipGetLastError());
     if (pos) {
       // the level's counts scanned in posting order -- the order of d_pos --, its d_tpos, and the guard: all before n_pos sizes anything
@@ -847,12 +912,287 @@ int open_levels_impl(ss_shard* s, const ss_index_bin* ix, int mode) {
   return SS_OK;
 }
 
+// ---- SEVERAL indexed fields (ss_bm25_open_index_bin_levels_fields): one ss_raw_level_mf per level of the file, ONE
+// ssi_bm25_rebuild_from_raw_fields over all of them.  A posting of a block is one merged entry (term, doc) of its level, so d_moff
+// follows from the key heads' counts; the fields instantiation of the decode kernels writes d_mdoc, the rows of d_mtf and a flag per
+// (term, field, rank); the 64-bit scan over the flags gives every (term, field) list its place (rbd_foff_kernel) and every entry its own
+// (rbd_fsplit_kernel) -- the level mf_level_prepare would make of the same entries, without a host pass over them.
+struct OpenStateFields {
+  std::vector<ss_raw_level_mf> levels;
+  std::unique_ptr<ss_shard> img{new ss_shard};
+  ss_shard* owner = nullptr;
+  hipStream_t st = nullptr;
+  bool taken = false;
+  ~OpenStateFields() {
+    if (!taken) {
+      for (ss_raw_level_mf& L : levels) raw_level_mf_free(L);
+      bm_image_arrays(img.get(), [&](auto*& p) { if (p && !owner->blocks.release(p)) (void)hipFree(p); });
+    }
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+int decode_levels_fields_device(const ss_index_bin* ix, uint32_t n_terms, const std::vector<uint32_t>& level_docs, OpenStateFields& O, OpenCounts* counts) {
+  static const bool trace = getenv("SS_LOAD_TRACE") != nullptr;
+  const auto t_0 = std::chrono::steady_clock::now();
+  const uint32_t nl = (uint32_t)level_docs.size(), F = ix->n_fields;
+  hipStream_t st = O.st;
+  // the blocks, level by level, in term order
+  std::vector<uint64_t> lvl_first((size_t)nl + 1, 0);
+  for (const ss_index_bin::Blk& e : ix->blocks) {
+    if (e.b.block_id >= nl) return SS_EINVAL;
+    lvl_first[e.b.block_id + 1]++;
+  }
+  for (uint32_t l = 0; l < nl; l++) lvl_first[l + 1] += lvl_first[l];
+  NoInitVec<LevelEntry> ent(ix->blocks.size());
+  {
+    std::vector<uint64_t> at(lvl_first.begin(), lvl_first.end() - 1);
+    for (uint32_t t = 0; t < n_terms; t++)
+      for (uint64_t bi = ix->term_block_off[t]; bi < ix->term_block_off[t + 1]; bi++) {
+        const ss_index_bin::Blk& e = ix->blocks[bi];
+        if (e.b.byte_array_len > 0xFFFFFFFFull) return SS_EINVAL;
+        LevelEntry& E = ent[at[e.b.block_id]++];
+        E.d = RbdDesc{};
+        E.d.body_len = (uint32_t)e.b.byte_array_len;
+        E.d.ctp = e.b.compression_type_pointer;
+        E.d.count_m1 = e.b.posting_count_m1; E.d.pivot = e.b.pointer_pivot_p_docid;
+        E.d.n_comp = e.n_comp; E.d.comp = e.comp;
+        E.body = e.b.byte_array;
+        E.term = t;
+      }
+  }
+  DevBuf d_stage, d_flat, d_wg, d_status, d_flag, d_scan, d_tiles;
+  SS_TRY(d_status.reserve(sizeof(uint32_t)));
+  SS_HIP(hipMemsetAsync(d_status.p, 0, sizeof(uint32_t), st));
+  std::vector<uint64_t> moff((size_t)n_terms + 1);
+  NoInitVec<RbdDesc> flat, wg;
+  double ms_host = 0, ms_dev = 0;
+  uint64_t n_post_all = 0, n_bytes_all = 0;
+  O.levels.resize(nl);
+  for (uint32_t l = 0; l < nl; l++) {
+    const auto t_a = std::chrono::steady_clock::now();
+    const uint8_t* lv_begin = ix->doclen[l];  // the level's bytes begin with its F x 65 536 length bytes
+    const uint8_t* lv_end = l + 1 < nl ? ix->doclen[l + 1] : ix->bytes + ix->len;
+    const uint64_t lv_bytes = (uint64_t)(lv_end - lv_begin);
+    const LevelEntry* E = ent.data() + lvl_first[l];
+    const uint64_t ne = lvl_first[l + 1] - lvl_first[l];
+    std::fill(moff.begin(), moff.end(), 0ull);
+    for (uint64_t i = 0; i < ne; i++) moff[E[i].term + 1] = (uint64_t)E[i].d.count_m1 + 1u;
+    for (uint32_t t = 0; t < n_terms; t++) moff[t + 1] += moff[t];
+    const uint64_t n_ment = moff[n_terms], n_flag = n_ment * F;
+    flat.clear(); wg.clear();
+    uint64_t n_flat_post = 0;
+    for (uint64_t i = 0; i < ne; i++) {
+      if (E[i].body < lv_begin || E[i].body + E[i].d.body_len > lv_end) return SS_EINVAL;
+      RbdDesc d = E[i].d;
+      d.body = (uint64_t)(E[i].body - lv_begin);
+      d.dst = moff[E[i].term];
+      if ((d.ctp >> 30) == 1u) {
+        if (n_flat_post + 65536u > 0xFFFFFFFFull) return SS_ENOTSUP;  // (2^32 postings in the Array blocks of one level)
+        d.first = (uint32_t)n_flat_post;
+        n_flat_post += (uint64_t)d.count_m1 + 1u;
+        flat.push_back(d);
+      } else {
+        wg.push_back(d);
+      }
+    }
+    if ((n_ment + 255u) / 256u > 0x7FFFFFFFull) return SS_ENOTSUP;
+    ss_raw_level_mf& L = O.levels[l];
+    L.n_docs = level_docs[l]; L.n_terms = n_terms; L.n_fields = F; L.n_ment = n_ment;
+    L.h_mdf.resize(n_terms);
+    for (uint32_t t = 0; t < n_terms; t++) L.h_mdf[t] = (uint32_t)(moff[t + 1] - moff[t]);
+    const uint64_t n_lists = (uint64_t)n_terms * F;
+    SS_HIP(hipMalloc(&L.d_moff, ((size_t)n_terms + 1) * sizeof(uint64_t)));
+    SS_HIP(hipMalloc(&L.d_foff, (n_lists + 1) * sizeof(uint64_t)));
+    SS_HIP(hipMalloc(&L.d_mdoc, std::max<uint64_t>(n_ment, 1) * sizeof(uint32_t)));
+    SS_HIP(hipMalloc(&L.d_mtf, std::max<uint64_t>(n_flag, 1) * sizeof(uint16_t)));
+    SS_HIP(hipMalloc(&L.d_doclen, (size_t)F * L.n_docs));
+    SS_TRY(d_stage.reserve(lv_bytes));
+    SS_TRY(d_flag.reserve(std::max<uint64_t>(n_flag, 1) * sizeof(uint16_t)));
+    SS_TRY(d_scan.reserve((n_flag + 1) * sizeof(uint64_t)));
+    SS_TRY(d_flat.reserve(std::max<size_t>(flat.size(), 1) * sizeof(RbdDesc)));
+    SS_TRY(d_wg.reserve(std::max<size_t>(wg.size(), 1) * sizeof(RbdDesc)));
+    const auto t_b = std::chrono::steady_clock::now();
+    SS_HIP(hipMemcpyAsync(L.d_moff, moff.data(), ((size_t)n_terms + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    SS_HIP(hipMemcpyAsync(d_stage.p, lv_begin, lv_bytes, hipMemcpyHostToDevice, st));
+    if (!flat.empty()) SS_HIP(hipMemcpyAsync(d_flat.p, flat.data(), flat.size() * sizeof(RbdDesc), hipMemcpyHostToDevice, st));
+    if (!wg.empty()) SS_HIP(hipMemcpyAsync(d_wg.p, wg.data(), wg.size() * sizeof(RbdDesc), hipMemcpyHostToDevice, st));
+    const uint8_t* d_bytes = (const uint8_t*)d_stage.p;
+    for (uint32_t f = 0; f < F; f++)  // [F][level docs] from the staged [F][65 536]
+      SS_HIP(hipMemcpyAsync(L.d_doclen + (size_t)f * L.n_docs, d_bytes + (size_t)f * 65536u, L.n_docs, hipMemcpyDeviceToDevice, st));
+    RbdDst D{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, l << 16, level_docs[l], L.d_mdoc, L.d_mtf, (uint16_t*)d_flag.p, F, ix->longest_field_id};
+    if (n_flat_post)
+      rbd_flat_kernel<RBD_FIELDS><<<(uint32_t)((n_flat_post + 255u) / 256u), 256, 0, st>>>(d_bytes, (const RbdDesc*)d_flat.p, (uint32_t)flat.size(),
+                                                                                         (uint32_t)n_flat_post, D, (uint32_t*)d_status.p);
+    if (!wg.empty()) rbd_wg_kernel<RBD_FIELDS><<<(uint32_t)wg.size(), 256, 0, st>>>(d_bytes, (const RbdDesc*)d_wg.p, D, (uint32_t*)d_status.p);
+    SS_HIP(hipGetLastError());
+    const uint64_t* d_total = nullptr;
+    SS_TRY(rbd_scan_launch<true>((const uint16_t*)d_flag.p, n_flag, d_tiles, (uint64_t*)d_scan.p, st, &d_total));
+    rbd_foff_kernel<<<(uint32_t)(n_lists / 256u + 1u), 256, 0, st>>>(L.d_moff, n_terms, F, (const uint64_t*)d_scan.p, L.d_foff);
+    SS_HIP(hipGetLastError());
+    uint32_t status_l = 0;
+    SS_HIP(hipMemcpyAsync(&status_l, d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipMemcpyAsync(&L.n_ent, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    SS_HIP(hipStreamSynchronize(st));
+    if (status_l) return status_l == (uint32_t)(-SS_ENOTSUP) ? SS_ENOTSUP : SS_EINVAL;  // (flags of a refused level size nothing)
+    if (L.n_ent > n_flag) return SS_EDEVICE;
+    SS_HIP(hipMalloc(&L.d_fdoc, std::max<uint64_t>(L.n_ent, 1) * sizeof(uint32_t)));
+    SS_HIP(hipMalloc(&L.d_ftf, std::max<uint64_t>(L.n_ent, 1) * sizeof(uint16_t)));
+    if (n_ment)
+      rbd_fsplit_kernel<<<(uint32_t)((n_ment + 255u) / 256u), 256, 0, st>>>(L.d_moff, n_terms, F, n_ment, L.d_mdoc, L.d_mtf, (const uint64_t*)d_scan.p, L.d_fdoc,
+                                                                          L.d_ftf, L.n_ent);
+    SS_HIP(hipGetLastError());
+    SS_HIP(hipStreamSynchronize(st));  // (the host arrays and the staging serve the next level)
+    const auto t_c = std::chrono::steady_clock::now();
+    ms_host += std::chrono::duration<double, std::milli>(t_b - t_a).count();
+    ms_dev += std::chrono::duration<double, std::milli>(t_c - t_b).count();
+    n_post_all += n_ment;
+    n_bytes_all += lv_bytes;
+  }
+  if (trace)
+    fprintf(stderr, "[load] open levels (fields): block lists %.0f ms; %u levels, %llu postings, %llu file bytes: descriptors %.0f ms, copies + decode kernels %.0f ms\n",
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_0).count() - ms_host - ms_dev, nl,
+            (unsigned long long)n_post_all, (unsigned long long)n_bytes_all, ms_host, ms_dev);
+  counts->post_dev = n_post_all;
+  return SS_OK;
+}
+
+// with positions: the host decoder's entries and positions (what ss_bm25_upload_index_bin_fields_positions decodes), cut per level; every
+// level through mf_level_prepare, as a commit of it
+int decode_levels_fields_host(const ss_index_bin* ix, uint32_t n_terms, const std::vector<uint32_t>& level_docs, OpenStateFields& O, OpenCounts* counts) {
+  const uint32_t nl = (uint32_t)level_docs.size(), F = ix->n_fields;
+  DecodedFields D;
+  SS_TRY(ssi_index_bin_decode_fields_range(ix, 0, n_terms, true, &D));
+  if (D.offs.size() != (size_t)n_terms + 1 || D.npos.size() != D.docs.size()) return SS_EINVAL;
+  // every term's next entry and its first position; entries of a term ascend by doc, so a level's are a run
+  std::vector<uint64_t> cur_e(D.offs.begin(), D.offs.end() - 1), cur_p((size_t)n_terms + 1, 0);
+  ss_parallel_for(n_terms, 256, [&](size_t a, size_t b, unsigned) {
+    for (size_t t = a; t < b; t++) {
+      uint64_t c = 0;
+      for (uint64_t j = D.offs[t]; j < D.offs[t + 1]; j++) c += D.npos[j];
+      cur_p[t + 1] = c;
+    }
+  });
+  for (uint32_t t = 0; t < n_terms; t++) cur_p[t + 1] += cur_p[t];
+  if (cur_p[n_terms] != D.pos.size()) return SS_EINVAL;
+  std::vector<uint64_t> offs((size_t)n_terms + 1), poff((size_t)n_terms + 1);
+  std::vector<uint32_t> docs;
+  std::vector<uint8_t> fields, dl;
+  std::vector<uint16_t> tfs, npos, pos;
+  O.levels.resize(nl);
+  for (uint32_t l = 0; l < nl; l++) {
+    offs[0] = 0; poff[0] = 0;
+    ss_parallel_for(n_terms, 256, [&](size_t a, size_t b, unsigned) {
+      for (size_t t = a; t < b; t++) {
+        uint64_t j = cur_e[t], c = 0;
+        for (; j < D.offs[t + 1] && (D.docs[j] >> 16) == l; j++) c += D.npos[j];
+        offs[t + 1] = j - cur_e[t]; poff[t + 1] = c;
+      }
+    });
+    for (uint32_t t = 0; t < n_terms; t++) { offs[t + 1] += offs[t]; poff[t + 1] += poff[t]; }
+    const uint64_t n_ent = offs[n_terms], n_pos = poff[n_terms];
+    docs.resize(std::max<uint64_t>(n_ent, 1)); fields.resize(docs.size()); tfs.resize(docs.size()); npos.resize(docs.size());
+    pos.resize(std::max<uint64_t>(n_pos, 1));
+    ss_parallel_for(n_terms, 256, [&](size_t a, size_t b, unsigned) {
+      for (size_t t = a; t < b; t++) {
+        const uint64_t n = offs[t + 1] - offs[t], np = poff[t + 1] - poff[t];
+        if (n) {
+          std::memcpy(&docs[offs[t]], D.docs.data() + cur_e[t], n * sizeof(uint32_t));
+          std::memcpy(&fields[offs[t]], D.fields.data() + cur_e[t], n);
+          std::memcpy(&tfs[offs[t]], D.tfs.data() + cur_e[t], n * sizeof(uint16_t));
+          std::memcpy(&npos[offs[t]], D.npos.data() + cur_e[t], n * sizeof(uint16_t));
+        }
+        if (np) std::memcpy(&pos[poff[t]], D.pos.data() + cur_p[t], np * sizeof(uint16_t));
+        cur_e[t] += n; cur_p[t] += np;
+      }
+    });
+    dl.resize((size_t)F * level_docs[l]);
+    for (uint32_t f = 0; f < F; f++) std::memcpy(dl.data() + (size_t)f * level_docs[l], ix->doclen[l] + (size_t)f * 65536u, level_docs[l]);
+    mf_level_host H;
+    SS_TRY(mf_level_prepare(l, level_docs[l], F, n_terms, offs.data(), docs.data(), fields.data(), tfs.data(), npos.data(), pos.data(), n_pos, &H));
+    SS_TRY(raw_level_mf_upload(O.levels[l], H, dl.data(), O.st));
+    counts->pos_host += n_pos;
+  }
+  for (uint32_t t = 0; t < n_terms; t++)
+    if (cur_e[t] != D.offs[t + 1]) return SS_EINVAL;  // an entry behind the last level
+  return SS_OK;
+}
+
+int open_levels_fields_impl(ss_shard* s, const ss_index_bin* ix, const float* boost, int mode) {
+  const int ran = mode == SS_OPEN_POSITIONS ? (int)SS_OPEN_POSITIONS_HOST : mode;
+  const auto t_begin = std::chrono::steady_clock::now();
+  static const bool trace = getenv("SS_LOAD_TRACE") != nullptr;
+  const uint32_t n_terms = (uint32_t)ix->keys.size(), F = ix->n_fields;
+  const uint32_t nl = (uint32_t)ix->doclen.size();
+  if (nl == 0 || ix->n_docs > 0xFFFFFFFFull || ix->n_docs <= (uint64_t)(nl - 1u) * 65536u || ix->n_docs > (uint64_t)nl * 65536u) return SS_EINVAL;
+  if (ix->longest_field_id >= F) return SS_EINVAL;
+  // every level's docs and the sum of their lengths as the file states it (cumulative behind the level's F x 65 536 length bytes)
+  std::vector<uint32_t> level_docs(nl);
+  std::vector<uint64_t> level_psum(nl);
+  uint64_t cum = 0;
+  for (uint32_t l = 0; l < nl; l++) {
+    level_docs[l] = (uint32_t)std::min<uint64_t>(65536u, ix->n_docs - (uint64_t)l * 65536u);
+    const uint64_t c = rd64(ix->doclen[l] + (size_t)F * 65536u + 8u);
+    if (c < cum) return SS_EINVAL;
+    level_psum[l] = c - cum;
+    cum = c;
+  }
+  // a term holds at most one block per level, levels ascending: a key head in two segments of one level would send two blocks to one
+  // destination -- refused here, before anything is staged or launched
+  {
+    std::atomic<int> bad{0};
+    ss_parallel_for(n_terms, 16384, [&](size_t a, size_t b, unsigned) {
+      for (size_t t = a; t < b; t++)
+        for (uint64_t bi = ix->term_block_off[t]; bi < ix->term_block_off[t + 1]; bi++)
+          if (ix->blocks[bi].b.block_id >= nl || (bi > ix->term_block_off[t] && ix->blocks[bi].b.block_id <= ix->blocks[bi - 1].b.block_id)) { bad.store(1); return; }
+    });
+    if (bad.load()) return SS_EINVAL;
+  }
+  std::vector<float> b(F, 1.0f);
+  if (boost) b.assign(boost, boost + F);
+  ss_mf_levels* const M = ssi_mf_levels(s, true);
+  std::lock_guard<std::mutex> commits(M->commit_mu);  // an open is a commit of every level: one after the other with the shard's commits
+  SS_HIP(hipSetDevice(s->device));
+  OpenStateFields O;
+  O.owner = s;
+  if (const hipError_t e = hipStreamCreateWithFlags(&O.st, hipStreamNonBlocking)) return e == hipErrorOutOfMemory ? SS_ENOMEM : SS_EDEVICE;
+  OpenCounts counts;
+  if (ran == SS_OPEN_POSITIONS_HOST) SS_TRY(decode_levels_fields_host(ix, n_terms, level_docs, O, &counts));
+  else SS_TRY(decode_levels_fields_device(ix, n_terms, level_docs, O, &counts));
+  for (uint32_t l = 0; l < nl; l++) O.levels[l].psum = level_psum[l];
+  const auto t_build = std::chrono::steady_clock::now();
+  SS_TRY(ssi_bm25_rebuild_from_raw_fields(s, O.levels, F, b.data(), O.img.get(), O.st));
+  auto ms = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
+  const auto t_swap = std::chrono::steady_clock::now();
+  SS_TRY(ssi_bm25_install_levels_fields(s, O.levels, b, O.img.get(), ms(t_build, t_swap), ms(t_begin, t_swap)));
+  O.taken = true;
+  {
+    ShardLock g(s);
+    s->open_mode_ran = ran; s->open_post_dev = counts.post_dev; s->open_pos_dev = 0; s->open_pos_host = counts.pos_host;
+  }
+  if (trace)
+    fprintf(stderr, "[load] open levels (fields): decode %.0f ms, rebuild %.0f ms, swap %.0f ms\n", ms(t_begin, t_build), ms(t_build, t_swap),
+            ms(t_swap, std::chrono::steady_clock::now()));
+  return SS_OK;
+}
+
 }  // namespace
+
+extern "C" int ss_bm25_open_index_bin_levels_fields(ss_shard* s, const ss_index_bin* ix, const float* boost, int with_positions) {
+  if (!s || !ix) return SS_EINVAL;
+  if (ix->keys.empty() || ix->n_docs == 0) return SS_EINVAL;
+  if (ix->n_fields < 2) return SS_EINVAL;  // one indexed field: ss_bm25_open_index_bin_levels
+  if (ix->n_fields > 8) return SS_ENOTSUP;
+  if (with_positions < SS_OPEN_NO_POSITIONS || with_positions > SS_OPEN_POSITIONS_DEVICE) return SS_EINVAL;
+  if (with_positions == SS_OPEN_POSITIONS_DEVICE) return SS_ENOTSUP;  // field-tagged positions decoded on the device: not built
+  if (ix->n_dense < ix->keys.size()) return SS_ENOTSUP;                // a tiered ix: a multi-field tier that takes levels is not built from whole lists
+  return ss_guard([&] { return open_levels_fields_impl(s, ix, boost, with_positions); }, SS_ENOMEM, SS_EDEVICE);
+}
 
 extern "C" int ss_bm25_open_index_bin_levels(ss_shard* s, const ss_index_bin* ix, int with_positions) {
   if (!s || !ix) return SS_EINVAL;
   if (ix->keys.empty() || ix->n_docs == 0) return SS_EINVAL;
-  if (ix->n_fields > 1) return SS_ENOTSUP;  // several indexed fields: ss_bm25_upload_index_bin_fields (their decode on the device is not built)
+  if (ix->n_fields > 1) return SS_ENOTSUP;  // several indexed fields: ss_bm25_open_index_bin_levels_fields
   if (with_positions < SS_OPEN_NO_POSITIONS || with_positions > SS_OPEN_POSITIONS_DEVICE) return SS_EINVAL;
   return ss_guard([&] { return open_levels_impl(s, ix, with_positions); }, SS_ENOMEM, SS_EDEVICE);
 }
@@ -900,6 +1240,52 @@ extern "C" int ss_bm25_level_read(ss_shard* s, uint32_t level, uint32_t t0, uint
     if (tfs_out) SS_TRY(read_dev(tfs_out, L.d_tf + j0, *n_post));
     if (npos_out && L.d_npos) SS_TRY(read_dev(npos_out, L.d_npos + j0, *n_post));
     if (pos_out && L.d_pos) SS_TRY(read_dev(pos_out, L.d_pos + p0, *n_pos));
+    return SS_OK;
+  }, SS_ENOMEM, SS_EDEVICE);
+}
+
+extern "C" int ss_bm25_level_read_fields(ss_shard* s, uint32_t level, uint32_t t0, uint32_t t1, uint64_t* foff_out, uint32_t* fdoc_out, uint16_t* ftf_out,
+                                         uint64_t* moff_out, uint32_t* mdoc_out, uint16_t* mtf_out, uint32_t* mnpos_out, uint64_t* tpos_out, uint32_t* pos_out,
+                                         uint8_t* doclen_out, uint64_t ent_cap, uint64_t ment_cap, uint64_t pos_cap, uint64_t doclen_cap, uint64_t* n_ent,
+                                         uint64_t* n_ment, uint64_t* n_pos, uint32_t* n_fields, uint32_t* n_docs) {
+  if (!s || !n_ent || !n_ment || !n_pos || !n_fields || !n_docs) return SS_EINVAL;
+  return ss_guard([&]() -> int {
+    const ss_mf_levels* M = ssi_mf_levels(s, false);
+    ShardLock g(s);
+    if (!M || M->raw.empty()) return SS_ESTATE;  // no levels of several indexed fields kept in HBM
+    if (level >= M->raw.size()) return SS_EINVAL;
+    const ss_raw_level_mf& L = M->raw[level];
+    if (t0 > t1 || t1 > L.n_terms) return SS_EINVAL;
+    SS_HIP(hipSetDevice(s->device));
+    SS_HIP(hipDeviceSynchronize());
+    const uint64_t F = L.n_fields;
+    std::vector<uint64_t> fo((size_t)(t1 - t0) * F + 1), mo((size_t)(t1 - t0) + 1);
+    SS_TRY(read_dev(fo.data(), L.d_foff + (size_t)t0 * F, fo.size()));
+    SS_TRY(read_dev(mo.data(), L.d_moff + t0, mo.size()));
+    const uint64_t e0 = fo.front(), e1 = fo.back(), m0 = mo.front(), m1 = mo.back();
+    uint64_t p0 = 0, p1 = 0;
+    if (L.d_tpos) { SS_TRY(read_dev(&p0, L.d_tpos + t0, 1)); SS_TRY(read_dev(&p1, L.d_tpos + t1, 1)); }
+    if (e1 < e0 || e1 > L.n_ent || m1 < m0 || m1 > L.n_ment || p1 < p0 || p1 > L.n_pos) return SS_EDEVICE;
+    *n_ent = e1 - e0; *n_ment = m1 - m0; *n_pos = p1 - p0; *n_fields = L.n_fields; *n_docs = L.n_docs;
+    if (((fdoc_out || ftf_out) && ent_cap < *n_ent) || ((mdoc_out || mtf_out || mnpos_out) && ment_cap < *n_ment) || (pos_out && pos_cap < *n_pos) ||
+        (doclen_out && doclen_cap < F * L.n_docs))
+      return SS_EINVAL;
+    if (foff_out) for (size_t i = 0; i < fo.size(); i++) foff_out[i] = fo[i] - e0;
+    if (moff_out) for (size_t i = 0; i < mo.size(); i++) moff_out[i] = mo[i] - m0;
+    if (fdoc_out) SS_TRY(read_dev(fdoc_out, L.d_fdoc + e0, *n_ent));
+    if (ftf_out) SS_TRY(read_dev(ftf_out, L.d_ftf + e0, *n_ent));
+    if (mdoc_out) SS_TRY(read_dev(mdoc_out, L.d_mdoc + m0, *n_ment));
+    if (mtf_out) SS_TRY(read_dev(mtf_out, L.d_mtf + m0 * F, *n_ment * F));
+    if (doclen_out) SS_TRY(read_dev(doclen_out, L.d_doclen, F * L.n_docs));
+    if (L.d_tpos) {
+      if (mnpos_out) SS_TRY(read_dev(mnpos_out, L.d_mnpos + m0, *n_ment));
+      if (tpos_out) {
+        std::vector<uint64_t> tp((size_t)(t1 - t0) + 1);
+        SS_TRY(read_dev(tp.data(), L.d_tpos + t0, tp.size()));
+        for (size_t i = 0; i < tp.size(); i++) tpos_out[i] = tp[i] - p0;
+      }
+      if (pos_out) SS_TRY(read_dev(pos_out, L.d_pos + p0, *n_pos));
+    }
     return SS_OK;
   }, SS_ENOMEM, SS_EDEVICE);
 }

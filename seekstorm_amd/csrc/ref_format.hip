@@ -1249,3 +1249,6 @@ int upload_index_bin_single(ss_shard* s, const ss_index_bin* ix, bool with_posit
 int ssi_index_bin_decode_range(const ss_index_bin* ix, uint32_t t0, uint32_t t1, bool with_positions, DecodedRange* out) {
   return index_bin_decode_range(ix, t0, t1, with_positions, out);
 }
+int ssi_index_bin_decode_fields_range(const ss_index_bin* ix, uint32_t t0, uint32_t t1, bool with_positions, DecodedFields* out) {
+  return decode_fields_range(ix, t0, t1, out->offs, out->docs, out->fields, out->tfs, with_positions ? &out->pos : nullptr, with_positions ? &out->npos : nullptr);
+}

@@ -50,3 +50,12 @@ struct DecodedRange {
   RawBuf<uint16_t> tfs, pos, npos;
 };
 int ssi_index_bin_decode_range(const ss_index_bin* ix, uint32_t t0, uint32_t t1, bool with_positions, DecodedRange* out);
+// ... of an index of SEVERAL indexed fields: the entries (doc, field, tf) of every term, sorted by (doc, field), with the positions of
+// every entry in that order and their number per entry (an n-gram key's own stand behind its first component)
+struct DecodedFields {
+  std::vector<uint64_t> offs;  // [t1 - t0 + 1]
+  NoInitVec<uint32_t> docs;
+  NoInitVec<uint8_t> fields;
+  NoInitVec<uint16_t> tfs, pos, npos;
+};
+int ssi_index_bin_decode_fields_range(const ss_index_bin* ix, uint32_t t0, uint32_t t1, bool with_positions, DecodedFields* out);

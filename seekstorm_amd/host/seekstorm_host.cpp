@@ -173,11 +173,12 @@ int Shard::upload_vectors(uint64_t n_rows, uint32_t dim, const float* rows, cons
 }
 
 int Shard::open_index_bin(const uint8_t* bytes, uint64_t len, uint32_t key_head_size, std::vector<uint64_t>* term_keys,
-                          int with_positions, bool levels) {
+                          int with_positions, bool levels, uint32_t indexed_field_count, const float* boost) {
   if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
-  lexical_fields_ = 1;
+  if (indexed_field_count == 0) return SS_EINVAL;
+  lexical_fields_ = indexed_field_count;
   ss_index_bin* ix = nullptr;
-  int rc = ss_index_bin_open(bytes, len, 1, key_head_size, 11, &ix);  // open_index always uses 2048 segments (index.rs:3285)
+  int rc = ss_index_bin_open(bytes, len, indexed_field_count, key_head_size, 11, &ix);  // open_index always uses 2048 segments (index.rs:3285)
   if (rc) return rc;
   uint64_t n_docs = 0;
   uint32_t n_terms = 0;
@@ -192,7 +193,9 @@ int Shard::open_index_bin(const uint8_t* bytes, uint64_t len, uint32_t key_head_
   ngram_component_.assign(n_terms, 0);
   ngram_component_df_.assign(n_terms, 0);
   if (n_terms) ss_index_bin_term_ngram(ix, ngram_components_.data(), ngram_component_.data(), ngram_component_df_.data());
-  if (levels) rc = ss_bm25_open_index_bin_levels(h_, ix, with_positions);  // (the mode as it came: SS_OPEN_*)
+  if (levels && indexed_field_count > 1) rc = ss_bm25_open_index_bin_levels_fields(h_, ix, boost, with_positions);  // (ready for ss_bm25_commit_level_fields)
+  else if (levels) rc = ss_bm25_open_index_bin_levels(h_, ix, with_positions);  // (the mode as it came: SS_OPEN_*)
+  else if (indexed_field_count > 1) rc = with_positions ? ss_bm25_upload_index_bin_fields_positions(h_, ix, boost) : ss_bm25_upload_index_bin_fields(h_, ix, boost);
   else rc = with_positions ? ss_bm25_upload_index_bin_positions(h_, ix) : ss_bm25_upload_index_bin(h_, ix);
   ss_index_bin_close(ix);
   n_docs_ = rc == SS_OK ? n_docs : 0;

@@ -199,8 +199,11 @@ class Shard {
   // if it was incomplete.  Term ids are term_keys' at this call; keys that commits bring take the next ids, so the host keeps the map.
   // With levels, with_positions is the entry's mode: SS_OPEN_NO_POSITIONS (0 / false), SS_OPEN_POSITIONS (1 / true: the path the library
   // prefers), SS_OPEN_POSITIONS_HOST (2), SS_OPEN_POSITIONS_DEVICE (3: positions decoded on the device as well); the same image each.
+  // indexed_field_count > 1: an index of several indexed fields with the schema's boost per field (null: all 1); with levels it is
+  // opened by ss_bm25_open_index_bin_levels_fields -- the field vectors decoded on the device without positions, modes 1 and 2 through the
+  // host decoder, mode 3 SS_ENOTSUP -- and ss_bm25_commit_level_fields takes the next level with the same boosts.
   int open_index_bin(const uint8_t* bytes, uint64_t len, uint32_t key_head_size, std::vector<uint64_t>* term_keys,
-                     int with_positions = 0, bool levels = false);
+                     int with_positions = 0, bool levels = false, uint32_t indexed_field_count = 1, const float* boost = nullptr);
   int open_vector_bin(const uint8_t* bytes, uint64_t len, uint32_t dim, bool i8 = false, bool use_record_scale = false);
   // Precision::I8 records; queries given as f32 are quantised with quantize_f32_to_i8 like the reference's
   int upload_vectors_i8(uint64_t n_rows, uint32_t dim, const int8_t* rows, const float* row_scale, const uint32_t* row_doc_ids);

@@ -639,8 +639,46 @@ class Shard:
         self.lexical_field_count = 1
         self._df_cache.clear()
 
+    def open_index_bin_levels_fields(self, ix: "IndexBin", boost=None, positions=False):
+        """index.bin of SEVERAL indexed fields opened level by level, ready for commit_level_fields
+        (ss_bm25_open_index_bin_levels_fields): one level kept in HBM per level of the file, one device rebuild.  boost: schema boost per
+        indexed field (None: all 1), which later commits repeat.  positions: False -- the field vectors are decoded on the device;
+        True / "host" -- entries and positions through the host decoder, cut per level; "device" is not built (SS_ENOTSUP)"""
+        modes = {False: 0, True: 1, "host": 2, "device": 3}
+        mode = modes[positions] if isinstance(positions, (bool, str)) and positions in modes else int(positions)
+        b = None if boost is None else np.ascontiguousarray(boost, np.float32)
+        if b is not None and len(b) != int(ix.indexed_field_count):
+            raise ValueError("one boost per indexed field")
+        N.check(N.lib().ss_bm25_open_index_bin_levels_fields(self._h, ix._h, N.ptr(b, N.f32p), mode), "ss_bm25_open_index_bin_levels_fields")
+        self.indexed_doc_count = int(ix.indexed_doc_count)
+        self.lexical_field_count = int(ix.indexed_field_count)
+        self._df_cache.clear()
+
+    def read_level_fields(self, level, t0, t1):
+        """the arrays of one kept level of SEVERAL indexed fields for its terms [t0, t1), as open_index_bin_levels_fields or
+        commit_level_fields left them in HBM: a dict of foff / moff / tpos (relative to the first element read), fdoc, ftf, mdoc,
+        mtf [merged entries][fields], doclen [fields][level docs] and, with positions, mnpos and pos (field << 20 | position); a level
+        without positions: tpos, mnpos and pos are None"""
+        fn, nm = N.lib().ss_bm25_level_read_fields, "ss_bm25_level_read_fields"
+        level, t0, t1 = int(level), int(t0), int(t1)
+        ne, nm_, npz, nf, nd = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        sizes = (C.byref(ne), C.byref(nm_), C.byref(npz), C.byref(nf), C.byref(nd))
+        N.check(fn(self._h, level, t0, t1, None, None, None, None, None, None, None, None, None, None, 0, 0, 0, 0, *sizes), nm)
+        n_ent, n_ment, n_pos, F, n_docs = int(ne.value), int(nm_.value), int(npz.value), int(nf.value), int(nd.value)
+        foff, moff, tpos = np.zeros((t1 - t0) * F + 1, np.uint64), np.zeros(t1 - t0 + 1, np.uint64), np.zeros(t1 - t0 + 1, np.uint64)
+        fdoc, ftf = np.zeros(max(n_ent, 1), np.uint32), np.zeros(max(n_ent, 1), np.uint16)
+        mdoc, mtf, mnpos = np.zeros(max(n_ment, 1), np.uint32), np.zeros(max(n_ment, 1) * F, np.uint16), np.full(max(n_ment, 1), 0xFFFFFFFF, np.uint32)
+        pos, doclen = np.zeros(max(n_pos, 1), np.uint32), np.zeros(F * n_docs, np.uint8)
+        N.check(fn(self._h, level, t0, t1, N.ptr(foff, N.u64p), N.ptr(fdoc, N.u32p), N.ptr(ftf, N.u16p), N.ptr(moff, N.u64p), N.ptr(mdoc, N.u32p),
+                   N.ptr(mtf, N.u16p), N.ptr(mnpos, N.u32p), N.ptr(tpos, N.u64p), N.ptr(pos, N.u32p), N.ptr(doclen, N.u8p), n_ent, n_ment, n_pos,
+                   len(doclen), *sizes), nm)
+        with_pos = n_pos > 0 or (n_ment > 0 and mnpos[0] != 0xFFFFFFFF)  # (a level without positions leaves mnpos alone)
+        return {"foff": foff, "fdoc": fdoc[:n_ent], "ftf": ftf[:n_ent], "moff": moff, "mdoc": mdoc[:n_ment], "mtf": mtf[:n_ment * F].reshape(n_ment, F),
+                "doclen": doclen.reshape(F, n_docs), "mnpos": mnpos[:n_ment] if with_pos else None, "tpos": tpos if with_pos else None,
+                "pos": pos[:n_pos] if with_pos else None}
+
     def open_info(self):
-        """what the last open_index_bin_levels did: (mode that ran: 0 none, 2 host, 3 device; postings decoded on the device; positions
+        """what the last open_index_bin_levels[_fields] did: (mode that ran: 0 none, 2 host, 3 device; postings decoded on the device; positions
         decoded on the device; positions brought by the host decoder)"""
         m, a, b, c = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         N.check(N.lib().ss_bm25_open_info(self._h, C.byref(m), C.byref(a), C.byref(b), C.byref(c)), "ss_bm25_open_info")
