@@ -892,6 +892,33 @@ int ss_docs_search(ss_shard* s, uint64_t skip, uint32_t k, uint32_t result_type,
                    const uint64_t* range_lower_bounds, const ss_facet_point* bases,
                    uint32_t* out_doc, uint32_t* out_count, uint64_t* out_total, uint64_t* out_facet_counts);
 
+/* delete_documents_by_query (index.rs:5147-5205): a lexical search with ResultType::Topk and enable_empty_query = false under the
+ * caller's offset, length, field_filter (in the queries), facet_filter and result_sort, whose docs are then deleted.  For every query i
+ * take the list the corresponding search entry returns for k = offset + length (the sum saturates) -- ss_bm25_search_filtered when
+ * n_sorts = 0, ss_bm25_search_sorted otherwise -- and of it the entries from rank `offset` on: the crate's page.  Every page is
+ * computed against the shard AS IT IS WHEN THE CALL BEGINS; the union of all pages is then added to the tombstones in one step, exactly
+ * as if the n searches were followed by ONE ss_add_deleted of the union.
+ *   out_matched [n_queries] or NULL   the query's out_total: its live matches under the filters
+ *   out_selected [n_queries] or NULL  the docs of its page
+ *   out_deleted (one value) or NULL   distinct docs newly tombstoned, over all queries
+ *   out_doc [doc_cap] or NULL         those docs, ascending (a host's own delete_hashset and delete.bin)
+ * flags: SS_DELETE_DRY_RUN -- every output is what it would be and nothing changes; any other bit SS_EINVAL.  n_queries = 0 or
+ * length = 0: SS_OK, nothing deleted.  out_doc with doc_cap below the count: SS_EINVAL, *out_deleted = the count needed, nothing changed.
+ * Two paths, chosen per query.  The WHOLE MATCH SET -- offset = 0, length >= the query's matches, the query not marked
+ * SS_OP_ALL_TERMS_FREQUENT and of a shape the match-set step of the facet entries takes (dense and sparse-tier terms, phrases, merged
+ * lists): the page is the match set itself (every match scores above zero), so no search runs and no doc id moves -- the match sets of
+ * a chunk of <= 64 queries are built once under the filter's exclusion bitmap and ORed into a pending bitmap.  A PAGE -- everything
+ * else: the search entries' own locked paths run with k no larger than the matches need (none at all when offset >= matched) and the
+ * page's docs are scattered into the pending bitmap.  One kernel then takes the tombstones off the pending bitmap and counts what is
+ * left, the count is checked against doc_cap, and only then the same kernel writes the live bitmap, grown as ss_add_deleted grows it.
+ * Errors as the search entries give them (SS_EINVAL, SS_ESTATE, and SS_ENOTSUP, the routing answer of INTEGRATION.md section 4); on any
+ * failure the shard is exactly as before.  The call holds the shard lock with the shard's streams idle, as ss_add_deleted does: a
+ * search sees none of it or all of it. */
+#define SS_DELETE_DRY_RUN 1u /* count and list, change nothing */
+int ss_bm25_delete_by_query(ss_shard* s, uint32_t n_queries, const ss_bm25_query* queries, uint32_t n_sorts, const ss_result_sort* sorts,
+                            uint64_t offset, uint64_t length, uint32_t n_filters, const ss_facet_filter* filters, uint32_t flags,
+                            uint64_t* out_matched, uint64_t* out_selected, uint64_t* out_deleted, uint32_t* out_doc, uint64_t doc_cap);
+
 /* ------------------------------------------------------------------ vector image
  * rows: row-major [n_rows x dim] f32, already L2-normalised for cosine (vector.rs:585-596); the uploader of
  * a real vector.bin strips the 24-byte VectorHeader (vector.rs:62-73).  row_doc_ids may be NULL (= row index).

@@ -74,6 +74,7 @@ class ResultSortC(C.Structure):  # ss_result_sort
 
 
 SS_MAX_SORT_FIELDS = 4
+SS_DELETE_DRY_RUN = 1
 SS_MAX_STRING_RANKS = 8
 
 
@@ -222,6 +223,8 @@ SYMBOLS = [
                                       u32p, u32p, u32p, u64p, C.c_void_p, u32p, f32p, u32p, u64p, u64p]),
     ("ss_docs_search", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                  C.c_uint32, u32p, u32p, u32p, u64p, C.c_void_p, u32p, u32p, u64p, u64p]),
+    ("ss_bm25_delete_by_query", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                          C.c_uint32, u64p, u64p, u64p, u32p, C.c_uint64]),
     ("ss_bm25_search_sharded", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     ("ss_rrf_merge_dev", C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int,

@@ -5,6 +5,7 @@
 //   api_image.hip     the lexical and facet images built and committed: uploads, level and sparse-tier commits, tombstones, string ranks
 //   api_coalesce.hip  the futex coalescer of concurrent callers, its SS_CO_TRACE report and its stats
 //   api_deep.hip      deep pages: lexical and vector searches of more than SS_MAX_K results, in passes
+//   api_delete.hip    delete_documents_by_query: match sets and pages of a batch into the tombstones (ss_bm25_delete_by_query)
 //   ref_decode_dev.hip  index.bin opened level by level, its blocks decoded on the device (ss_bm25_open_index_bin_levels)
 // A function that one file defines and another calls is declared here, once, with its default arguments, under the ssi_ prefix and with
 // C++ linkage (as in ss_common.h); everything else is static in its file.  The helpers defined here are static too: every file gets its
@@ -16,6 +17,7 @@
 
 #include "ss_common.h"
 #include "facet_commit.h"
+#include "bm25_match.h"
 
 #define SS_TRY(x)          \
   do {                     \
@@ -99,6 +101,21 @@ int ssi_bm25_search_direct(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uin
                            const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total);
 int ssi_bm25_search_direct_lane(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t* out_doc, float* out_score,
                                 uint32_t* out_count, uint64_t* out_total, hipEvent_t ev, uint32_t lane_slot, std::vector<uint32_t>& row_of);
+// A chunk of <= 64 queries planned for the MATCH-SET STEP (ss_api.hip: match_prepare / match_enqueue, where the contract stands): the
+// tiers planned and the phrases in intersection form.  The staged forms are read by asynchronous copies: a MatchChunk lives until the
+// call's synchronisation.
+struct MatchChunk {
+  BmTierPlan tier;
+  std::vector<ss_bm25_query> staged;
+  bool any_phrase() const { return !staged.empty(); }
+  const ss_bm25_query* form(const ss_bm25_query* qc) const { return staged.empty() ? qc : staged.data(); }
+};
+// match_prepare without `info` (a union under a field filter is SS_ENOTSUP) and match_enqueue with the filter's bitmap built inside
+int ssi_match_prepare(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, MatchChunk* mc);
+int ssi_match_enqueue(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, const MatchChunk& mc, uint32_t n_filters, const ss_facet_filter* filters,
+                      ss_bm25_query* d_q, ss_bm25_query* d_sub, ss_bm25_query* d_ph, unsigned long long* d_bits, unsigned long long* d_total);
+int ssi_bm25_search_deep_filtered_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
+                                         const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count, uint64_t* out_total);
 struct QueryFacets;  // (the query_facets of a sorted search: ss_api.hip)
 // a batch whose queries each carry their OWN facet filters (ss_bm25_search_each): query i's are filters[filter_begin[i] .. filter_begin[i + 1]),
 // checked by ssi_filter_rows (filter_rows.h) and free of SS_FACET_IDS_EXTERN sets
@@ -180,6 +197,8 @@ enum { SS_CO_PLAIN = 0, SS_CO_FILTERED, SS_CO_FACETS, SS_CO_SORTED, SS_CO_SORTED
 #define SS_CO_FACETED_DEFAULT 64u
 struct ss_shard_abi : ss_shard {
   ss_coalescer co_fac;
+  void* d_delete_ws = nullptr;  // ss_bm25_delete_by_query's workspace (api_delete.hip), grow-only
+  size_t delete_ws_cap = 0;
 };
 static inline ss_coalescer& ssi_co_fac(ss_shard* s) { return static_cast<ss_shard_abi*>(s)->co_fac; }
 // the faceted kind.  *submitted = the call went through the coalescer and the return value is its answer; false -- the kind

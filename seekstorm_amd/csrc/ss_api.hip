@@ -2,7 +2,7 @@
 // reference seams each entry point replaces): shard life, lexical search and its routing, match sets with sorts, facets and browse, the
 // sharded searches, merge and the profile hooks.  Host-side plumbing only; the kernels live in bm25*.hip.
 // The vector side stands in api_vec.hip, the lexical and facet images (uploads and commits) in api_image.hip, the coalescer of concurrent
-// callers in api_coalesce.hip, the deep pages in api_deep.hip; api_internal.h is what the five share.
+// callers in api_coalesce.hip, the deep pages in api_deep.hip, delete_documents_by_query in api_delete.hip; api_internal.h is what they share.
 #include <sched.h>
 #include <time.h>
 #include <unistd.h>
@@ -124,6 +124,7 @@ int ss_shard_destroy(ss_shard* s) {
   ssi_mf_levels_drop(s);
   ssi_facet_side_drop(s);
   for (void* p_ : {(void*)s->d_vq, (void*)s->d_vdoc, (void*)s->d_vscore, (void*)s->d_vcount, (void*)s->d_vtotal}) if (p_) (void)hipFree(p_);
+  if (static_cast<ss_shard_abi*>(s)->d_delete_ws) (void)hipFree(static_cast<ss_shard_abi*>(s)->d_delete_ws);
   void* ptrs[] = {s->d_qstage, s->d_out_doc, s->d_out_score, s->d_out_count, s->d_out_total, s->d_bq, s->d_deleted, s->d_facets, s->d_filter_bits, s->d_facet_ws, s->d_pool_stage, s->d_tier_ws, s->d_tier_hold, s->d_excl_bits, s->d_sort_ws, s->d_route_ws, s->d_peel_bits, s->d_gate_ws};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   (void)hipDeviceSynchronize();  // searches queued on the callers' own streams may still use their workspaces
@@ -1762,12 +1763,7 @@ static int tier_prepare(ss_shard* s, uint32_t nq, const ss_bm25_query* q, BmTier
 // SS_ENOTSUP for what stays with the caller's own path -- and writes the chunk with its phrases in intersection
 // form into mc->staged.  A chunk without a phrase leaves it empty: form() is then the caller's own array and every call below is the
 // one such a chunk has always taken.  The staged forms are read by asynchronous copies: a MatchChunk lives until the call's synchronisation.
-struct MatchChunk {
-  BmTierPlan tier;
-  std::vector<ss_bm25_query> staged;
-  bool any_phrase() const { return !staged.empty(); }
-  const ss_bm25_query* form(const ss_bm25_query* qc) const { return staged.empty() ? qc : staged.data(); }
-};
+// (struct MatchChunk: api_internal.h -- api_delete.hip plans chunks too)
 static int match_stage_phrases(const ss_shard* s, uint32_t nb, const ss_bm25_query* qc, MatchChunk* mc) {
   mc->staged.clear();
   bool any = false;
@@ -1818,6 +1814,19 @@ static int match_enqueue(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, cons
                               : ssi_bm25_match_bits(s, d_q, d_bits, d_total, s->stream, nb));
     return mc.any_phrase() ? ssi_bm25_phrase_refine(s, d_ph, d_bits, d_total, s->stream, nb) : SS_OK;
   }, prebuilt);
+}
+
+// the two halves for the ABI layer's other files (api_delete.hip): match_prepare in its form without `info`
+extern "C++" int ssi_match_prepare(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, MatchChunk* mc) { return match_prepare(s, nb, qc, mc); }
+extern "C++" int ssi_match_enqueue(ss_shard* s, uint32_t nb, const ss_bm25_query* qc, const MatchChunk& mc, uint32_t n_filters, const ss_facet_filter* filters,
+                                   ss_bm25_query* d_q, ss_bm25_query* d_sub, ss_bm25_query* d_ph, unsigned long long* d_bits, unsigned long long* d_total) {
+  return match_enqueue(s, nb, qc, mc, n_filters, filters, false, d_q, d_sub, d_ph, d_bits, d_total);
+}
+// ss_bm25_search_filtered's deep page for a caller that holds the shard lock: the filter's bitmap built, then the passes
+extern "C++" int ssi_bm25_search_deep_filtered_locked(ss_shard* s, uint32_t nq, const ss_bm25_query* q, uint32_t k, uint32_t rt, uint32_t n_filters,
+                                                      const ss_facet_filter* filters, uint32_t* out_doc, float* out_score, uint32_t* out_count,
+                                                      uint64_t* out_total) {
+  return with_facet_filter(s, n_filters, filters, s->stream, [&]() { return ssi_bm25_search_deep_locked(s, nq, q, k, rt, out_doc, out_score, out_count, out_total); });
 }
 
 // ONE query's match set, as ss_bm25_facet_count and ss_bm25_facet_kth build it: the query prepared, then the facet's place in the record

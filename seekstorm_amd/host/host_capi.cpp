@@ -331,6 +331,28 @@ int ssh_upload_lexical_fields_positions(ssh_index* ix, int shard, uint64_t n_doc
 }
 int ssh_set_deleted(ssh_index* ix, int shard, const uint64_t* doc_ids, uint64_t n) { return ix->shards[shard]->set_deleted(doc_ids, n); }
 int ssh_add_deleted(ssh_index* ix, int shard, const uint64_t* doc_ids, uint64_t n) { return ix->shards[shard]->add_deleted(doc_ids, n); }
+// Index::delete_documents_by_query: length = UINT64_MAX for every match; *out_n = the number of global ids it deleted, the first
+// min(*out_n, cap) of them, ascending, in out_doc
+int ssh_delete_documents_by_query(ssh_index* ix, const uint32_t* terms, uint32_t n_terms, uint32_t query_type, uint64_t offset, uint64_t length,
+                                  uint32_t n_filters, const ss_facet_filter* filters, const ssh_result_sort* sorts, uint32_t n_sorts,
+                                  const uint32_t* not_terms, uint32_t n_not, uint32_t dry_run, uint64_t cap, uint64_t* out_doc, uint64_t* out_n) {
+  std::vector<ResultSort> rs(n_sorts);
+  for (uint32_t i = 0; i < n_sorts; i++) {
+    rs[i].facet_offset = sorts[i].facet_offset;
+    rs[i].facet_type = sorts[i].facet_type;
+    rs[i].descending = sorts[i].descending != 0;
+    rs[i].base[0] = sorts[i].base[0];
+    rs[i].base[1] = sorts[i].base[1];
+  }
+  if (!ix->index) ix->index.reset(new Index(ix->shards));
+  std::vector<uint64_t> ids;
+  const int rc = ix->index->delete_documents_by_query(std::vector<uint32_t>(terms, terms + n_terms), (QueryType)query_type, offset, length, &ids, {},
+                                                      std::vector<ss_facet_filter>(filters, filters + n_filters), rs,
+                                                      std::vector<uint32_t>(not_terms, not_terms + n_not), dry_run != 0);
+  if (out_n) *out_n = ids.size();
+  if (out_doc) std::memcpy(out_doc, ids.data(), (size_t)std::min<uint64_t>(cap, ids.size()) * sizeof(uint64_t));
+  return rc;
+}
 int ssh_commit_level(ssh_index* ix, int shard, uint32_t level, uint32_t n_level_docs, const uint8_t* level_doclen, uint32_t n_terms,
                      uint32_t n_dense_terms, const uint64_t* offs, const uint32_t* docs, const uint16_t* tfs, const uint16_t* positions,
                      uint64_t n_positions) {

@@ -283,6 +283,36 @@ int Shard::add_deleted(const uint64_t* doc_ids, uint64_t n) {
   return rc;
 }
 
+int Shard::delete_by_query(const std::vector<ss_bm25_query>& queries, uint64_t offset, uint64_t length, const std::vector<ss_facet_filter>& facet_filter,
+                           const std::vector<ResultSort>& result_sort, bool dry_run, std::vector<uint64_t>* matched, std::vector<uint64_t>* selected,
+                           uint64_t* deleted, std::vector<uint32_t>* docs) {
+  if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
+  std::vector<ss_result_sort> rs;
+  for (const ResultSort& sf : result_sort) {
+    if (sf.field != ResultSort::Field::Facet) return SS_EINVAL;  // (`_id` / `_score` belong to the empty query)
+    rs.push_back(ss_result_sort{sf.facet_offset, sf.facet_type, sf.descending ? 1u : 0u, 0, sf.base[0], sf.base[1]});
+  }
+  const size_t nq = queries.size();
+  std::vector<uint64_t> m(nq, 0), sel(nq, 0);
+  uint64_t n = 0;
+  uint64_t cap = 0;
+  if (docs) {  // no page holds more docs than the shard or than the queries may select
+    cap = n_docs_;
+    if (length != kDeleteAll && (nq == 0 || length <= cap / nq)) cap = length * nq;
+    docs->assign((size_t)std::max<uint64_t>(cap, 1), 0u);
+  }
+  const int rc = ss_bm25_delete_by_query(h_, (uint32_t)nq, nq ? queries.data() : nullptr, (uint32_t)rs.size(), rs.empty() ? nullptr : rs.data(), offset,
+                                         length, (uint32_t)facet_filter.size(), facet_filter.empty() ? nullptr : facet_filter.data(),
+                                         dry_run ? SS_DELETE_DRY_RUN : 0u, m.data(), sel.data(), &n, docs ? docs->data() : nullptr, cap);
+  if (docs) docs->resize(rc == SS_OK ? (size_t)n : 0);
+  if (rc != SS_OK) return rc;
+  if (!dry_run) n_deleted_ += n;
+  if (matched) *matched = std::move(m);
+  if (selected) *selected = std::move(sel);
+  if (deleted) *deleted = n;
+  return SS_OK;
+}
+
 int Shard::synth_lexical(uint64_t seed, uint64_t n_docs, uint32_t n_terms, const uint32_t* thresh32,
                          const uint8_t* len_table1024) {
   if (!h_) return create_rc_ ? create_rc_ : SS_ESTATE;
@@ -1265,6 +1295,94 @@ ResultObject Index::search(const std::vector<uint32_t>& query_terms, const float
   }
   ro.result_count = ro.results.size();
   return ro;
+}
+
+int Index::delete_documents_by_query(const std::vector<uint32_t>& query_terms, QueryType query_type_default, uint64_t offset, uint64_t length,
+                                     std::vector<uint64_t>* deleted_ids, const std::vector<uint16_t>& field_filter,
+                                     const std::vector<ss_facet_filter>& facet_filter, const std::vector<ResultSort>& result_sort,
+                                     const std::vector<uint32_t>& not_terms, bool dry_run) {
+  if (deleted_ids) deleted_ids->clear();
+  const size_t S = shards_.size();
+  if (query_terms.empty() || S == 0) return SS_OK;  // (enable_empty_query = false: nothing matches, no shard is asked)
+  const bool all = length == Shard::kDeleteAll;
+  std::vector<uint64_t> ids;
+  auto shard_query = [&](Shard& sh, bool bounded, ss_bm25_query* q) {
+    const int rc = sh.make_query(query_terms, query_type_default, q, not_terms, sh.lexical_field_count() > 1 ? field_filter : std::vector<uint16_t>());
+    // a bounded page by score is the search's, with the reference's all_terms_frequent shortcut where its condition holds
+    if (rc == SS_OK && bounded && !all && facet_filter.empty() && result_sort.empty()) sh.mark_all_terms_frequent(q, (size_t)(offset + length));
+    return rc;
+  };
+  auto run = [&](Shard& sh, bool bounded, uint64_t off, uint64_t len, bool dry, uint64_t* matched, std::vector<uint32_t>* docs) {
+    ss_bm25_query q;
+    int rc = shard_query(sh, bounded, &q);
+    if (rc != SS_OK) return rc;
+    std::vector<uint64_t> m;
+    rc = sh.delete_by_query({q}, off, len, facet_filter, result_sort, dry, &m, nullptr, nullptr, docs);
+    if (rc == SS_OK && matched) *matched = m[0];
+    return rc;
+  };
+  uint64_t total = 0;
+  bool counted = false;
+  int rc = SS_OK;
+  if (S == 1) {
+    std::vector<uint32_t> docs;
+    rc = run(*shards_[0], true, offset, length, dry_run, nullptr, &docs);
+    if (rc == SS_OK) {
+      for (uint32_t d : docs) ids.push_back((uint64_t)d * S + shards_[0]->shard_id());
+      if (deleted_ids) *deleted_ids = std::move(ids);
+      return SS_OK;
+    }
+  } else {
+    for (size_t i = 0; i < S && rc == SS_OK; i++) {
+      uint64_t m = 0;
+      rc = run(*shards_[i], false, 0, Shard::kDeleteAll, true, &m, nullptr);
+      total += m;
+    }
+    counted = rc == SS_OK;
+    if (counted && offset == 0 && length >= total) {
+      for (size_t i = 0; i < S; i++) {
+        std::vector<uint32_t> docs;
+        rc = run(*shards_[i], false, 0, Shard::kDeleteAll, dry_run, nullptr, &docs);
+        if (rc != SS_OK) return rc;
+        for (uint32_t d : docs) ids.push_back((uint64_t)d * S + shards_[i]->shard_id());
+      }
+      std::sort(ids.begin(), ids.end());
+      if (deleted_ids) *deleted_ids = std::move(ids);
+      return SS_OK;
+    }
+  }
+  if (rc != SS_OK && rc != SS_ENOTSUP) return rc;
+  // the search route: the merged page, its ids to their shards
+  auto search = [&](size_t off, size_t len, ResultType rt) {
+    return result_sort.empty() ? this->search(query_terms, nullptr, query_type_default, SearchMode::Lexical, off, len, rt, nullptr, true, AnnMode(), {},
+                                              facet_filter, not_terms, field_filter)
+                               : search_lexical_sorted(query_terms, query_type_default, off, len, result_sort, facet_filter, not_terms, {}, rt);
+  };
+  if (!counted && all) {  // (no shard counted: the search's own total bounds the page)
+    ResultObject c = search(0, 1, ResultType::TopkCount);
+    if (c.last_error) return c.last_error;
+    total = c.result_count_total;
+    counted = true;
+  }
+  uint64_t want = length;
+  if (counted) want = std::min<uint64_t>(want, total > offset ? total - offset : 0);
+  if (want == 0) return SS_OK;
+  ResultObject ro = search((size_t)offset, (size_t)want, ResultType::Topk);
+  if (ro.last_error) return ro.last_error;
+  for (const Result& r : ro.results) ids.push_back(r.doc_id);
+  std::sort(ids.begin(), ids.end());
+  ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+  if (!dry_run)
+    for (size_t i = 0; i < S; i++) {
+      std::vector<uint64_t> local;
+      for (uint64_t g : ids)
+        if (g % S == shards_[i]->shard_id()) local.push_back(g / S);
+      if (local.empty()) continue;
+      rc = shards_[i]->add_deleted(local.data(), local.size());
+      if (rc != SS_OK) return rc;
+    }
+  if (deleted_ids) *deleted_ids = std::move(ids);
+  return SS_OK;
 }
 
 Index::~Index() {

@@ -213,6 +213,17 @@ class Shard {
   int set_deleted(const uint64_t* doc_ids, uint64_t n);
   // delete_document / delete_documents (index.rs:5099-5140): the docs are ADDED to the set on the device (ss_add_deleted), O(n)
   int add_deleted(const uint64_t* doc_ids, uint64_t n);
+  // delete_documents_by_query on this shard (index.rs:5147-5205; ss_bm25_delete_by_query): every query's page -- the entries from rank
+  // `offset` on of its search for k = offset + length (under result_sort: the sorted search), length = kDeleteAll: everything --
+  // computed against the shard as it is; the union of the pages is then added to the tombstones in one step.  A query whose page is
+  // its whole match set runs no search and moves no doc id.  dry_run: the same numbers and docs, nothing changes.
+  // matched / selected [queries]: live matches under the filters / docs of the page; *deleted: distinct docs newly tombstoned; docs
+  // (optional): those docs, ascending.  Returns the entry's code (SS_ENOTSUP: the caller's own route).
+  static constexpr uint64_t kDeleteAll = ~0ull;
+  int delete_by_query(const std::vector<ss_bm25_query>& queries, uint64_t offset, uint64_t length, const std::vector<ss_facet_filter>& facet_filter,
+                      const std::vector<ResultSort>& result_sort, bool dry_run, std::vector<uint64_t>* matched, std::vector<uint64_t>* selected,
+                      uint64_t* deleted, std::vector<uint32_t>* docs = nullptr);
+  uint32_t lexical_field_count() const { return lexical_fields_; }
   int synth_lexical(uint64_t seed, uint64_t n_docs, uint32_t n_terms, const uint32_t* thresh32, const uint8_t* len_table1024);
   int synth_vectors(uint64_t seed, uint64_t n_rows, uint32_t dim);
 
@@ -361,6 +372,16 @@ class Index {
   // in the tie direction), totals summed, facets merged.
   ResultObject search_empty(size_t offset, size_t length, ResultType result_type, const std::vector<ss_facet_filter>& facet_filter,
                             const std::vector<ResultSort>& result_sort, const std::vector<QueryFacet>& query_facets);
+  // delete_documents_by_query (index.rs:5147-5205): the docs that search(query_terms, .., ResultType::Topk, offset, length, ..) returns
+  // are deleted; length = Shard::kDeleteAll: every match.  *deleted_ids = the global ids it deleted, ascending (dry_run: would delete).
+  // No terms: nothing is deleted and no shard is asked.  One shard: one Shard::delete_by_query.  S shards: a dry run on every shard
+  // gives the matches; with offset = 0 and length >= their sum every shard deletes its whole match set on the device, else the page
+  // is the merged search's (search / search_lexical_sorted) and its ids go to their shards' add_deleted -- the route that also
+  // serves what a shard leaves to the caller's own path (SS_ENOTSUP).
+  int delete_documents_by_query(const std::vector<uint32_t>& query_terms, QueryType query_type_default, uint64_t offset, uint64_t length,
+                                std::vector<uint64_t>* deleted_ids, const std::vector<uint16_t>& field_filter = {},
+                                const std::vector<ss_facet_filter>& facet_filter = {}, const std::vector<ResultSort>& result_sort = {},
+                                const std::vector<uint32_t>& not_terms = {}, bool dry_run = false);
 
  private:
   std::vector<std::shared_ptr<Shard>> shards_;

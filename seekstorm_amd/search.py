@@ -752,6 +752,34 @@ class Shard:
         N.check(N.lib().ss_add_deleted(self._h, N.ptr(ids, N.u64p) if len(ids) else None, len(ids)), "ss_add_deleted")
         self._n_deleted = getattr(self, "_n_deleted", 0) + len(ids)  # (read as "any": an upper bound of the set's size)
 
+    def delete_by_query(self, queries, offset=0, length=None, facet_filter=None, result_sort=None, dry_run=False, return_docs=False):
+        """delete_documents_by_query on this shard (index.rs:5147-5205; ss_bm25_delete_by_query): every query's page -- the entries from
+        rank `offset` on of what search_lexical_batch (search_lexical_sorted_batch under a result_sort) returns for k = offset + length,
+        length = None: everything -- computed against the shard as it is, the union of the pages then added to the tombstones in one
+        step.  A query whose page is its whole match set never runs a search and moves no doc id.  dry_run: the same numbers and docs,
+        nothing changes.
+        -> (matched [nq], selected [nq], deleted[, docs]): live matches under the filters, docs of the page, distinct docs newly
+        tombstoned over all queries[, those docs ascending]"""
+        q = np.ascontiguousarray(queries)
+        nq, off = len(q), int(offset)
+        ln = 0xFFFFFFFFFFFFFFFF if length is None else int(length)
+        n, arr = self._result_sorts(result_sort) if result_sort else (0, None)
+        farr, nf = self.facet_filters(facet_filter) if facet_filter else (None, 0)
+        matched = np.zeros(nq, np.uint64)
+        selected = np.zeros(nq, np.uint64)
+        deleted = C.c_uint64(0)
+        cap = min(int(self.indexed_doc_count), nq * ln) if return_docs else 0
+        docs = np.empty(max(cap, 1), np.uint32) if return_docs else None
+        N.check(N.lib().ss_bm25_delete_by_query(self._h, nq, q.ctypes.data_as(C.c_void_p) if nq else None, n, None if arr is None else C.cast(arr, C.c_void_p),
+                                                off, ln, nf, None if farr is None else C.cast(farr, C.c_void_p),
+                                                N.SS_DELETE_DRY_RUN if dry_run else 0, N.ptr(matched, N.u64p), N.ptr(selected, N.u64p),
+                                                C.byref(deleted), N.ptr(docs, N.u32p), cap), "ss_bm25_delete_by_query")
+        if not dry_run:
+            self._n_deleted = getattr(self, "_n_deleted", 0) + int(deleted.value)
+        if return_docs:
+            return matched, selected, int(deleted.value), docs[:int(deleted.value)].copy()
+        return matched, selected, int(deleted.value)
+
     def synth_partition(self, shard_id, n_shards):
         """the following synth_* calls build shard `shard_id` of `n_shards` of one generator stream (doc g -> shard g % S)"""
         N.check(N.lib().ss_synth_set_partition(self._h, int(shard_id), int(n_shards)), "ss_synth_set_partition")
@@ -1948,6 +1976,66 @@ class Index:
             ro.facets = merge_facets(query_facets, shard_maps, result_type)
         ro.result_count = len(ro.results)
         return ro
+
+    def delete_documents_by_query(self, query_terms, query_type_default=QueryType.Union, offset=0, length=None, field_filter=None,
+                                  facet_filter=None, result_sort=None, not_terms=(), dry_run=False):
+        """delete_documents_by_query (index.rs:5147-5205): the docs that search(query_terms, ..., ResultType.Topk, offset, length, ...)
+        returns are deleted; length = None: every match.  -> the global ids it deleted, ascending (dry_run: would delete).
+        No terms: nothing is deleted and no shard is asked (the crate passes enable_empty_query = false).  One shard: one
+        Shard.delete_by_query.  S shards: a dry run on every shard gives the matches; with offset = 0 and length >= their sum every
+        shard deletes its whole match set on the device, else the page is the merged search's and its ids go to their shards'
+        add_deleted.  The search route also serves what a shard leaves to the caller's own path (SS_ENOTSUP) and the unions the
+        mirror composes from sub-queries (Shard.compose_filtered_unions)."""
+        if not query_terms:
+            return []
+        S = self.shard_number
+        offset = int(offset)
+        sorts = list(result_sort) if result_sort else None
+
+        def shard_query(sh, bounded=False):
+            q = sh.make_queries([list(query_terms)], query_type_default, [list(not_terms)],
+                                field_filter=field_filter if sh.lexical_field_count > 1 else None)
+            # a bounded page by score is search_lexical_batch's, with the reference's all_terms_frequent shortcut where its condition holds
+            if bounded and length is not None and not facet_filter and not sorts and (sh.lexical_field_count == 1 or sh.fields_info()[1]):
+                q = sh.mark_all_terms_frequent(q, offset + int(length))
+            return q
+
+        composed = any(field_filter and sh.lexical_field_count > 1 and int(query_type_default) == int(QueryType.Union)
+                       and len(set(int(t) for t in query_terms)) > 1 and sh.compose_filtered_unions for sh in self.shards)
+        total = None
+        try:
+            if not composed and S == 1:
+                sh = self.shards[0]
+                _, _, _, docs = sh.delete_by_query(shard_query(sh, True), offset, length, facet_filter, sorts, dry_run, return_docs=True)
+                return [int(d) * S + sh.shard_id for d in docs]
+            if not composed:
+                total = sum(int(sh.delete_by_query(shard_query(sh), 0, None, facet_filter, sorts, dry_run=True)[0][0]) for sh in self.shards)
+                if offset == 0 and (length is None or int(length) >= total):
+                    ids = []
+                    for sh in self.shards:
+                        _, _, _, docs = sh.delete_by_query(shard_query(sh), 0, None, facet_filter, sorts, dry_run, return_docs=True)
+                        ids += [int(d) * S + sh.shard_id for d in docs]
+                    return sorted(ids)
+        except N.SeekStormHipError as e:
+            if e.code != N.SS_ENOTSUP:
+                raise
+        if total is None and length is None:  # (no shard counted: the search's own total bounds the page)
+            total = self.search(query_terms, None, query_type_default, SearchMode.Lexical, 0, 1, ResultType.TopkCount, strict=True, not_terms=not_terms,
+                                field_filter=field_filter, facet_filter=facet_filter, result_sort=sorts).result_count_total
+        want = int(length) if length is not None else max(int(total) - offset, 0)
+        if total is not None:
+            want = min(want, max(int(total) - offset, 0))
+        if want == 0:
+            return []
+        ro = self.search(query_terms, None, query_type_default, SearchMode.Lexical, offset, want, ResultType.Topk, strict=True, not_terms=not_terms,
+                         field_filter=field_filter, facet_filter=facet_filter, result_sort=sorts)
+        ids = sorted(set(int(r.doc_id) for r in ro.results))
+        if not dry_run:
+            for sh in self.shards:
+                local = [g // S for g in ids if g % S == sh.shard_id]
+                if local:
+                    sh.add_deleted(local)
+        return ids
 
     def _search_empty(self, offset, length, result_type, facet_filter, result_sort, query_facets) -> ResultObject:
         """The empty query (search.rs:1413-1432 and 3374-3386).  field_filter plays no part.
